@@ -1,6 +1,6 @@
 """bench.py — images/sec of the Drone-YOLO-s detection pass on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype bf16|fp16|fp32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype bf16|fp16|fp32] [--full] [--dump-outputs DIR]
 
 One "step" = one whole pass over a batch of B synthetic 640x640 images already resident in HBM (B = 256 by default,
 SURVEY §8d config 2): fused stem (fp32 NCHW in), 70 convolution launches (MFMA kernels), SPPF pools, fused Detect tail
@@ -10,11 +10,14 @@ batch's convolutions fill the CUs that a batch's NMS and small tail kernels leav
 N > 1 (launched by torch.distributed.run, one rank per GPU) shards by image with no data-path
 collective: every rank runs B images, value = N*B*K / max-over-ranks time ("weak" scaling).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps and prints
+the headline; `--full` adds everything measured beside it (each in runs of its own, after the timed steps), among them
   roofline      MFMA-bound view of the dominant kernel family (every launch that convolves): algorithmic conv
                 FLOPs per pass / summed per-launch durations measured with HIP events on the launch stream
   cpu_baseline  the oracle (CPU restatement of the reference path, oracle/) timed on the host cores on a
                 bounded sample of the same workload (rank 0, N=1 only)
+and the parity gate, breakdown, batch sweep, public-API, other-scale, tiled and training records.
+`--dump-outputs DIR` writes what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB.
 `--mode train` prints the secondary line of SURVEY §8d config 3 (training step, B = 64 per GPU).
 """
 from __future__ import annotations
@@ -40,6 +43,8 @@ if ROOT not in sys.path:
 MFMA_PEAK_TFLOPS = {"bf16": 2500.0, "fp16": 2500.0, "fp32": 157.3, "fp8": 5000.0, "fp8-mixed": 2500.0, "f16x2": 2500.0 / 3}
 ELEM_BYTES = {"bf16": 2, "fp16": 2, "fp32": 4, "fp8": 1, "fp8-mixed": 2, "f16x2": 4}
 HBM_PEAK_GBS = 8000.0
+DUMP_MAX_BYTES = 60_000_000  # --dump-outputs: the arrays of one run together (under 64 MB with the .npy headers)
+DUMP_SAMPLE_SEED = 0
 
 
 def synthetic_state_dict(model, seed: int, cls_bias=None, bn_stats="file", gamma_scale=None, variant=""):
@@ -407,6 +412,7 @@ def train_steps(model_yaml: str, batch: int, dtype: str, steps: int, warmup: int
                              "cfs_throttle_during_timed_steps": {k: v - thr0.get(k, 0) for k, v in thr1.items()}}}
     gc.callbacks.remove(_gc_cb)
     tr.host_phases = None
+    tr.last_step = (loss, items)  # the last timed step's results (--dump-outputs)
     return dt, t_enq, float(loss), tr
 
 
@@ -447,6 +453,8 @@ def train_bench(a):
     dev = torch.device("cuda", local_rank)
     torch.cuda.set_device(dev)
     dt, t_enq, loss, tr = train_steps(a.model, a.batch, a.dtype, a.steps, a.warmup, rank, world, dev)
+    if rank == 0 and a.dump_outputs:
+        write_outputs(a.dump_outputs, train_outputs(tr))
     if rank == 0:
         print(json.dumps(train_record(a, dt, t_enq, loss, tr, a.batch, world, a.steps, a.warmup, a.dtype)))
 
@@ -620,6 +628,55 @@ def bar_exact_row(sweep):
             "note": "hipGraph replay on one stream; the headline's fp16 storage is 3x faster and flips 0.1-0.4 % of the detections near the confidence threshold (`parity`)"}
 
 
+def seeded_positions(n: int, k: int) -> torch.Tensor:
+    """k of range(n): a fixed seeded choice in ascending order (all n when k >= n)."""
+    import numpy as np
+
+    if k >= n:
+        return torch.arange(n)
+    return torch.from_numpy(np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, k, replace=False)))
+
+
+def infer_outputs(cf) -> dict:
+    """What a caller of the timed pass receives from one step (engine/predictor.py::postprocess reads the same buffers): every image's kept rows
+    x1 y1 x2 y2 conf cls and their anchor indices (past an image's count zero / -1: the buffer's tail is not part of the result), and the decoded
+    (N, 4+nc, A) predictions over a fixed seeded sample of anchors when the whole tensor would not fit the budget."""
+    nms = cf.nms
+    count = nms.count.long().cpu()
+    keep = torch.arange(nms.out.shape[1])[None, :] < count[:, None]
+    out = {"det_count": count, "det": torch.where(keep[..., None], nms.out.cpu(), 0.0), "det_index": torch.where(keep, nms.index.long().cpu(), -1)}
+    n, c, A = cf.pred.shape
+    room = DUMP_MAX_BYTES - sum(v.numel() * 8 for v in out.values()) - A * 8
+    anchors = seeded_positions(A, room // (n * c * 4))
+    out["pred_anchors"] = anchors
+    out["pred"] = cf.pred.index_select(2, anchors.to(cf.pred.device))
+    return out
+
+
+def train_outputs(tr) -> dict:
+    """What the last timed training step leaves its caller: the loss, the loss items and the updated weights (one flat vector in parameter order,
+    over a fixed seeded sample of positions when it would not fit the budget)."""
+    loss, items = tr.last_step
+    flat = torch.cat([p.detach().reshape(-1).float() for p in tr.model.parameters()])
+    pos = seeded_positions(flat.numel(), (DUMP_MAX_BYTES - (1 << 20)) // 12)  # float32 value + float64 position
+    return {"loss": loss, "loss_items": items, "params_positions": pos, "params": flat.index_select(0, pos.to(flat.device))}
+
+
+def write_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: DIR/<name>.npy per array; float64 stays float64, other floats become float32, integers float64 (exact)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach().cpu()
+        a = (t.float() if t.is_floating_point() and t.dtype != torch.float64 else t.double()).numpy()
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES} byte budget at {name}")
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -632,15 +689,20 @@ def main():
                          "misses it: see `parity`); train: bf16 by default (SURVEY config 3: AMP bf16; fp16 runs under the device-side GradScaler)")
     ap.add_argument("--model", default="yolov8s-p2-repvgg.yaml")
     ap.add_argument("--no-graph", action="store_true", help="replay the launch plan from Python instead of a hipGraph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the B = 1 / 8 / 64 batch sweep")
-    ap.add_argument("--no-train", action="store_true", help="skip the training sub-record (30 steps of SURVEY config 3 at B = 64)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the public-API rows (YOLO.predict) and the other-scales rows of the default line")
-    ap.add_argument("--bare", action="store_true", help="profiling runs: no parity gate, breakdown, batch sweep or CPU baseline (only the passes of the timed workload)")
-    ap.add_argument("--layers", default="", help="write a per-conv-launch timing table to this file")
+    ap.add_argument("--full", action="store_true", help="infer: after the timed steps also measure the roofline, parity gate, breakdown, batch sweep, public-API, "
+                                                         "other-scale, tiled and training records and the CPU baseline (a plain run prints the headline only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed (rank 0) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-sweep", action="store_true", help="with --full: skip the B = 1 / 8 / 64 batch sweep")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip the training sub-record (30 steps of SURVEY config 3 at B = 64)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the public-API rows (YOLO.predict) and the other-scales rows")
+    ap.add_argument("--bare", action="store_true", help="profiling runs with --full: no parity gate, breakdown, batch sweep or CPU baseline (the timed workload and the roofline's passes)")
+    ap.add_argument("--layers", default="", help="with --full: write a per-conv-launch timing table to this file")
     ap.add_argument("--streams", type=int, default=2, help="independent batches in flight on separate HIP streams (2 measured best: 1 -> 14.5k, 2 -> 15.1k, 3 -> 14.9k img/s)")
     ap.add_argument("--mode", default="infer", choices=["infer", "train"], help="infer = the headline metric (default); train = SURVEY §8(d) config 3")
     a = ap.parse_args()
+    if a.layers and not a.full:
+        ap.error("--layers needs --full (the per-launch table comes from the roofline's timing passes)")
     if a.bare:
         a.no_sweep = a.no_cpu_baseline = a.no_extra = True
     if a.batch is None:
@@ -651,6 +713,8 @@ def main():
         a.steps = 30 if a.mode == "train" else 200
     if a.warmup is None:
         a.warmup = 5 if a.mode == "train" else 10
+    if a.steps < 1 or a.warmup < 0:
+        ap.error(f"--steps must be >= 1 and --warmup >= 0 (got {a.steps}, {a.warmup})")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: this process becomes the launcher (reference: utils/dist.py:56-66 + trainer.py:185-205).
         # It has not touched the GPU (device_count() only reads the topology) and starts the ranks as CHILD processes — one per
@@ -715,12 +779,14 @@ def main():
     torch.cuda.synchronize()
     P.barrier()
     dt = P.max_over_ranks(time.perf_counter() - t0, dev)
+    if rank == 0 and a.dump_outputs:  # the last timed step's buffers, before any later pass overwrites them
+        write_outputs(a.dump_outputs, infer_outputs(cfs[(a.steps - 1) % ns]))
     kept = float(cf.nms.count.float().mean())
     cand = float((cf.pred[:, 4:].amax(1) > 0.25).float().mean())
 
     # dominant-kernel roofline (rank 0): HIP events around every conv launch of the recorded plan
     roof = None
-    if rank == 0:
+    if rank == 0 and a.full:
         work, times, knames = time_convs(cf.plan)
         flops = sum(w[1] for w in work)
         nbytes = sum(w[2] for w in work)
@@ -774,7 +840,7 @@ def main():
                     f.write(f"{i:3d}  {name:<28s} {times[i] * 1e6:9.1f} {fl / times[i] / 1e12:8.1f} {nb_ / times[i] / 1e9:8.0f}  {knames.get(i, '')}\n")
 
     parity = breakdown = sweep = alt = tiled = None
-    if rank == 0:
+    if rank == 0 and a.full:
         scale_letter = os.path.basename(a.model).replace("yolov8", "")[:1]
         tag = {("s", 640): "s640bench", ("x", 1536): "x1536", ("l", 1280): "l1280t8"}.get((scale_letter, a.imgsz))
         if tag == "l1280t8" and not a.bare:  # config 4: the fixture's input is a frame cut into tiles (engine/tiling.py)
@@ -789,14 +855,14 @@ def main():
             sweep = batch_sweep(model, a.dtype, local_rank) + [{"batch": a.batch, "dtype": a.dtype, "ms_per_pass": round(dt / a.steps * 1e3, 3), "img_s": round(a.batch * a.steps / dt, 1),
                                                                 "note": f"headline: {ns} batches in flight"}]
     api = scales = None
-    if rank == 0 and world == 1 and not a.no_extra and a.imgsz == 640 and "yolov8s-p2-repvgg" in a.model:
+    if rank == 0 and world == 1 and a.full and not a.no_extra and a.imgsz == 640 and "yolov8s-p2-repvgg" in a.model:
         del preds, xs, cfs, pred, x, cf
         preds = xs = cfs = pred = x = cf = None
         torch.cuda.empty_cache()
         api = predict_api_record(a.model, sd, local_rank, batch=a.batch)
         scales = other_scales_record(local_rank, batch=a.batch)
     train = None
-    if world == 1 and not a.bare and not a.no_train and a.imgsz == 640 and "yolov8s-p2-repvgg" in a.model:
+    if world == 1 and a.full and not a.bare and not a.no_train and a.imgsz == 640 and "yolov8s-p2-repvgg" in a.model:
         # SURVEY §8(d) config 3 in the driver's record: 30 graphed training steps at B = 64 (bf16 storage), after the inference state is gone
         # (r04: 10 steps after 4 warm-up steps read 29.5 ms on one box and 34.1 on the next -- 0.3 s is too short a window beside the
         # allocator's and the graph's first replays; `python bench.py --mode train` always timed 30)
@@ -807,7 +873,7 @@ def main():
         del tr
         torch.cuda.empty_cache()
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.imgsz == 640 and "yolov8s-p2-repvgg" in a.model:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline and a.imgsz == 640 and "yolov8s-p2-repvgg" in a.model:
         cpu = cpu_baseline(model.yaml, sd)
 
     if rank == 0:

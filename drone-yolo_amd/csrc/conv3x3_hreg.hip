@@ -23,9 +23,11 @@
 //     them (bias-initialised accumulator, SiLU, optional Bottleneck residual) as 8 bytes straight from registers.
 //
 // Persistent workgroups, XCD-aware tile order (the tiles an XCD's workgroups visit are contiguous in the image, so the
-// halo columns / rows shared by neighbouring tiles are L2 hits), one raw s_barrier per (tile, chunk) item.  TWO items' DMA
-// stay in flight per workgroup behind counted s_waitcnt vmcnt(N) (the first version had one and waited vmcnt(0), output
-// stores included: 46 KB in flight per CU made the kernel latency bound — 2.7 TB/s x 4.4 us = all that was in flight).
+// halo columns / rows shared by neighbouring tiles are L2 hits), one raw s_barrier per (tile, chunk) item.  The DMA of item
+// i + 2 is issued at the start of item i and drained (s_waitcnt vmcnt(0)) before the barrier that ends it.  Counted waits
+// (vmcnt(4) / vmcnt(8): item i + 1 landed, item i + 2 left in flight) published a stage before all of its DMA had landed
+// when another stream's kernels shared the CUs: the 64 -> 128 layers then read stale halo pixels, and results differed from
+// run to run.  The full drain measured the same pass time.
 // Reference semantics: Conv (nn/modules/conv.py:37-55, BatchNorm folded), Bottleneck shortcut (block.py:337-350).
 #include "common_hip.h"
 #include "conv_args.h"
@@ -123,7 +125,7 @@ __global__ __launch_bounds__(256, NCH <= 2 ? (BNB ? BW : 3) : 2) void conv3x3_hr
   // constant of the launch; the tile contributes a SCALAR offset (the DMA instruction's soffset).  Interior tiles use rel[k] as it is;
   // border tiles replace the out-of-image slots by an out-of-range offset — the range check then feeds zeros (the zero padding) — so the
   // 64-bit address sums, the integer multiplies per slot (quarter-rate instructions) and the zero-page selects of the first version are gone.
-  constexpr int NDMA = 4;  // every wave issues exactly 4 wave-instructions per item (w, w + 4, w + 8, w + 12): the waits below are counted
+  constexpr int NDMA = 4;  // every wave issues exactly 4 wave-instructions per item (w, w + 4, w + 8, w + 12)
   constexpr unsigned kOob = 0xfffffff0u;  // >= num_records of every descriptor here (the host checks the sizes)
   const unsigned pre = (unsigned)((p.W + 1) * p.ldx) * 2u;
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.x)) - pre, 0, p.x_bytes + pre, 0x00020000);
@@ -175,7 +177,7 @@ __global__ __launch_bounds__(256, NCH <= 2 ? (BNB ? BW : 3) : 2) void conv3x3_hr
       }
     } else {
 #pragma unroll
-      for (int k = 0; k < NDMA; ++k)  // keeps the per-item instruction count (the counted waits) — every lane out of range: zeros
+      for (int k = 0; k < NDMA; ++k)  // keeps the per-item instruction count — every lane out of range: zeros
         __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void*)(sa + (k * 4 + wave) * 1024), 16, (int)kOob, 0, 0, 0);
     }
   };
@@ -314,15 +316,15 @@ __global__ __launch_bounds__(256, NCH <= 2 ? (BNB ? BW : 3) : 2) void conv3x3_hr
     }
   };
 
-  // ---- item pipeline: ring of three stages, two items' DMA in flight, counted waits, raw barriers ----
+  // ---- item pipeline: ring of three stages, raw barriers ----
   // Item i lives in stage i % 3.  At the start of item i the DMA of item i + 2 goes into stage (i + 2) % 3, last read in
-  // item i - 1 (every wave has passed the barrier that ended it).  At the end of item i the wave waits until ITS pieces of
-  // item i + 1 have landed: younger than those are only the 4 DMA instructions of item i + 2 and, when the item ended a
-  // tile, the tile's 4 output stores -> s_waitcnt vmcnt(4) / vmcnt(8); the barrier then publishes everyone's pieces.
+  // item i - 1 (every wave has passed the barrier that ended it).  At the end of item i the wave drains its vector-memory
+  // operations (vmcnt(0): its pieces of items i + 1 and i + 2, and the tile's output stores); the barrier then publishes
+  // everyone's pieces.  (Counted waits that left item i + 2 in flight were not safe: see the header.)
   setup_tile(l_tile);
   issue_dma(0);
   issue_dma(1 % kHrStages);
-  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   int c_tile = sb;
   int stage = 0;
@@ -337,10 +339,8 @@ __global__ __launch_bounds__(256, NCH <= 2 ? (BNB ? BW : 3) : 2) void conv3x3_hr
       if (c == NCH - 1) {
         epilogue(c_tile);
         c_tile += Gs;
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
       }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       stage = stage + 1 == kHrStages ? 0 : stage + 1;
     }
@@ -546,11 +546,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hreg_s2_kernel(const HregArgs 
     }
   };
 
-  // item pipeline as in the stride-1 kernel: 6 DMA instructions per item and wave, 2 output stores per tile
+  // item pipeline as in the stride-1 kernel: 6 DMA instructions per item and wave, 2 output stores per tile, drained before each barrier
   setup_tile(l_tile);
   issue_dma(0);
   issue_dma(1);
-  asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   int c_tile = sb;
   int stage = 0;
@@ -562,10 +562,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hreg_s2_kernel(const HregArgs 
       if (c == NCH - 1) {
         epilogue(c_tile);
         c_tile += Gs;
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
       }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       stage = stage + 1 == kHrStages ? 0 : stage + 1;
     }

@@ -661,7 +661,9 @@ class DetectionTrainer:
             cut = bk is not None and os.environ.get("DYOLO_DDP_GRAPH_CUT", "1") != "0"
             if not cut:
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g), H.batched_weight_packing(packs):
+                # thread_local: RCCL's watchdog thread polls its events at any time; under the default global mode such a call during the
+                # capture fails and the watchdog aborts the process
+                with torch.cuda.graph(g, capture_error_mode="thread_local"), H.batched_weight_packing(packs):
                     body()
                 gs.update(graphs=[g], ends=[len(bk.buckets) if bk is not None else 0])
             else:

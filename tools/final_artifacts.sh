@@ -2,7 +2,7 @@
 # GPU box: the bench lines the round's documents quote, written under gpurun_out/final_TAG/ (copy into profiles/ as rNN_*.json).
 TAG=${1:-r05}
 O=gpurun_out/final_$TAG; mkdir -p $O
-run() { out=$1; shift; python bench.py "$@" 2>$O/$out.err | tail -1 > $O/$out.json; python -c "
+run() { out=$1; shift; python bench.py --full "$@" 2>$O/$out.err | tail -1 > $O/$out.json; python -c "
 import json,sys
 d=json.load(open('$O/$out.json')); r=d.get('roofline') or {}; p=d.get('parity') or {}
 print('$out', d.get('value'), d.get('unit'), d.get('ms_per_step'), 'frac', r.get('frac'), 'match', p.get('match_rate'), 'iou_min', p.get('iou_min'))"; }

@@ -12,7 +12,7 @@ for f in glob.glob(root + "/**/*counter_collection.csv", recursive=True):
         acc[fam][r["Counter_Name"]] += float(r["Counter_Value"])
         sym[r["Kernel_Name"][:70]][r["Counter_Name"]] += float(r["Counter_Value"])
         sym[r["Kernel_Name"][:70]]["n_" + r["Counter_Name"]] += 1
-out = {"round": int(sys.argv[4]) if len(sys.argv) > 4 else 4, "dtype": DT, "command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python3 bench.py --steps 2 --warmup 1 --streams 1 --bare --no-graph" + ("" if DT == "fp16" else " --dtype " + DT),
+out = {"round": int(sys.argv[4]) if len(sys.argv) > 4 else 4, "dtype": DT, "command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python3 bench.py --steps 2 --warmup 1 --streams 1 --full --bare --no-graph" + ("" if DT == "fp16" else " --dtype " + DT),
        "correction": "FETCH_SIZE doubled (gfx950 tallies 128-B requests at 64 B, MI355X_MICROARCH.md HBM section); counters are KiB; "
                      "%d passes profiled (1 record + 1 warm-up + 2 steps + 5 event-timing passes of the conv launches)" % passes_per_run,
        "batch": batch, "families": {}}
