@@ -181,6 +181,7 @@ SIGNATURES = {
     "dy_detect_head_decode": (_i32, [C.POINTER(HeadDecodeDesc), _vp]),
     "dy_nms_workspace_bytes": (_i64, [_i32, _i32]),
     "dy_nms": (_i32, [C.POINTER(NmsDesc), _vp]),
+    "dy_nms_small_cap": (_i32, []),
     "dy_scale_boxes": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp]),
     "dy_detection_loss_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "dy_conv2d_wgrad_nhwc": (_i32, [C.POINTER(ConvDesc), _vp, _i32, _vp, _vp]),

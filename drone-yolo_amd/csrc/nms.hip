@@ -15,7 +15,10 @@
 //                          64 candidates: every lane tests its candidate against the kept
 //                          list (LDS), then the chunk is resolved in score order with
 //                          ballot/shuffle.  The scan stops at max_det kept (ops.py:313), which is
-//                          exact because greedy NMS never revisits a kept box.
+//                          exact because greedy NMS never revisits a kept box.  Serves the images with
+//                          more than NMS_SMALL_CAP candidates (the validator's conf 0.001, multi_label).
+//   K2s nms_small_kernel   the same for images with at most NMS_SMALL_CAP candidates, in 256 threads and
+//                          22 KB of LDS with the scan on four waves (described at the kernel).
 //
 // IoU and box arithmetic follow the reference operation by operation in fp32 with
 // contraction off, so that kept indices are bit-identical to the CPU path for identical
@@ -147,6 +150,164 @@ __device__ __forceinline__ bool iou_gt(float ix1, float iy1, float ix2, float iy
   return ovr > thr;
 }
 
+// ---- K2s nms_small_kernel: images with at most NMS_SMALL_CAP candidates (what the predictor produces at conf 0.25) ----------------
+// One workgroup of 256 threads (4 waves) per image and LDS by need: the keys of NMS_SMALL_CAP entries, the kept list, a 64 x 64
+// suppression bit matrix and one verdict word per wave: 16,928 + 20 * max_det bytes (22,928 B at max_det 300), so that the convolution
+// workgroups of another stream fit on the same CU.  Same order, same arithmetic, same outputs as nms_suppress_kernel below:
+//   sort     bitonic in LDS, 256 threads over the P2 / 2 <= 1024 compare-exchange pairs of a pass;
+//   scan     per chunk of 64 candidates (lane = candidate, every wave holds the same 64): wave w tests them against kept boxes
+//            w, w + 4, ... and publishes a ballot of the suppressed lanes; wave w also computes rows 16 w .. 16 w + 15 of the chunk's
+//            bit matrix (row i, bit j: box i as the kept box suppresses candidate j).  After one barrier every wave ORs the four
+//            verdicts, takes row[lane] into a register and resolves the chunk in score order with bit operations only
+//            (lowest live bit t is kept; live &= ~row[t]), the same on all four waves, so no second exchange is needed.  Wave 0
+//            appends the kept boxes and writes their rows; a barrier publishes the kept list to the next chunk.
+// The next chunk's keys, classes and boxes are fetched while the current chunk is scanned.
+// The count is known on the device only, so dy_nms launches both kernels and each returns at once for the images of the other.
+constexpr int NMS_SMALL_CAP = 2048;
+constexpr int NMS_SMALL_THREADS = 256;
+constexpr int NMS_SMALL_WAVES = NMS_SMALL_THREADS / 64;
+constexpr int NMS_SMALL_FIXED_LDS = NMS_SMALL_CAP * 8 + 64 * 8 + NMS_SMALL_WAVES * 8;  // keys, bit matrix, verdict words
+
+static inline size_t nms_small_lds_bytes(int max_det) { return (size_t)NMS_SMALL_FIXED_LDS + (size_t)max_det * 20; }
+
+struct NmsCand {  // what a lane fetches for its candidate of a chunk
+  float cx, cy, w, h, score;
+  int anchor, cls;
+};
+
+__device__ __forceinline__ NmsCand nms_small_fetch(const NmsArgs& p, const u64* skeys, const float* pr, int b, int i, int nn) {
+  NmsCand c{0.f, 0.f, 0.f, 0.f, 0.f, 0, 0};
+  if (i < nn) {
+    const u64 key = skeys[i];
+    c.anchor = (int)(unsigned)(key & 0xffffffffull);
+    c.score = __uint_as_float(~(unsigned)(key >> 32));
+    if (p.multi) {
+      c.cls = c.anchor % p.nc;
+      c.anchor = c.anchor / p.nc;
+    } else {
+      c.cls = (int)p.cls[(size_t)b * p.A + c.anchor];
+    }
+    c.cx = pr[c.anchor];
+    c.cy = pr[(size_t)p.A + c.anchor];
+    c.w = pr[(size_t)2 * p.A + c.anchor];
+    c.h = pr[(size_t)3 * p.A + c.anchor];
+  }
+  return c;
+}
+
+// a value every lane holds alike, moved to scalar registers (the compiler cannot see that an LDS read is wave-uniform)
+__device__ __forceinline__ u64 nms_uniform64(u64 v) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+  return ((u64)hi << 32) | (u64)lo;
+}
+
+__global__ __launch_bounds__(NMS_SMALL_THREADS) void nms_small_kernel(const NmsArgs p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
+  const int b = blockIdx.x;
+  int n = p.counts[b];
+  if (n > p.cap) n = p.cap;
+  if (n > NMS_SMALL_CAP) return;  // nms_suppress_kernel's image
+  u64* skeys = reinterpret_cast<u64*>(dyn_smem);
+  u64* rows = skeys + NMS_SMALL_CAP;  // [64]
+  u64* verdict = rows + 64;           // [NMS_SMALL_WAVES]
+  float4* kbox = reinterpret_cast<float4*>(dyn_smem + NMS_SMALL_FIXED_LDS);  // [max_det] offset xyxy of the kept boxes
+  float* kar = reinterpret_cast<float*>(kbox + p.max_det);                   // [max_det] their areas
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const u64* gkeys = p.keys + (size_t)b * p.P;
+
+  int P2 = 1;
+  while (P2 < n) P2 <<= 1;
+  for (int i = tid; i < P2; i += NMS_SMALL_THREADS) skeys[i] = i < n ? gkeys[i] : ~0ull;
+  __syncthreads();
+  for (int k = 2; k <= P2; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < (P2 >> 1); t += NMS_SMALL_THREADS) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));  // element with bit j clear
+        const int ixj = i | j;
+        const u64 x = skeys[i], y = skeys[ixj];
+        const bool up = (i & k) == 0;
+        if ((x > y) == up) {
+          skeys[i] = y;
+          skeys[ixj] = x;
+        }
+      }
+      __syncthreads();
+    }
+  }
+
+  const int nn = n < p.max_nms ? n : p.max_nms;
+  const float* pr = p.pred + (size_t)b * p.nch * (size_t)p.A;
+  float* outb = p.out + (size_t)b * p.max_det * 6;
+  const u64 lane_bit = 1ull << lane;
+  int nk = 0;
+  NmsCand nxt = nms_small_fetch(p, skeys, pr, b, lane, nn);
+  for (int c0 = 0; c0 < nn && nk < p.max_det; c0 += 64) {
+    const NmsCand c = nxt;
+    nxt = nms_small_fetch(p, skeys, pr, b, c0 + 64 + lane, nn);
+    const bool in = c0 + lane < nn;
+    const float hw = c.w / 2.f, hh = c.h / 2.f;
+    const float x1 = c.cx - hw, y1 = c.cy - hh, x2 = c.cx + hw, y2 = c.cy + hh;
+    const float off = p.agnostic ? 0.f : (float)c.cls * p.max_wh;
+    const float ox1 = x1 + off, oy1 = y1 + off, ox2 = x2 + off, oy2 = y2 + off;
+    const float area = (ox2 - ox1) * (oy2 - oy1);
+    // this wave's share of the kept list
+    bool sup = false;
+    for (int k = wave; k < nk; k += NMS_SMALL_WAVES) {
+      const float4 kb = kbox[k];
+      sup |= iou_gt(kb.x, kb.y, kb.z, kb.w, kar[k], ox1, oy1, ox2, oy2, area, p.iou);
+    }
+    const u64 sm = __ballot(sup);
+    // this wave's 16 rows of the chunk's suppression matrix
+    u64 myrow = 0ull;
+    for (int r = 0; r < 16; ++r) {
+      const int i = wave * 16 + r;  // wave-uniform: v_readlane
+      auto bcast = [&](float v) { return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(v), i)); };
+      const u64 m = __ballot(iou_gt(bcast(ox1), bcast(oy1), bcast(ox2), bcast(oy2), bcast(area), ox1, oy1, ox2, oy2, area, p.iou));
+      if (lane == r) myrow = m;
+    }
+    if (lane < 16) rows[wave * 16 + lane] = myrow;
+    if (lane == 0) verdict[wave] = sm;
+    __syncthreads();
+    u64 dead = 0ull;
+    for (int w = 0; w < NMS_SMALL_WAVES; ++w) dead |= verdict[w];
+    const u64 row = rows[lane];
+    const unsigned row_lo = (unsigned)row, row_hi = (unsigned)(row >> 32);
+    u64 am = __ballot(in) & ~nms_uniform64(dead);  // candidates of the chunk that no earlier kept box suppresses
+    u64 km = 0ull;                                 // those the chunk keeps
+    int cnt = 0;
+    while (am != 0ull) {
+      const int t = __ffsll((long long)am) - 1;  // best live candidate of the chunk (wave-uniform)
+      km |= 1ull << t;
+      ++cnt;
+      if (nk + cnt >= p.max_det) break;
+      const u64 rt = ((u64)(unsigned)__builtin_amdgcn_readlane((int)row_hi, t) << 32) | (u64)(unsigned)__builtin_amdgcn_readlane((int)row_lo, t);
+      am &= ~(rt | (1ull << t));
+    }
+    if (wave == 0 && (km & lane_bit) != 0ull) {
+      const int at = nk + __popcll(km & (lane_bit - 1ull));
+      kbox[at] = make_float4(ox1, oy1, ox2, oy2);
+      kar[at] = area;
+      float* o = outb + (size_t)at * 6;
+      o[0] = x1;
+      o[1] = y1;
+      o[2] = x2;
+      o[3] = y2;
+      o[4] = c.score;
+      o[5] = (float)c.cls;
+      if (p.out_index) p.out_index[(size_t)b * p.max_det + at] = c.anchor;
+    }
+    nk += cnt;
+    __syncthreads();  // the kept list is complete before the next chunk reads it; rows / verdict may be rewritten
+  }
+  for (int r = nk * 6 + tid; r < p.max_det * 6; r += NMS_SMALL_THREADS) outb[r] = 0.f;
+  if (p.out_index)
+    for (int r = nk + tid; r < p.max_det; r += NMS_SMALL_THREADS) p.out_index[(size_t)b * p.max_det + r] = -1;
+  if (tid == 0) p.out_count[b] = nk;
+}
+
 __global__ __launch_bounds__(1024) void nms_suppress_kernel(const NmsArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
   u64* skeys = reinterpret_cast<u64*>(dyn_smem);
@@ -155,6 +316,7 @@ __global__ __launch_bounds__(1024) void nms_suppress_kernel(const NmsArgs p) {
   const int tid = threadIdx.x;
   int n = p.counts[b];
   if (n > p.cap) n = p.cap;
+  if (n <= NMS_SMALL_CAP) return;  // nms_small_kernel's image
   u64* gkeys = p.keys + (size_t)b * p.P;
 
   int P2 = 1;
@@ -348,12 +510,22 @@ extern "C" int32_t dy_nms(const dy_nms_desc* d, dy_stream_t stream) {
     const int rc = check_launch(multi ? "nms_filter_ml_kernel" : "nms_filter_kernel");
     if (rc != DY_OK) return rc;
   }
+  // Both suppress kernels are launched: which of them an image belongs to (at most NMS_SMALL_CAP candidates or more) is known on
+  // the device only, and the workgroups of the other kernel return in their first instructions.
+  static const hipError_t attr_small = hipFuncSetAttribute((const void*)nms_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  (void)attr_small;
+  hipLaunchKernelGGL(nms_small_kernel, dim3((unsigned)d->batch), dim3(NMS_SMALL_THREADS), nms_small_lds_bytes(d->max_det), st, a);
+  const int rc = check_launch("nms_small_kernel");
+  if (rc != DY_OK) return rc;
+  if (wcap <= NMS_SMALL_CAP) return DY_OK;  // no image can have more candidates
   const size_t smem = (size_t)a.SL * 8 + align_up((size_t)d->max_det * 5 * 4, 16);
   static const hipError_t attr_once = hipFuncSetAttribute((const void*)nms_suppress_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   (void)attr_once;
   hipLaunchKernelGGL(nms_suppress_kernel, dim3((unsigned)d->batch), dim3(1024), smem, st, a);
   return check_launch("nms_suppress_kernel");
 }
+
+extern "C" int32_t dy_nms_small_cap(void) { return NMS_SMALL_CAP; }
 
 extern "C" int32_t dy_scale_boxes(float* boxes, const int32_t* counts, const float* params, int32_t batch,
                                   int32_t max_det, dy_stream_t stream) {

@@ -480,6 +480,10 @@ typedef struct dy_nms_desc {
 } dy_nms_desc;
 int64_t dy_nms_workspace_bytes(int32_t batch, int32_t anchors);
 int32_t dy_nms(const dy_nms_desc* d, dy_stream_t stream);
+/* Images with at most this many candidates are sorted and scanned by the small suppress kernel (256 threads, about 22 KB of LDS at
+ * max_det 300, so that another stream's convolution workgroups share the CU); images with more take the 1024-thread kernel.
+ * Which kernel serves an image is decided on the device; the results are the same. */
+int32_t dy_nms_small_cap(void);
 
 /* Replaces: ops.scale_boxes + ops.clip_boxes (utils/ops.py:92-127, 335-354) as applied by
  * DetectionPredictor.construct_result (models/yolo/detect/predict.py:59-73) to the kept rows.
