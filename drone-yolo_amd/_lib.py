@@ -149,6 +149,21 @@ class BnDesc(C.Structure):
     ]  # fmt: skip
 
 
+DY_AUG_FLIPLR, DY_AUG_FLIPUD, DY_AUG_HSV_OFF = 1, 2, 4
+
+
+class AugSrc(C.Structure):
+    """Mirror of ``dy_aug_src``: one pasted rectangle of an augmented image."""
+
+    _fields_ = [("index", _i32), ("x1a", _i32), ("y1a", _i32), ("x2a", _i32), ("y2a", _i32), ("x1b", _i32), ("y1b", _i32), ("reserved", _i32)]
+
+
+class AugRow(C.Structure):
+    """Mirror of ``dy_aug_row``: the table row of one output image of ``dy_augment_u8_nchw``."""
+
+    _fields_ = [("n_src", _i32), ("ch", _i32), ("cw", _i32), ("flags", _i32), ("src", AugSrc * 4), ("minv", _f32 * 9), ("hsv", _f32 * 3)]
+
+
 # name -> (restype, argtypes); every symbol include/dyolo.h declares must appear here
 # (tests/test_cabi.py checks both directions).
 SIGNATURES = {
@@ -215,6 +230,7 @@ SIGNATURES = {
     "dy_silu_fwd": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "dy_silu_bwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dy_detection_loss": (_i32, [C.POINTER(LossDesc), _vp]),
+    "dy_augment_u8_nchw": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
 }
 
 _lib = None

@@ -22,8 +22,9 @@ the clip norm is one reduction, each optimizer group one kernel launch and the E
   * validation inside the loop (trainer.py:427-442, 605-615; r04): rank 0 evaluates the EMA weights every epoch (``val: true``) with the
     validator's NMS (multi_label, conf 0.001) — mAP50 / mAP50-95 / fitness into results.csv, ``best.pt`` beside ``last.pt``
     (engine/validator.py).
-Out of scope: dataset files, augmentation, callbacks, plots, early stopping.  The loader here serves
-tensor datasets (uint8 images + labels in the reference's collate layout) or the synthetic VisDrone-shaped set of SURVEY §8(d).
+Out of scope: callbacks, plots.  The loader here serves tensor datasets (uint8 images + labels in the reference's collate
+layout), the synthetic VisDrone-shaped set of SURVEY §8(d), or a YOLO-format dataset YAML decoded once into that layout; with
+``device_augment`` the training batches go through Mosaic / RandomPerspective / RandomHSV / RandomFlip on the device (``AugmentLoader``).
 """
 from __future__ import annotations
 
@@ -58,10 +59,11 @@ def get_cfg(overrides: Optional[dict] = None) -> dict:
 
 
 # argument classes of the reference's check_cfg (ultralytics/cfg/__init__.py:147-236, 324-395), for the keys this path reads
-CFG_FLOAT_KEYS = frozenset({"warmup_epochs", "box", "cls", "dfl", "time", "batch"})  # int or float
-CFG_FRACTION_KEYS = frozenset({"lr0", "lrf", "momentum", "weight_decay", "warmup_momentum", "warmup_bias_lr", "conf", "iou"})  # 0.0 <= v <= 1.0
-CFG_INT_KEYS = frozenset({"epochs", "patience", "seed", "max_det", "nbs"})
-CFG_BOOL_KEYS = frozenset({"save", "verbose", "single_cls", "half", "agnostic_nms", "stream", "amp", "multi_scale"})
+CFG_FLOAT_KEYS = frozenset({"warmup_epochs", "box", "cls", "dfl", "time", "batch", "degrees", "shear"})  # int or float
+CFG_FRACTION_KEYS = frozenset({"lr0", "lrf", "momentum", "weight_decay", "warmup_momentum", "warmup_bias_lr", "conf", "iou", "hsv_h", "hsv_s", "hsv_v",
+                               "translate", "scale", "perspective", "flipud", "fliplr", "mosaic"})  # 0.0 <= v <= 1.0
+CFG_INT_KEYS = frozenset({"epochs", "patience", "seed", "max_det", "nbs", "close_mosaic"})
+CFG_BOOL_KEYS = frozenset({"save", "verbose", "single_cls", "half", "agnostic_nms", "stream", "amp", "multi_scale", "device_augment"})
 
 
 def check_cfg(cfg: dict, hard: bool = True) -> None:
@@ -220,7 +222,8 @@ def synthetic_dataset(n: int, imgsz: int, seed: int, nc: int = 10) -> Dict[str, 
 
 def load_dataset(data, imgsz: int, nc: int, seed: int) -> Dict[str, torch.Tensor]:
     """``data``: a dict / a ``.pt`` file of tensors ``img`` (N,3,H,W) uint8, ``batch_idx`` (M,), ``cls`` (M,1), ``bboxes`` (M,4
-    normalised xywh) — the reference's collate layout (data/dataset.py:232-248) over the whole set — or ``"synthetic[:N]"``."""
+    normalised xywh) — the reference's collate layout (data/dataset.py:232-248) over the whole set — or ``"synthetic[:N]"``, or a
+    YOLO-format dataset YAML (``load_yaml_dataset``: decoded once into the same tensor layout)."""
     if isinstance(data, dict):
         d = data
     elif isinstance(data, str) and data.startswith("synthetic"):
@@ -228,14 +231,115 @@ def load_dataset(data, imgsz: int, nc: int, seed: int) -> Dict[str, torch.Tensor
         d = synthetic_dataset(n, imgsz, seed=1000 + seed, nc=nc)
     elif isinstance(data, (str, Path)) and str(data).endswith(".pt"):
         d = torch.load(str(data), map_location="cpu", weights_only=True)
+    elif isinstance(data, (str, Path)) and str(data).endswith((".yaml", ".yml")):
+        if not imgsz:  # the argument check of DetectionTrainer.__init__: the file must exist; it is decoded when training is set up
+            if not os.path.isfile(str(data)):
+                raise DatasetNotFoundError(f"data={str(data)!r}: dataset YAML not found")
+            return {}
+        d = load_yaml_dataset(str(data), imgsz)
     else:
-        raise NotImplementedError(f"data={data!r}: tensor datasets (.pt / dict) and 'synthetic[:N]' are built; image folders and dataset YAMLs "
-                                  "(decoding, mosaic, augmentation) are outside the accelerated path")
+        raise NotImplementedError(f"data={data!r}: tensor datasets (.pt / dict), 'synthetic[:N]' and YOLO-format dataset YAMLs are built; bare image "
+                                  "folders, video and rectangular training are outside the accelerated path")
     missing = {"img", "batch_idx", "cls", "bboxes"} - set(d)
     if missing:
         raise KeyError(f"dataset lacks {sorted(missing)}")
     if d["img"].dtype != torch.uint8 or d["img"].dim() != 4:
         raise ValueError("dataset 'img' must be uint8 (N, 3, H, W)")
+    return d
+
+
+class DatasetNotFoundError(FileNotFoundError, NotImplementedError):
+    """``data`` names a dataset YAML (or something inside one) that does not exist.  Also a NotImplementedError: until dataset YAMLs were built
+    every such name was refused with that type before any device work, and callers that catch it keep working."""
+
+
+IMG_FORMATS = (".bmp", ".jpeg", ".jpg", ".png", ".tif", ".tiff", ".webp")  # of data/utils.py:39 the ones PIL decodes here
+
+
+def _host_memory_available() -> int:
+    try:
+        with open("/proc/meminfo") as f:
+            for line in f:
+                if line.startswith("MemAvailable:"):
+                    return int(line.split()[1]) * 1024
+    except OSError:
+        pass
+    return os.sysconf("SC_PAGE_SIZE") * os.sysconf("SC_PHYS_PAGES")
+
+
+def _yaml_split(root: Path, entry, imgsz: int, what: str, budget: int) -> Dict[str, torch.Tensor]:
+    """One split of a dataset YAML as tensors.  Images under ``images/...``, labels under the parallel ``labels/... .txt`` (rows
+    ``cls cx cy w h``, data/utils.py:46-49); decoded with PIL (RGB), resized so that the long side equals ``imgsz`` (the size rule of
+    BaseDataset.load_image, data/base.py:160-166; PIL bilinear), stored centred on a 114-filled (imgsz, imgsz) square with ``rect`` =
+    (top, left, h, w) of the valid region and the labels re-normalised to the square."""
+    from PIL import Image
+
+    files: List[str] = []
+    for e in entry if isinstance(entry, (list, tuple)) else [entry]:
+        d = Path(e) if os.path.isabs(str(e)) else root / str(e)
+        if not d.is_dir():
+            raise DatasetNotFoundError(f"dataset YAML: '{what}' directory {d} does not exist")
+        files += sorted(str(f) for f in d.rglob("*.*") if f.suffix.lower() in IMG_FORMATS)
+    if not files:
+        raise DatasetNotFoundError(f"dataset YAML: no images under {entry!r} of {root}")
+    s = int(imgsz)
+    need = len(files) * 3 * s * s
+    if need > budget:
+        raise MemoryError(f"dataset YAML: '{what}' holds {len(files)} images = {need / 2**30:.2f} GiB as uint8 ({s} x {s}), more than the {budget / 2**30:.2f} GiB "
+                          "of host memory this loader may take (half of what is available); a tensor dataset on disk (.pt) or a smaller imgsz is needed")
+    img = np.full((len(files), 3, s, s), 114, dtype=np.uint8)
+    rect = np.zeros((len(files), 4), dtype=np.int32)
+    bi, cls, boxes = [], [], []
+    sa, sb = f"{os.sep}images{os.sep}", f"{os.sep}labels{os.sep}"
+    for i, f in enumerate(files):
+        with Image.open(f) as im:
+            im = im.convert("RGB")
+            w0, h0 = im.size
+            r = s / max(h0, w0)
+            w, h = (min(math.ceil(w0 * r), s), min(math.ceil(h0 * r), s)) if r != 1 else (w0, h0)
+            if (w, h) != (w0, h0):
+                im = im.resize((w, h), Image.BILINEAR)
+            a = np.asarray(im, dtype=np.uint8)
+        top, left = int(round((s - h) / 2 - 0.1)), int(round((s - w) / 2 - 0.1))
+        img[i, :, top : top + h, left : left + w] = a.transpose(2, 0, 1)
+        rect[i] = (top, left, h, w)
+        lf = sb.join(f.rsplit(sa, 1)).rsplit(".", 1)[0] + ".txt"
+        if os.path.isfile(lf):
+            with open(lf) as fh:
+                rows = [ln.split() for ln in fh.read().strip().splitlines() if ln.strip()]
+            if rows:
+                lb = np.array(rows, dtype=np.float32)
+                if lb.shape[1] != 5:
+                    raise ValueError(f"{lf}: label rows must be 'cls cx cy w h' (segments and keypoints are not built)")
+                lb[:, 1] = (lb[:, 1] * w + left) / s
+                lb[:, 2] = (lb[:, 2] * h + top) / s
+                lb[:, 3] = lb[:, 3] * w / s
+                lb[:, 4] = lb[:, 4] * h / s
+                bi.append(np.full((len(lb),), float(i), dtype=np.float32)), cls.append(lb[:, :1]), boxes.append(lb[:, 1:])
+    cat = lambda xs, shape: torch.from_numpy(np.concatenate(xs, 0) if xs else np.zeros(shape, dtype=np.float32))  # noqa: E731
+    return dict(img=torch.from_numpy(img), batch_idx=cat(bi, (0,)), cls=cat(cls, (0, 1)), bboxes=cat(boxes, (0, 4)), rect=torch.from_numpy(rect))
+
+
+def load_yaml_dataset(path: str, imgsz: int) -> Dict[str, torch.Tensor]:
+    """A YOLO-format dataset YAML (``path``, ``train``, ``val``, ``names``; data/utils.py ``check_det_dataset``) as the ordinary tensor
+    dataset with a ``val`` split of the same form.  No cache on disk, no corrupt-image recovery, no rectangular training, no video."""
+    import yaml
+
+    if not os.path.isfile(path):
+        raise DatasetNotFoundError(f"data={path!r}: dataset YAML not found")
+    with open(path) as f:
+        y = yaml.safe_load(f) or {}
+    for k in ("train", "val", "names"):
+        if k not in y:
+            raise KeyError(f"{path}: dataset YAML lacks '{k}'")
+    root = Path(y.get("path") or ".")
+    if not root.is_absolute():
+        root = Path(path).resolve().parent / root
+    budget = _host_memory_available() // 2
+    d = _yaml_split(root, y["train"], imgsz, "train", budget)
+    d["val"] = _yaml_split(root, y["val"], imgsz, "val", budget - d["img"].numel())
+    names = y["names"]
+    d["names"] = dict(enumerate(names)) if isinstance(names, (list, tuple)) else {int(k): v for k, v in names.items()}
     return d
 
 
@@ -281,6 +385,88 @@ class TensorLoader:
             rows = torch.cat(rows) if rows else torch.zeros(0, dtype=torch.long)
             yield dict(img=self.d["img"][take], batch_idx=torch.cat(bi) if bi else torch.zeros(0), cls=self.d["cls"][rows].view(-1, 1).float(),
                        bboxes=self.d["bboxes"][rows].float())
+
+
+class AugmentLoader(TensorLoader):
+    """``TensorLoader`` whose batches are augmented on the device (``device_augment: true``): a batch is B output samples; the table of
+    dy_augment_u8_nchw and the labels are built on the host with numpy (data/augment.py ``DeviceAugment``), the pixels by one kernel launch.
+    The dataset's ``img`` tensor is moved to the device once when it fits ``resident_fraction`` of the free device memory; otherwise the
+    unique source images of each batch are uploaded and the table's indices remapped — the same kernel and the same bytes either way.
+    ``close_mosaic`` (engine/trainer.py:338-356 of the reference): the four-image branch is off from epoch ``epochs - close_mosaic`` on;
+    the switch is a function of the epoch alone, so a resumed run starts on the right side of it.
+    ``out_provider(b)``: an optional resident (b, 3, S, S) uint8 tensor to write into (the graphed step's ``static_image()``)."""
+
+    resident_fraction = 0.5
+
+    def __init__(self, data, batch: int, args: dict, imgsz: int, device, epochs: int, rank: int = 0, world: int = 1, seed: int = 0, shuffle: bool = True,
+                 resident: Optional[bool] = None, out_provider=None):
+        super().__init__(data, batch, rank, world, seed, shuffle)
+        from ..data.augment import DeviceAugment
+
+        self.s, self.device, self.epochs, self.close_mosaic = int(imgsz), torch.device(device), int(epochs), int(args.get("close_mosaic") or 0)
+        np_data = {k: data[k].numpy() if isinstance(data[k], torch.Tensor) else data[k] for k in ("img", "batch_idx", "cls", "bboxes")}
+        if data.get("rect") is not None:
+            np_data["rect"] = data["rect"].numpy() if isinstance(data["rect"], torch.Tensor) else data["rect"]
+        self.aug = DeviceAugment(args, imgsz, np_data, seed=seed)
+        self._img_np = np_data["img"]
+        if resident is None:
+            free, _ = torch.cuda.mem_get_info(self.device)
+            resident = data["img"].numel() <= self.resident_fraction * free
+        self.resident = bool(resident)
+        self._src = data["img"].contiguous().to(self.device) if self.resident else None
+        self.out_provider = out_provider
+        self.last_table = None  # the table of the batch produced last (numpy, AUG_ROW_DTYPE): what was drawn, for logs and tests
+        self._ring = None  # pinned host copies of the table (see _upload_table)
+
+    def mosaic_on(self) -> bool:
+        return self.close_mosaic <= 0 or self.epoch < self.epochs - self.close_mosaic
+
+    def label_capacity(self) -> int:
+        """Rows per image the step's static label table needs at most, in its granularity of 64 rows."""
+        from ..data.augment import MAX_LABEL_ROWS
+
+        return min(max(-(-self.aug.label_bound() // 64) * 64, 128), MAX_LABEL_ROWS)
+
+    def _upload_table(self, table: np.ndarray) -> torch.Tensor:
+        """The table on the device through a ring of three PINNED host buffers and one asynchronous copy each — the label table's finding
+        (``_forward_backward``): a copy from pageable memory returns only when it has run, i.e. after the previous step's whole graph."""
+        from ..data.augment import AUG_ROW_DTYPE
+
+        rows, width = len(table), AUG_ROW_DTYPE.itemsize
+        ring = self._ring
+        if ring is None or ring["rows"] < rows:
+            ring = self._ring = dict(rows=max(rows, self.batch), at=0, events=[None] * 3,
+                                     bufs=[torch.zeros((max(rows, self.batch), width), dtype=torch.uint8).pin_memory() for _ in range(3)])
+        k = ring["at"]
+        ring["at"] = (k + 1) % 3
+        if ring["events"][k] is not None:
+            ring["events"][k].synchronize()  # the copy that last read this buffer (three batches ago)
+        host = ring["bufs"][k][:rows]
+        host.numpy()[:] = table.view(np.uint8).reshape(rows, width)
+        dev = host.to(self.device, non_blocking=True)
+        ev = ring["events"][k] = ring["events"][k] or torch.cuda.Event()
+        ev.record()
+        return dev
+
+    def __iter__(self) -> Iterator[Dict[str, torch.Tensor]]:
+        from .. import hip_ops as H
+
+        idx, on = self.indices(), self.mosaic_on()
+        for s in range(0, len(idx), self.batch):
+            take = idx[s : s + self.batch]
+            if self.resident:
+                src, remap = self._src, None
+            else:
+                uniq = self.aug.sources_of(self.epoch, take, on)
+                remap = {i: k for k, i in enumerate(uniq)}
+                src = torch.from_numpy(self._img_np[uniq]).to(self.device, non_blocking=True)
+            table, lab = self.aug.build(self.epoch, take, on, remap)
+            self.last_table = table
+            out = self.out_provider(len(take)) if self.out_provider is not None else None
+            if out is not None and (tuple(out.shape) != (len(take), 3, self.s, self.s) or out.dtype != torch.uint8):
+                out = None
+            img = H.augment_batch(src, self._upload_table(table), self.s, out=out)
+            yield dict(img=img, batch_idx=torch.from_numpy(lab["batch_idx"]), cls=torch.from_numpy(lab["cls"]), bboxes=torch.from_numpy(lab["bboxes"]))
 
 
 # ---- optimizer selection and schedules (host logic only) -------------------------------------------------------------------
@@ -340,6 +526,12 @@ class DetectionTrainer:
         data = a.get("data")
         if isinstance(data, (str, Path)) and not (str(data).startswith("synthetic") or str(data).endswith(".pt")):
             load_dataset(data, 0, 0, 0)  # raises NotImplementedError naming what is built, before any device work
+        if not a.get("device_augment"):
+            from ..data.augment import AUG_KEYS
+
+            ignored = sorted(k for k in AUG_KEYS if k in (overrides or {}))
+            if ignored:
+                LOGGER.info(f"augmentation argument(s) {ignored} have no effect without device_augment=True (the training batches are not augmented)")
         if not torch.cuda.is_available():
             raise RuntimeError("training needs an MI355X: no HIP device visible and this path has no CPU fallback")
         self.rank, self.local_rank, self.world = P.dist_env()
@@ -778,6 +970,13 @@ class DetectionTrainer:
         g = getattr(self, "_graph", None)
         return None if g is None else g["img"]
 
+    def _static_image_for(self, b: int) -> Optional[torch.Tensor]:
+        """``static_image()`` when it is the uint8 batch of ``b`` images the graphed step reads next (the augmenting loader writes there)."""
+        t = self.static_image()
+        if t is None or t.shape[0] != b or t.dtype != torch.uint8 or self.args.get("multi_scale"):
+            return None
+        return t
+
     def _unit_seed(self, loss: torch.Tensor) -> torch.Tensor:
         """ones_like(loss), allocated once (the seed autograd would create per call; a device fp32 scalar the head-gradient kernel reads)."""
         u = self.__dict__.get("_unit")
@@ -866,7 +1065,15 @@ class DetectionTrainer:
             self.iterations_hint = math.ceil(data["img"].shape[0] / max(int(a["batch"]), a["nbs"])) * self.epochs
             self._setup_model_state()
         per_rank = max(self.batch_size // max(world, 1), 1)  # trainer.py:286
-        self.train_loader = TensorLoader(data, per_rank, self.rank if world > 1 else 0, max(world, 1), seed=int(a.get("seed", 0)))
+        if a.get("device_augment"):
+            self.train_loader = AugmentLoader(data, per_rank, a, int(a["imgsz"]), self.device, self.epochs, self.rank if world > 1 else 0, max(world, 1),
+                                              seed=int(a.get("seed", 0)), out_provider=self._static_image_for)
+            # a mosaic carries up to four images' boxes: the static label table of the training shape starts at the loader's bound, so the
+            # step is captured once instead of again whenever a batch's largest count crosses a multiple of 64 (_forward_backward)
+            shape_key = ((per_rank, 3, int(a["imgsz"]), int(a["imgsz"])), torch.uint8, self.model.train_dtype)
+            self.__dict__.setdefault("_graph_caps", {})[shape_key] = self.train_loader.label_capacity()
+        else:
+            self.train_loader = TensorLoader(data, per_rank, self.rank if world > 1 else 0, max(world, 1), seed=int(a.get("seed", 0)))
         if self.rank == 0:
             self.wdir.mkdir(parents=True, exist_ok=True)
             if a.get("val", True):

@@ -1517,6 +1517,26 @@ def scale_img(img: torch.Tensor, ratio: float, gs: int = 32, flip_lr: bool = Fal
     return out
 
 
+def augment_batch(src: torch.Tensor, table: torch.Tensor, s: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Mosaic + affine / perspective warp + HSV + flips of a training batch in one ``dy_augment_u8_nchw`` launch.  src: device uint8
+    (N, 3, Hs, Ws) source images (channel 0 = R); table: device uint8 (B, sizeof(dy_aug_row)) rows built by ``data.augment.DeviceAugment``;
+    returns (or fills ``out``) the uint8 (B, 3, s, s) batch the image stem reads."""
+    require_device(src, "augmentation sources")
+    require_device(table, "augmentation table")
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[1] != 3 or not src.is_contiguous():
+        raise ValueError("augment_batch expects contiguous uint8 (N, 3, Hs, Ws) sources")
+    if table.dtype != torch.uint8 or table.dim() != 2 or table.shape[1] != C.sizeof(_lib.AugRow) or not table.is_contiguous() or table.device != src.device:
+        raise ValueError(f"augment_batch: table must be a contiguous uint8 (B, {C.sizeof(_lib.AugRow)}) tensor on the sources' device")
+    b, s = int(table.shape[0]), int(s)
+    if out is None:
+        out = torch.empty((b, 3, s, s), dtype=torch.uint8, device=src.device)
+    elif tuple(out.shape) != (b, 3, s, s) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != src.device:
+        raise ValueError(f"augment_batch: out must be a contiguous uint8 ({b}, 3, {s}, {s}) tensor on the sources' device")
+    n, _, hs, ws = src.shape
+    _launch(lib().dy_augment_u8_nchw, (src.data_ptr(), table.data_ptr(), out.data_ptr(), n, hs, ws, b, s), keep=(src, table, out))
+    return out
+
+
 # ---- fused C2f block ------------------------------------------------------------------------------------------------------
 
 

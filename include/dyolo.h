@@ -656,6 +656,38 @@ int32_t dy_amp_update(float* amp_state, const double* grad_sumsq, float growth_f
 int32_t dy_ema_update(float* ema, const float* p, int64_t n, float decay, dy_stream_t stream);
 int32_t dy_grad_sink_flush(const int64_t* entries, int32_t n_entries, float* grad, float* sink, dy_stream_t stream);
 
+/* ---- training augmentation on the device (Mosaic + RandomPerspective + RandomHSV + RandomFlip, ultralytics/data/augment.py:490-864,
+ * 952-1300, 1303-1390, 1392-1483) -----------------------------------------------------------------
+ * dy_augment_u8_nchw: uint8 source images (n_src_imgs, 3, hs, ws) (channel 0 = R) -> ONE augmented uint8 NCHW batch (batch, 3, s, s),
+ * what dy_stem_conv3x3s2_nchw_u8 reads.  `table` (DEVICE, one dy_aug_row per output image) holds what the host drew:
+ *   n_src = 4: the rectangles of Mosaic._mosaic4 (augment.py:684-708) -- src[i].index's pixels [y1b.., x1b..] pasted at
+ *              [y1a:y2a, x1a:x2a] of a ch x cw canvas filled with 114;  n_src = 1: one image on its canvas (the LetterBox pre_transform);
+ *   minv:      inverse of M = T S R P C (RandomPerspective.affine_transform, augment.py:1041-1071), row-major, output pixel -> canvas;
+ *   hsv:       the three offsets r of RandomHSV.__call__ (augment.py:1379-1384); flags: DY_AUG_FLIPLR | DY_AUG_FLIPUD | DY_AUG_HSV_OFF.
+ * Per output pixel: undo the flips, (u, v) = minv (x, y, 1) with the perspective divide, the four bilinear neighbours ON THE CANVAS (a
+ * neighbour is the pixel of the source rectangle that covers it, else 114; outside the canvas 114 = borderValue), blended in fp32, rounded
+ * to nearest; then RGB -> (H in [0,180), S, V in [0,255]) rounded to integers, H' = trunc((H + r0) mod 180), S' = S ? trunc(clip(S + r1, 0,
+ * 255)) : 0, V' = trunc(clip(V + r2, 0, 255)), back to RGB, rounded.  The canvas is never materialised.  s % 4 == 0 (one thread writes four
+ * pixels of a plane as one 32-bit word).  A row whose n_src is not 1 or 4, or a source whose index is outside [0, n_src_imgs) or whose
+ * pixel lies outside hs x ws, reads nothing and yields 114 there. */
+#define DY_AUG_FLIPLR 1
+#define DY_AUG_FLIPUD 2
+#define DY_AUG_HSV_OFF 4
+typedef struct dy_aug_src {
+  int32_t index;              /* image of the source tensor */
+  int32_t x1a, y1a, x2a, y2a; /* destination rectangle on the canvas (exclusive end) */
+  int32_t x1b, y1b;           /* source pixel that lands on (x1a, y1a) */
+  int32_t reserved;
+} dy_aug_src;
+typedef struct dy_aug_row {
+  int32_t n_src, ch, cw, flags;
+  dy_aug_src src[4];
+  float minv[9];
+  float hsv[3];
+} dy_aug_row;
+int32_t dy_augment_u8_nchw(const uint8_t* src, const dy_aug_row* table, uint8_t* dst, int32_t n_src_imgs, int32_t hs, int32_t ws, int32_t batch,
+                           int32_t s, dy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
