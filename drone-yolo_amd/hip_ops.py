@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import os
 import warnings
@@ -202,20 +202,18 @@ def _launch(fn, args: tuple, keep: Sequence[object] = (), record: bool = True) -
 # ---- convolution --------------------------------------------------------------------------------
 
 
-def _pad_to(t: torch.Tensor, shape) -> torch.Tensor:
-    """``t`` (fp32) zero-padded at the end of every dim to ``shape``; ``t`` itself when nothing is to pad (no kernel)."""
-    if tuple(t.shape) == tuple(shape):
-        return t
-    out = torch.zeros(shape, dtype=t.dtype, device=t.device)
+def _zero_padded(t: torch.Tensor, n_elems: int, shape) -> torch.Tensor:
+    """``t`` zero-padded at the end of every dim to ``shape``: ``n_elems`` elements (a packed image is sized by its plan)."""
+    out = torch.zeros(n_elems, dtype=t.dtype, device=t.device).view(shape)
     out[tuple(slice(0, n) for n in t.shape)] = t
     return out
 
 
-def _permute_cast(view: torch.Tensor, dtype: torch.dtype, device) -> torch.Tensor:
-    """Contiguous copy of a permuted view in ``dtype`` — one copy kernel for layout change + cast."""
-    out = torch.empty(view.shape, dtype=dtype, device=view.device)
+def _permute_cast(view: torch.Tensor, dtype: torch.dtype, n_elems: int) -> torch.Tensor:
+    """Contiguous copy of a permuted view, ``n_elems`` elements of ``dtype``, flat — one copy kernel for layout change + cast."""
+    out = torch.empty(n_elems, dtype=dtype, device=view.device).view(view.shape)
     out.copy_(view)
-    return out.view(-1).to(device)
+    return out.view(-1)
 
 
 _ZERO_BIAS = {}
@@ -343,8 +341,8 @@ class PackCache:
 
 
 _PACK_CACHE = {"active": None}
-HREG_128 = [os.environ.get("DYOLO_HREG_128", "1") != "0"]  # see PackedConv: 128-channel 3x3 layers on the register-weight kernel (0: the virtual-flat GEMM, for A/B runs)
-FLAT_K_3X3 = [os.environ.get("DYOLO_FLAT_K_3X3", "1") != "0"]  # see PackedConv: odd-width 3x3 layers on the flat-K kernel (0: the halo kernel, for A/B runs)
+HREG_128 = [os.environ.get("DYOLO_HREG_128", "1") != "0"]  # see conv_pack_plan: 128-channel 3x3 layers on the register-weight kernel (0: the virtual-flat GEMM, for A/B runs)
+FLAT_K_3X3 = [os.environ.get("DYOLO_FLAT_K_3X3", "1") != "0"]  # see conv_pack_plan: odd-width 3x3 layers on the flat-K kernel (0: the halo kernel, for A/B runs)
 
 
 @contextlib.contextmanager
@@ -358,12 +356,185 @@ def batched_weight_packing(cache: Optional[PackCache]):
         _PACK_CACHE["active"] = prev
 
 
+class ConvPackPlan(NamedTuple):
+    """What ``conv_pack_plan`` decides for one convolution: the weight layout and the geometry of the packed image."""
+    layout: int   # DY_WLAYOUT_* (include/dyolo.h)
+    cin: int      # logical input channels (zero-padded ones included)
+    k_pad: int    # DY_WLAYOUT_ROWS: elements per row; 0 in the fragment layouts
+    cout_pad: int  # entries of the padded bias (and rows of a DY_WLAYOUT_ROWS image)
+    groups: int
+    e: int        # elements per 16-byte chunk; the tile geometry below is 0 in DY_WLAYOUT_ROWS
+    kc: int       # input channels per K chunk (4 * e)
+    bn: int       # output channels per tile
+    nt: int       # cout tiles
+    nch: int      # K chunks (HALO3X3) / K groups (FRAG1X1) of kc channels
+    n_elems: int  # elements of the packed image, in the storage type
+
+
+def _frag1x1_plan(cout: int, cin: int, dtype: torch.dtype, cout_pad: int = 0) -> ConvPackPlan:
+    """DY_WLAYOUT_FRAG1X1 geometry: the tile width follows from cout alone; the bias covers whole tiles (and ``cout_pad`` at least)."""
+    e = elems_per_chunk(dtype)
+    kc, bn = 4 * e, (128 if cout > 64 else (64 if cout > 16 else 16))
+    nt, nkg = -(-cout // bn), -(-cin // kc)
+    return ConvPackPlan(_lib.DY_WLAYOUT_FRAG1X1, cin, 0, max(cout_pad, nt * bn), 1, e, kc, bn, nt, nkg, nt * nkg * (bn // 16) * 64 * e)
+
+
+def conv_pack_plan(cout: int, cin: int, k: int, stride: int, pad: int, groups: int, act_code: int, dtype: torch.dtype,
+                   halo: Optional[bool] = None, for_out_f32: bool = False) -> ConvPackPlan:
+    """This shape -> this weight layout, this geometry: the one place that decides which kernel family a convolution is packed for.
+    Integers and flags only.  ``cin``: the logical input channels — after ``cin_pad``, and for dense split float16 rounded up to 8;
+    ``halo`` / ``for_out_f32``: as for ``PackedConv``.  Host and device packers both size their image by ``n_elems``."""
+    if groups != 1:
+        if dtype == F16X2 and (cout != groups or cin // groups not in (1, 2, 4) or cout % 8):
+            # DWConv of the -sf YAML: the small-group kernel multiplies joined fp32 inputs by fp32 weights (rows [cout][taps][cin / groups])
+            raise NotImplementedError("split-float16 storage of a grouped convolution: one output channel per group, 1 / 2 / 4 inputs each, cout % 8 == 0")
+        if dtype == FP8:
+            raise NotImplementedError("fp8 storage is built for dense convolutions")
+        k_pad = k * k * (cin // groups)  # grouped rows carry no padding
+        return ConvPackPlan(_lib.DY_WLAYOUT_ROWS, cin, k_pad, cout, groups, 0, 0, 0, 0, 0, cout * k_pad)
+    L = lib()
+    k_pad, cout_pad = L.dy_conv_k_pad(cin, k, dy_dtype(dtype)), L.dy_conv_cout_pad(cout)
+    rows = ConvPackPlan(_lib.DY_WLAYOUT_ROWS, cin, k_pad, cout_pad, 1, 0, 0, 0, 0, 0, cout_pad * k_pad)
+    if dtype in (F16X2, FP8):  # rows layout only
+        return rows
+    # stride-2 halo tiles are 17x33 pixels (2 x 45 KB of LDS): only a weight set of <= 36 KB fits beside them
+    s2_fits = cin <= 4 * elems_per_chunk(dtype) and cout > 32 or cin <= 8 * elems_per_chunk(dtype) and cout <= 32
+    # r03: the 64-channel downsampling layers run on the register-weight stride-2 kernel (conv3x3_hreg_s2), same fragment layout
+    s2_fits = s2_fits or (dtype in (torch.bfloat16, torch.float16) and cin == 64 and cout % 64 == 0 and cout <= 256 and halo is not False)
+    # deep 3x3 layers (small maps, weight sets far beyond LDS) run faster as a flat-M implicit GEMM on the LDS-DMA
+    # big-tile kernel behind DY_WLAYOUT_ROWS (conv_gemm_glds.hip): measured at batch 128, 256->256 @20x20 90 vs 162 us
+    kstep = 8 * elems_per_chunk(dtype)
+    # r04: 128 input channels fit the register-weight kernel too (four 32-channel chunks: 144 weight registers, two workgroups per CU):
+    # 128->128 @40x40 149 -> 136 us, @80x80 543 -> 437 us (1,100 TFLOP/s) at B = 256 against the virtual-flat GEMM
+    # r05: bf16 INFERENCE packs stay on the virtual-flat GEMM: the four-chunk summation order moved the s640 fixture's worst bf16 box from
+    # IoU 0.9981 to 0.9979, under the 0.998 floor of tests/test_model_gpu.py, and the floor is not what gives way (ADVICE r4); fp16 -- the
+    # 16-bit inference dtype, 8x finer -- did not move, and the raw convolutions of a training step (no activation: BatchNorm follows) keep
+    # the kernel for its statistics epilogue
+    hreg128 = HREG_128[0] and halo is None and k == 3 and stride == 1 and pad == 1 and groups == 1 and \
+        (dtype == torch.float16 or (dtype == torch.bfloat16 and act_code == 0)) and cin == 128 and cout % 64 == 0 and cout <= 256
+    deep3x3 = halo is None and k == 3 and stride == 1 and cin % kstep == 0 and cout % 64 == 0 and \
+        cin >= 128 and cout >= 128 and not hreg128
+    # (r04: deep layers whose cout is no multiple of 128 — scale x: 320 -> 320 — take the flat-K kernel's 160-wide tiles behind the same
+    # layout (csrc/conv_igemm.hip: fk_first): 19.09 -> 18.68 ms per x1536 pass against the halo kernel, 536 -> 860 TFLOP/s against the
+    # 64-cout persistent tiles of the tap-aligned kernel)
+    # r04: 3x3 layers whose channel counts are not whole 64-channel K-steps / 64-cout tiles (the n / m / x scales: 80, 160, 320 ...)
+    # run on the flat-K LDS-DMA kernel behind DY_WLAYOUT_ROWS (conv_gemm_fk.hip) instead of the halo kernel's 32-channel chunks
+    flat3x3 = FLAT_K_3X3[0] and halo is None and k == 3 and pad == 1 and groups == 1 and dtype in (torch.bfloat16, torch.float16) and \
+        cin >= 64 and (cin % 64 != 0 or cout % 64 != 0) and cin % 8 == 0 and cout % 8 == 0
+    if (halo is None or halo) and not deep3x3 and not flat3x3 and groups == 1 and k == 3 and pad == 1 and (stride == 1 or (stride == 2 and s2_fits)) \
+            and cout % 4 == 0 and cin >= 4 * elems_per_chunk(dtype) // 2:
+        # LDS-halo 3x3 kernel: MFMA-fragment-ordered weights (include/dyolo.h, DY_WLAYOUT_HALO3X3)
+        e = elems_per_chunk(dtype)
+        kc, bn = 4 * e, (64 if cout > 32 else 32)
+        nt, nch = -(-cout // bn), -(-cin // kc)
+        return ConvPackPlan(_lib.DY_WLAYOUT_HALO3X3, cin, 0, cout_pad, 1, e, kc, bn, nt, nch, nt * nch * 9 * (bn // 16) * 64 * e)
+    frag = _frag1x1_plan(cout, cin, dtype, cout_pad)
+    e, bn, nkg = frag.e, frag.bn, frag.nch
+    frag_ok = nkg in (2, 3, 4, 6, 8, 12) and (cout > 16 or nkg == 2) and cin % e == 0
+    if for_out_f32 and dtype != torch.float32:
+        frag_ok = frag_ok and nkg == 2 and cout <= 64
+    if frag_ok:  # the streaming kernel's LDS footprint (conv1x1_stream.hip::launch_1x1) must fit 160 KB
+        osz = 4 if (for_out_f32 or dtype == torch.float32) else 2
+        smem = nkg * (bn // 16) * 1024 + bn * 4 + 8 * (2 if nkg <= 2 else 1) * 16 * (bn * osz + 16)
+        frag_ok = smem <= 160 * 1024
+    if (halo is None or halo) and groups == 1 and k == 1 and stride == 1 and pad == 0 and frag_ok:
+        # streaming 1x1 kernel: fragment-ordered weights, single tap (include/dyolo.h, DY_WLAYOUT_FRAG1X1)
+        return frag
+    return rows
+
+
+def _split_f16x2(rows: torch.Tensor):
+    """The split-float16 rule (include/dyolo.h, DY_F16X2), (hi, lo, inverse row scale) of fp32 ``rows``: every row (dim 0) times the power
+    of two that puts its largest weight in [2^13, 2^14) (exact; the inverse goes to w_scale and multiplies the accumulator), then
+    hi = rn_f16(w) — 0 below float16's smallest normal — and lo = rn_f16(w - hi), UNSCALED: the kernel multiplies x_hi by it directly and
+    forms w_hi 2^-11 for the x_lo term itself."""
+    amax = rows.abs().amax(tuple(range(1, rows.dim()))).clamp_min(1e-30)
+    sc = torch.exp2(13.0 - torch.floor(torch.log2(amax)))
+    ws = rows * sc.view(-1, *([1] * (rows.dim() - 1)))
+    hi = torch.where(ws.abs() < 2.0 ** -14, torch.zeros_like(ws), ws).to(torch.float16)
+    lo = (ws - hi.to(torch.float32)).to(torch.float16)
+    return hi, lo, 1.0 / sc
+
+
+def _padded_bias(bias: torch.Tensor, n: int, device) -> torch.Tensor:
+    """fp32 ``bias`` zero-padded to ``n`` entries on ``device``.  A training step must not pay a fill + copy per convolution: a bias that
+    already is fp32 on the GPU at that length is used as it is, the shared zeros (``zero_bias``: training, gradient convolutions) stay
+    the shared zeros."""
+    if bias.numel() == n and bias.is_cuda and bias.dtype == torch.float32:
+        return bias.detach()
+    if bias is _ZERO_BIAS.get((bias.numel(), str(device))):
+        return zero_bias(n, device)
+    bp = torch.zeros((n,), dtype=torch.float32, device=device)
+    bp[: bias.numel()] = bias.detach().to(torch.float32).to(device)
+    return bp
+
+
+def _rows_image(weight: torch.Tensor, plan: ConvPackPlan, dtype: torch.dtype) -> torch.Tensor:
+    """DY_WLAYOUT_ROWS in a plain storage type: (cout, k, k, cin / groups) rows, zero padded to (cout_pad, k_pad)."""
+    if plan.groups == 1 and plan.n_elems == weight.numel():  # nothing to pad: one permute + cast kernel
+        return _permute_cast(weight.permute(0, 2, 3, 1), dtype, plan.n_elems)
+    rows = weight.to(torch.float32).permute(0, 2, 3, 1).reshape(weight.shape[0], -1)
+    if plan.n_elems != rows.numel():  # (grouped rows carry no padding)
+        rows = _zero_padded(rows, plan.n_elems, (plan.cout_pad, plan.k_pad))
+    return rows.to(dtype).contiguous()
+
+
+def _rows_image_fp8(weight: torch.Tensor, plan: ConvPackPlan, act_scale: float):
+    """DY_WLAYOUT_ROWS in e4m3 with one scale per OUTPUT channel (absmax -> 448): (image, scales); the epilogue multiplies the
+    accumulator by act_scale * weight_scale[co] (include/dyolo.h)."""
+    cout = weight.shape[0]
+    rows = weight.to(torch.float32).permute(0, 2, 3, 1).reshape(cout, -1)
+    ws = (rows.abs().amax(1) / 448.0).clamp_min(1e-12)
+    wp = _zero_padded(rows / ws[:, None], plan.n_elems, (plan.cout_pad, plan.k_pad))
+    return wp.to(FP8).contiguous(), torch.nn.functional.pad(ws * act_scale, (0, plan.cout_pad - cout), value=1.0)
+
+
+def _rows_image_split(weight: torch.Tensor, plan: ConvPackPlan):
+    """DY_WLAYOUT_ROWS in split float16: (image, inverse row scales).  K order (r, q, c), every 8 channels as [hi x 8 | lo x 8]:
+    4 bytes per element, carried as float16 pairs."""
+    cout, cin_g, k, _ = weight.shape
+    w = weight.to(torch.float32).permute(0, 2, 3, 1).reshape(cout, k * k, cin_g)
+    hi, lo, inv = _split_f16x2(torch.nn.functional.pad(w, (0, plan.cin - cin_g)))
+    pair = torch.stack((hi.reshape(cout, k * k, plan.cin // 8, 8), lo.reshape(cout, k * k, plan.cin // 8, 8)), 3)  # (cout, taps, groups, 2, 8)
+    wp = _zero_padded(pair.reshape(cout, -1), 2 * plan.n_elems, (plan.cout_pad, plan.k_pad * 2))
+    return wp, torch.nn.functional.pad(inv, (0, plan.cout_pad - cout), value=1.0)
+
+
+def _halo3x3_image(weight: torch.Tensor, p: ConvPackPlan, dtype: torch.dtype) -> torch.Tensor:
+    """DY_WLAYOUT_HALO3X3 (include/dyolo.h): MFMA-fragment order per (cout tile, K chunk, tap)."""
+    wpad = _zero_padded(weight.to(torch.float32), p.n_elems, (p.nt * p.bn, p.nch * p.kc, 3, 3))
+    return _permute_cast(wpad.reshape(p.nt, p.bn // 16, 16, p.nch, 4, p.e, 3, 3).permute(0, 3, 6, 7, 1, 4, 2, 5), dtype, p.n_elems)
+
+
+def _frag1x1_image(w2d: torch.Tensor, p: ConvPackPlan, dtype: torch.dtype) -> torch.Tensor:
+    """DY_WLAYOUT_FRAG1X1 (include/dyolo.h) of fp32 (cout, cin) weights: MFMA-fragment order per (cout tile, K group)."""
+    wpad = _zero_padded(w2d, p.n_elems, (p.nt * p.bn, p.nch * p.kc))
+    return wpad.view(p.nt, p.bn // 16, 16, p.nch, 4, p.e).permute(0, 3, 1, 4, 2, 5).contiguous().view(-1).to(dtype).contiguous()
+
+
+def _device_pack(src: torch.Tensor, transpose_flip: bool, cin_logical: int, plan: ConvPackPlan, dtype: torch.dtype) -> torch.Tensor:
+    """fp32 weights on the GPU -> the packed image in ONE ``dy_pack_conv_weights`` launch (layout + zero padding + cast, transpose + flip
+    for the input-gradient convolution), or this step's ``dy_pack_conv_weights_batched`` result when a ``PackCache`` is active."""
+    st = src.stride()
+    job = (src.data_ptr(), st[0], st[1], st[2], st[3], src.shape[0], src.shape[1], src.shape[2], int(transpose_flip), cin_logical, plan.layout, plan.n_elems)
+    cache = _PACK_CACHE["active"]
+    if cache is not None and cache.dtype == dtype and cache.lo <= job[0] < cache.hi:
+        hit = cache.lookup(job)
+        if hit is not None:  # packed by this step's dy_pack_conv_weights_batched launch
+            return hit
+        out = cache.slot(job, src)
+    else:
+        out = torch.empty(plan.n_elems, dtype=dtype, device=src.device)
+    _launch(lib().dy_pack_conv_weights, job[:10] + (out.data_ptr(), plan.n_elems, dy_dtype(dtype), plan.layout), record=False)
+    return out
+
+
 class PackedConv:
     """Folded + packed weights of one convolution in the layout ``dy_conv2d_nhwc`` expects.
 
     ``weight``: (cout, cin/groups, k, k) fp32 with BatchNorm / RepVGG branches already folded,
     ``bias``: (cout,) fp32.  Packing = (cout, k, k, cin) row-major, rows padded to k_pad, rows
-    count padded to cout_pad with zeros (include/dyolo.h).
+    count padded to cout_pad with zeros (include/dyolo.h); ``conv_pack_plan`` says which layers take a fragment layout instead.
     """
 
     def __init__(self, weight: torch.Tensor, bias: torch.Tensor, stride: int, pad: int, groups: int, act: bool,
@@ -373,201 +544,49 @@ class PackedConv:
         will be called with out_f32=True (Detect heads), which narrows the shapes the streaming kernel is built for.
         ``transpose_flip``: pack W'[ci][co][r][q] = weight[co][ci][k-1-r][k-1-q] (the input-gradient convolution) — device packing only.
         fp32 weights that already live on the device (training: the master weights, every step) are packed by ONE
-        ``dy_pack_conv_weights`` launch instead of the pad / permute / flip / cast chain below."""
-        L = lib()
-        # what a DY_WLAYOUT_ROWS pack of the same layer is built from (``rows()``: calls the special layout's kernels refuse)
-        self._rows_args = (weight, bias, stride, pad, groups, act, dtype, device, cin_pad, for_out_f32, transpose_flip)
-        self._rows_pack = None
+        ``dy_pack_conv_weights`` launch instead of the host packers' pad / permute / flip / cast chain."""
         dev_pack = weight.is_cuda and weight.dtype == torch.float32 and dtype not in (FP8, F16X2) and groups == 1 and weight.device == torch.device(device)
         if transpose_flip and not dev_pack:
             raise ValueError("PackedConv(transpose_flip=True) needs fp32 weights on the target device")
         self._src = weight if dev_pack else None
-        cin_logical = 0
-        if dev_pack:
-            src = weight.detach()
-            if cin_pad is not None and cin_pad > weight.shape[1]:
-                cin_logical = cin_pad
-            lshape = (src.shape[1], src.shape[0], src.shape[2], src.shape[3]) if transpose_flip else tuple(src.shape)
-            if cin_logical:
-                lshape = (lshape[0], cin_logical, lshape[2], lshape[3])
-            weight = torch.empty(lshape, device="meta")  # shape carrier for the layout decision below; data moves in _device_pack
-
-            def _device_pack(layout: int, n_elems: int) -> torch.Tensor:
-                st = src.stride()
-                job = (src.data_ptr(), st[0], st[1], st[2], st[3], src.shape[0], src.shape[1], src.shape[2], int(transpose_flip), cin_logical, layout, n_elems)
-                cache = _PACK_CACHE["active"]
-                if cache is not None and cache.dtype == dtype and cache.lo <= job[0] < cache.hi:
-                    hit = cache.lookup(job)
-                    if hit is not None:  # packed by this step's dy_pack_conv_weights_batched launch
-                        return hit
-                    out = cache.slot(job, src)
-                else:
-                    out = torch.empty(n_elems, dtype=dtype, device=src.device)
-                _launch(L.dy_pack_conv_weights, job[:10] + (out.data_ptr(), n_elems, dy_dtype(dtype), layout), record=False)
-                return out
-
-            def _device_bias(n: int) -> torch.Tensor:
-                if bias.numel() == n and bias.is_cuda and bias.dtype == torch.float32:
-                    return bias.detach()
-                if bias is _ZERO_BIAS.get((bias.numel(), str(src.device))):  # the shared zeros (training, gradient convolutions): no fill + copy per call
-                    return zero_bias(n, src.device)
-                bp = torch.zeros((n,), dtype=torch.float32, device=src.device)
-                bp[: bias.numel()] = bias.detach().to(torch.float32)
-                return bp
-        elif cin_pad is not None and cin_pad > weight.shape[1]:
-            # the input view carries zero-padded channels (the 3-channel image padded to one 16-byte chunk)
-            if groups != 1:
-                raise ValueError("cin_pad is only meaningful for dense convolutions")
-            weight = torch.nn.functional.pad(weight.detach().float(), (0, 0, 0, 0, 0, cin_pad - weight.shape[1]))
         cout, cin_g, k, k2 = weight.shape
-        wdev = weight.device  # pack where the weights live (CPU for inference setup, the GPU in training: no host round trip)
+        if transpose_flip:
+            cout, cin_g = cin_g, cout
         assert k == k2, "square kernels only"
-        self.cout, self.cin, self.k, self.stride, self.pad, self.groups = cout, cin_g * groups, k, stride, pad, groups
-        self.act = _act_code(act)  # bool (SiLU or none) or a dy_act code
-        self.dtype = dtype
-        self.layout = _lib.DY_WLAYOUT_ROWS
-        self.wscale, self.act_scale = None, 1.0
-        if dtype == F16X2:
-            # split float16 (include/dyolo.h, DY_F16X2): every output-channel row times the power of two that puts its largest weight in
-            # [2^13, 2^14) (exact; the inverse goes to w_scale and multiplies the accumulator), then hi = rn_f16(w) — 0 below float16's
-            # smallest normal — and lo = rn_f16(w - hi), UNSCALED: the kernel multiplies x_hi by it directly and forms w_hi 2^-11 for the
-            # x_lo term itself.  Row layout: K order (r, q, c), every 8 channels as [hi x 8 | lo x 8]: 4 bytes per element.
-            if groups != 1:
-                # DWConv of the -sf YAML: the small-group kernel multiplies joined fp32 inputs by fp32 weights (rows [cout][taps][cin / groups])
-                if cout != groups or cin_g not in (1, 2, 4) or cout % 8:
-                    raise NotImplementedError("split-float16 storage of a grouped convolution: one output channel per group, 1 / 2 / 4 inputs each, cout % 8 == 0")
-                self.w = weight.detach().to(torch.float32).permute(0, 2, 3, 1).reshape(cout, k * k * cin_g).contiguous().to(device)
-                self.b = bias.detach().to(torch.float32).contiguous().to(device)
-                self.k_pad, self.cout_pad = k * k * cin_g, cout
-                self._rows_args = None
-                return
-            w = weight.detach().to(torch.float32).permute(0, 2, 3, 1).reshape(cout, k * k, cin_g)
-            if cin_g % 8:
-                w = torch.nn.functional.pad(w, (0, 8 - cin_g % 8))
-            self.cin = w.shape[2]
-            amax = w.abs().amax((1, 2)).clamp_min(1e-30)
-            sc = torch.exp2(13.0 - torch.floor(torch.log2(amax)))
-            ws = w * sc[:, None, None]
-            hi = torch.where(ws.abs() < 2.0 ** -14, torch.zeros_like(ws), ws).to(torch.float16)
-            lo = (ws - hi.to(torch.float32)).to(torch.float16)
-            self.k_pad, self.cout_pad = L.dy_conv_k_pad(self.cin, k, dy_dtype(dtype)), L.dy_conv_cout_pad(cout)
-            pair = torch.stack((hi.reshape(cout, k * k, self.cin // 8, 8), lo.reshape(cout, k * k, self.cin // 8, 8)), 3)  # (cout, taps, groups, 2, 8)
-            wp = torch.zeros((self.cout_pad, self.k_pad * 2), dtype=torch.float16, device=wdev)
-            wp[:cout, : k * k * self.cin * 2] = pair.reshape(cout, -1)
-            bp = torch.zeros((self.cout_pad,), dtype=torch.float32, device=wdev)
-            bp[:cout] = bias.detach().to(torch.float32).to(wdev)
-            sp = torch.ones((self.cout_pad,), dtype=torch.float32, device=wdev)
-            sp[:cout] = 1.0 / sc
-            self.w, self.b, self.wscale = wp.contiguous().to(device), bp.contiguous().to(device), sp.contiguous().to(device)
-            self._rows_args = None
-            return
-        if dtype == FP8:
-            # e4m3 weights with one scale per OUTPUT channel (absmax -> 448), rows layout only; the epilogue multiplies the
-            # accumulator by act_scale * weight_scale[co] (include/dyolo.h)
-            if groups != 1:
-                raise NotImplementedError("fp8 storage is built for dense convolutions")
-            self.act_scale = fp8_act_scale()
-            w = weight.detach().to(torch.float32).permute(0, 2, 3, 1).reshape(cout, k * k * cin_g)
-            ws = (w.abs().amax(1) / 448.0).clamp_min(1e-12)
-            self.k_pad, self.cout_pad = L.dy_conv_k_pad(self.cin, k, dy_dtype(dtype)), L.dy_conv_cout_pad(cout)
-            wp = torch.zeros((self.cout_pad, self.k_pad), dtype=torch.float32, device=wdev)
-            wp[:cout, : w.shape[1]] = w / ws[:, None]
-            bp = torch.zeros((self.cout_pad,), dtype=torch.float32, device=wdev)
-            bp[:cout] = bias.detach().to(torch.float32).to(wdev)
-            sp = torch.ones((self.cout_pad,), dtype=torch.float32, device=wdev)
-            sp[:cout] = ws * self.act_scale
-            self.w = wp.to(FP8).contiguous().to(device)
-            self.b, self.wscale = bp.contiguous().to(device), sp.contiguous().to(device)
-            self._rows_args = None
-            return
-        # stride-2 halo tiles are 17x33 pixels (2 x 45 KB of LDS): only a weight set of <= 36 KB fits beside them
-        s2_fits = self.cin <= 4 * elems_per_chunk(dtype) and cout > 32 or self.cin <= 8 * elems_per_chunk(dtype) and cout <= 32
-        # r03: the 64-channel downsampling layers run on the register-weight stride-2 kernel (conv3x3_hreg_s2), same fragment layout
-        s2_fits = s2_fits or (dtype in (torch.bfloat16, torch.float16) and self.cin == 64 and cout % 64 == 0 and cout <= 256 and halo is not False)
-        # deep 3x3 layers (small maps, weight sets far beyond LDS) run faster as a flat-M implicit GEMM on the LDS-DMA
-        # big-tile kernel behind DY_WLAYOUT_ROWS (conv_gemm_glds.hip): measured at batch 128, 256->256 @20x20 90 vs 162 us
-        kstep = 8 * elems_per_chunk(dtype)
-        # r04: 128 input channels fit the register-weight kernel too (four 32-channel chunks: 144 weight registers, two workgroups per CU):
-        # 128->128 @40x40 149 -> 136 us, @80x80 543 -> 437 us (1,100 TFLOP/s) at B = 256 against the virtual-flat GEMM
-        # r05: bf16 INFERENCE packs stay on the virtual-flat GEMM: the four-chunk summation order moved the s640 fixture's worst bf16 box from
-        # IoU 0.9981 to 0.9979, under the 0.998 floor of tests/test_model_gpu.py, and the floor is not what gives way (ADVICE r4); fp16 -- the
-        # 16-bit inference dtype, 8x finer -- did not move, and the raw convolutions of a training step (no activation: BatchNorm follows) keep
-        # the kernel for its statistics epilogue
-        hreg128 = HREG_128[0] and halo is None and k == 3 and stride == 1 and pad == 1 and groups == 1 and \
-            (dtype == torch.float16 or (dtype == torch.bfloat16 and _act_code(act) == 0)) and self.cin == 128 and cout % 64 == 0 and cout <= 256
-        deep3x3 = halo is None and k == 3 and stride == 1 and self.cin % kstep == 0 and cout % 64 == 0 and \
-            self.cin >= 128 and cout >= 128 and not hreg128
-        # (r04: deep layers whose cout is no multiple of 128 — scale x: 320 -> 320 — take the flat-K kernel's 160-wide tiles behind the same
-        # layout (csrc/conv_igemm.hip: fk_first): 19.09 -> 18.68 ms per x1536 pass against the halo kernel, 536 -> 860 TFLOP/s against the
-        # 64-cout persistent tiles of the tap-aligned kernel)
-        # r04: 3x3 layers whose channel counts are not whole 64-channel K-steps / 64-cout tiles (the n / m / x scales: 80, 160, 320 ...)
-        # run on the flat-K LDS-DMA kernel behind DY_WLAYOUT_ROWS (conv_gemm_fk.hip) instead of the halo kernel's 32-channel chunks
-        flat3x3 = FLAT_K_3X3[0] and halo is None and k == 3 and pad == 1 and groups == 1 and dtype in (torch.bfloat16, torch.float16) and \
-            self.cin >= 64 and (self.cin % 64 != 0 or cout % 64 != 0) and self.cin % 8 == 0 and cout % 8 == 0
-        if (halo is None or halo) and not deep3x3 and not flat3x3 and groups == 1 and k == 3 and pad == 1 and (stride == 1 or (stride == 2 and s2_fits)) \
-                and cout % 4 == 0 and self.cin >= 4 * elems_per_chunk(dtype) // 2:
-            # LDS-halo 3x3 kernel: MFMA-fragment-ordered weights (include/dyolo.h, DY_WLAYOUT_HALO3X3)
-            self.layout = _lib.DY_WLAYOUT_HALO3X3
-            e = elems_per_chunk(dtype)
-            kc, bn = 4 * e, (64 if cout > 32 else 32)
-            nt, nch = -(-cout // bn), -(-self.cin // kc)
-            self.k_pad, self.cout_pad = 0, L.dy_conv_cout_pad(cout)
-            if dev_pack:
-                self.w, self.b = _device_pack(self.layout, nt * nch * 9 * (bn // 16) * 64 * e), _device_bias(self.cout_pad)
-                return
-            wpad = _pad_to(weight.detach().to(torch.float32), (nt * bn, nch * kc, 3, 3))
-            self.w = _permute_cast(wpad.reshape(nt, bn // 16, 16, nch, 4, e, 3, 3).permute(0, 3, 6, 7, 1, 4, 2, 5), dtype, device)
-            self.b = _pad_to(bias.detach().to(torch.float32).to(wdev), (self.cout_pad,)).to(device)
-            return
-        e = elems_per_chunk(dtype)
-        nkg = -(-self.cin // (4 * e))
-        frag_ok = nkg in (2, 3, 4, 6, 8, 12) and (cout > 16 or nkg == 2) and self.cin % e == 0
-        if for_out_f32 and dtype != torch.float32:
-            frag_ok = frag_ok and nkg == 2 and cout <= 64
-        if frag_ok:  # the streaming kernel's LDS footprint (conv1x1_stream.hip::launch_1x1) must fit 160 KB
-            bn_ = 128 if cout > 64 else (64 if cout > 16 else 16)
-            osz = 4 if (for_out_f32 or dtype == torch.float32) else 2
-            smem = nkg * (bn_ // 16) * 1024 + bn_ * 4 + 8 * (2 if nkg <= 2 else 1) * 16 * (bn_ * osz + 16)
-            frag_ok = smem <= 160 * 1024
-        if (halo is None or halo) and groups == 1 and k == 1 and stride == 1 and pad == 0 and frag_ok:
-            # streaming 1x1 kernel: fragment-ordered weights, single tap (include/dyolo.h, DY_WLAYOUT_FRAG1X1)
-            self.layout = _lib.DY_WLAYOUT_FRAG1X1
-            kc, bn = 4 * e, (128 if cout > 64 else (64 if cout > 16 else 16))
-            nt = -(-cout // bn)
-            if dev_pack:
-                self.k_pad, self.cout_pad = 0, max(L.dy_conv_cout_pad(cout), nt * bn)
-                self.w, self.b = _device_pack(self.layout, nt * nkg * (bn // 16) * 64 * e), _device_bias(self.cout_pad)
-                return
-            wpad = torch.zeros((nt * bn, nkg * kc), dtype=torch.float32, device=wdev)
-            wpad[:cout, : self.cin] = weight.detach().to(torch.float32).view(cout, self.cin)
-            wp = wpad.view(nt, bn // 16, 16, nkg, 4, e).permute(0, 3, 1, 4, 2, 5).contiguous().view(-1)
-            self.k_pad, self.cout_pad = 0, max(L.dy_conv_cout_pad(cout), nt * bn)
-            bp = torch.zeros((self.cout_pad,), dtype=torch.float32, device=wdev)
-            bp[:cout] = bias.detach().to(torch.float32).to(wdev)
-            self.w = wp.to(dtype).contiguous().to(device)
-            self.b = bp.contiguous().to(device)
-            return
-        if groups == 1:
-            self.k_pad = L.dy_conv_k_pad(self.cin, k, dy_dtype(dtype))
-            self.cout_pad = L.dy_conv_cout_pad(cout)
-            if dev_pack:
-                self.w, self.b = _device_pack(self.layout, self.cout_pad * self.k_pad), _device_bias(self.cout_pad)
-                return
-            if self.k_pad == k * k * cin_g and self.cout_pad == cout:  # nothing to pad: one permute + cast kernel
-                self.w = _permute_cast(weight.detach().permute(0, 2, 3, 1), dtype, device)
-                self.b = bias.detach().to(torch.float32).to(device)
-                return
-            w = weight.detach().to(torch.float32).permute(0, 2, 3, 1).reshape(cout, k * k * cin_g)
-            wp = torch.zeros((self.cout_pad, self.k_pad), dtype=torch.float32, device=wdev)
-            wp[:cout, : w.shape[1]] = w
-            bp = torch.zeros((self.cout_pad,), dtype=torch.float32, device=wdev)
-            bp[:cout] = bias.detach().to(torch.float32).to(wdev)
+        padded = cin_pad is not None and cin_pad > weight.shape[1]  # the input view carries zero-padded channels (the image: 3 -> one 16-byte chunk)
+        if padded and groups != 1:
+            raise ValueError("cin_pad is only meaningful for dense convolutions")
+        cin = cin_pad if padded else cin_g * groups
+        if dtype == F16X2 and groups == 1:
+            cin = -(-cin // 8) * 8
+        self.act, self.dtype = _act_code(act), dtype  # act: bool (SiLU or none) or a dy_act code
+        plan = conv_pack_plan(cout, cin, k, stride, pad, groups, self.act, dtype, halo, for_out_f32)
+        self.cout, self.cin, self.k, self.stride, self.pad, self.groups = cout, plan.cin, k, stride, pad, groups
+        self.layout, self.k_pad, self.cout_pad = plan.layout, plan.k_pad, plan.cout_pad
+        self.wscale, self.act_scale = None, (fp8_act_scale() if dtype == FP8 else 1.0)
+        # what a DY_WLAYOUT_ROWS pack of the same layer is built from (``rows()``: calls the special layout's kernels refuse)
+        self._rows_args = None if plan.layout == _lib.DY_WLAYOUT_ROWS else (weight, bias, stride, pad, groups, act, dtype, device, cin_pad, for_out_f32, transpose_flip)
+        self._rows_pack = None
+        if dev_pack:  # (either way packed where the weights live — the CPU for inference setup, the GPU in training: no host round trip)
+            self.w = _device_pack(weight.detach(), transpose_flip, cin_pad if padded else 0, plan, dtype)
         else:
-            w = weight.detach().to(torch.float32).permute(0, 2, 3, 1).reshape(cout, k * k * cin_g)
-            self.k_pad, self.cout_pad = w.shape[1], cout
-            wp, bp = w, bias.detach().to(torch.float32)
-        self.w = wp.to(dtype).contiguous().to(device)
-        self.b = bp.contiguous().to(device)
+            w = weight.detach()
+            if padded:
+                w = torch.nn.functional.pad(w.float(), (0, 0, 0, 0, 0, cin_pad - cin_g))
+            if dtype == F16X2 and groups == 1:
+                w, self.wscale = _rows_image_split(w, plan)
+            elif dtype == FP8:
+                w, self.wscale = _rows_image_fp8(w, plan, self.act_scale)
+            elif plan.layout == _lib.DY_WLAYOUT_HALO3X3:
+                w = _halo3x3_image(w, plan, dtype)
+            elif plan.layout == _lib.DY_WLAYOUT_FRAG1X1:
+                w = _frag1x1_image(w.to(torch.float32).reshape(cout, plan.cin), plan, dtype)
+            else:  # (grouped split float16: the small-group kernel multiplies joined fp32 inputs by fp32 weights)
+                w = _rows_image(w, plan, torch.float32 if dtype == F16X2 else dtype)
+            self.w = w.to(device)
+            if self.wscale is not None:
+                self.wscale = self.wscale.to(device)
+        self.b = _padded_bias(bias, plan.cout_pad, weight.device).to(device)
 
     def rows(self) -> "PackedConv":
         """The same layer packed in DY_WLAYOUT_ROWS (built on first use, kept): the layout every call shape has a kernel for.
@@ -731,24 +750,16 @@ class PackedStem:
         self.cout, self.cin, self.dtype = cout, cin, dtype
         self.act = _act_code(act)
         cp = -(-cout // 16) * 16
-        wp = torch.zeros((cp, 32), dtype=torch.float32)
-        wp[:cout, : cin * 9] = weight.detach().to(torch.float32).cpu().reshape(cout, cin * 9)
-        bp = torch.zeros((cp,), dtype=torch.float32)
-        bp[:cout] = bias.detach().to(torch.float32).cpu()
-        if dtype == F16X2:  # [hi rows | lo rows | inverse row scales] in one buffer (include/dyolo.h); the split rules of PackedConv
+        wp = _zero_padded(weight.detach().to(torch.float32).cpu().reshape(cout, cin * 9), cp * 32, (cp, 32))
+        self.b = _padded_bias(bias.detach().cpu(), cp, "cpu").to(device)
+        if dtype == F16X2:  # [hi rows | lo rows | inverse row scales] in one buffer (include/dyolo.h)
             if cout % 8 or cout > 64:
                 raise ValueError("PackedStem: split-float16 storage needs cout a multiple of 8 up to 64")
-            sc = torch.exp2(13.0 - torch.floor(torch.log2(wp.abs().amax(1).clamp_min(1e-30))))
-            ws = wp * sc[:, None]
-            hi = torch.where(ws.abs() < 2.0 ** -14, torch.zeros_like(ws), ws).to(torch.float16)
-            lo = (ws - hi.to(torch.float32)).to(torch.float16)
-            inv = (1.0 / sc).to(torch.float32)
+            hi, lo, inv = _split_f16x2(wp)
             raw = torch.cat((hi.reshape(-1).view(torch.uint8), lo.reshape(-1).view(torch.uint8), inv.view(torch.uint8)))
             self.w = raw.contiguous().to(device)
-            self.b = bp.contiguous().to(device)
             return
         self.w = wp.to(dtype).contiguous().to(device)
-        self.b = bp.contiguous().to(device)
 
 
 def stem_conv(src: torch.Tensor, ps: PackedStem, out: Optional[torch.Tensor] = None, mark_input: bool = False) -> torch.Tensor:
@@ -989,32 +1000,17 @@ def detect_branch_fused(x: torch.Tensor, pc3: "PackedConv", w1: torch.Tensor, b1
 
 def pack_frag1x1(weight: torch.Tensor, bias: torch.Tensor, dtype: torch.dtype, device) -> Tuple[torch.Tensor, torch.Tensor]:
     """(cout, cin[,1,1]) weights + bias in DY_WLAYOUT_FRAG1X1 order (include/dyolo.h), whatever kernel PackedConv would pick."""
-    if dtype == F16X2:
-        # split float16 (dy_detect_head_decode with DY_F16X2): the float16 fragment image of the hi halves, then of the lo halves (rows scaled by
-        # a power of two into [2^13, 2^14) first, hi flushed to 0 below float16's smallest normal: PackedConv's rule); bias followed by the
-        # inverse row scales
-        w2 = weight.detach().to(torch.float32).cpu().reshape(weight.shape[0], -1)
-        sc = torch.exp2(13.0 - torch.floor(torch.log2(w2.abs().amax(1).clamp_min(1e-30))))
-        ws = w2 * sc[:, None]
-        hi = torch.where(ws.abs() < 2.0 ** -14, torch.zeros_like(ws), ws).to(torch.float16)
-        lo = (ws - hi.to(torch.float32)).to(torch.float16)
-        zb = torch.zeros(weight.shape[0])
-        wh, bp = pack_frag1x1(hi.to(torch.float32), bias, torch.float16, "cpu")
-        wl, _ = pack_frag1x1(lo.to(torch.float32), zb, torch.float16, "cpu")
-        sp = torch.ones_like(bp)
-        sp[: weight.shape[0]] = 1.0 / sc
-        return torch.cat((wh, wl)).contiguous().to(device), torch.cat((bp, sp)).contiguous().to(device)
-    e = elems_per_chunk(dtype)
     w2 = weight.detach().to(torch.float32).cpu().reshape(weight.shape[0], -1)
-    cout, cin = w2.shape
-    kc, bn = 4 * e, (128 if cout > 64 else (64 if cout > 16 else 16))
-    nt, nkg = -(-cout // bn), -(-cin // kc)
-    wpad = torch.zeros((nt * bn, nkg * kc), dtype=torch.float32)
-    wpad[:cout, :cin] = w2
-    wp = wpad.view(nt, bn // 16, 16, nkg, 4, e).permute(0, 3, 1, 4, 2, 5).contiguous().view(-1)
-    bp = torch.zeros((nt * bn,), dtype=torch.float32)
-    bp[:cout] = bias.detach().to(torch.float32).cpu()
-    return wp.to(dtype).contiguous().to(device), bp.to(device)
+    dt = torch.float16 if dtype == F16X2 else dtype
+    plan = _frag1x1_plan(*w2.shape, dt)
+    bp = _padded_bias(bias.detach().cpu(), plan.cout_pad, "cpu")
+    if dtype != F16X2:
+        return _frag1x1_image(w2, plan, dt).to(device), bp.to(device)
+    # split float16 (dy_detect_head_decode with DY_F16X2): the float16 fragment image of the hi halves, then of the lo halves; bias
+    # followed by the inverse row scales
+    hi, lo, inv = _split_f16x2(w2)
+    wp = torch.cat([_frag1x1_image(h.to(torch.float32), plan, dt) for h in (hi, lo)])
+    return wp.to(device), torch.cat((bp, torch.nn.functional.pad(inv, (0, plan.cout_pad - inv.numel()), value=1.0))).to(device)
 
 
 def head_decode_supported(c_box: int, c_cls: int, nc: int, reg_max: int, dtype: torch.dtype) -> bool:
