@@ -101,6 +101,17 @@ class NmsDesc(C.Structure):
     ]  # fmt: skip
 
 
+class ValMatchDesc(C.Structure):
+    """Mirror of ``dy_val_match_desc``."""
+
+    _fields_ = [
+        ("rows", _vp), ("counts", _vp), ("tbox", _vp), ("tcls", _vp), ("timg", _vp), ("iouv", C.POINTER(_f32)),
+        ("batch", _i32), ("max_det", _i32), ("n_labels", _i32), ("n_iouv", _i32),
+        ("clip_w", _f32), ("clip_h", _f32), ("single_cls", _i32),
+        ("tp", _vp), ("best_iou", _vp), ("best_label", _vp),
+    ]  # fmt: skip
+
+
 class LossDesc(C.Structure):
     """Mirror of ``dy_loss_desc``."""
 
@@ -198,6 +209,7 @@ SIGNATURES = {
     "dy_nms": (_i32, [C.POINTER(NmsDesc), _vp]),
     "dy_nms_small_cap": (_i32, []),
     "dy_scale_boxes": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp]),
+    "dy_val_match": (_i32, [C.POINTER(ValMatchDesc), _vp]),
     "dy_detection_loss_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "dy_conv2d_wgrad_nhwc": (_i32, [C.POINTER(ConvDesc), _vp, _i32, _vp, _vp]),
     "dy_conv2d_wgrad_nhwc_ws": (_i32, [C.POINTER(ConvDesc), _vp, _i32, _vp, _vp, C.c_int64, _vp]),

@@ -124,8 +124,8 @@ class Model(nn.Module):
 
     def val(self, validator=None, **kwargs) -> dict:
         """Reference engine/model.py:620-656 (``Model.val``): the model's own weights scored on a dataset by the task's validator
-        (models/yolo/detect/val.py; engine/validator.py here: the model pass and the ``multi_label`` NMS at conf 0.001 on the device, matching and
-        AP on the host).  ``data``: a tensor dataset — a dict / ``.pt`` in the training layout, its ``"val"`` split when it has one — or
+        (models/yolo/detect/val.py; engine/validator.py here: the model pass, the ``multi_label`` NMS at conf 0.001 and the matching of detections
+        to labels on the device, AP on the host; ``device_match=False`` matches on the host as the reference does, with the same result).  ``data``: a tensor dataset — a dict / ``.pt`` in the training layout, its ``"val"`` split when it has one — or
         ``"synthetic[:N]"`` (engine/trainer.py::load_dataset; image folders and dataset YAMLs are outside the accelerated path);
         ``batch``, ``imgsz``, ``conf``, ``iou``, ``max_det``, ``half`` / ``dtype``, ``device`` as the reference's arguments.  Returns the
         reference's ``results_dict`` (metrics/precision(B) ... metrics/mAP50-95(B), fitness) with the validation losses; kept in ``self.metrics``."""

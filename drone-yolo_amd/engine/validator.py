@@ -3,8 +3,12 @@ in its training branch, and models/yolo/detect/val.py ``DetectionValidator``: ``
 at conf 0.001, ``update_metrics`` :126-174, ``_process_batch`` :213-231, ``get_stats`` :181-190).
 
 What runs where: the model pass (EMA weights, eval mode: BatchNorm folded, the trainer's storage type) and the validator's NMS
-(``dy_nms`` with ``multi_label``: one candidate per (anchor, class) pair) on the device; matching and AP on the host in numpy, as in
-the reference (utils/metrics.py).  The validation loss is the criterion on Detect's raw maps of the same pass (validator.py:186-187).
+(``dy_nms`` with ``multi_label``: one candidate per (anchor, class) pair) on the device; AP on the host in numpy, as in the reference
+(utils/metrics.py).  The matching of detections to labels runs on the device as well (``device_match``, on by default): ``dy_val_match`` matches every
+batch on the padded NMS output behind the NMS, the statistics stay on the device for the whole set and come to the host once per
+validation (``_collect_device``).  ``device_match=False`` is the reference's data flow, on the host image by image (``box_iou`` +
+``match_predictions``, ``_collect_host``); the returned numbers are the same ("Validation matching on the device").
+The validation loss is the criterion on Detect's raw maps of the same pass (validator.py:186-187).
 Tensor datasets only (dataset files / augmentation are out of scope): ``data["val"]`` — a dict in the training set's
 layout — or, when the dataset has no split, the training tensors themselves."""
 from __future__ import annotations
@@ -21,12 +25,13 @@ from ..utils.metrics import DetMetrics, box_iou, match_predictions
 
 class DetectionValidator:
     def __init__(self, args: Optional[dict] = None):
-        a = dict(conf=None, iou=0.7, max_det=300, single_cls=False, agnostic_nms=False)
+        a = dict(conf=None, iou=0.7, max_det=300, single_cls=False, agnostic_nms=False, device_match=True)
         a.update({k: v for k, v in (args or {}).items() if k in a})
         self.conf = 0.001 if a["conf"] is None else float(a["conf"])  # default 0.001 in val mode (validator.py:134)
         self.iou, self.max_det = float(a["iou"]), int(a["max_det"])
         self.agnostic = bool(a["single_cls"] or a["agnostic_nms"])
         self.single_cls = bool(a["single_cls"])
+        self.device_match = bool(a["device_match"])  # package extension (cfg/default.yaml): matching through dy_val_match
         self.iouv = np.linspace(0.5, 0.95, 10)  # detect/val.py:37
         self.metrics = DetMetrics()
 
@@ -48,6 +53,63 @@ class DetectionValidator:
             det.fuse_tail = fuse_tail  # (a predictor that shares the model keeps its fused tail: ADVICE r4)
 
     def _evaluate(self, model, loader, device, dtype, nc, stats, loss, det) -> Dict[str, float]:
+        nb = (self._collect_device if self.device_match else self._collect_host)(model, loader, device, dtype, nc, stats, loss, det)
+        out = {k: 0.0 for k in DetMetrics.keys + ("fitness",)}
+        if stats["tp"]:
+            cat = {k: np.concatenate(v, 0) for k, v in stats.items()}
+            if len(cat["target_cls"]):
+                self.metrics.process(cat["tp"], cat["conf"], cat["pred_cls"], cat["target_cls"])
+                out = self.metrics.results_dict
+        vl = (loss / max(nb, 1)).cpu().tolist()
+        out.update({"val/box_loss": vl[0], "val/cls_loss": vl[1], "val/dfl_loss": vl[2]})
+        return {k: round(float(v), 5) for k, v in out.items()}
+
+    def _collect_device(self, model, loader, device, dtype, nc, stats, loss, det) -> int:
+        """``device_match``: fills ``stats`` with what ``_collect_host`` gathers (image order, then row order), matched by ``dy_val_match``.
+        Nothing in the loop waits for the device; the accumulated tensors go to the host once each after it."""
+        nb = n_img = 0
+        rows, counts, tps, tcls, timg = [], [], [], [], []
+        lim = {}
+        for batch in loader:
+            nb += 1
+            img = batch["img"].to(device)
+            b, _, h, w = img.shape
+            x = (img.float() / 255.0) if img.dtype == torch.uint8 else img.float()  # detect/val.py:49-52
+            with torch.no_grad():
+                det.fuse_tail = False  # the raw maps are needed for the loss: Detect returns (y, feats)
+                y, feats = model._predict_once(x.contiguous(), image_dtype=dtype)
+                loss += model.criterion(feats, batch)[1]  # validator.py:186-187: loss items of the same pass
+                bufs = ops.non_max_suppression(y, self.conf, self.iou, nc=nc, multi_label=True, agnostic=self.agnostic, max_det=self.max_det,
+                                               return_padded=True)
+            if (w, h) not in lim:
+                lim[(w, h)] = torch.tensor((w, h, w, h), dtype=torch.float32, device=device)
+            # the labels as _collect_host prepares them, in the same elementwise fp32 arithmetic (the same bits): scale to pixels, clip to the image
+            cls = batch["cls"].to(device).view(-1).float()
+            bi = batch["batch_idx"].to(device).view(-1).to(torch.int32)
+            tbox = ops.xywh2xyxy(batch["bboxes"].to(device).float()) * lim[(w, h)]
+            tbox = torch.minimum(tbox.clamp_min(0), lim[(w, h)])
+            tps.append(H.val_match(bufs, tbox, cls, bi, self.iouv, (w, h), single_cls=self.single_cls))  # (new tensors on every call)
+            rows.append(bufs.out[..., 4:6].clone()), counts.append(bufs.count.clone())  # (the NMS buffers may be reused by the next batch)
+            tcls.append(cls), timg.append(bi + n_img)
+            n_img += b
+        if nb == 0:
+            return nb
+        rows, counts, tp = (torch.cat(v).cpu().numpy() for v in (rows, counts, tps))
+        tcls, timg = torch.cat(tcls).cpu().numpy(), torch.cat(timg).cpu().numpy().astype(np.int64)
+        keep = np.arange(self.max_det)[None, :] < counts[:, None]
+        conf, pred_cls = rows[keep][:, 0], rows[keep][:, 1]
+        if self.single_cls:
+            pred_cls = np.zeros_like(pred_cls)
+        # an image without predictions but with labels adds float64 zeros(0) on the host path, which makes its concatenated conf / pred_cls
+        # float64: the same type here, so that AP's argsort sees the same array
+        if bool(((counts == 0) & (np.bincount(timg, minlength=len(counts))[: len(counts)] > 0)).any()):
+            conf, pred_cls = conf.astype(np.float64), pred_cls.astype(np.float64)
+        if len(conf) or len(tcls):
+            stats["tp"].append(tp[keep].astype(bool)), stats["conf"].append(conf), stats["pred_cls"].append(pred_cls)
+            stats["target_cls"].append(tcls[np.argsort(timg, kind="stable")])
+        return nb
+
+    def _collect_host(self, model, loader, device, dtype, nc, stats, loss, det) -> int:
         nb = 0
         for batch in loader:
             nb += 1
@@ -81,12 +143,4 @@ class DetectionValidator:
                 if len(cls):
                     tp = match_predictions(pn[:, 5], cls, box_iou(tbox, pn[:, :4]), self.iouv)
                 stats["tp"].append(tp), stats["conf"].append(pn[:, 4]), stats["pred_cls"].append(pn[:, 5]), stats["target_cls"].append(cls)
-        out = {k: 0.0 for k in DetMetrics.keys + ("fitness",)}
-        if stats["tp"]:
-            cat = {k: np.concatenate(v, 0) for k, v in stats.items()}
-            if len(cat["target_cls"]):
-                self.metrics.process(cat["tp"], cat["conf"], cat["pred_cls"], cat["target_cls"])
-                out = self.metrics.results_dict
-        vl = (loss / max(nb, 1)).cpu().tolist()
-        out.update({"val/box_loss": vl[0], "val/cls_loss": vl[1], "val/dfl_loss": vl[2]})
-        return {k: round(float(v), 5) for k, v in out.items()}
+        return nb

@@ -21,7 +21,7 @@ import warnings
 import torch
 
 from . import _lib
-from ._lib import DY_ACT_NONE, DY_ACT_SILU, DY_ACT_SILU_L2E, BnDesc, BranchDesc, C2fDesc, ConvDesc, DecodeDesc, HeadDecodeDesc, LossDesc, NmsDesc, Stem2Desc, check, lib
+from ._lib import DY_ACT_NONE, DY_ACT_SILU, DY_ACT_SILU_L2E, BnDesc, BranchDesc, C2fDesc, ConvDesc, DecodeDesc, HeadDecodeDesc, LossDesc, NmsDesc, Stem2Desc, ValMatchDesc, check, lib
 
 FP8 = torch.float8_e4m3fn  # OCP e4m3fn: gfx950's fp8 (MI300's fnuz is another encoding)
 # DY_F16X2 (include/dyolo.h): split float16 pairs, x ~= hi + lo * 2^-11 — the bar-exact precision on the 16-bit MFMA.  torch has no such
@@ -1101,6 +1101,43 @@ def scale_boxes_(bufs: NmsBuffers, params: torch.Tensor) -> None:
     """In-place scale_boxes + clip_boxes of the kept rows; params: device fp32 (N,5)."""
     _launch(lib().dy_scale_boxes, (bufs.out.data_ptr(), bufs.count.data_ptr(), params.data_ptr(), bufs.batch, bufs.max_det),
             keep=(bufs, params))
+
+
+def val_match(bufs: NmsBuffers, tbox: torch.Tensor, tcls: torch.Tensor, timg: torch.Tensor, iouv: Sequence[float], clip_wh: Tuple[float, float],
+              single_cls: bool = False, want_best: bool = False):
+    """The validator's matching (``BaseValidator.match_predictions`` on ``box_iou``, predictions clipped to ``clip_wh``) of a whole batch
+    on the padded NMS output through ``dy_val_match``; no host synchronisation.
+
+    ``bufs``: what ``nms`` returned; ``tbox`` (L, 4): the batch's label boxes, xyxy in pixels, clipped; ``tcls`` (L,) their classes and
+    ``timg`` (L,) the image each belongs to (any order; converted here, on the device, to the fp32 / int32 the kernel reads); ``iouv``:
+    1..16 thresholds (host values, rounded to fp32 as the host comparison rounds them).  Returns ``tp`` uint8 (N, max_det, len(iouv)),
+    new tensors on every call; with ``want_best`` ``(tp, best_iou fp32 (N, max_det), best_label int32 (N, max_det))``.  Rows at or
+    beyond ``bufs.count`` are 0 / 0 / -1."""
+    n, max_det, dev = bufs.batch, bufs.max_det, bufs.out.device
+    L = int(tbox.shape[0])
+    if L:
+        for t in (tbox, tcls, timg):
+            require_device(t, "label")
+        if tbox.dim() != 2 or tbox.shape[1] != 4 or tcls.numel() != L or timg.numel() != L:
+            raise ValueError("val_match: tbox must be (L, 4) with L classes and L image indices")
+        tbox = tbox.to(torch.float32).contiguous()
+        tcls = tcls.reshape(-1).to(torch.float32).contiguous()
+        timg = timg.reshape(-1).to(torch.int32).contiguous()
+    thr = (C.c_float * len(iouv))(*[float(v) for v in iouv])
+    tp = torch.empty((n, max_det, len(iouv)), dtype=torch.uint8, device=dev)
+    best_iou = torch.empty((n, max_det), dtype=torch.float32, device=dev) if want_best else None
+    best_label = torch.empty((n, max_det), dtype=torch.int32, device=dev) if want_best else None
+    d = ValMatchDesc()
+    d.rows, d.counts = bufs.out.data_ptr(), bufs.count.data_ptr()
+    d.tbox, d.tcls, d.timg = (tbox.data_ptr(), tcls.data_ptr(), timg.data_ptr()) if L else (None, None, None)
+    d.iouv = thr
+    d.batch, d.max_det, d.n_labels, d.n_iouv = n, max_det, L, len(iouv)
+    d.clip_w, d.clip_h, d.single_cls = float(clip_wh[0]), float(clip_wh[1]), int(bool(single_cls))
+    d.tp = tp.data_ptr()
+    d.best_iou = best_iou.data_ptr() if want_best else None
+    d.best_label = best_label.data_ptr() if want_best else None
+    _launch(lib().dy_val_match, (C.byref(d),), keep=(d, thr, bufs, tbox, tcls, timg, tp, best_iou, best_label))
+    return (tp, best_iou, best_label) if want_best else tp
 
 
 # ---- training loss (forward) ----------------------------------------------------------------------------

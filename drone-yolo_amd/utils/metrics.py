@@ -2,7 +2,8 @@
 ``compute_ap`` :505-534, ``ap_per_class`` :537-623, ``Metric`` :626-760; ``BaseValidator.match_predictions``, engine/validator.py:224-264).
 
 Host logic in numpy, as in the reference (its metrics leave the device too: validator.get_stats() does ``.cpu().numpy()``): a few
-thousand kept rows per validation set.  Every function restates the reference's arithmetic step by step and is pinned against the
+thousand kept rows per validation set.  ``box_iou`` and ``match_predictions`` are what the validator runs with ``device_match=False``
+and what ``dy_val_match`` (csrc/val_match.hip, the default) is tested against; AP is computed here in both cases.  Every function restates the reference's arithmetic step by step and is pinned against the
 reference's own functions on synthetic statistics (tests/golden/val_metrics.npz, oracle/make_golden.py::val_metric_vectors)."""
 from __future__ import annotations
 

@@ -493,6 +493,38 @@ int32_t dy_nms_small_cap(void);
 int32_t dy_scale_boxes(float* boxes, const int32_t* counts, const float* params, int32_t batch,
                        int32_t max_det, dy_stream_t stream);
 
+/* ---- validation matching on the padded NMS output ------------------------------------------------------
+ * Replaces: BaseValidator.match_predictions (engine/validator.py:224-264, the non-scipy branch) and the box_iou it is fed
+ * (utils/metrics.py:52-71), with the clip of the predictions to the image (_prepare_pred, models/yolo/detect/val.py:119-124), for a
+ * whole batch in one launch behind dy_nms; no host synchronisation, capturable in a hipGraph.
+ * rows: fp32 (batch, max_det, 6) and counts: int32 (batch): the dy_nms outputs (rows >= counts[i] are not read).
+ * tbox: fp32 (n_labels, 4) label boxes, xyxy in pixels, already clipped, 16-byte aligned; tcls: fp32 (n_labels) their classes;
+ * timg: int32 (n_labels) the image each label belongs to (by value: the labels need not be sorted).  n_labels = 0 with null label
+ * pointers is valid.  iouv: HOST array of n_iouv (1..16) IoU thresholds, read during the call.
+ * For detection d (clipped to [0, clip_w] x [0, clip_h]; class 0 with single_cls) and the labels l of its image:
+ *   m(l, d) = box_iou(l, d) if tcls[l] == cls[d] else 0, in fp32 in box_iou's order of operations (bit-equal to the host's);
+ *   best(d) = argmax_l m(l, d), biou(d) = max_l m(l, d); exact ties go to the label that comes first in tbox (the reference's order on
+ *   exact ties comes from an unstable sort and is not defined);
+ *   tp[d][i] = biou(d) >= iouv[i] and no d' < d of the image has best(d') == best(d) and biou(d') >= iouv[i].
+ * tp: uint8 (batch, max_det, n_iouv).  best_iou: optional fp32 (batch, max_det) = biou; best_label: optional int32 (batch, max_det) =
+ * position of best(d) in tbox, -1 when the image has no label.  Every element is written: rows >= counts[i] get 0 / 0 / -1.
+ * max_det <= 4096 (32 bytes of LDS per detection).  One workgroup per image; labels per image are unbounded. */
+typedef struct dy_val_match_desc {
+  const float* rows;
+  const int32_t* counts;
+  const float* tbox;
+  const float* tcls;
+  const int32_t* timg;
+  const float* iouv;
+  int32_t batch, max_det, n_labels, n_iouv;
+  float clip_w, clip_h;
+  int32_t single_cls;
+  uint8_t* tp;
+  float* best_iou;
+  int32_t* best_label;
+} dy_val_match_desc;
+int32_t dy_val_match(const dy_val_match_desc* d, dy_stream_t stream);
+
 /* ---- training loss (forward + gradient w.r.t. the head outputs) -----------------------------------------------------
  * Replaces: v8DetectionLoss.__call__ (utils/loss.py:206-260) = TaskAlignedAssigner (utils/tal.py:14-295, topk /
  * alpha / beta as given) + BCE class loss + CIoU box loss (utils/metrics.py:74-134) + DFL (loss.py:65-113), on the
