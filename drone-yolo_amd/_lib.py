@@ -112,6 +112,18 @@ class ValMatchDesc(C.Structure):
     ]  # fmt: skip
 
 
+class TrackDesc(C.Structure):
+    """Mirror of ``dy_track_desc``."""
+
+    _fields_ = [
+        ("rows", _vp), ("counts", _vp), ("state", _vp), ("state_bytes", _i64), ("workspace", _vp), ("workspace_bytes", _i64),
+        ("out", _vp), ("out_count", _vp),
+        ("frames", _i32), ("streams", _i32), ("max_det", _i32), ("max_tracks", _i32),
+        ("track_high_thresh", _f32), ("track_low_thresh", _f32), ("new_track_thresh", _f32), ("match_thresh", _f32),
+        ("fuse_score", _i32), ("max_time_lost", _i32),
+    ]  # fmt: skip
+
+
 class LossDesc(C.Structure):
     """Mirror of ``dy_loss_desc``."""
 
@@ -210,6 +222,10 @@ SIGNATURES = {
     "dy_nms_small_cap": (_i32, []),
     "dy_scale_boxes": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp]),
     "dy_val_match": (_i32, [C.POINTER(ValMatchDesc), _vp]),
+    "dy_track_state_bytes": (_i64, [_i32, _i32]),
+    "dy_track_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "dy_track_reset": (_i32, [_vp, _i32, _i32, _vp]),
+    "dy_track_step": (_i32, [C.POINTER(TrackDesc), _vp]),
     "dy_detection_loss_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "dy_conv2d_wgrad_nhwc": (_i32, [C.POINTER(ConvDesc), _vp, _i32, _vp, _vp]),
     "dy_conv2d_wgrad_nhwc_ws": (_i32, [C.POINTER(ConvDesc), _vp, _i32, _vp, _vp, C.c_int64, _vp]),

@@ -76,12 +76,37 @@ class Model(nn.Module):
         """Reference engine/model.py:501-560: predictor created on first use, conf defaults to 0.25."""
         if source is None:
             raise ValueError("'source' is missing; the device path takes a BCHW float tensor in [0, 1]")
-        args = {**self.overrides, "conf": 0.25, **kwargs}
+        track = kwargs.get("mode") == "track"
+        args = {**self.overrides, "conf": 0.1 if track else 0.25, **kwargs}
         args.pop("model", None), args.pop("task", None), args.pop("mode", None)
-        if self.predictor is None or getattr(self, "_pred_args", None) != args:
+        persist = bool(args.pop("persist", False))
+        if not track:
+            args.pop("tracker", None)
+        if self.predictor is None or getattr(self, "_pred_args", None) != (args, track):
             self.predictor = (predictor or DetectionPredictor)(self.model, overrides=args)
-            self._pred_args = args
+            self._pred_args = (args, track)
+        if track:
+            # the tracker outlives the predictor (a predict call in between rebuilds that): persist=True goes on with its tracks and ids
+            p = self.predictor
+            key = (str(p.args["tracker"]), bool(p.args["device_track"]), int(p.args["track_streams"]), int(p.args["max_det"]), int(p.args["max_tracks"]), str(p.device))
+            if getattr(self, "_tracker_key", None) != key:
+                self._tracker, self._tracker_key = p.make_tracker(), key
+            elif not persist:
+                self._tracker.reset()
+            p.tracker = self._tracker
+        else:
+            self.predictor.tracker = None
         return self.predictor(source, stream=stream)
+
+    def track(self, source=None, stream: bool = False, persist: bool = False, tracker="bytetrack.yaml", **kwargs) -> List[Results]:
+        """Reference engine/model.py:562-620: ``predict`` with ``mode="track"`` and conf defaulting to 0.1 (ByteTrack wants the low-score
+        detections), each batch's detections handed to the tracker (trackers/track.py).  Results whose tracker returned rows carry 7-column
+        boxes (``boxes.is_track``, ``boxes.id``).  ``persist=False`` resets the tracker at the start of the call, ``persist=True`` continues
+        tracks and ids across calls.  ``tracker``: settings under cfg/trackers or a path (ByteTrack only).  Package extensions:
+        ``device_track`` (default true: the dy_track_step kernel behind the NMS, no extra synchronisation; false: the same tracker on the host)
+        and ``track_streams`` = S independent video streams per batch (image k is stream k % S at time step k // S; the batch size must be
+        a multiple of it)."""
+        return self.predict(source, stream, **{**kwargs, "mode": "track", "persist": persist, "tracker": tracker})
 
     def profile(self, source, **kwargs) -> list:
         """Per-layer device time of one pass over ``source`` (reference ``predict(profile=True)`` -> ``_profile_one_layer``, nn/tasks.py:171-191):

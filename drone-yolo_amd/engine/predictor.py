@@ -91,9 +91,11 @@ class DetectionPredictor:
 
     def __init__(self, model, overrides: Optional[dict] = None):
         a = dict(conf=0.25, iou=0.7, max_det=300, classes=None, agnostic_nms=False, half=False, dtype=None, device="",
-                 verbose=False, graph=True, max_nms=30000, max_wh=7680, imgsz=640, fp8_layers=None, batch=None, augment=False)
+                 verbose=False, graph=True, max_nms=30000, max_wh=7680, imgsz=640, fp8_layers=None, batch=None, augment=False,
+                 tracker="bytetrack.yaml", device_track=True, track_streams=1, max_tracks=512)
         a.update(overrides or {})
         self.args = a
+        self.tracker = None  # mode="track" (Model.track): a trackers.DeviceByteTracker / ByteTracker fed behind the NMS and box scaling of every batch
         self.device = select_device(a["device"])
         # dtype="fp8-mixed" (BASELINE config 5): float16 storage with the internals of the C2f blocks the error budget allows in
         # e4m3 (BaseModel.fp8_plan_off_p2, or the blocks given as overrides["fp8_layers"]); dtype="fp8": the whole trunk in e4m3, Detect tail float16
@@ -329,15 +331,50 @@ class DetectionPredictor:
         cf = self._compiled.get((tuple(shape), self.dtype))
         return None if cf is None else cf.static_in
 
+    def make_tracker(self):
+        """The tracker of ``mode="track"`` for this predictor's arguments: ``device_track`` picks the kernel or the host path."""
+        from ..trackers import ByteTracker, DeviceByteTracker
+
+        a = self.args
+        cls = DeviceByteTracker if a["device_track"] else ByteTracker
+        return cls(a["tracker"], frame_rate=30, max_tracks=int(a["max_tracks"]), streams=int(a["track_streams"]), max_det=int(a["max_det"]), device=self.device)
+
+    def _track_launch(self, cf: CompiledForward):
+        """Device tracker: the track step behind this batch's NMS and box scaling, on the same stream; returns copies (rows, counts) that
+        outlive the next batch.  Host tracker: None (it runs where the rows reach the host)."""
+        if self.tracker is None or not hasattr(self.tracker, "bufs"):
+            return None
+        out, cnt = self.tracker.update_batch(cf.nms.out, cf.nms.count)
+        return out.clone(), cnt
+
+    def _boxes_of(self, i: int, k: int, rows: torch.Tensor, tracked) -> torch.Tensor:
+        """The rows of image i's ``Results``: its k detections, or — when the tracker returned rows for it — those tracks
+        [x1, y1, x2, y2, id, conf, cls] (trackers/track.py:79-88: an image without detections or without returned tracks keeps its plain result)."""
+        if self.tracker is None or k == 0:
+            return rows[i, :k]
+        if tracked is None:  # host tracker, images in order
+            t = torch.from_numpy(self.tracker.update(rows[i, :k].cpu().numpy(), stream=i % self.tracker.streams)).to(rows.device)
+        else:
+            t = tracked[0][i, : tracked[1][i]]
+        return t[:, :7] if len(t) else rows[i, :k]
+
     def postprocess(self, cf: CompiledForward, im: torch.Tensor, paths=None) -> List[Results]:
-        counts = cf.nms.count.tolist()  # the pass's only device->host synchronisation
+        n = cf.nms.count.shape[0]
+        if self.tracker is not None and n % self.tracker.streams:
+            raise ValueError(f"a batch of {n} images is no multiple of track_streams = {self.tracker.streams}")
+        tracked = self._track_launch(cf)
+        # the pass's only device->host synchronisation: the NMS counts, with the tracker's counts behind them in the same copy
+        both = (torch.cat([cf.nms.count, tracked[1]]) if tracked is not None else cf.nms.count).tolist()
+        counts = both[:n]
+        if tracked is not None:
+            tracked = (tracked[0], both[n:])
         names = self.model.names
         out = []
         info = getattr(self, "letterbox_info", None)
         rows = cf.nms.out.clone()  # ONE copy of the padded (N, max_det, 6) rows: the next pass overwrites the buffer, the Results keep views of this one
         for i, k in enumerate(counts):
             one = (info[i] if isinstance(info, list) else info) if info else None
-            out.append(Results(im[i], paths[i] if paths else f"image{i}.jpg", names, boxes=rows[i, :k],
+            out.append(Results(im[i], paths[i] if paths else f"image{i}.jpg", names, boxes=self._boxes_of(i, k, rows, tracked),
                                orig_shape=(one[0], one[1]) if one else im.shape[2:]))
         return out
 
@@ -413,14 +450,16 @@ class DetectionPredictor:
         pending = None
 
         def finish(item):
-            lo, im, rows, counts_host, ev, info, t_pre, t_inf, paths, frames = item
+            lo, im, rows, counts_host, ev, info, t_pre, t_inf, paths, frames, trows = item
             t0 = time.perf_counter()
             ev.synchronize()
-            counts = counts_host.tolist()
+            both = counts_host.tolist()
+            counts = both[: rows.shape[0]]
+            tracked = (trows, both[rows.shape[0] :]) if trows is not None else None
             out = []
             for i, k in enumerate(counts):
                 one = (info[i] if isinstance(info, list) else info) if info else None
-                r = Results(frames[i] if frames is not None else im[i], paths[i] if paths else f"image{lo + i}.jpg", names, boxes=rows[i, :k],
+                r = Results(frames[i] if frames is not None else im[i], paths[i] if paths else f"image{lo + i}.jpg", names, boxes=self._boxes_of(i, k, rows, tracked),
                             orig_shape=(one[0], one[1]) if one else im.shape[2:])
                 out.append(r)
             dt = (time.perf_counter() - t0) * 1e3 / max(len(out), 1)
@@ -434,14 +473,18 @@ class DetectionPredictor:
             t1 = time.perf_counter()
             cf = self.forward_device(im)
             rows = cf.nms.out.clone()  # stream-ordered behind this batch's launches, in front of the next batch's (which overwrite the buffer)
-            counts_host = torch.empty(cf.nms.count.shape, dtype=cf.nms.count.dtype, pin_memory=True)
-            counts_host.copy_(cf.nms.count, non_blocking=True)
+            if self.tracker is not None and rows.shape[0] % self.tracker.streams:
+                raise ValueError(f"a batch of {rows.shape[0]} images is no multiple of track_streams = {self.tracker.streams}")
+            tracked = self._track_launch(cf)
+            counts_dev = torch.cat([cf.nms.count, tracked[1]]) if tracked is not None else cf.nms.count  # one copy for both
+            counts_host = torch.empty(counts_dev.shape, dtype=counts_dev.dtype, pin_memory=True)
+            counts_host.copy_(counts_dev, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
             t2 = time.perf_counter()
             n = max(im.shape[0], 1)
             item = (lo, im, rows, counts_host, ev, getattr(self, "letterbox_info", None), (t1 - t0) * 1e3 / n, (t2 - t1) * 1e3 / n, paths,
-                    piece if paths is not None else None)  # (file sources keep the decoded frame as the result's orig_img)
+                    piece if paths is not None else None, tracked[0] if tracked is not None else None)  # (file sources keep the decoded frame as the result's orig_img)
             if pending is not None:
                 yield from finish(pending)
             pending = item

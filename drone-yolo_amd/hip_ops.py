@@ -21,7 +21,7 @@ import warnings
 import torch
 
 from . import _lib
-from ._lib import DY_ACT_NONE, DY_ACT_SILU, DY_ACT_SILU_L2E, BnDesc, BranchDesc, C2fDesc, ConvDesc, DecodeDesc, HeadDecodeDesc, LossDesc, NmsDesc, Stem2Desc, ValMatchDesc, check, lib
+from ._lib import DY_ACT_NONE, DY_ACT_SILU, DY_ACT_SILU_L2E, BnDesc, BranchDesc, C2fDesc, ConvDesc, DecodeDesc, HeadDecodeDesc, LossDesc, NmsDesc, Stem2Desc, TrackDesc, ValMatchDesc, check, lib
 
 FP8 = torch.float8_e4m3fn  # OCP e4m3fn: gfx950's fp8 (MI300's fnuz is another encoding)
 # DY_F16X2 (include/dyolo.h): split float16 pairs, x ~= hi + lo * 2^-11 — the bar-exact precision on the 16-bit MFMA.  torch has no such
@@ -1138,6 +1138,67 @@ def val_match(bufs: NmsBuffers, tbox: torch.Tensor, tcls: torch.Tensor, timg: to
     d.best_label = best_label.data_ptr() if want_best else None
     _launch(lib().dy_val_match, (C.byref(d),), keep=(d, thr, bufs, tbox, tcls, timg, tp, best_iou, best_label))
     return (tp, best_iou, best_label) if want_best else tp
+
+
+# ---- tracking ---------------------------------------------------------------------------------------------
+
+
+class TrackBuffers:
+    """Persistent state, workspace and outputs of ``dy_track_step`` for (streams, max_tracks, max_det).  ``out`` / ``count`` grow with the
+    largest batch seen; the state lives as long as the object (``track_reset`` empties it)."""
+
+    def __init__(self, streams: int, max_tracks: int, max_det: int, device):
+        self.streams, self.max_tracks, self.max_det, self.device = int(streams), int(max_tracks), int(max_det), torch.device(device)
+        nstate = lib().dy_track_state_bytes(self.streams, self.max_tracks)
+        nws = lib().dy_track_workspace_bytes(self.streams, self.max_tracks, self.max_det)
+        if nstate < 0 or nws < 0:
+            check(int(min(nstate, nws)), "dy_track_state_bytes / dy_track_workspace_bytes")
+        self.state = torch.zeros((nstate,), dtype=torch.uint8, device=self.device)
+        self.workspace = torch.empty((nws,), dtype=torch.uint8, device=self.device)
+        self.out: Optional[torch.Tensor] = None
+        self.count: Optional[torch.Tensor] = None
+
+    def outputs(self, images: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        if self.out is None or self.out.shape[0] < images:
+            self.out = torch.empty((images, self.max_tracks, 8), dtype=torch.float32, device=self.device)
+            self.count = torch.empty((images,), dtype=torch.int32, device=self.device)
+        return self.out[:images], self.count[:images]
+
+
+def track_reset(bufs: TrackBuffers) -> None:
+    """No tracks, frame and id counters 0 (``BYTETracker.reset``), stream-ordered."""
+    _launch(lib().dy_track_reset, (bufs.state.data_ptr(), bufs.streams, bufs.max_tracks), keep=(bufs,), record=False)
+
+
+def track_counters(bufs: TrackBuffers):
+    """(streams, 3) int32 on the host: frame counter, id counter, overflow counter of every stream (synchronises)."""
+    per = bufs.state.numel() // bufs.streams
+    return bufs.state.view(bufs.streams, per)[:, :12].contiguous().view(torch.int32).cpu().numpy()
+
+
+def track_step(bufs: TrackBuffers, nms_bufs, frames: int, streams: int, cfg, max_time_lost: Optional[int] = None, frame_rate: int = 30):
+    """ByteTrack over ``frames`` time steps of ``streams`` video streams in one ``dy_track_step`` launch; no host synchronisation.
+    ``nms_bufs``: ``NmsBuffers`` (after ``scale_boxes_``) or a ``(rows, counts)`` pair of device tensors, (frames * streams, max_det, 6)
+    fp32 / int32; ``cfg``: the tracker settings (``trackers.load_tracker_cfg``).  Returns views ``(out (frames * streams, max_tracks, 8),
+    count (frames * streams,))`` of ``bufs``' output tensors: rows [x1, y1, x2, y2, id, score, cls, idx] in ascending id."""
+    rows, counts = (nms_bufs.out, nms_bufs.count) if hasattr(nms_bufs, "out") else nms_bufs
+    require_device(rows, "detection rows")
+    require_device(counts, "detection counts")
+    n = int(frames) * int(streams)
+    if streams != bufs.streams or rows.dtype != torch.float32 or counts.dtype != torch.int32 or not rows.is_contiguous() or not counts.is_contiguous() \
+            or tuple(rows.shape) != (n, bufs.max_det, 6) or counts.numel() != n:
+        raise ValueError(f"track_step: rows must be contiguous fp32 ({n}, {bufs.max_det}, 6) with {n} int32 counts for {bufs.streams} streams")
+    out, cnt = bufs.outputs(n)
+    d = TrackDesc()
+    d.rows, d.counts = rows.data_ptr(), counts.data_ptr()
+    d.state, d.state_bytes, d.workspace, d.workspace_bytes = bufs.state.data_ptr(), bufs.state.numel(), bufs.workspace.data_ptr(), bufs.workspace.numel()
+    d.out, d.out_count = out.data_ptr(), cnt.data_ptr()
+    d.frames, d.streams, d.max_det, d.max_tracks = int(frames), int(streams), bufs.max_det, bufs.max_tracks
+    d.track_high_thresh, d.track_low_thresh, d.new_track_thresh = float(cfg.track_high_thresh), float(cfg.track_low_thresh), float(cfg.new_track_thresh)
+    d.match_thresh, d.fuse_score = float(cfg.match_thresh), int(bool(cfg.fuse_score))
+    d.max_time_lost = int(frame_rate / 30.0 * cfg.track_buffer) if max_time_lost is None else int(max_time_lost)
+    _launch(lib().dy_track_step, (C.byref(d),), keep=(d, bufs, rows, counts), record=False)
+    return out, cnt
 
 
 # ---- training loss (forward) ----------------------------------------------------------------------------

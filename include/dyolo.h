@@ -720,6 +720,46 @@ typedef struct dy_aug_row {
 int32_t dy_augment_u8_nchw(const uint8_t* src, const dy_aug_row* table, uint8_t* dst, int32_t n_src_imgs, int32_t hs, int32_t ws, int32_t batch,
                            int32_t s, dy_stream_t stream);
 
+/* ---- multi-object tracking on the padded NMS output: ByteTrack ----------------------------------------------
+ * Replaces: BYTETracker.update (trackers/byte_tracker.py:293-405) with STrack, KalmanFilterXYAH (trackers/utils/kalman_filter.py:65-236),
+ * iou_distance / fuse_score / linear_assignment (trackers/utils/matching.py) and the per-image rules of on_predict_postprocess_end
+ * (trackers/track.py:71-88), for `streams` independent video streams and `frames` time steps in ONE launch behind dy_nms + dy_scale_boxes;
+ * no host synchronisation.  One workgroup per stream walks its time steps in order.
+ * rows: fp32 (frames * streams, max_det, 6) x1, y1, x2, y2, conf, cls in source-frame pixels and counts: int32 (frames * streams): what
+ * result.boxes holds in the reference; image k is stream k % streams at time step k / streams.  An image with count 0 does not reach the
+ * tracker: its stream's frame counter stands still and its output count is 0.
+ * state: dy_track_state_bytes(streams, max_tracks) bytes, 16-byte aligned, kept by the caller between calls; dy_track_reset (or zero
+ * bytes) = no tracks, frame and id counters 0.  Per stream: int32 frame counter, id counter, overflow counter (first 12 of 64 header
+ * bytes), then per slot mean[8] and covariance[8][8] in float64 ([component][slot]) and int32 state (0 free, 1 tracked, 2 lost,
+ * 3 removed and waiting out its last update), is_activated, mean-still-float32, id-in-removed-list, id, detection idx, frame_id,
+ * start_frame, tracklet_len, then fp32 score and cls.  max_tracks slots hold tracked, lost and unconfirmed tracks together; when they are
+ * full, new tracks are not started and the overflow counter grows by the number left out.  max_tracks even, <= 1024; max_det <= 1024;
+ * 92 bytes of LDS per slot and 68 per detection (160 KB at most).
+ * workspace: dy_track_workspace_bytes(streams, max_tracks, max_det) bytes, 16-byte aligned (the image's measurements; costs are not stored).
+ * out: fp32 (frames * streams, max_tracks, 8) x1, y1, x2, y2, id, score, cls, idx = STrack.result of the activated tracked tracks of each
+ * step in ASCENDING TRACK ID (the reference emits its Python list order), rows >= out_count zero; out_count: int32 (frames * streams).
+ * Ids count from 1 per stream.  The second association's limit 0.5, the unconfirmed one's 0.7 and the duplicate distance 0.15 are the
+ * reference's constants.  max_time_lost = int(frame_rate / 30 * track_buffer).
+ * The assignments are solved exactly (shortest augmenting paths, float64 potentials); among equal optima the choice is not the
+ * reference's (lap's is not defined either). */
+typedef struct dy_track_desc {
+  const float* rows;
+  const int32_t* counts;
+  void* state;
+  int64_t state_bytes;
+  void* workspace;
+  int64_t workspace_bytes;
+  float* out;
+  int32_t* out_count;
+  int32_t frames, streams, max_det, max_tracks;
+  float track_high_thresh, track_low_thresh, new_track_thresh, match_thresh;
+  int32_t fuse_score, max_time_lost;
+} dy_track_desc;
+int64_t dy_track_state_bytes(int32_t streams, int32_t max_tracks);
+int64_t dy_track_workspace_bytes(int32_t streams, int32_t max_tracks, int32_t max_det);
+int32_t dy_track_reset(void* state, int32_t streams, int32_t max_tracks, dy_stream_t stream);
+int32_t dy_track_step(const dy_track_desc* d, dy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
