@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256, 3) void conv3x3_hhead_kernel(const HheadArgs p
   __shared__ __attribute__((aligned(1024))) unsigned char smem[kHhStages * kHhStage + kHhMid + 4 * kHhTH * kHhTW * 4];
   unsigned char* const mid = smem + kHhStages * kHhStage;
   float* const dsm = reinterpret_cast<float*>(mid + kHhMid);  // [side 4][pixel 128]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (wave: a scalar, it enters scalar store offsets)
   const int lq = lane >> 4, lr = lane & 15;
 
   const int G = (int)gridDim.x;
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256, 3) void conv3x3_hhead_kernel(const HheadArgs p
   if (myTiles <= 0) return;
   const int nItems = myTiles * NCH;
 
-  // ---- register-resident weights: the wave's 16-cout fragment of the 3x3, and its fragment(s) of the 1x1 ----
+  // ---- register-resident weights: the wave's 16-cout fragment of the 3x3 ----
   u32x4 wreg[NCH][9];
   {
     const u32x4* wg = reinterpret_cast<const u32x4*>(p.w3);
@@ -106,17 +106,27 @@ __global__ __launch_bounds__(256, 3) void conv3x3_hhead_kernel(const HheadArgs p
       for (int t = 0; t < 9; ++t) wreg[c][t] = wg[((c * 9 + t) * 4 + wave) * 64 + lane];
   }
   const f32x4 bias3 = *reinterpret_cast<const f32x4*>(p.b3 + wave * 16 + lq * 4);
-  // the 1x1 fragments (2 x 16 B per lane) and its bias are re-read per tile (L2 / L1 hits): 12 registers the 3x3 loop needs more
-  const u32x4* const w1g = reinterpret_cast<const u32x4*>(p.w1) + (KIND == 1 ? wave * 64 : 0) + lane;
-  const float* const b1g = p.b1 + (KIND == 1 ? wave * 16 : 0) + lq * 4;
+  // The 1x1 fragments (2 x 16 B per lane) and its bias are re-read per tile (L2 / L1 hits): 12 registers the 3x3 loop needs more.
+  // r06: they are requested at the END of the tile's last item (load_w1, in front of tail_mid), so that the item's closing drain covers
+  // them.  Requested inside tail_out they were younger than the next item's halo DMA, and vmcnt retires in order: their first use made
+  // every wave wait for the DMA it had just issued, once per tile.
+  constexpr unsigned kOob = 0xfffffff0u;
+  constexpr int kVmcnt0 = 0x0f70;  // s_waitcnt vmcnt(0) alone (gfx9 encoding: expcnt 7 and lgkmcnt 15 = no wait)
+  const __amdgpu_buffer_rsrc_t w1rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w1), 0, NCH * (KIND == 1 ? 4 : 1) * 1024, 0x00020000);
+  const __amdgpu_buffer_rsrc_t b1rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.b1), 0, (KIND == 1 ? 64 : 16) * 4, 0x00020000);
+  u32x4 w1reg[NCH];
+  f32x4 bias1;
+  auto load_w1 = [&]() {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) w1reg[c] = __builtin_amdgcn_raw_buffer_load_b128(w1rs, lane * 16, (c * (KIND == 1 ? 4 : 1) + (KIND == 1 ? wave : 0)) * 1024, 0);
+    bias1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(b1rs, lq * 16, (KIND == 1 ? wave : 0) * 64, 0));
+  };
 
   // ---- halo loader (conv3x3_hreg.hip): buffer-addressed LDS-DMA, lane-constant offsets + a scalar tile offset, zeros by range check ----
   constexpr int NDMA = 4;
-  constexpr unsigned kOob = 0xfffffff0u;
   const unsigned pre = (unsigned)((p.W + 1) * p.ldx) * 2u;
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.x)) - pre, 0, p.x_bytes + pre, 0x00020000);
   unsigned rel[NDMA];
-  int hyx[NDMA];
 #pragma unroll
   for (int k = 0; k < NDMA; ++k) {
     const int s = (k * 4 + wave) * 64 + lane;
@@ -124,7 +134,6 @@ __global__ __launch_bounds__(256, 3) void conv3x3_hhead_kernel(const HheadArgs p
     const int hy = pix / kHhHW, hx = pix - hy * kHhHW;
     const bool dead = hx >= kHhTW + 2 || hy >= kHhHH;
     rel[k] = dead ? kOob : (unsigned)((hy * p.W + hx) * p.ldx + (part ^ ((hx >> 1) & 3)) * EPC) * 2u;
-    hyx[k] = hy | (hx << 8);
   }
   unsigned voff[NDMA];
   unsigned l_base = 0;
@@ -140,9 +149,15 @@ __global__ __launch_bounds__(256, 3) void conv3x3_hhead_kernel(const HheadArgs p
 #pragma unroll
       for (int k = 0; k < NDMA; ++k) voff[k] = rel[k];
     } else {
+      // the slots' halo pixels again, on border tiles only: as a table (or hoisted out of the tile loop, which the empty asm forbids) they cost
+      // four registers, and the class branch is then back in scratch (8-12 bytes)
+      int l4 = lane >> 2;
+      asm volatile("" : "+v"(l4));
 #pragma unroll
       for (int k = 0; k < NDMA; ++k) {
-        const int gy = y0 - 1 + (hyx[k] & 255), gx = x0 - 1 + (hyx[k] >> 8);
+        const int pix = (k * 4 + wave) * 16 + l4;
+        const int hy = pix / kHhHW, hx = pix - hy * kHhHW;
+        const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
         voff[k] = ((unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W) ? rel[k] : kOob;
       }
     }
@@ -214,35 +229,51 @@ __global__ __launch_bounds__(256, 3) void conv3x3_hhead_kernel(const HheadArgs p
   // the first form used it at once — every wave stood still for the round trip (1-2 us of an 11 us tile, in front of the item's MFMAs):
   // the class branch ran 17 % slower than the box branch for 1/6 of its 1x1 work.  Now the atomic is issued at the end of tail_out and
   // its value read at the start of the next one (or after the last tile): it returns under a whole item of matrix work.
-  int pv_base = 0, pv_n = 0, pv_n0 = 0, pv_total = 0;
+  // r06: nothing in tail_out waits for vector memory.  Every store goes through a per-image buffer descriptor (a scalar base from the tile id)
+  // with a 32-bit lane offset and a scalar offset; lanes outside the map / beyond nc get an out-of-range offset instead of a branch.  The
+  // 64-bit store pointers and the candidate state of the first form (two ballot masks, anchors, image) did not fit the 168 registers
+  // beside the 3x3 loop: 124 bytes of scratch per lane in the class branch, and every reload was a vector-memory load queued behind the halo DMA.
+  // What waits a tile: the two ballot masks and the tile id (scalars), best score / class per row (4 registers), the counter's return (1).
+  struct TileAt { int n, y0, x0; };
+  auto tile_at = [&](int tile) {
+    const int tx = tile % p.tilesX;
+    const int r_ = tile / p.tilesX;
+    return TileAt{r_ / p.tilesY, (r_ % p.tilesY) * kHhTH, tx * kHhTW};
+  };
+  const unsigned img_bytes = (unsigned)((4 + p.nc) * p.A) * 4u;
+  auto out_rsrc = [&](int n) { return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(p.out) + (size_t)n * img_bytes, 0, (int)img_bytes, 0x00020000); };
+  unsigned cm_bits = 0xffffu;  // classes_mask as bits (nc <= 16): no byte load behind the DMA in the filter
+  if constexpr (KIND == 2) {
+    if (p.keys != nullptr && p.cmask != nullptr) cm_bits = (unsigned)__ballot(lane < p.nc && p.cmask[lane < p.nc ? lane : 0] != 0);
+  }
+  int pv_tile = 0, pv_base = 0;
   unsigned long long pv_mk0 = 0ull, pv_mk1 = 0ull;
   float pv_best[2] = {0.f, 0.f};
-  int pv_bj[2] = {0, 0}, pv_a[2] = {0, 0};
+  int pv_bj[2] = {0, 0};
   auto flush_keys = [&]() {
-    if (pv_total != 0) {
-      const int base = __shfl(pv_base, 0);
-      const unsigned long long below = (1ull << lane) - 1ull;
+    if ((pv_mk0 | pv_mk1) != 0ull) {
+      const TileAt t = tile_at(pv_tile);
+      const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(p.keys + (size_t)t.n * p.P, 0, p.P * 8, 0x00020000);
+      const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc(p.cls + (size_t)t.n * p.A, 0, p.A * 2, 0x00020000);
+      const int base = __builtin_amdgcn_readfirstlane(pv_base);
+      const int n0 = __popcll(pv_mk0);
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const unsigned long long mk = j ? pv_mk1 : pv_mk0;
-        if ((mk >> lane) & 1ull) {
-          const int pos = base + (j ? pv_n0 : 0) + __popcll(mk & below);
-          p.keys[(size_t)pv_n * p.P + pos] = ((unsigned long long)(~__float_as_uint(pv_best[j])) << 32) | (unsigned long long)(unsigned)pv_a[j];
-          p.cls[(size_t)pv_n * p.A + pv_a[j]] = (unsigned short)pv_bj[j];
-        }
+        const bool hit = (mk >> lane) & 1ull;  // (lanes of quarter 0 only: lane == lr)
+        const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0u));
+        const int a_row = p.a0 + (t.y0 + wave * 2 + j) * p.W + t.x0;  // scalar: the anchor of the row's first pixel
+        const u32x2 key = {(unsigned)(a_row + lr), ~__float_as_uint(pv_best[j])};  // = ~score bits << 32 | anchor
+        __builtin_amdgcn_raw_buffer_store_b64(key, krs, hit ? below * 8u : kOob, (base + (j ? n0 : 0)) * 8, 0);
+        __builtin_amdgcn_raw_buffer_store_b16((unsigned short)pv_bj[j], crs, hit ? (unsigned)lr * 2u : kOob, a_row * 2, 0);
       }
-      pv_total = 0;
+      pv_mk0 = pv_mk1 = 0ull;
     }
   };
   auto tail_out = [&](int tile) {
     if constexpr (KIND == 2) flush_keys();
-    const int tx = tile % p.tilesX;
-    const int r_ = tile / p.tilesX;
-    const int ty = r_ % p.tilesY, n = r_ / p.tilesY;
-    u32x4 w1reg[NCH];
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) w1reg[c] = w1g[c * (KIND == 1 ? 4 : 1) * 64];
-    const f32x4 bias1 = *reinterpret_cast<const f32x4*>(b1g);
+    const TileAt t = tile_at(tile);
+    const __amdgpu_buffer_rsrc_t ors = out_rsrc(t.n);
     if constexpr (KIND == 1) {
       // 1x1: side `wave`, bins lq*4 .. +3 of pixel (o, lr); then DFL = softmax expectation over the side's 16 bins
 #pragma unroll
@@ -263,26 +294,26 @@ __global__ __launch_bounds__(256, 3) void conv3x3_hhead_kernel(const HheadArgs p
         num = wave_quarters_sum(num);
         if (lq == 0) dsm[wave * (kHhTH * kHhTW) + o * kHhTW + lr] = num * __builtin_amdgcn_rcpf(den);
       }
-      __syncthreads();
+      // (a raw barrier: __syncthreads' release fence also drains the vector-memory counter, that is the halo DMA issued a moment ago)
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
       // dist2bbox (tal.py:348-357) x stride: thread -> (pixel, axis); sides: 0 left, 1 top, 2 right, 3 bottom
       const int px = tid & 127, axis = tid >> 7;
       const int o = px >> 4, xi = px & 15;
-      const int yy = ty * kHhTH + o, xx = tx * kHhTW + xi;
-      if (yy < p.H && xx < p.W) {
-        const float d_lo = dsm[axis * (kHhTH * kHhTW) + px], d_hi = dsm[(axis + 2) * (kHhTH * kHhTW) + px];
-        const float ctr = (float)(axis == 0 ? xx : yy) + 0.5f;
-        const float lo = ctr - d_lo, hi = ctr + d_hi;
-        float* op = p.out + (size_t)n * (size_t)(4 + p.nc) * p.A + (size_t)(p.a0 + yy * p.W + xx);
-        op[(size_t)axis * p.A] = (lo + hi) * 0.5f * p.stride;
-        op[(size_t)(axis + 2) * p.A] = (hi - lo) * p.stride;
-      }
+      const int yy = t.y0 + o, xx = t.x0 + xi;
+      const float d_lo = dsm[axis * (kHhTH * kHhTW) + px], d_hi = dsm[(axis + 2) * (kHhTH * kHhTW) + px];
+      const float ctr = (float)(axis == 0 ? xx : yy) + 0.5f;
+      const float lo = ctr - d_lo, hi = ctr + d_hi;
+      const unsigned vo = (yy < p.H && xx < p.W) ? (unsigned)(axis * p.A + o * p.W + xi) * 4u : kOob;
+      const int so = (p.a0 + t.y0 * p.W + t.x0) * 4;  // scalar: the tile's first anchor
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint((lo + hi) * 0.5f * p.stride), ors, vo, so, 0);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint((hi - lo) * p.stride), ors, vo, so + 2 * p.A * 4, 0);
     } else {
       // 1x1 64 -> nc (one 16-cout fragment): the waves split the rows; sigmoid, scores out, first arg-max, candidate filter.
       // The wave's two rows are filtered together: ONE counter atomic (with return: the wave waits for it) per wave and tile
       // instead of one per row - on the P2 level every tile has candidates and the atomics of an image all hit one address.
-      float bestv[2];
-      int bjv[2], av[2];
       bool passv[2];
+      const unsigned sc_lane = (unsigned)((4 + lq * 4) * p.A + lr) * 4u;  // row 4 + lq * 4 of pred, column lr
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int o = wave * 2 + j;
@@ -290,20 +321,16 @@ __global__ __launch_bounds__(256, 3) void conv3x3_hhead_kernel(const HheadArgs p
 #pragma unroll
         for (int c2 = 0; c2 < NCH; ++c2)
           lg = Elem<T>::mma(w1reg[c2], *reinterpret_cast<const u32x4*>(mid + mid_r + c2 * (kHhTH * kHhTW * 64) + o * (kHhTW * 64)), lg);
-        const int yy = ty * kHhTH + o, xx = tx * kHhTW + lr;
-        const bool inside = yy < p.H && xx < p.W;
-        const int a = p.a0 + yy * p.W + xx;
-        float* op = p.out + (size_t)n * (size_t)(4 + p.nc) * p.A + (size_t)a;
+        const bool inside = t.y0 + o < p.H && t.x0 + lr < p.W;
+        const int a_row = p.a0 + (t.y0 + o) * p.W + t.x0;  // scalar
         float best = -1.f;
         int bj = 0x7fff;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int c = lq * 4 + e;
           const float pr = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(lg[e] * -1.4426950408889634f));
-          if (c < p.nc) {
-            if (inside) op[(size_t)(4 + c) * p.A] = pr;
-            if (pr > best) best = pr, bj = c;  // ascending c: the first maximum stays
-          }
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(pr), ors, (inside && c < p.nc) ? sc_lane : kOob, (a_row + e * p.A) * 4, 0);
+          if (c < p.nc && pr > best) best = pr, bj = c;  // ascending c: the first maximum stays
         }
 #pragma unroll
         for (int sh = 16; sh <= 32; sh <<= 1) {  // the four quarters hold classes 0-3, 4-7, 8-11, 12-15 of this pixel
@@ -311,19 +338,14 @@ __global__ __launch_bounds__(256, 3) void conv3x3_hhead_kernel(const HheadArgs p
           const int oj = __shfl_xor(bj, sh);
           if (ob > best || (ob == best && oj < bj)) best = ob, bj = oj;
         }
-        bool pass = p.keys != nullptr && inside && lq == 0 && best > p.conf;
-        if (pass && p.cmask) pass = p.cmask[bj] != 0;
-        bestv[j] = best, bjv[j] = bj, av[j] = a, passv[j] = pass;
+        passv[j] = inside && lq == 0 && best > p.conf && ((cm_bits >> (bj & 15)) & 1u) != 0u;
+        pv_best[j] = best, pv_bj[j] = bj;
       }
       if (p.keys != nullptr) {
-        const unsigned long long mk0 = __ballot(passv[0]), mk1 = __ballot(passv[1]);
-        const int n0 = __popcll(mk0), total = n0 + __popcll(mk1);
-        if (total != 0) {
-          if (lane == 0) pv_base = atomicAdd(p.counts + n, total);  // (value used by flush_keys, one tile later)
-          pv_n = n, pv_n0 = n0, pv_total = total, pv_mk0 = mk0, pv_mk1 = mk1;
-#pragma unroll
-          for (int j = 0; j < 2; ++j) pv_best[j] = bestv[j], pv_bj[j] = bjv[j], pv_a[j] = av[j];
-        }
+        pv_mk0 = __ballot(passv[0]), pv_mk1 = __ballot(passv[1]);
+        pv_tile = tile;
+        const int total = __popcll(pv_mk0) + __popcll(pv_mk1);
+        if (total != 0 && lane == 0) pv_base = atomicAdd(p.counts + t.n, total);  // (value used by flush_keys, one tile later)
       }
     }
   };
@@ -345,16 +367,17 @@ __global__ __launch_bounds__(256, 3) void conv3x3_hhead_kernel(const HheadArgs p
       }
       compute(c & 1, c);
       if (c == NCH - 1) {
+        load_w1();  // (the accumulators' last MFMAs and the SiLU pass cover the round trip; nothing of the 3x3 loop is live beside them but acc)
         tail_mid();
         pending = c_tile;
         c_tile += G;
       }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();  // next item's halo complete and visible; `mid` written (last chunk) / `dsm` free again
+      __builtin_amdgcn_s_waitcnt(kVmcnt0);  // (the builtin, not an asm: the compiler then knows that load_w1's registers and the counter's return are valid)
+      __syncthreads();  // next item's halo complete and visible; `mid` written (last chunk) / `dsm` free again; the 1x1 operands landed
     }
   }
   if (pending >= 0) tail_out(pending);
-  if constexpr (KIND == 2) flush_keys();
+  if constexpr (KIND == 2) flush_keys();  // (the only place where the counter's return is waited for: once per workgroup)
 }
 
 template <typename T>
@@ -410,6 +433,7 @@ int32_t branch_entry(const dy_branch_desc* d, dy_stream_t stream) {
   DY_REQUIRE(d->anchors > 0 && d->anchor0 >= 0 && d->anchor0 + d->h * d->w <= d->anchors, DY_ERR_INVALID_ARG, "dy_detect_branch_fused: the level's anchors [%d, %d) exceed A = %d",
              d->anchor0, d->anchor0 + d->h * d->w, d->anchors);
   DY_REQUIRE((long long)d->batch * d->h * d->w * d->ld_x * 2 < (1ll << 31), DY_ERR_UNSUPPORTED, "dy_detect_branch_fused: input view exceeds 2 GiB (32-bit element offsets)");
+  DY_REQUIRE((long long)(4 + d->nc) * d->anchors * 4 < (1ll << 31), DY_ERR_UNSUPPORTED, "dy_detect_branch_fused: one image of pred exceeds 2 GiB (32-bit store offsets)");
   HheadArgs a{};
   a.x = d->x, a.w3 = d->w3, a.b3 = d->b3, a.w1 = d->w1, a.b1 = d->b1, a.out = d->out;
   a.N = d->batch, a.H = d->h, a.W = d->w, a.ldx = d->ld_x, a.A = d->anchors, a.a0 = d->anchor0, a.nc = d->nc, a.stride = d->stride;
