@@ -139,6 +139,16 @@ class LossDesc(C.Structure):
     ]  # fmt: skip
 
 
+class C2fTailDesc(C.Structure):
+    """Mirror of ``dy_c2f_tail_desc``."""
+
+    _fields_ = [
+        ("t", _vp), ("buf", _vp), ("y", _vp), ("w3", _vp), ("b3", _vp), ("w1", _vp), ("b1", _vp),
+        ("batch", _i32), ("h", _i32), ("w", _i32), ("hidden", _i32), ("cout", _i32), ("n_bottlenecks", _i32), ("shortcut", _i32),
+        ("ld_t", _i32), ("ld_buf", _i32), ("ld_y", _i32), ("dtype", _i32), ("act_l2e", _i32),
+    ]  # fmt: skip
+
+
 class C2fDesc(C.Structure):
     """Mirror of ``dy_c2f_desc``."""
 
@@ -203,6 +213,8 @@ SIGNATURES = {
     "dy_conv_stats_written": (_i32, []),
     "dy_c2f_fused_supported": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "dy_c2f_fused": (_i32, [C.POINTER(C2fDesc), _vp]),
+    "dy_c2f_tail_fused_supported": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "dy_c2f_tail_fused": (_i32, [C.POINTER(C2fTailDesc), _vp]),
     "dy_stem2_fused_supported": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "dy_stem2_fused": (_i32, [C.POINTER(Stem2Desc), _vp]),
     "dy_stem_conv3x3s2_nchw": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -21,7 +21,7 @@ import warnings
 import torch
 
 from . import _lib
-from ._lib import DY_ACT_NONE, DY_ACT_SILU, DY_ACT_SILU_L2E, BnDesc, BranchDesc, C2fDesc, ConvDesc, DecodeDesc, HeadDecodeDesc, LossDesc, NmsDesc, Stem2Desc, TrackDesc, ValMatchDesc, check, lib
+from ._lib import DY_ACT_NONE, DY_ACT_SILU, DY_ACT_SILU_L2E, BnDesc, BranchDesc, C2fDesc, C2fTailDesc, ConvDesc, DecodeDesc, HeadDecodeDesc, LossDesc, NmsDesc, Stem2Desc, TrackDesc, ValMatchDesc, check, lib
 
 FP8 = torch.float8_e4m3fn  # OCP e4m3fn: gfx950's fp8 (MI300's fnuz is another encoding)
 # DY_F16X2 (include/dyolo.h): split float16 pairs, x ~= hi + lo * 2^-11 — the bar-exact precision on the 16-bit MFMA.  torch has no such
@@ -1681,4 +1681,50 @@ def c2f_fused(x: torch.Tensor, pk: PackedC2f, out: Optional[torch.Tensor] = None
     d.batch, d.h, d.w, d.cin, d.cin_lo, d.hidden, d.cout = n, h, w, pk.cin, c_lo, pk.hidden, pk.cout
     d.shortcut, d.dtype, d.act_l2e = int(pk.shortcut), dy_dtype(x.dtype), int(pk.act_l2e)
     _launch(lib().dy_c2f_fused, (C.byref(d),), keep=(d, x, x_lo, out, pk))
+    return out
+
+
+# ---- tail of a hidden-64 C2f block: last Bottleneck 3x3 + closing 1x1 -----------------------------------------------------
+
+
+class PackedC2fTail:
+    """Folded + packed weights for ``dy_c2f_tail_fused``: (w, b) of the last Bottleneck's cv2 (3x3) and of the block's closing cv2 (1x1)."""
+
+    def __init__(self, mcv2, cv2, n: int, shortcut: bool, dtype: torch.dtype, device, act_l2e: bool = False):
+        """``act_l2e``: both (w, b) pairs were folded for the log2(e)-scaled activation domain (biases times log2 e)."""
+        (w3, b3), (w1, b1) = mcv2, cv2
+        self.hidden, self.cout, self.n = w3.shape[0], w1.shape[0], int(n)
+        if w1.shape[1] != (2 + self.n) * self.hidden:
+            raise ValueError("PackedC2fTail: cv2 must read (2 + n) * hidden channels")
+        p3 = PackedConv(w3, b3, 1, 1, 1, True, dtype, device, halo=True)
+        if p3.layout != _lib.DY_WLAYOUT_HALO3X3:
+            raise ValueError("PackedC2fTail: the Bottleneck convolution did not pack as DY_WLAYOUT_HALO3X3")
+        self.w3, self.b3 = p3.w, p3.b
+        self.w1, self.b1 = pack_frag1x1(w1, b1, dtype, device)
+        self.shortcut, self.dtype, self.act_l2e = bool(shortcut), dtype, bool(act_l2e)
+
+
+def c2f_tail_fused_supported(hidden: int, cout: int, n: int, dtype: torch.dtype, k1: int = 3, k2: int = 3, groups: int = 1) -> bool:
+    return dtype in (torch.bfloat16, torch.float16) and bool(lib().dy_c2f_tail_fused_supported(hidden, cout, n, k1, k2, groups, dy_dtype(dtype)))
+
+
+def c2f_tail_fused(t: torch.Tensor, ybuf: torch.Tensor, pk: PackedC2fTail, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """SiLU(conv3x3(t)) (+ the last group of ``ybuf`` with the shortcut) and the closing 1x1 over cat(ybuf, that) in one
+    ``dy_c2f_tail_fused`` launch.  t: (N, hidden, H, W), the last Bottleneck's cv1 output; ybuf: (N, (1 + n) * hidden, H, W), the
+    head y0 | .. | y_n of the concat buffer; out: (N, cout, H, W), possibly a channel slice of a wider buffer."""
+    require_device(t, "c2f tail input")
+    require_device(ybuf, "c2f tail concat buffer")
+    n, c, h, w = t.shape
+    if t.dtype != pk.dtype or ybuf.dtype != pk.dtype or c != pk.hidden or tuple(ybuf.shape) != (n, (1 + pk.n) * pk.hidden, h, w):
+        raise ValueError("c2f_tail_fused: inputs do not match the packed block")
+    if out is None:
+        out = alloc_nhwc(n, pk.cout, h, w, t.dtype, t.device)
+    elif tuple(out.shape) != (n, pk.cout, h, w) or out.dtype != t.dtype:
+        raise ValueError("c2f_tail_fused: out must be a (N, cout, H, W) view of the inputs' dtype")
+    d = C2fTailDesc()
+    (d.t, d.ld_t), (d.buf, d.ld_buf), (d.y, d.ld_y) = view_params(t), view_params(ybuf), view_params(out)
+    d.w3, d.b3, d.w1, d.b1 = pk.w3.data_ptr(), pk.b3.data_ptr(), pk.w1.data_ptr(), pk.b1.data_ptr()
+    d.batch, d.h, d.w, d.hidden, d.cout, d.n_bottlenecks = n, h, w, pk.hidden, pk.cout, pk.n
+    d.shortcut, d.dtype, d.act_l2e = int(pk.shortcut), dy_dtype(t.dtype), int(pk.act_l2e)
+    _launch(lib().dy_c2f_tail_fused, (C.byref(d),), keep=(d, t, ybuf, out, pk))
     return out

@@ -59,7 +59,12 @@ class C2f(nn.Module):
         self.cv2 = Conv((2 + n) * self.c, c2, 1)
         self.m = nn.ModuleList(Bottleneck(self.c, self.c, shortcut, g, k=((3, 3), (3, 3)), e=1.0) for _ in range(n))
 
-    fuse_block = True  # one-kernel execution where dy_c2f_fused is built for the shape (the stride-4 backbone and neck blocks)
+    # one-kernel execution where dy_c2f_fused is built for the shape (the stride-4 backbone and neck blocks); the last Bottleneck's 3x3 +
+    # the closing 1x1 in one launch where dy_c2f_tail_fused is (the hidden-64 blocks at stride 8)
+    fuse_block = True
+    # Which forms of dy_c2f_tail_fused are dispatched, by (n, shortcut): what was measured below the sum of its own two launches
+    # (profiles/README.md, round 7) — the forms Drone-YOLO-s has.  The kernel is built for the other two as well.
+    fuse_tail_forms = ((1, False), (2, True))
 
     def _packed_block(self, dtype, device):
         convs = (self.cv1, self.m[0].cv1, self.m[0].cv2, self.cv2)
@@ -71,6 +76,22 @@ class C2f(nn.Module):
             cache = (key, H.PackedC2f(*folded, shortcut=self.m[0].add, dtype=dtype, device=device, act_l2e=H.scaled_domain()))
             self.__dict__["_block_cache"] = cache
         return cache[1]
+
+    def _packed_tail(self, dtype, device):
+        convs = (self.m[-1].cv2, self.cv2)
+        key = (dtype, str(device), H.scaled_domain(),
+               tuple((c.conv.weight.data_ptr(), c.conv.weight._version, c.bn.weight._version, c.bn.running_var._version) for c in convs))
+        cache = self.__dict__.get("_tail_cache")
+        if cache is None or cache[0] != key:
+            folded = [H.domain_fold(*fold_conv_bn(c.conv.weight, c.conv.bias, c.bn), True)[:2] for c in convs]
+            cache = (key, H.PackedC2fTail(*folded, n=len(self.m), shortcut=self.m[-1].add, dtype=dtype, device=device, act_l2e=H.scaled_domain()))
+            self.__dict__["_tail_cache"] = cache
+        return cache[1]
+
+    def _tail_fusable(self, dtype):
+        last = self.m[-1]
+        return (len(self.m), bool(last.add)) in self.fuse_tail_forms and H.c2f_tail_fused_supported(
+            self.c, self.cv2.conv.out_channels, len(self.m), dtype, last.cv1.conv.kernel_size[0], last.cv2.conv.kernel_size[0], last.cv2.conv.groups)
 
     def forward(self, x, out=None, **kw):
         """cv1 -> [y0 | y1]; y_{i+2} = m_i(y_{i+1}); cv2(cat(y)).  One buffer holds every y_i.
@@ -92,6 +113,15 @@ class C2f(nn.Module):
         n, _, hb, wb = x.shape
         h, w = (2 * hb, 2 * wb) if kw.get("up2x") else (hb, wb)
         c = self.c
+        if self.fuse_block and len(self.m) and self._tail_fusable(x.dtype):
+            # the last Bottleneck's output never reaches memory: the buffer ends with that Bottleneck's input
+            nm = len(self.m)
+            ybuf = H.alloc_nhwc(n, (1 + nm) * c, h, w, x.dtype, x.device)
+            self.cv1(x, out=ybuf[:, : 2 * c], **kw)
+            for i, m in enumerate(self.m[:-1]):
+                m(ybuf[:, (1 + i) * c : (2 + i) * c], out=ybuf[:, (2 + i) * c : (3 + i) * c])
+            t = self.m[-1].cv1(ybuf[:, nm * c :])
+            return H.c2f_tail_fused(t, ybuf, self._packed_tail(x.dtype, x.device), out=out)
         ybuf = H.alloc_nhwc(n, (2 + len(self.m)) * c, h, w, x.dtype, x.device)
         self.cv1(x, out=ybuf[:, : 2 * c], **kw)
         for i, m in enumerate(self.m):

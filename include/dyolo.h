@@ -271,6 +271,31 @@ typedef struct dy_c2f_desc {
 int32_t dy_c2f_fused_supported(int32_t cin, int32_t cin_lo, int32_t hidden, int32_t cout, int32_t n_bottlenecks, int32_t dtype);
 int32_t dy_c2f_fused(const dy_c2f_desc* d, dy_stream_t stream);
 
+/* ---- tail of a hidden-64 C2f block: last Bottleneck 3x3 + closing 1x1 in ONE kernel ------------------------
+ * Replaces, 16-bit storage: the last Bottleneck's cv2 (Conv 3x3 hidden -> hidden, block.py:337-350, with the shortcut add
+ * x + cv2(cv1(x)) when `shortcut`) and C2f.forward's closing cv2 (Conv 1x1 (2 + n) * hidden -> cout over cat(y), block.py:237-242),
+ * each Conv = SiLU(conv + folded BatchNorm bias) (conv.py:53-55), for the stride-8 blocks of Drone-YOLO-s (yaml layers 4, 15, 21).
+ * t: NHWC (batch, h, w, hidden) pitch ld_t, the output of the last Bottleneck's cv1.  buf: the head of the concat buffer,
+ * NHWC (batch, h, w, (1 + n) * hidden) pitch ld_buf = y0 | y1 | .. | y_n (y_n is the shortcut's source); the block's last
+ * hidden channels (the fused 3x3's output) never reach memory.  y: NHWC (batch, h, w, cout) pitch ld_y (may be a channel slice).
+ * w3 / b3: DY_WLAYOUT_HALO3X3 of (hidden, hidden, 3, 3), fp32[hidden].  w1 / b1: DY_WLAYOUT_FRAG1X1 of (cout, (2 + n) * hidden) in
+ * C2f.cv2's input order (buffer channels first, the 3x3's output last), fp32[cout].  Intermediates are rounded to `dtype` where the
+ * layer-by-layer path rounds them and summed in its order: the result is that of the two dy_conv2d_nhwc calls, bit for bit.
+ * Built for hidden 64, cout 128, n 1 or 2, 3x3 / 3x3 Bottlenecks with groups 1, DY_BF16 / DY_F16 (dy_c2f_tail_fused_supported tells). */
+typedef struct dy_c2f_tail_desc {
+  const void* t;
+  const void* buf;
+  void* y;
+  const void* w3;
+  const float* b3;
+  const void* w1;
+  const float* b1;
+  int32_t batch, h, w, hidden, cout, n_bottlenecks, shortcut, ld_t, ld_buf, ld_y, dtype;
+  int32_t act_l2e; /* 1: both SiLUs are DY_ACT_SILU_L2E (inputs, output and biases in the log2(e)-scaled domain) */
+} dy_c2f_tail_desc;
+int32_t dy_c2f_tail_fused_supported(int32_t hidden, int32_t cout, int32_t n_bottlenecks, int32_t ksize1, int32_t ksize2, int32_t groups, int32_t dtype);
+int32_t dy_c2f_tail_fused(const dy_c2f_tail_desc* d, dy_stream_t stream);
+
 /* Fused stem.  Replaces in one pass: the predictor's dtype/layout step for tensor sources
  * (engine/predictor.py:118-136) AND the model's first layer Conv(cin<=3, cout, 3, 2) (nn/modules/conv.py:37-55,
  * yolov8-p2-repvgg.yaml layer 0), so the image is never materialised in NHWC.
