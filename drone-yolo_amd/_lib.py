@@ -149,6 +149,16 @@ class C2fTailDesc(C.Structure):
     ]  # fmt: skip
 
 
+class C2fFrontDesc(C.Structure):
+    """Mirror of ``dy_c2f_front_desc``."""
+
+    _fields_ = [
+        ("x", _vp), ("other", _vp), ("y", _vp), ("w3", _vp), ("b3", _vp), ("w1", _vp), ("b1", _vp),
+        ("batch", _i32), ("h", _i32), ("w", _i32), ("cin", _i32), ("cmid", _i32), ("c_other", _i32), ("cout", _i32),
+        ("ld_x", _i32), ("ld_other", _i32), ("ld_y", _i32), ("act", _i32), ("dtype", _i32),
+    ]  # fmt: skip
+
+
 class C2fDesc(C.Structure):
     """Mirror of ``dy_c2f_desc``."""
 
@@ -215,6 +225,8 @@ SIGNATURES = {
     "dy_c2f_fused": (_i32, [C.POINTER(C2fDesc), _vp]),
     "dy_c2f_tail_fused_supported": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "dy_c2f_tail_fused": (_i32, [C.POINTER(C2fTailDesc), _vp]),
+    "dy_c2f_front_fused_supported": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "dy_c2f_front_fused": (_i32, [C.POINTER(C2fFrontDesc), _vp]),
     "dy_stem2_fused_supported": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "dy_stem2_fused": (_i32, [C.POINTER(Stem2Desc), _vp]),
     "dy_stem_conv3x3s2_nchw": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),

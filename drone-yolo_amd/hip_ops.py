@@ -21,7 +21,7 @@ import warnings
 import torch
 
 from . import _lib
-from ._lib import DY_ACT_NONE, DY_ACT_SILU, DY_ACT_SILU_L2E, BnDesc, BranchDesc, C2fDesc, C2fTailDesc, ConvDesc, DecodeDesc, HeadDecodeDesc, LossDesc, NmsDesc, Stem2Desc, TrackDesc, ValMatchDesc, check, lib
+from ._lib import DY_ACT_NONE, DY_ACT_SILU, DY_ACT_SILU_L2E, BnDesc, BranchDesc, C2fDesc, C2fFrontDesc, C2fTailDesc, ConvDesc, DecodeDesc, HeadDecodeDesc, LossDesc, NmsDesc, Stem2Desc, TrackDesc, ValMatchDesc, check, lib
 
 FP8 = torch.float8_e4m3fn  # OCP e4m3fn: gfx950's fp8 (MI300's fnuz is another encoding)
 # DY_F16X2 (include/dyolo.h): split float16 pairs, x ~= hi + lo * 2^-11 — the bar-exact precision on the 16-bit MFMA.  torch has no such
@@ -1727,4 +1727,57 @@ def c2f_tail_fused(t: torch.Tensor, ybuf: torch.Tensor, pk: PackedC2fTail, out: 
     d.batch, d.h, d.w, d.hidden, d.cout, d.n_bottlenecks = n, h, w, pk.hidden, pk.cout, pk.n
     d.shortcut, d.dtype, d.act_l2e = int(pk.shortcut), dy_dtype(t.dtype), int(pk.act_l2e)
     _launch(lib().dy_c2f_tail_fused, (C.byref(d),), keep=(d, t, ybuf, out, pk))
+    return out
+
+
+# ---- front of a hidden-64 C2f block: the stride-2 3x3 in front of it + the opening 1x1 ------------------------------------
+
+
+class PackedC2fFront:
+    """Folded + packed weights for ``dy_c2f_front_fused``: (w, b) of the stride-2 3x3 in front of the block and of the block's cv1 (1x1)."""
+
+    def __init__(self, conv3, cv1, act: int, dtype: torch.dtype, device):
+        """``act``: the activation code both convolutions were folded for (``domain_fold``): DY_ACT_SILU or DY_ACT_SILU_L2E."""
+        (w3, b3), (w1, b1) = conv3, cv1
+        self.cin, self.cmid, self.cout = w3.shape[1], w3.shape[0], w1.shape[0]
+        self.c_other = w1.shape[1] - self.cmid
+        if self.c_other < 0 or tuple(w3.shape[2:]) != (3, 3):
+            raise ValueError("PackedC2fFront: cv1 must read the 3x3's output first (+ the other Concat source)")
+        p3 = PackedConv(w3, b3, 2, 1, 1, act, dtype, device, halo=True)
+        if p3.layout != _lib.DY_WLAYOUT_HALO3X3:
+            raise ValueError("PackedC2fFront: the stride-2 convolution did not pack as DY_WLAYOUT_HALO3X3")
+        self.w3, self.b3 = p3.w, p3.b
+        self.w1, self.b1 = pack_frag1x1(w1, b1, dtype, device)
+        self.act, self.dtype = int(act), dtype
+
+
+def c2f_front_fused_supported(cin: int, cmid: int, c_other: int, cout: int, dtype: torch.dtype, act: int = DY_ACT_SILU, k: int = 3, stride: int = 2, groups: int = 1) -> bool:
+    return dtype in (torch.bfloat16, torch.float16) and bool(lib().dy_c2f_front_fused_supported(cin, cmid, c_other, cout, k, stride, groups, int(act), dy_dtype(dtype)))
+
+
+def c2f_front_fused(x: torch.Tensor, pk: PackedC2fFront, other: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """SiLU(conv3x3 stride 2 (x)) and the C2f's opening 1x1 over cat(that, other) in one ``dy_c2f_front_fused`` launch.  x: (N, cin, H, W);
+    other: (N, c_other, Ho, Wo), the second source of the Concat in front of the block (None without one); out: (N, cout, Ho, Wo), possibly
+    a channel slice of a wider buffer."""
+    require_device(x, "c2f front input")
+    n, c, h, w = x.shape
+    ho, wo = conv_out_hw(h, w, 3, 2, 1)
+    if x.dtype != pk.dtype or c != pk.cin or (other is None) != (pk.c_other == 0):
+        raise ValueError("c2f_front_fused: inputs do not match the packed pair")
+    if other is not None:
+        require_device(other, "c2f front second source")
+        if tuple(other.shape) != (n, pk.c_other, ho, wo) or other.dtype != pk.dtype:
+            raise ValueError("c2f_front_fused: other must be a (N, c_other, Ho, Wo) view of the input's dtype")
+    if out is None:
+        out = alloc_nhwc(n, pk.cout, ho, wo, x.dtype, x.device)
+    elif tuple(out.shape) != (n, pk.cout, ho, wo) or out.dtype != x.dtype:
+        raise ValueError("c2f_front_fused: out must be a (N, cout, Ho, Wo) view of the input's dtype")
+    d = C2fFrontDesc()
+    (d.x, d.ld_x), (d.y, d.ld_y) = view_params(x), view_params(out)
+    if other is not None:
+        d.other, d.ld_other = view_params(other)
+    d.w3, d.b3, d.w1, d.b1 = pk.w3.data_ptr(), pk.b3.data_ptr(), pk.w1.data_ptr(), pk.b1.data_ptr()
+    d.batch, d.h, d.w, d.cin, d.cmid, d.c_other, d.cout = n, h, w, pk.cin, pk.cmid, pk.c_other, pk.cout
+    d.act, d.dtype = pk.act, dy_dtype(x.dtype)
+    _launch(lib().dy_c2f_front_fused, (C.byref(d),), keep=(d, x, other, out, pk))
     return out

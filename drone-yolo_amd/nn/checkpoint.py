@@ -145,7 +145,7 @@ _REF_PATHS = {"Conv": "ultralytics.nn.modules.conv", "DWConv": "ultralytics.nn.m
               "DFL": "ultralytics.nn.modules.block", "SPPF": "ultralytics.nn.modules.block", "C2f": "ultralytics.nn.modules.block",
               "Bottleneck": "ultralytics.nn.modules.block", "RepVGGBlock": "ultralytics.nn.modules.block", "SEBlock": "ultralytics.nn.modules.block",
               "Detect": "ultralytics.nn.modules.head", "DetectionModel": "ultralytics.nn.tasks", "BaseModel": "ultralytics.nn.tasks"}
-_DROP_ATTRS = ("_packed", "_block_cache", "_tail_cache", "_first_cache", "_stem2_cache", "_sig_tensors", "_weights_epoch", "_place", "_srcs", "_virtual", "_skip",
+_DROP_ATTRS = ("_packed", "_block_cache", "_tail_cache", "_front_cache", "_first_cache", "_stem2_cache", "_sig_tensors", "_weights_epoch", "_place", "_srcs", "_virtual", "_skip", "_front",
                "_consumers0", "_out_ch", "_cum_stride", "criterion", "train_dtype", "args", "fused_nms", "fuse_tail")
 
 

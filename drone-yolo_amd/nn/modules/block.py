@@ -65,6 +65,10 @@ class C2f(nn.Module):
     # Which forms of dy_c2f_tail_fused are dispatched, by (n, shortcut): what was measured below the sum of its own two launches
     # (profiles/README.md, round 7) — the forms Drone-YOLO-s has.  The kernel is built for the other two as well.
     fuse_tail_forms = ((1, False), (2, True))
+    # Which forms of dy_c2f_front_fused are dispatched: "A" (a stride-2 3x3 64 -> 128 straight in front of cv1) and "B" (64 -> 64 as the
+    # first source of a two-source Concat in front of it) — what was measured below the sum of its own two launches (profiles/README.md,
+    # round 8).  The kernel is built and tested for both.
+    fuse_front_forms = ("A", "B")
 
     def _packed_block(self, dtype, device):
         convs = (self.cv1, self.m[0].cv1, self.m[0].cv2, self.cv2)
@@ -88,22 +92,71 @@ class C2f(nn.Module):
             self.__dict__["_tail_cache"] = cache
         return cache[1]
 
+    @staticmethod
+    def _down3x3(prod):
+        """(cin, cout) of ``prod`` when it is a plain 3x3 stride-2 pad-1 SiLU convolution (Conv / RepVGGBlock without SE), else None."""
+        if isinstance(prod, RepVGGBlock):
+            c = prod.rbr_reparam if hasattr(prod, "rbr_reparam") else prod.rbr_dense.conv
+            ok = isinstance(prod.se, nn.Identity) and prod.stride == 2 and prod.padding == 1 and prod.groups == 1
+            return (c.in_channels, c.out_channels) if ok else None
+        if type(prod) is Conv:
+            c = prod.conv
+            ok = c.kernel_size == (3, 3) and c.stride == (2, 2) and c.padding == (1, 1) and c.groups == 1 and isinstance(prod.act, nn.SiLU)
+            return (c.in_channels, c.out_channels) if ok else None
+        return None
+
+    def front_fusable(self, prod, c_other, dtype) -> bool:
+        """Whether ``prod`` (the layer whose output only this block's cv1 reads, with ``c_other`` channels of a second Concat source
+        behind it) runs inside cv1's launch: inference, 16-bit storage, a dispatched form, a shape ``dy_c2f_front_fused`` is built for."""
+        io = self._down3x3(prod)
+        if io is None or self.training or prod.training or not self.fuse_block or ("B" if c_other else "A") not in self.fuse_front_forms:
+            return False
+        if self.cv1.conv.in_channels != io[1] + c_other or getattr(prod, "_raw_input", False):
+            return False
+        act = H.DY_ACT_SILU_L2E if H.scaled_domain() else H.DY_ACT_SILU  # what domain_fold hands both convolutions
+        return isinstance(self.cv1.act, nn.SiLU) and H.c2f_front_fused_supported(io[0], io[1], c_other, self.cv1.conv.out_channels, dtype, act)
+
+    def _packed_front(self, prod, dtype, device):
+        srcs = list(prod.parameters()) + list(prod.buffers()) + list(self.cv1.parameters()) + list(self.cv1.buffers())
+        key = (dtype, str(device), H.scaled_domain(), tuple((t.data_ptr(), t._version) for t in srcs))
+        cache = self.__dict__.get("_front_cache")
+        if cache is None or cache[0] != key:
+            w3, b3, act = prod._folded()
+            w1, b1, act1 = self.cv1._folded()
+            assert act == act1
+            cache = (key, H.PackedC2fFront((w3, b3), (w1, b1), act, dtype, device))
+            self.__dict__["_front_cache"] = cache
+        return cache[1]
+
+    def _cv1(self, x, out, front, kw):
+        """[y0 | y1] into ``out``: cv1 on ``x``, or — ``front`` = (producer, other Concat source or None) — the producer's stride-2 3x3 on
+        ``x`` and cv1 on its output (| other) in one launch."""
+        if front is None:
+            return self.cv1(x, out=out, **kw)
+        prod, other = front
+        return H.c2f_front_fused(x, self._packed_front(prod, x.dtype, x.device), other=other, out=out)
+
     def _tail_fusable(self, dtype):
         last = self.m[-1]
         return (len(self.m), bool(last.add)) in self.fuse_tail_forms and H.c2f_tail_fused_supported(
             self.c, self.cv2.conv.out_channels, len(self.m), dtype, last.cv1.conv.kernel_size[0], last.cv2.conv.kernel_size[0], last.cv2.conv.groups)
 
-    def forward(self, x, out=None, **kw):
+    def forward(self, x, out=None, front=None, **kw):
         """cv1 -> [y0 | y1]; y_{i+2} = m_i(y_{i+1}); cv2(cat(y)).  One buffer holds every y_i.
 
         ``kw`` (x2= / up2x=) is forwarded to cv1 so that a Concat(+Upsample) in front of this block
-        can be folded into cv1's gather.
+        can be folded into cv1's gather.  ``front`` = (producer module, other Concat source or None): ``x`` is the INPUT of the stride-2
+        3x3 in front of this block, which runs inside cv1's launch (the caller asked ``front_fusable``).
         """
         if self.training:
-            return _train_forward(self, "c2f_train", x, out=out, **kw)
+            return _train_forward(self, "c2f_train", x, out=out, front=front, **kw)
         if kw.pop("fp8_internal", False):
+            if front is not None:
+                raise NotImplementedError("C2f: fp8 internals take the block's own input")
             return self._forward_fp8_internal(x, out)
-        if self.fuse_block and len(self.m) == 1:
+        if front is not None and kw:
+            raise NotImplementedError(f"C2f: front= does not combine with {sorted(kw)}")
+        if self.fuse_block and len(self.m) == 1 and front is None:
             cout = self.cv2.conv.out_channels
             if not kw and H.c2f_fused_supported(x.shape[1], self.c, cout, 1, x.dtype):
                 return H.c2f_fused(x, self._packed_block(x.dtype, x.device), out=out)
@@ -112,18 +165,20 @@ class C2f(nn.Module):
                 return H.c2f_fused(x2, self._packed_block(x.dtype, x.device), out=out, x_lo=x)  # Upsample + Concat + C2f in one launch
         n, _, hb, wb = x.shape
         h, w = (2 * hb, 2 * wb) if kw.get("up2x") else (hb, wb)
+        if front is not None:
+            h, w = H.conv_out_hw(hb, wb, 3, 2, 1)
         c = self.c
         if self.fuse_block and len(self.m) and self._tail_fusable(x.dtype):
             # the last Bottleneck's output never reaches memory: the buffer ends with that Bottleneck's input
             nm = len(self.m)
             ybuf = H.alloc_nhwc(n, (1 + nm) * c, h, w, x.dtype, x.device)
-            self.cv1(x, out=ybuf[:, : 2 * c], **kw)
+            self._cv1(x, ybuf[:, : 2 * c], front, kw)
             for i, m in enumerate(self.m[:-1]):
                 m(ybuf[:, (1 + i) * c : (2 + i) * c], out=ybuf[:, (2 + i) * c : (3 + i) * c])
             t = self.m[-1].cv1(ybuf[:, nm * c :])
             return H.c2f_tail_fused(t, ybuf, self._packed_tail(x.dtype, x.device), out=out)
         ybuf = H.alloc_nhwc(n, (2 + len(self.m)) * c, h, w, x.dtype, x.device)
-        self.cv1(x, out=ybuf[:, : 2 * c], **kw)
+        self._cv1(x, ybuf[:, : 2 * c], front, kw)
         for i, m in enumerate(self.m):
             m(ybuf[:, (1 + i) * c : (2 + i) * c], out=ybuf[:, (2 + i) * c : (3 + i) * c])
         return self.cv2(ybuf, out=out)
@@ -255,12 +310,16 @@ class RepVGGBlock(_PackedMixin, nn.Module):
             self.deploy = True
             self.invalidate_packed()
 
-    def _pack(self, dtype, device, cin_pad=None) -> H.PackedConv:
+    def _folded(self):
+        """(weight, bias, activation code) of the deploy form, for the activation domain in force (``H.domain_fold``)."""
         if hasattr(self, "rbr_reparam"):
             w, b = self.rbr_reparam.weight, self.rbr_reparam.bias
         else:
             w, b = self.get_equivalent_kernel_bias()
-        w, b, act = H.domain_fold(w, b, True, raw_input=getattr(self, "_raw_input", False))
+        return H.domain_fold(w, b, True, raw_input=getattr(self, "_raw_input", False))
+
+    def _pack(self, dtype, device, cin_pad=None) -> H.PackedConv:
+        w, b, act = self._folded()
         return H.PackedConv(w, b, self.stride, self.padding, self.groups, act, dtype, device, cin_pad=cin_pad)
 
     def forward(self, inputs, out=None):

@@ -111,14 +111,18 @@ class Conv(_PackedMixin, nn.Module):
         if not isinstance(self.act, (nn.SiLU, nn.Identity)):
             raise NotImplementedError("only SiLU / identity activations are built into the conv epilogue")
 
-    def _pack(self, dtype, device, cin_pad=None) -> H.PackedConv:
+    def _folded(self):
+        """(weight, bias, activation code) with BatchNorm folded in, for the activation domain in force (``H.domain_fold``)."""
         w, b = fold_conv_bn(self.conv.weight, self.conv.bias, self.bn) if hasattr(self, "bn") else (
             self.conv.weight, self.conv.bias)
-        c = self.conv
         if b is None:
             b = torch.zeros(w.shape[0], device=w.device)
         # _raw_input: set by the model executor on the layer that reads the image (its input is not in the scaled domain)
-        w, b, act = H.domain_fold(w, b, isinstance(self.act, nn.SiLU), raw_input=getattr(self, "_raw_input", False))
+        return H.domain_fold(w, b, isinstance(self.act, nn.SiLU), raw_input=getattr(self, "_raw_input", False))
+
+    def _pack(self, dtype, device, cin_pad=None) -> H.PackedConv:
+        w, b, act = self._folded()
+        c = self.conv
         return H.PackedConv(w, b, c.stride[0], c.padding[0], c.groups, act, dtype, device, cin_pad=cin_pad)
 
     def forward(self, x, out=None, residual=None, **kw):

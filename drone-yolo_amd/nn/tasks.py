@@ -214,6 +214,28 @@ class BaseModel(nn.Module):
                 if s not in self._place and n_cat == 1 and not isinstance(layers[s], (Concat, Detect, nn.Sequential)):
                     self._place[s] = (m.i, off)
                 off += c
+        # A stride-2 3x3 whose output only a C2f's cv1 reads — directly, or as the first source of a two-source Concat — can run inside
+        # that cv1's launch (dy_c2f_front_fused): C2f layer -> (producer, its input, Concat layer or None, other source or None).  The
+        # structure is decided here; shapes, dtype and mode per pass (_front_active).  Stride-8 blocks only: that is where the forms were
+        # measured against their two launches (the same channel counts occur at stride 16 of scale n, on maps a quarter the size).
+        self._front: Dict[int, tuple] = {}
+        for m in layers:
+            if not isinstance(m, C2f) or len(self._srcs[m.i]) != 1 or self._cum_stride[m.i] != 8:
+                continue
+            s, cat, other = self._srcs[m.i][0], None, None
+            if isinstance(layers[s], Concat) and s not in self._virtual and len(self._srcs[s]) == 2 and consumers[s] == [m.i]:
+                cat, (s, other) = s, self._srcs[s]
+            if s > 1 and s != other and consumers[s] == [m.i if cat is None else cat] and len(self._srcs[s]) == 1 and C2f._down3x3(layers[s]) is not None:
+                self._front[m.i] = (s, self._srcs[s][0], cat, other)
+
+    fuse_front = True  # a stride-2 3x3 in front of a stride-8 C2f inside the block's cv1 launch where dy_c2f_front_fused is built for it
+
+    def _front_active(self, dtype, f8) -> Dict[int, tuple]:
+        """The entries of ``_front`` that fire in a pass with ``dtype`` storage (16-bit, eval, no fp8 internals on the block)."""
+        if not self.fuse_front or self.training or dtype not in (torch.bfloat16, torch.float16):
+            return {}
+        return {i: e for i, e in self._front.items()
+                if i not in f8 and self.model[i].front_fusable(self.model[e[0]], 0 if e[3] is None else self._out_ch[e[3]], dtype)}
 
     def _scaled_domain_for(self, dtype) -> bool:
         """Whether a pass in ``dtype`` runs in the log2(e)-scaled activation domain (hip_ops.scaled_activations): 16-bit and fp8 storage
@@ -261,14 +283,19 @@ class BaseModel(nn.Module):
         f8 = self.__dict__.get("fp8_layers") or frozenset()
         if f8 and x.dtype != torch.float16:
             raise NotImplementedError("a mixed fp8 plan (fp8_layers) runs on float16 storage")
+        front = self._front_active(x.dtype, f8)
+        front_skip = {j for e in front.values() for j in (e[0], e[2]) if j is not None}  # producers and Concats that launch nothing
         for m in self.model:
             i = m.i
-            if i in self._skip:
+            if i in self._skip or i in front_skip:
                 y.append(None)
                 continue
             src = self._srcs[i]
             kw = {}
-            if isinstance(m, C2f) and src[0] in self._virtual:
+            if i in front:  # the stride-2 3x3 in front (and the Concat behind it) inside the block's cv1 launch
+                prod, pin, _, other = front[i]
+                xin, kw = y[pin], {"front": (self.model[prod], None if other is None else y[other])}
+            elif isinstance(m, C2f) and src[0] in self._virtual:
                 lo, skip = self._virtual[src[0]]
                 xin, kw = y[lo], {"x2": y[skip], "up2x": True}
             elif isinstance(m.f, int):
@@ -279,7 +306,7 @@ class BaseModel(nn.Module):
                 if not isinstance(m, C2f) or kw:
                     raise NotImplementedError(f"fp8_layers: layer {i} ({type(m).__name__}) — fp8 internals are built for C2f blocks with one plain input")
                 kw["fp8_internal"] = True
-            if i in self._place:
+            if i in self._place and self._place[i][0] not in front_skip:  # (a Concat folded into dy_c2f_front_fused has no buffer)
                 ci, off = self._place[i]
                 if ci not in cat_bufs:
                     n = x.shape[0]
@@ -303,7 +330,8 @@ class BaseModel(nn.Module):
             elif i == 1 and fused_stem2 is not None:
                 out = fused_stem2
             else:
-                with H.layer_tag((i, type(m).__name__)):
+                tag = type(m).__name__ if i not in front else f"{type(self.model[front[i][0]]).__name__} + C2f (layers {front[i][0]} + {i}, cv1 fused)"
+                with H.layer_tag((i, tag)):
                     out = m(xin, **kw)
             y.append(out)
         return y[-1]
@@ -362,7 +390,7 @@ class BaseModel(nn.Module):
         s = self._cum_stride[i]
         return int(round(h / s)), int(round(w / s))
 
-    _PACK_CACHES = ("_packed", "_block_cache", "_tail_cache", "_first_cache", "_stem2_cache")
+    _PACK_CACHES = ("_packed", "_block_cache", "_tail_cache", "_front_cache", "_first_cache", "_stem2_cache")
 
     def drop_packed(self) -> None:
         """Forget every packed (BatchNorm-folded, device-layout) copy of the weights and advance the weights epoch that

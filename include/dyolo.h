@@ -296,6 +296,30 @@ typedef struct dy_c2f_tail_desc {
 int32_t dy_c2f_tail_fused_supported(int32_t hidden, int32_t cout, int32_t n_bottlenecks, int32_t ksize1, int32_t ksize2, int32_t groups, int32_t dtype);
 int32_t dy_c2f_tail_fused(const dy_c2f_tail_desc* d, dy_stream_t stream);
 
+/* ---- front of a hidden-64 C2f block: the stride-2 3x3 in front of it + the block's opening 1x1 in ONE kernel ----
+ * Replaces, 16-bit storage: a Conv / folded RepVGGBlock 3x3 stride 2 pad 1, cin -> cmid, whose only consumer is C2f.cv1 (Conv 1x1 ->
+ * cout = 2 * hidden, block.py:237-242), directly (c_other = 0: yaml layers 3 -> 4 of Drone-YOLO-s) or as the FIRST source of a two-source
+ * Concat (c_other channels from `other`: layers 19 -> 20 -> 21); each Conv = SiLU(conv + folded BatchNorm bias) (conv.py:53-55).
+ * x: NHWC (batch, h, w, cin) pitch ld_x.  other: NHWC (batch, ho, wo, c_other) pitch ld_other, ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1
+ * (NULL when c_other = 0).  y: NHWC (batch, ho, wo, cout) pitch ld_y (may be a channel slice).  The 3x3's output never reaches memory.
+ * w3 / b3: DY_WLAYOUT_HALO3X3 of (cmid, cin, 3, 3), fp32[cmid].  w1 / b1: DY_WLAYOUT_FRAG1X1 of (cout, cmid + c_other) in cv1's input
+ * order (the 3x3's output first), fp32[cout].  act: the activation code both convolutions would receive layer by layer, DY_ACT_SILU or
+ * DY_ACT_SILU_L2E (inputs, output and biases in the log2(e)-scaled domain).  The intermediate is rounded to `dtype` where the layer-by-layer
+ * path rounds it and both convolutions sum in that path's order: the result is that of the two dy_conv2d_nhwc calls, bit for bit.
+ * Built for cin 64, (cmid, c_other) = (128, 0) or (64, 128), cout 128, DY_BF16 / DY_F16 (dy_c2f_front_fused_supported tells). */
+typedef struct dy_c2f_front_desc {
+  const void* x;
+  const void* other;
+  void* y;
+  const void* w3;
+  const float* b3;
+  const void* w1;
+  const float* b1;
+  int32_t batch, h, w, cin, cmid, c_other, cout, ld_x, ld_other, ld_y, act, dtype;
+} dy_c2f_front_desc;
+int32_t dy_c2f_front_fused_supported(int32_t cin, int32_t cmid, int32_t c_other, int32_t cout, int32_t ksize, int32_t stride, int32_t groups, int32_t act, int32_t dtype);
+int32_t dy_c2f_front_fused(const dy_c2f_front_desc* d, dy_stream_t stream);
+
 /* Fused stem.  Replaces in one pass: the predictor's dtype/layout step for tensor sources
  * (engine/predictor.py:118-136) AND the model's first layer Conv(cin<=3, cout, 3, 2) (nn/modules/conv.py:37-55,
  * yolov8-p2-repvgg.yaml layer 0), so the image is never materialised in NHWC.
