@@ -1,0 +1,366 @@
+// Tiled inference for batches of frames: the slicer of F frames in one launch and the cross-tile merge of F frames in one launch.
+//
+//   tiles_batch_kernel  F frames (F, hf, wf, 3) uint8 -> (F * K, 3, th, tw) fp32 / 255, tile f * K + k cut at offsets[k] = (y, x).  A lane owns four
+//                       consecutive x of one tile row: twelve source bytes in one load where the four pixels lie inside the frame, three float4
+//                       stores (one per plane).  Values are those of tiles_kernel (preproc.hip): (float)byte / 255.0f, pad_value / 255.0f outside.
+//   tile_merge_kernel   one workgroup per frame over the per-tile dy_nms outputs rows (F * K, max_det, 6) + counts (F * K):
+//                         compact   the rows r < counts[tile] are appended (wave-aggregated, one LDS atomic per wave) as 64-bit keys
+//                                       key = (~float_bits(score) << 32) | slot,   slot = k * max_det + r
+//                                   so that ascending key order is descending score, ties by ascending slot;
+//                         sort      bitonic, in LDS when the keys fit, in the workspace otherwise (two loops: see nms.hip on flat accesses);
+//                         scan      greedy, in chunks of 64 candidates held alike by all 16 waves (lane = candidate): wave w tests them against
+//                                   the kept boxes w, w + 16, ... and publishes a ballot; wave w also computes rows 4 w .. 4 w + 3 of the chunk's
+//                                   64 x 64 suppression bit matrix.  After one barrier every wave resolves the chunk in score order with bit
+//                                   operations (lowest live bit t is kept; live &= ~row[t]); wave 0 appends the kept boxes and writes their rows.
+//                       A box is the row's xyxy plus its tile's (ox, oy): one fp32 add of an integer-valued float.  Classes are compared as
+//                       integers; nothing is added to the coordinates.  All arithmetic is fp32 with contraction off, the IoU in the expression
+//                       order of nms.hip's iou_gt (the reference's), intersection over the smaller area for metric 1.
+#include "common_hip.h"
+#include "nms_ws.h"
+
+#pragma clang fp contract(off)
+
+namespace dy {
+
+typedef unsigned long long u64;
+
+// ---- slicer -------------------------------------------------------------------------------------------------------------------------------
+template <bool VEC>
+__global__ __launch_bounds__(256) void tiles_batch_kernel(const uint8_t* __restrict__ src, const int* __restrict__ offs, float* __restrict__ dst, int frames, int k,
+                                                          int hf, int wf, int th, int tw, int swap_rb, float pad) {
+  const int qw = (tw + 3) >> 2;  // quads of four x per tile row
+  const long long total = (long long)frames * k * th * qw;
+  const size_t plane = (size_t)th * tw;
+  const size_t frame_bytes = (size_t)hf * wf * 3;
+  const float padv = pad / 255.0f;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int x = (int)(i % qw) * 4;
+    long long t = i / qw;
+    const int y = (int)(t % th);
+    const int tile = (int)(t / th);  // f * k + tile of the frame
+    const int f = tile / k, kk = tile - f * k;
+    const int sy = offs[2 * kk] + y, sx = offs[2 * kk + 1] + x;
+    float c0[4], c1[4], c2[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) c0[j] = c1[j] = c2[j] = padv;
+    if ((unsigned)sy < (unsigned)hf) {
+      const uint8_t* q = src + (size_t)f * frame_bytes + ((size_t)sy * wf + sx) * 3;
+      if (sx >= 0 && sx + 3 < wf) {  // the four pixels are twelve consecutive bytes of the frame
+        uint8_t b[12];
+        __builtin_memcpy(b, q, 12);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          c0[j] = (float)b[3 * j] / 255.0f;
+          c1[j] = (float)b[3 * j + 1] / 255.0f;
+          c2[j] = (float)b[3 * j + 2] / 255.0f;
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if ((unsigned)(sx + j) < (unsigned)wf) {
+            c0[j] = (float)q[3 * j] / 255.0f;
+            c1[j] = (float)q[3 * j + 1] / 255.0f;
+            c2[j] = (float)q[3 * j + 2] / 255.0f;
+          }
+      }
+    }
+    float* d = dst + (size_t)tile * 3 * plane + (size_t)y * tw + x;
+    const float* first = swap_rb ? c2 : c0;
+    const float* last = swap_rb ? c0 : c2;
+    if (VEC) {  // tw % 4 == 0 and dst 16-byte aligned: every quad is one aligned float4 per plane
+      *reinterpret_cast<float4*>(d) = make_float4(first[0], first[1], first[2], first[3]);
+      *reinterpret_cast<float4*>(d + plane) = make_float4(c1[0], c1[1], c1[2], c1[3]);
+      *reinterpret_cast<float4*>(d + 2 * plane) = make_float4(last[0], last[1], last[2], last[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (x + j < tw) {
+          d[j] = first[j];
+          d[plane + j] = c1[j];
+          d[2 * plane + j] = last[j];
+        }
+    }
+  }
+}
+
+// ---- merge --------------------------------------------------------------------------------------------------------------------------------
+constexpr int TM_THREADS = 1024;
+constexpr int TM_WAVES = TM_THREADS / 64;
+constexpr int TM_ROWS = 64 / TM_WAVES;                  // bit-matrix rows a wave computes per chunk
+constexpr int TM_MAX_SLOTS = 32768;                     // K * max_det
+constexpr int TM_MAX_KEEP = 4096;                       // merge_max_det
+constexpr int TM_MAX_LDS_KEYS = 16384;                  // 128 KiB of the CU's 160 KiB
+constexpr int TM_FIXED_LDS = 64 * 8 + TM_WAVES * 8 + 16;  // bit matrix, verdict words, two counters
+constexpr int TM_KEEP_BYTES = 24;                       // float4 box, area, class per kept row
+
+struct TmArgs {
+  const float* rows;
+  const int* counts;
+  const int* offs;
+  float* out;
+  int* out_count;
+  int* out_index;
+  u64* keys;  // [frames][P]
+  int K, max_det, N, P, SL;
+  float fw, fh, thr;
+  int metric, agnostic, keep;
+};
+
+struct TmCand {
+  float x1, y1, x2, y2, score;
+  int slot, cls;
+};
+
+// box i (kept) suppresses box j: same class unless agnostic, then the overlap measure against thr
+__device__ __forceinline__ bool tm_suppresses(int metric, int agnostic, float thr, float ix1, float iy1, float ix2, float iy2, float iarea, int icls, float jx1,
+                                              float jy1, float jx2, float jy2, float jarea, int jcls) {
+  const float xx1 = fmaxf(ix1, jx1), yy1 = fmaxf(iy1, jy1);
+  const float xx2 = fminf(ix2, jx2), yy2 = fminf(iy2, jy2);
+  const float w = fmaxf(0.f, xx2 - xx1), h = fmaxf(0.f, yy2 - yy1);
+  const float inter = w * h;
+  const float den = metric ? fminf(iarea, jarea) : (iarea + jarea - inter);
+  const float ovr = inter / den;
+  return (agnostic || icls == jcls) && ovr > thr;
+}
+
+__device__ __forceinline__ u64 tm_uniform64(u64 v) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+  return ((u64)hi << 32) | (u64)lo;
+}
+
+__device__ __forceinline__ TmCand tm_fetch(const TmArgs& p, const u64* skeys, const u64* gkeys, bool in_lds, const float* frows, int i, int n) {
+  TmCand c{0.f, 0.f, 0.f, 0.f, 0.f, 0, -1};
+  if (i < n) {
+    const u64 key = in_lds ? skeys[i] : gkeys[i];
+    c.slot = (int)(unsigned)(key & 0xffffffffull);
+    c.score = __uint_as_float(~(unsigned)(key >> 32));
+    const int tile = c.slot / p.max_det;
+    const float oy = (float)p.offs[2 * tile], ox = (float)p.offs[2 * tile + 1];
+    const float* q = frows + (size_t)c.slot * 6;
+    c.x1 = q[0] + ox;
+    c.y1 = q[1] + oy;
+    c.x2 = q[2] + ox;
+    c.y2 = q[3] + oy;
+    c.cls = (int)q[5];
+  }
+  return c;
+}
+
+__global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(const TmArgs p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
+  u64* skeys = reinterpret_cast<u64*>(dyn_smem);  // [SL]
+  u64* mrows = skeys + p.SL;                      // [64]
+  u64* verdict = mrows + 64;                      // [TM_WAVES]
+  int* ctr = reinterpret_cast<int*>(verdict + TM_WAVES);  // candidates of the frame, append cursor
+  float4* kbox = reinterpret_cast<float4*>(dyn_smem + (size_t)p.SL * 8 + TM_FIXED_LDS);  // [keep]
+  float* kar = reinterpret_cast<float*>(kbox + p.keep);
+  int* kcls = reinterpret_cast<int*>(kar + p.keep);
+  const int f = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const float* frows = p.rows + (size_t)f * p.N * 6;
+  const int* fcounts = p.counts + (size_t)f * p.K;
+  u64* gkeys = p.keys + (size_t)f * p.P;
+
+  // how many candidates the frame has decides where they are sorted
+  if (tid == 0) ctr[0] = ctr[1] = 0;
+  __syncthreads();
+  int part = 0;
+  for (int t = tid; t < p.K; t += TM_THREADS) {
+    const int c = fcounts[t];
+    part += c < 0 ? 0 : (c > p.max_det ? p.max_det : c);
+  }
+  for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
+  if (lane == 0 && part != 0) atomicAdd(&ctr[0], part);
+  __syncthreads();
+  const int n = ctr[0];
+  int P2 = 1;
+  while (P2 < n) P2 <<= 1;
+  const bool in_lds = P2 <= p.SL;
+
+  // compact: every wave runs the same number of rounds so that the ballot is well defined
+  for (int j0 = 0; j0 < p.N; j0 += TM_THREADS) {
+    const int j = j0 + tid;
+    bool valid = false;
+    float score = 0.f;
+    if (j < p.N) {
+      const int tile = j / p.max_det, r = j - tile * p.max_det;
+      valid = r < fcounts[tile];
+      if (valid) score = frows[(size_t)j * 6 + 4];
+    }
+    const u64 m = __ballot(valid);
+    int base = 0;
+    if (lane == 0 && m != 0ull) base = atomicAdd(&ctr[1], __popcll(m));
+    base = __shfl(base, 0);
+    if (valid) {
+      const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+      const u64 key = ((u64)(~__float_as_uint(score)) << 32) | (u64)(unsigned)j;
+      if (in_lds) skeys[pos] = key;
+      else gkeys[pos] = key;
+    }
+  }
+  if (in_lds) {
+    for (int i = n + tid; i < P2; i += TM_THREADS) skeys[i] = ~0ull;
+  } else {
+    for (int i = n + tid; i < P2; i += TM_THREADS) gkeys[i] = ~0ull;
+  }
+  __syncthreads();
+  auto bitonic = [&](auto* keys) {
+    for (int k = 2; k <= P2; k <<= 1) {
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int t = tid; t < (P2 >> 1); t += TM_THREADS) {
+          const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));  // element with bit j clear
+          const int ixj = i | j;
+          const u64 x = keys[i], y = keys[ixj];
+          const bool up = (i & k) == 0;
+          if ((x > y) == up) {
+            keys[i] = y;
+            keys[ixj] = x;
+          }
+        }
+        __syncthreads();
+      }
+    }
+  };
+  if (in_lds) bitonic(skeys);
+  else bitonic(gkeys);
+
+  float* outb = p.out + (size_t)f * p.keep * 6;
+  int* outi = p.out_index ? p.out_index + (size_t)f * p.keep : nullptr;
+  const u64 lane_bit = 1ull << lane;
+  int nk = 0;
+  TmCand nxt = tm_fetch(p, skeys, gkeys, in_lds, frows, lane, n);
+  for (int c0 = 0; c0 < n && nk < p.keep; c0 += 64) {
+    const TmCand c = nxt;
+    nxt = tm_fetch(p, skeys, gkeys, in_lds, frows, c0 + 64 + lane, n);
+    const bool in = c0 + lane < n;
+    const float area = (c.x2 - c.x1) * (c.y2 - c.y1);
+    // this wave's share of the kept list
+    bool sup = false;
+    for (int k = wave; k < nk; k += TM_WAVES) {
+      const float4 kb = kbox[k];
+      sup |= tm_suppresses(p.metric, p.agnostic, p.thr, kb.x, kb.y, kb.z, kb.w, kar[k], kcls[k], c.x1, c.y1, c.x2, c.y2, area, c.cls);
+    }
+    const u64 sm = __ballot(sup);
+    // this wave's rows of the chunk's suppression matrix
+    u64 myrow = 0ull;
+#pragma unroll
+    for (int r = 0; r < TM_ROWS; ++r) {
+      const int i = wave * TM_ROWS + r;  // wave-uniform: v_readlane
+      auto bcast = [&](float v) { return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(v), i)); };
+      const int icls = __builtin_amdgcn_readlane(c.cls, i);
+      const u64 m = __ballot(tm_suppresses(p.metric, p.agnostic, p.thr, bcast(c.x1), bcast(c.y1), bcast(c.x2), bcast(c.y2), bcast(area), icls, c.x1, c.y1,
+                                           c.x2, c.y2, area, c.cls));
+      if (lane == r) myrow = m;
+    }
+    if (lane < TM_ROWS) mrows[wave * TM_ROWS + lane] = myrow;
+    if (lane == 0) verdict[wave] = sm;
+    __syncthreads();
+    u64 dead = 0ull;
+    for (int w = 0; w < TM_WAVES; ++w) dead |= verdict[w];
+    const u64 row = mrows[lane];
+    const unsigned row_lo = (unsigned)row, row_hi = (unsigned)(row >> 32);
+    u64 am = __ballot(in) & ~tm_uniform64(dead);  // candidates of the chunk that no earlier kept box suppresses
+    u64 km = 0ull;                                // those the chunk keeps
+    int cnt = 0;
+    while (am != 0ull) {
+      const int t = __ffsll((long long)am) - 1;  // best live candidate of the chunk (wave-uniform)
+      km |= 1ull << t;
+      ++cnt;
+      if (nk + cnt >= p.keep) break;
+      const u64 rt = ((u64)(unsigned)__builtin_amdgcn_readlane((int)row_hi, t) << 32) | (u64)(unsigned)__builtin_amdgcn_readlane((int)row_lo, t);
+      am &= ~(rt | (1ull << t));
+    }
+    if (wave == 0 && (km & lane_bit) != 0ull) {
+      const int at = nk + __popcll(km & (lane_bit - 1ull));
+      kbox[at] = make_float4(c.x1, c.y1, c.x2, c.y2);
+      kar[at] = area;
+      kcls[at] = c.cls;
+      float* o = outb + (size_t)at * 6;
+      o[0] = fminf(fmaxf(c.x1, 0.f), p.fw);
+      o[1] = fminf(fmaxf(c.y1, 0.f), p.fh);
+      o[2] = fminf(fmaxf(c.x2, 0.f), p.fw);
+      o[3] = fminf(fmaxf(c.y2, 0.f), p.fh);
+      o[4] = c.score;
+      o[5] = (float)c.cls;
+      if (outi) outi[at] = c.slot;
+    }
+    nk += cnt;
+    __syncthreads();  // the kept list is complete before the next chunk reads it; mrows / verdict may be rewritten
+  }
+  for (int r = nk * 6 + tid; r < p.keep * 6; r += TM_THREADS) outb[r] = 0.f;
+  if (outi)
+    for (int r = nk + tid; r < p.keep; r += TM_THREADS) outi[r] = -1;
+  if (tid == 0) p.out_count[f] = nk;
+}
+
+}  // namespace dy
+
+using namespace dy;
+
+extern "C" int32_t dy_tiles_batch_u8_to_nchw_f32(const uint8_t* frames, const int32_t* offsets_yx, float* dst, int32_t f, int32_t k, int32_t hf, int32_t wf,
+                                                 int32_t th, int32_t tw, int32_t swap_rb, float pad_value, dy_stream_t stream) {
+  DY_REQUIRE(frames && offsets_yx && dst, DY_ERR_INVALID_ARG, "dy_tiles_batch_u8_to_nchw_f32: null pointer");
+  DY_REQUIRE(f > 0 && k > 0 && hf > 0 && wf > 0 && th > 0 && tw > 0, DY_ERR_INVALID_ARG, "dy_tiles_batch_u8_to_nchw_f32: bad dims");
+  DY_REQUIRE((long long)f * k <= 0x7fffffffll / 2, DY_ERR_INVALID_ARG, "dy_tiles_batch_u8_to_nchw_f32: frames * tiles too large");
+  const long long total = (long long)f * k * th * ((tw + 3) / 4);
+  long long blocks = (total + 255) / 256;
+  if (blocks > 16384) blocks = 16384;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (tw % 4 == 0 && aligned16(dst))
+    hipLaunchKernelGGL(tiles_batch_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, frames, offsets_yx, dst, f, k, hf, wf, th, tw, swap_rb ? 1 : 0, pad_value);
+  else
+    hipLaunchKernelGGL(tiles_batch_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, frames, offsets_yx, dst, f, k, hf, wf, th, tw, swap_rb ? 1 : 0, pad_value);
+  return check_launch("dy_tiles_batch_u8_to_nchw_f32");
+}
+
+extern "C" int64_t dy_tile_merge_workspace_bytes(int32_t frames, int32_t tiles, int32_t max_det) {
+  if (frames <= 0 || tiles <= 0 || max_det <= 0 || (long long)tiles * max_det > TM_MAX_SLOTS) return -1;
+  return (int64_t)frames * nms_next_pow2(tiles * max_det) * 8;
+}
+
+extern "C" int32_t dy_tile_merge(const dy_tile_merge_desc* d, dy_stream_t stream) {
+  DY_REQUIRE(d && d->rows && d->counts && d->offsets_yx && d->out && d->out_count && d->workspace, DY_ERR_INVALID_ARG,
+             "dy_tile_merge: null pointer (rows / counts / offsets_yx / out / out_count / workspace)");
+  DY_REQUIRE(d->frames > 0 && d->tiles > 0 && d->max_det > 0 && d->nc > 0 && d->frame_h > 0 && d->frame_w > 0 && d->merge_max_det > 0, DY_ERR_INVALID_ARG,
+             "dy_tile_merge: bad dims (frames %d, tiles %d, max_det %d, nc %d, frame %d x %d, merge_max_det %d)", d->frames, d->tiles, d->max_det, d->nc,
+             d->frame_h, d->frame_w, d->merge_max_det);
+  DY_REQUIRE(d->metric == 0 || d->metric == 1, DY_ERR_INVALID_ARG, "dy_tile_merge: metric %d (0 = IoU, 1 = IoS)", d->metric);
+  DY_REQUIRE(d->thr >= 0.f && d->thr <= 1.f, DY_ERR_INVALID_ARG, "dy_tile_merge: thr must be in [0,1]");
+  DY_REQUIRE((long long)d->tiles * d->max_det <= TM_MAX_SLOTS, DY_ERR_UNSUPPORTED, "dy_tile_merge: tiles * max_det = %lld > %d", (long long)d->tiles * d->max_det,
+             TM_MAX_SLOTS);
+  DY_REQUIRE(d->merge_max_det <= TM_MAX_KEEP, DY_ERR_UNSUPPORTED, "dy_tile_merge: merge_max_det %d > %d", d->merge_max_det, TM_MAX_KEEP);
+  const int64_t need = dy_tile_merge_workspace_bytes(d->frames, d->tiles, d->max_det);
+  DY_REQUIRE(d->workspace_bytes >= need, DY_ERR_WORKSPACE, "dy_tile_merge: workspace %lld < %lld bytes", (long long)d->workspace_bytes, (long long)need);
+  DY_REQUIRE(aligned16(d->workspace), DY_ERR_INVALID_ARG, "dy_tile_merge: workspace not 16-byte aligned");
+
+  TmArgs a{};
+  a.rows = d->rows;
+  a.counts = d->counts;
+  a.offs = d->offsets_yx;
+  a.out = d->out;
+  a.out_count = d->out_count;
+  a.out_index = d->out_index;
+  a.keys = reinterpret_cast<u64*>(d->workspace);
+  a.K = d->tiles;
+  a.max_det = d->max_det;
+  a.N = d->tiles * d->max_det;
+  a.P = nms_next_pow2(a.N);
+  a.fw = (float)d->frame_w;
+  a.fh = (float)d->frame_h;
+  a.thr = d->thr;
+  a.metric = d->metric;
+  a.agnostic = d->agnostic ? 1 : 0;
+  a.keep = d->merge_max_det;
+  // LDS by need: the keys of every slot when they fit beside the kept list, the largest power of two that does otherwise
+  const size_t rest = (size_t)TM_FIXED_LDS + nms_align_up((size_t)a.keep * TM_KEEP_BYTES, 16);
+  a.SL = a.P < TM_MAX_LDS_KEYS ? a.P : TM_MAX_LDS_KEYS;
+  while ((size_t)a.SL * 8 + rest > 160 * 1024) a.SL >>= 1;
+  const size_t smem = (size_t)a.SL * 8 + rest;
+  static const hipError_t attr_once = hipFuncSetAttribute((const void*)tile_merge_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  (void)attr_once;
+  hipLaunchKernelGGL(tile_merge_kernel, dim3((unsigned)d->frames), dim3(TM_THREADS), smem, reinterpret_cast<hipStream_t>(stream), a);
+  return check_launch("dy_tile_merge");
+}

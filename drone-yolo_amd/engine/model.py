@@ -82,13 +82,16 @@ class Model(nn.Module):
         persist = bool(args.pop("persist", False))
         if not track:
             args.pop("tracker", None)
+        elif args.get("tile") is not None and int(args.get("merge_max_det", 1000)) > 1024:  # (before a predictor is built or anything is launched)
+            raise ValueError(f"merge_max_det = {args['merge_max_det']} with tile in track mode: the track step takes at most 1024 detections per frame")
         if self.predictor is None or getattr(self, "_pred_args", None) != (args, track):
             self.predictor = (predictor or DetectionPredictor)(self.model, overrides=args)
             self._pred_args = (args, track)
         if track:
             # the tracker outlives the predictor (a predict call in between rebuilds that): persist=True goes on with its tracks and ids
             p = self.predictor
-            key = (str(p.args["tracker"]), bool(p.args["device_track"]), int(p.args["track_streams"]), int(p.args["max_det"]), int(p.args["max_tracks"]), str(p.device))
+            key = (str(p.args["tracker"]), bool(p.args["device_track"]), int(p.args["track_streams"]),
+                   int(p.args["merge_max_det"] if p.args["tile"] is not None else p.args["max_det"]), int(p.args["max_tracks"]), str(p.device))
             if getattr(self, "_tracker_key", None) != key:
                 self._tracker, self._tracker_key = p.make_tracker(), key
             elif not persist:

@@ -92,9 +92,20 @@ class DetectionPredictor:
     def __init__(self, model, overrides: Optional[dict] = None):
         a = dict(conf=0.25, iou=0.7, max_det=300, classes=None, agnostic_nms=False, half=False, dtype=None, device="",
                  verbose=False, graph=True, max_nms=30000, max_wh=7680, imgsz=640, fp8_layers=None, batch=None, augment=False,
-                 tracker="bytetrack.yaml", device_track=True, track_streams=1, max_tracks=512)
+                 tracker="bytetrack.yaml", device_track=True, track_streams=1, max_tracks=512,
+                 tile=None, tile_overlap=0.2, merge_iou=0.7, merge_metric="iou", merge_max_det=1000)
         a.update(overrides or {})
         self.args = a
+        if a["tile"] is not None:  # tiled inference: checked before anything touches the device
+            s = int(max(model.stride)) if hasattr(model, "stride") else 32
+            if int(a["tile"]) <= 0 or int(a["tile"]) % s:
+                raise ValueError(f"tile = {a['tile']} must be a positive multiple of the model's largest stride {s}")
+            if str(a["merge_metric"]).lower() not in H.TILE_MERGE_METRICS:
+                raise ValueError(f"merge_metric = '{a['merge_metric']}', expected one of {sorted(H.TILE_MERGE_METRICS)}")
+            if a["augment"]:
+                raise NotImplementedError("augment=True with tile: the image pyramid of test-time augmentation is not built for tiles")
+            if not 0.0 <= float(a["tile_overlap"]) < 1.0 or not 0.0 <= float(a["merge_iou"]) <= 1.0 or int(a["merge_max_det"]) < 1:
+                raise ValueError("tile_overlap must be in [0, 1), merge_iou in [0, 1] and merge_max_det positive")
         self.tracker = None  # mode="track" (Model.track): a trackers.DeviceByteTracker / ByteTracker fed behind the NMS and box scaling of every batch
         self.device = select_device(a["device"])
         # dtype="fp8-mixed" (BASELINE config 5): float16 storage with the internals of the C2f blocks the error budget allows in
@@ -105,6 +116,7 @@ class DetectionPredictor:
         self.backend = AutoBackend(model, device=self.device, fp16=bool(a["half"]), dtype=self.dtype, fuse=False, verbose=bool(a["verbose"]))
         self.model = self.backend.model
         self._compiled: Dict[Tuple, CompiledForward] = {}
+        self._tile_state: Dict[Tuple, tuple] = {}  # tile mode, per (frames, H, W): device tile offsets, the tile batch, the merge buffers
         self._classes_mask = None
         if a["classes"] is not None:
             m = torch.zeros(self.model.yaml["nc"], dtype=torch.uint8)
@@ -337,7 +349,12 @@ class DetectionPredictor:
 
         a = self.args
         cls = DeviceByteTracker if a["device_track"] else ByteTracker
-        return cls(a["tracker"], frame_rate=30, max_tracks=int(a["max_tracks"]), streams=int(a["track_streams"]), max_det=int(a["max_det"]), device=self.device)
+        max_det = int(a["max_det"])
+        if a["tile"] is not None:  # the tracker reads the merged rows of a frame
+            max_det = int(a["merge_max_det"])
+            if max_det > 1024:
+                raise ValueError(f"merge_max_det = {max_det} with mode='track': the track step takes at most 1024 detections per frame")
+        return cls(a["tracker"], frame_rate=30, max_tracks=int(a["max_tracks"]), streams=int(a["track_streams"]), max_det=max_det, device=self.device)
 
     def _track_launch(self, cf: CompiledForward):
         """Device tracker: the track step behind this batch's NMS and box scaling, on the same stream; returns copies (rows, counts) that
@@ -491,9 +508,127 @@ class DetectionPredictor:
         if pending is not None:
             yield from finish(pending)
 
+    # ---- tiled inference (``tile=``): frames larger than the model input, cut into overlapping tiles on the device ----------------
+    def _tile_pieces(self, source):
+        """``source`` as pieces (lo, frames, paths) of at most ``batch`` frames; frames: HWC uint8 numpy arrays (or rows of a uint8 NHWC tensor)."""
+        from pathlib import Path
+
+        batch = self.args.get("batch")
+        is_path = lambda v: isinstance(v, (str, Path))  # noqa: E731
+        if is_path(source) or (isinstance(source, (list, tuple)) and len(source) > 0 and all(is_path(v) for v in source)):
+            return self._file_pieces(self.list_image_files(source), int(batch or 1))
+        if type(source).__module__.startswith("PIL.") or (isinstance(source, (list, tuple)) and len(source) > 0 and type(source[0]).__module__.startswith("PIL.")):
+            ims = list(source) if isinstance(source, (list, tuple)) else [source]
+            frames = [self.decode_image(im) for im in ims]
+            paths = [getattr(im, "filename", "") or f"image{i}.jpg" for i, im in enumerate(ims)]
+            b = int(batch or len(frames))
+            return ((lo, frames[lo : lo + b], paths[lo : lo + b]) for lo in range(0, len(frames), b))
+        if isinstance(source, torch.Tensor):
+            if source.dtype != torch.uint8 or source.dim() not in (3, 4) or source.shape[-1] != 3:
+                raise NotImplementedError("tile with a float BCHW tensor: tiles are cut from pixels (uint8 HWC frames), not from a letterboxed tensor")
+            source = source[None] if source.dim() == 3 else source
+        elif type(source).__name__ == "ndarray":
+            source = [source] if source.ndim == 3 else list(source)
+        elif not isinstance(source, (list, tuple)) or len(source) == 0:
+            raise NotImplementedError("tile sources: uint8 HWC BGR frames (list of numpy arrays / uint8 NHWC tensor), image files, PIL images")
+        return self._chunks(source, int(batch or len(source)))
+
+    def _tiled_enqueue(self, lo: int, frames, paths):
+        """Everything one batch of frames launches — per group of frames of one shape: the slicer, the recorded pass over the (F * K)-tile batch,
+        the cross-tile merge and, in track mode, the track step — then ONE asynchronous copy of the merged (and the tracker's) counts."""
+        import numpy as np
+
+        from .tiling import tile_offsets
+
+        a = self.args
+        tile, t0 = int(a["tile"]), time.perf_counter()
+        n = len(frames)
+        groups: Dict[Tuple[int, int], List[int]] = {}
+        for i in range(n):
+            f = frames[i]
+            if f.ndim != 3 or f.shape[2] != 3 or f.dtype != (torch.uint8 if isinstance(f, torch.Tensor) else np.uint8):
+                raise ValueError("tile sources must be uint8 HWC BGR frames")
+            groups.setdefault((int(f.shape[0]), int(f.shape[1])), []).append(i)
+        if self.tracker is not None:
+            if len(groups) > 1:
+                raise NotImplementedError("mode='track' with tile: the frames of a batch must have one shape (they are consecutive time steps)")
+            if n % self.tracker.streams:
+                raise ValueError(f"a batch of {n} images is no multiple of track_streams = {self.tracker.streams}")
+        parts, mcounts, tcounts = [], [], []
+        for (hf, wf), idxs in groups.items():
+            if isinstance(frames, torch.Tensor):
+                stacked = frames[idxs[0] : idxs[-1] + 1].to(self.device, non_blocking=True).contiguous()
+            else:
+                stacked = torch.from_numpy(np.ascontiguousarray(np.stack([frames[i] for i in idxs]))).to(self.device, non_blocking=True)
+            key = (len(idxs), hf, wf)
+            st = self._tile_state.get(key)
+            if st is None:
+                while len(self._tile_state) >= self.max_compiled:
+                    self._tile_state.pop(next(iter(self._tile_state)))
+                offs = tile_offsets(hf, wf, tile, float(a["tile_overlap"]))
+                offs_d = torch.tensor(offs, dtype=torch.int32, device=self.device)
+                k = len(offs)
+                st = self._tile_state[key] = (offs_d, k, torch.empty((len(idxs) * k, 3, tile, tile), dtype=torch.float32, device=self.device),
+                                              H.TileMergeBuffers(len(idxs), k, int(a["max_det"]), int(a["merge_max_det"]), self.device))
+            offs_d, k, tiles, mbufs = st
+            H.tiles_batch(stacked, offs_d, tile, out=tiles)  # a frame no larger than the tile is one tile padded with 114
+            self.letterbox_info = None  # every tile is an image of its own to the pass: boxes clipped to the tile
+            cf = self.forward_device(tiles)
+            merged = H.tile_merge(cf.nms, offs_d, k, (hf, wf), self.model.yaml["nc"], float(a["merge_iou"]), str(a["merge_metric"]),
+                                  bool(a["agnostic_nms"]), int(a["merge_max_det"]), bufs=mbufs)
+            tracked = None
+            if self.tracker is not None and hasattr(self.tracker, "bufs"):
+                tout, tcnt = self.tracker.update_batch(merged.out, merged.count)
+                tracked = tout.clone()
+                tcounts.append(tcnt)
+            # copies that outlive the next batch (and the next group: groups of one size share the buffers)
+            parts.append((idxs, (hf, wf), merged.out.clone(), tracked))
+            mcounts.append(merged.count.clone() if len(groups) > 1 else merged.count)
+        counts_dev = mcounts + tcounts  # (track mode has one group: the tracker's counts follow the merged counts)
+        counts_dev = torch.cat(counts_dev) if len(counts_dev) > 1 else counts_dev[0]
+        counts_host = torch.empty(counts_dev.shape, dtype=counts_dev.dtype, pin_memory=True)
+        counts_host.copy_(counts_dev, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return lo, frames, paths, parts, counts_host, ev, (time.perf_counter() - t0) * 1e3 / max(n, 1)
+
+    def _tiled_finish(self, item) -> List[Results]:
+        lo, frames, paths, parts, counts_host, ev, t_inf = item
+        t0 = time.perf_counter()
+        ev.synchronize()  # the batch's only device->host synchronisation
+        both = counts_host.tolist()
+        names, out, o = self.model.names, [None] * len(frames), 0
+        for idxs, hw, rows, trows in parts:
+            counts = both[o : o + len(idxs)]
+            o += len(idxs)
+            tracked = (trows, both[o : o + len(idxs)]) if trows is not None else None
+            for j, i in enumerate(idxs):
+                img = frames[i]
+                if isinstance(img, torch.Tensor):
+                    img = img.cpu().numpy()
+                out[i] = Results(img, paths[i] if paths else f"image{lo + i}.jpg", names, boxes=self._boxes_of(j, counts[j], rows, tracked), orig_shape=hw)
+        dt = (time.perf_counter() - t0) * 1e3 / max(len(out), 1)
+        for r in out:
+            r.speed = {"preprocess": 0.0, "inference": t_inf, "postprocess": dt}
+        return out
+
+    def stream_tiled(self, pieces):
+        """Generator over the frames of ``pieces`` in order; as ``stream_batches``, the device works one batch ahead of the host."""
+        pending = None
+        for lo, frames, paths in pieces:
+            item = self._tiled_enqueue(lo, frames, paths)
+            if pending is not None:
+                yield from self._tiled_finish(pending)
+            pending = item
+        if pending is not None:
+            yield from self._tiled_finish(pending)
+
     def __call__(self, source, stream: bool = False):
         from pathlib import Path
 
+        if self.args.get("tile") is not None:
+            gen = self.stream_tiled(self._tile_pieces(source))
+            return gen if stream else list(gen)
         is_path = lambda v: isinstance(v, (str, Path))  # noqa: E731
         if is_path(source) or (isinstance(source, (list, tuple)) and len(source) > 0 and all(is_path(v) for v in source)):
             # image files: the reference's loader hands over `batch` files at a time (default 1: every image letterboxed to ITS minimum rectangle)

@@ -21,7 +21,7 @@ import warnings
 import torch
 
 from . import _lib
-from ._lib import DY_ACT_NONE, DY_ACT_SILU, DY_ACT_SILU_L2E, BnDesc, BranchDesc, C2fDesc, C2fFrontDesc, C2fTailDesc, ConvDesc, DecodeDesc, HeadDecodeDesc, LossDesc, NmsDesc, Stem2Desc, TrackDesc, ValMatchDesc, check, lib
+from ._lib import DY_ACT_NONE, DY_ACT_SILU, DY_ACT_SILU_L2E, BnDesc, BranchDesc, C2fDesc, C2fFrontDesc, C2fTailDesc, ConvDesc, DecodeDesc, HeadDecodeDesc, LossDesc, NmsDesc, Stem2Desc, TileMergeDesc, TrackDesc, ValMatchDesc, check, lib
 
 FP8 = torch.float8_e4m3fn  # OCP e4m3fn: gfx950's fp8 (MI300's fnuz is another encoding)
 # DY_F16X2 (include/dyolo.h): split float16 pairs, x ~= hi + lo * 2^-11 — the bar-exact precision on the 16-bit MFMA.  torch has no such
@@ -1609,6 +1609,86 @@ def scale_img(img: torch.Tensor, ratio: float, gs: int = 32, flip_lr: bool = Fal
     out = torch.empty((n, c, ho, wo), dtype=torch.float32, device=img.device)
     _launch(lib().dy_scale_img_nchw_f32, (img.data_ptr(), out.data_ptr(), n, c, h, w, hs, ws, ho, wo, int(flip_lr), 0.447), keep=(img, out))
     return out
+
+
+# ---- tiled inference on batches of frames (csrc/tile_merge.hip) -------------------------------------------------
+
+
+def tiles_batch(frames: torch.Tensor, offsets: torch.Tensor, tile: int, out: Optional[torch.Tensor] = None, swap_rb: bool = True,
+                pad_value: float = 114.0) -> torch.Tensor:
+    """uint8 (F, H, W, 3) frames -> fp32 (F * K, 3, tile, tile) / 255, tile ``f * K + k`` cut at ``offsets[k] = (y, x)`` (device int32 (K, 2),
+    shared by all frames), ``pad_value`` beyond the frame edge: one ``dy_tiles_batch_u8_to_nchw_f32`` launch, no host synchronisation."""
+    require_device(frames, "frames")
+    require_device(offsets, "tile offsets")
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise ValueError("tiles_batch expects a contiguous uint8 (F, H, W, 3) device tensor")
+    if offsets.dtype != torch.int32 or offsets.dim() != 2 or offsets.shape[1] != 2 or not offsets.is_contiguous():
+        raise ValueError("tiles_batch expects the tile offsets as a contiguous int32 (K, 2) device tensor")
+    f, hf, wf, _ = frames.shape
+    k, tile = int(offsets.shape[0]), int(tile)
+    if out is None:
+        out = torch.empty((f * k, 3, tile, tile), dtype=torch.float32, device=frames.device)
+    elif tuple(out.shape) != (f * k, 3, tile, tile) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"tiles_batch: out must be a contiguous fp32 ({f * k}, 3, {tile}, {tile}) tensor")
+    _launch(lib().dy_tiles_batch_u8_to_nchw_f32, (frames.data_ptr(), offsets.data_ptr(), out.data_ptr(), f, k, hf, wf, tile, tile, int(swap_rb), float(pad_value)),
+            keep=(frames, offsets, out))
+    return out
+
+
+class TileMergeBuffers:
+    """Persistent outputs + workspace of ``dy_tile_merge`` for one (frames, tiles, max_det, merge_max_det).  ``out`` / ``count`` / ``index`` /
+    ``batch`` / ``max_det`` mean what they mean on ``NmsBuffers`` (``max_det`` = merge_max_det), so whatever reads NMS output reads this."""
+
+    def __init__(self, frames: int, tiles: int, tile_max_det: int, merge_max_det: int, device):
+        self.batch, self.tiles, self.tile_max_det, self.max_det = int(frames), int(tiles), int(tile_max_det), int(merge_max_det)
+        nbytes = lib().dy_tile_merge_workspace_bytes(self.batch, self.tiles, self.tile_max_det)
+        if nbytes < 0:
+            raise ValueError(f"tile_merge: {tiles} tiles x max_det {tile_max_det} is beyond the kernel's 32768 slots per frame")
+        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+        self.out = torch.empty((self.batch, self.max_det, 6), dtype=torch.float32, device=device)
+        self.count = torch.empty((self.batch,), dtype=torch.int32, device=device)
+        self.index = torch.empty((self.batch, self.max_det), dtype=torch.int32, device=device)
+
+
+_TILE_MERGE_BUFS: dict = {}
+TILE_MERGE_METRICS = {"iou": 0, "ios": 1}
+
+
+def tile_merge(nms_bufs, offsets: torch.Tensor, K: int, frame_hw: Tuple[int, int], nc: int, thr: float, metric=0, agnostic: bool = False,
+               merge_max_det: int = 1000, bufs: Optional[TileMergeBuffers] = None) -> TileMergeBuffers:
+    """Cross-tile merge of F frames in one ``dy_tile_merge`` launch; no host synchronisation.  ``nms_bufs``: the per-tile ``NmsBuffers`` of the
+    (F * K)-tile batch (rows in tile pixels, clipped to the tile) or a ``(rows, counts)`` pair; ``offsets``: device int32 (K, 2) = (y, x);
+    ``metric``: 0 / "iou" or 1 / "ios" (intersection over the smaller box).  Returns rows in frame pixels, clamped to the frame, in buffers
+    that persist per (F, K, max_det, merge_max_det): the next call with the same sizes overwrites them."""
+    rows, counts = (nms_bufs.out, nms_bufs.count) if hasattr(nms_bufs, "out") else nms_bufs
+    require_device(rows, "per-tile rows")
+    require_device(counts, "per-tile counts")
+    require_device(offsets, "tile offsets")
+    K = int(K)
+    if rows.dtype != torch.float32 or rows.dim() != 3 or rows.shape[2] != 6 or not rows.is_contiguous() or rows.shape[0] % K or counts.dtype != torch.int32 \
+            or counts.numel() != rows.shape[0] or not counts.is_contiguous():
+        raise ValueError(f"tile_merge: rows must be contiguous fp32 (F * {K}, max_det, 6) with as many int32 counts")
+    if offsets.dtype != torch.int32 or tuple(offsets.shape) != (K, 2) or not offsets.is_contiguous():
+        raise ValueError(f"tile_merge: offsets must be a contiguous int32 ({K}, 2) device tensor")
+    if isinstance(metric, str):
+        if metric.lower() not in TILE_MERGE_METRICS:
+            raise ValueError(f"tile_merge: metric '{metric}', expected one of {sorted(TILE_MERGE_METRICS)}")
+        metric = TILE_MERGE_METRICS[metric.lower()]
+    f, md = rows.shape[0] // K, int(rows.shape[1])
+    if bufs is None or (bufs.batch, bufs.tiles, bufs.tile_max_det, bufs.max_det) != (f, K, md, int(merge_max_det)) or bufs.out.device != rows.device:
+        key = (rows.device, f, K, md, int(merge_max_det))
+        bufs = _TILE_MERGE_BUFS.get(key)
+        if bufs is None:
+            bufs = _TILE_MERGE_BUFS[key] = TileMergeBuffers(f, K, md, int(merge_max_det), rows.device)
+    d = TileMergeDesc()
+    d.rows, d.counts, d.offsets_yx = rows.data_ptr(), counts.data_ptr(), offsets.data_ptr()
+    d.frames, d.tiles, d.max_det, d.nc = f, K, md, int(nc)
+    d.frame_h, d.frame_w = int(frame_hw[0]), int(frame_hw[1])
+    d.thr, d.metric, d.agnostic, d.merge_max_det = float(thr), int(metric), int(bool(agnostic)), int(merge_max_det)
+    d.out, d.out_count, d.out_index = bufs.out.data_ptr(), bufs.count.data_ptr(), bufs.index.data_ptr()
+    d.workspace, d.workspace_bytes = bufs.workspace.data_ptr(), bufs.workspace.numel()
+    _launch(lib().dy_tile_merge, (C.byref(d),), keep=(d, rows, counts, offsets, bufs))
+    return bufs
 
 
 def augment_batch(src: torch.Tensor, table: torch.Tensor, s: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:

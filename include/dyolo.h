@@ -398,6 +398,43 @@ int32_t dy_tiles_u8_to_nchw_f32(const uint8_t* frame, const int32_t* offsets_yx,
 int32_t dy_rows_to_pred(const float* rows, const int32_t* counts, const int32_t* offsets_yx, float* pred, int32_t k, int32_t max_det,
                         int32_t nc, dy_stream_t stream);
 
+/* ---- tiled inference on batches of frames: batched slicer, one-launch merge (csrc/tile_merge.hip) -----------------
+ * dy_tiles_batch_u8_to_nchw_f32: the slicer for f frames of one shape.  frames: uint8 (f, hf, wf, 3) contiguous; offsets_yx: k offsets
+ *   (y, x), DEVICE int32, shared by all frames; dst: fp32 (f*k, 3, th, tw) / 255, frame-major (tile f*k + k'); swap_rb and pad_value as in
+ *   dy_tiles_u8_to_nchw_f32, whose output it reproduces bit for bit (f = 1).  A lane handles four consecutive x of a tile row: float4
+ *   stores when tw % 4 == 0 and dst is 16-byte aligned, scalar stores otherwise.
+ * dy_tile_merge: the cross-tile merge of f frames in one launch, one workgroup per frame.
+ *   rows: fp32 (f*k, max_det, 6) and counts: int32 (f*k): the per-tile dy_nms outputs, in tile pixels, clipped to the tile; offsets_yx (k, 2)
+ *   as above.  Candidates are the rows r < counts[tile]; a candidate's box is the row's xyxy plus its tile's (ox, oy) (one fp32 add of an
+ *   integer-valued float).  Order: descending score, ties by ascending slot k'*max_det + r.  Greedy suppression: a candidate is dropped when
+ *   an already kept box of the same class (any class with agnostic; classes are compared as integers, nothing is added to coordinates) has
+ *     metric 0 (IoU): inter / (area_i + area_j - inter) > thr      metric 1 (IoS): inter / fminf(area_i, area_j) > thr
+ *   in fp32 without contraction, the IoU in dy_nms's expression order.  The scan stops at merge_max_det kept boxes.
+ *   out: fp32 (f, merge_max_det, 6) = x1, y1, x2, y2 (clamped to [0, frame_w] x [0, frame_h]), conf, cls; rows >= count are zero.
+ *   out_count: int32 (f).  out_index: optional int32 (f, merge_max_det): the slot of every kept row, -1 beyond the count; or NULL.
+ *   nc: the number of classes of the rows (cls in [0, nc)).  workspace: dy_tile_merge_workspace_bytes(f, k, max_det) bytes, 16-byte aligned
+ *   (-1 for sizes the entry point refuses).  Limits: k * max_det <= 32768 and merge_max_det <= 4096, DY_ERR_UNSUPPORTED beyond; every
+ *   argument is checked before any launch.  The layout of out / out_count / out_index is dy_nms's, so dy_val_match and dy_track_step read it. */
+int32_t dy_tiles_batch_u8_to_nchw_f32(const uint8_t* frames, const int32_t* offsets_yx, float* dst, int32_t f, int32_t k, int32_t hf, int32_t wf,
+                                      int32_t th, int32_t tw, int32_t swap_rb, float pad_value, dy_stream_t stream);
+typedef struct dy_tile_merge_desc {
+  const float* rows;
+  const int32_t* counts;
+  const int32_t* offsets_yx;
+  int32_t frames, tiles, max_det, nc;
+  int32_t frame_h, frame_w;
+  float thr;
+  int32_t metric; /* 0 = IoU, 1 = IoS (intersection over the smaller area) */
+  int32_t agnostic, merge_max_det;
+  float* out;
+  int32_t* out_count;
+  int32_t* out_index;
+  void* workspace;
+  int64_t workspace_bytes;
+} dy_tile_merge_desc;
+int64_t dy_tile_merge_workspace_bytes(int32_t frames, int32_t tiles, int32_t max_det);
+int32_t dy_tile_merge(const dy_tile_merge_desc* d, dy_stream_t stream);
+
 /* ---- layout / copy ops ------------------------------------------------------ */
 
 /* Replaces: predictor preprocess `.half()/.float()` + the NCHW->device layout step
