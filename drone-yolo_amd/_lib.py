@@ -203,6 +203,32 @@ class BnDesc(C.Structure):
     ]  # fmt: skip
 
 
+class MaskGatherDesc(C.Structure):
+    """Mirror of ``dy_mask_gather_desc``."""
+
+    _fields_ = [
+        ("rows", _vp), ("counts", _vp), ("index", _vp),
+        ("level", _vp * DY_MAX_LEVELS),
+        ("h", _i32 * DY_MAX_LEVELS), ("w", _i32 * DY_MAX_LEVELS), ("ld", _i32 * DY_MAX_LEVELS),
+        ("n_levels", _i32),
+        ("pred", _vp), ("pred_ch", _i32), ("pred_c0", _i32), ("anchors", _i32),
+        ("batch", _i32), ("max_det", _i32), ("nm", _i32),
+        ("out", _vp),
+    ]  # fmt: skip
+
+
+class ProcessMaskDesc(C.Structure):
+    """Mirror of ``dy_process_mask_desc``."""
+
+    _fields_ = [
+        ("protos", _vp), ("side", _vp), ("counts", _vp), ("offsets", _vp), ("window", _vp), ("crop_rows", _vp),
+        ("batch", _i32), ("max_det", _i32), ("nm", _i32), ("mh", _i32), ("mw", _i32), ("ld_p", _i32), ("oh", _i32), ("ow", _i32),
+        ("total", _i32), ("crop_at_output", _i32),
+        ("ratio_x", _f32), ("ratio_y", _f32),
+        ("out", _vp),
+    ]  # fmt: skip
+
+
 DY_AUG_FLIPLR, DY_AUG_FLIPUD, DY_AUG_HSV_OFF = 1, 2, 4
 
 
@@ -297,6 +323,9 @@ SIGNATURES = {
     "dy_silu_bwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dy_detection_loss": (_i32, [C.POINTER(LossDesc), _vp]),
     "dy_augment_u8_nchw": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "dy_depth_to_space2_nhwc": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "dy_mask_gather": (_i32, [C.POINTER(MaskGatherDesc), _vp]),
+    "dy_process_mask": (_i32, [C.POINTER(ProcessMaskDesc), _vp]),
 }
 
 _lib = None

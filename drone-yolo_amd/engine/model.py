@@ -1,5 +1,5 @@
 """``YOLO`` / ``Model`` user API (reference: ultralytics/engine/model.py:29-1177,
-ultralytics/models/yolo/model.py:11-59) for the detection task on the MI355X path."""
+ultralytics/models/yolo/model.py:11-59) for the detection and (prediction only) segmentation tasks on the MI355X path."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -8,9 +8,9 @@ from typing import List, Union
 import torch
 import torch.nn as nn
 
-from ..nn.tasks import DetectionModel, yaml_model_load
+from ..nn.tasks import DetectionModel, SegmentationModel, guess_model_task, yaml_model_load
 from ..utils import LOGGER
-from .predictor import DetectionPredictor
+from .predictor import DetectionPredictor, SegmentationPredictor
 from .results import Results
 
 
@@ -26,24 +26,34 @@ class Model(nn.Module):
         self.cfg = None
         self.ckpt_path = None
         self.overrides = {}
-        self.task = task or "detect"
-        if self.task != "detect":
-            raise NotImplementedError(f"task '{self.task}': only 'detect' is on the accelerated path")
+        self.task = task
+        if task not in (None, "detect", "segment"):
+            raise NotImplementedError(f"task '{task}': only 'detect' and 'segment' are on the accelerated path")
         model = str(model).strip()
         if Path(model).suffix in {".yaml", ".yml"}:
             self._new(model, verbose=verbose)
         elif Path(model).suffix == ".pt":
             self._load(model)
+            self.task = guess_model_task(self.model)
         else:
             raise NotImplementedError(f"'{model}': give a model YAML (*.yaml) or a state-dict checkpoint (*.pt); "
                                       "weight-name downloads need network access and are out of scope")
         self.model_name = model
 
+    @property
+    def task_map(self):
+        return {"detect": {"model": DetectionModel, "predictor": DetectionPredictor},
+                "segment": {"model": SegmentationModel, "predictor": SegmentationPredictor}}
+
     def _new(self, cfg: str, task=None, model=None, verbose=False) -> None:
         """Build from a YAML — reference engine/model.py:231-264."""
         cfg_dict = yaml_model_load(cfg)
         self.cfg = cfg
-        self.model = (model or DetectionModel)(cfg_dict, verbose=verbose)
+        found = guess_model_task(cfg_dict)
+        if self.task is not None and self.task != found:
+            raise ValueError(f"task '{self.task}' was asked for, but the head of '{cfg}' makes it a '{found}' model")
+        self.task = found
+        self.model = (model or self.task_map[self.task]["model"])(cfg_dict, verbose=verbose)
         self.overrides["model"] = self.cfg
         self.overrides["task"] = self.task
 
@@ -76,6 +86,7 @@ class Model(nn.Module):
         """Reference engine/model.py:501-560: predictor created on first use, conf defaults to 0.25."""
         if source is None:
             raise ValueError("'source' is missing; the device path takes a BCHW float tensor in [0, 1]")
+        self._refuse_for_segment(kwargs)
         track = kwargs.get("mode") == "track"
         args = {**self.overrides, "conf": 0.1 if track else 0.25, **kwargs}
         args.pop("model", None), args.pop("task", None), args.pop("mode", None)
@@ -85,7 +96,7 @@ class Model(nn.Module):
         elif args.get("tile") is not None and int(args.get("merge_max_det", 1000)) > 1024:  # (before a predictor is built or anything is launched)
             raise ValueError(f"merge_max_det = {args['merge_max_det']} with tile in track mode: the track step takes at most 1024 detections per frame")
         if self.predictor is None or getattr(self, "_pred_args", None) != (args, track):
-            self.predictor = (predictor or DetectionPredictor)(self.model, overrides=args)
+            self.predictor = (predictor or self.task_map[self.task]["predictor"])(self.model, overrides=args)
             self._pred_args = (args, track)
         if track:
             # the tracker outlives the predictor (a predict call in between rebuilds that): persist=True goes on with its tracks and ids
@@ -111,6 +122,18 @@ class Model(nn.Module):
         a multiple of it)."""
         return self.predict(source, stream, **{**kwargs, "mode": "track", "persist": persist, "tracker": tracker})
 
+    def _refuse_for_segment(self, kwargs: dict) -> None:
+        """What a segmentation model does not do, refused by argument name before a predictor is built or anything is launched."""
+        if self.task != "segment":
+            return
+        a = {**self.overrides, **kwargs}
+        if a.get("mode") == "track":
+            raise NotImplementedError("track: tracking is not built for segmentation models")
+        if a.get("tile") is not None:
+            raise NotImplementedError("tile: tiled inference is not built for segmentation models")
+        if a.get("augment"):
+            raise NotImplementedError("augment=True: test-time augmentation is not built for segmentation models")
+
     def profile(self, source, **kwargs) -> list:
         """Per-layer device time of one pass over ``source`` (reference ``predict(profile=True)`` -> ``_profile_one_layer``, nn/tasks.py:171-191):
         [{layer, type, launches, ms, kernels}], see ``DetectionPredictor.profile_layers``."""
@@ -124,6 +147,8 @@ class Model(nn.Module):
         after which rank-less this process reloads ``weights/last.pt`` — as the reference does (model.py:806-813)."""
         from .trainer import DetectionTrainer
 
+        if self.task == "segment":
+            raise NotImplementedError("train: the segmentation loss (v8SegmentationLoss) is not built; segmentation models predict only")
         args = {**{k: v for k, v in self.overrides.items() if k not in ("task", "mode")}, **kwargs}
         devs = [x for x in str(args.get("device", "")).replace("cuda:", "").split(",") if x.strip() != ""]
         multi = len(devs) > 1
@@ -157,6 +182,8 @@ class Model(nn.Module):
         ``"synthetic[:N]"`` (engine/trainer.py::load_dataset; image folders and dataset YAMLs are outside the accelerated path);
         ``batch``, ``imgsz``, ``conf``, ``iou``, ``max_det``, ``half`` / ``dtype``, ``device`` as the reference's arguments.  Returns the
         reference's ``results_dict`` (metrics/precision(B) ... metrics/mAP50-95(B), fitness) with the validation losses; kept in ``self.metrics``."""
+        if self.task == "segment":
+            raise NotImplementedError("val: mask metrics are not built; segmentation models predict only")
         from .predictor import resolve_dtype
         from .trainer import TensorLoader, load_dataset
         from .validator import DetectionValidator
@@ -206,7 +233,3 @@ class YOLO(Model):
 
     def __init__(self, model="yolov8s-p2-repvgg.yaml", task=None, verbose=False):
         super().__init__(model=model, task=task, verbose=verbose)
-
-    @property
-    def task_map(self):
-        return {"detect": {"model": DetectionModel, "predictor": DetectionPredictor}}

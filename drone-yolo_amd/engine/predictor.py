@@ -93,7 +93,7 @@ class DetectionPredictor:
         a = dict(conf=0.25, iou=0.7, max_det=300, classes=None, agnostic_nms=False, half=False, dtype=None, device="",
                  verbose=False, graph=True, max_nms=30000, max_wh=7680, imgsz=640, fp8_layers=None, batch=None, augment=False,
                  tracker="bytetrack.yaml", device_track=True, track_streams=1, max_tracks=512,
-                 tile=None, tile_overlap=0.2, merge_iou=0.7, merge_metric="iou", merge_max_det=1000)
+                 tile=None, tile_overlap=0.2, merge_iou=0.7, merge_metric="iou", merge_max_det=1000, retina_masks=False)
         a.update(overrides or {})
         self.args = a
         if a["tile"] is not None:  # tiled inference: checked before anything touches the device
@@ -205,11 +205,12 @@ class DetectionPredictor:
         self.model.fp8_layers = plan8
         try:
             with H.record(cf.plan):
-                y, _ = self.model._predict_once(im, image_dtype=self.dtype)
+                y, aux = self.model._predict_once(im, image_dtype=self.dtype)
                 cf.pred = y
                 cf.nms = H.nms(y, float(a["conf"]), float(a["iou"]), max_det=int(a["max_det"]), max_nms=int(a["max_nms"]),
                                max_wh=float(a["max_wh"]), agnostic=bool(a["agnostic_nms"]), nc=self.model.yaml["nc"],
                                classes_mask=self._classes_mask, bufs=holder.get("bufs"), prefiltered="bufs" in holder)
+                self._record_masks(cf, aux)  # (a segmentation model: the coefficient gather, in front of the box rescale)
                 # construct_result: scale_boxes(img.shape[2:], boxes, orig.shape) — tensor sources are their own
                 # original image, so gain 1 / pad 0 and the clip to (h, w) remain (detect/predict.py:59-73)
                 H.scale_boxes_(cf.nms, params)
@@ -219,6 +220,17 @@ class DetectionPredictor:
             self.model.fp8_layers = None
         cf.plan.keep.append(params)
         return cf
+
+    def _record_masks(self, cf: CompiledForward, aux) -> None:
+        """Hook between the NMS and the box rescale of the recorded pass; the detection task launches nothing here."""
+
+    def _mask_stash(self, cf: CompiledForward, streamed: bool):
+        """What the masks of this batch are assembled from once its counts are on the host (None: a detection model)."""
+        return None
+
+    def _masks_for(self, stash, counts, rows, im, info) -> list:
+        """Per image the (k, H, W) masks of its k detections, or None."""
+        return [None] * len(counts)
 
     def _box_params(self, h: int, w: int, n: int):
         """Per image (gain, pad_x, pad_y, clip_w, clip_h) of ops.scale_boxes (utils/ops.py:92-127) for the current source: n rows."""
@@ -389,10 +401,11 @@ class DetectionPredictor:
         out = []
         info = getattr(self, "letterbox_info", None)
         rows = cf.nms.out.clone()  # ONE copy of the padded (N, max_det, 6) rows: the next pass overwrites the buffer, the Results keep views of this one
+        masks = self._masks_for(self._mask_stash(cf, streamed=False), counts, rows, im, info)
         for i, k in enumerate(counts):
             one = (info[i] if isinstance(info, list) else info) if info else None
             out.append(Results(im[i], paths[i] if paths else f"image{i}.jpg", names, boxes=self._boxes_of(i, k, rows, tracked),
-                               orig_shape=(one[0], one[1]) if one else im.shape[2:]))
+                               orig_shape=(one[0], one[1]) if one else im.shape[2:], masks=masks[i]))
         return out
 
     # ---- image files and PIL images as sources (reference data/build.py:160-200 check_source / load_inference_source, data/loaders.py:284-420
@@ -467,17 +480,18 @@ class DetectionPredictor:
         pending = None
 
         def finish(item):
-            lo, im, rows, counts_host, ev, info, t_pre, t_inf, paths, frames, trows = item
+            lo, im, rows, counts_host, ev, info, t_pre, t_inf, paths, frames, trows, stash = item
             t0 = time.perf_counter()
             ev.synchronize()
             both = counts_host.tolist()
             counts = both[: rows.shape[0]]
             tracked = (trows, both[rows.shape[0] :]) if trows is not None else None
             out = []
+            masks = self._masks_for(stash, counts, rows, im, info)
             for i, k in enumerate(counts):
                 one = (info[i] if isinstance(info, list) else info) if info else None
                 r = Results(frames[i] if frames is not None else im[i], paths[i] if paths else f"image{lo + i}.jpg", names, boxes=self._boxes_of(i, k, rows, tracked),
-                            orig_shape=(one[0], one[1]) if one else im.shape[2:])
+                            orig_shape=(one[0], one[1]) if one else im.shape[2:], masks=masks[i])
                 out.append(r)
             dt = (time.perf_counter() - t0) * 1e3 / max(len(out), 1)
             for r in out:  # host-side times per image (the device runs ahead: no synchronisation is placed around the stages)
@@ -501,7 +515,8 @@ class DetectionPredictor:
             t2 = time.perf_counter()
             n = max(im.shape[0], 1)
             item = (lo, im, rows, counts_host, ev, getattr(self, "letterbox_info", None), (t1 - t0) * 1e3 / n, (t2 - t1) * 1e3 / n, paths,
-                    piece if paths is not None else None, tracked[0] if tracked is not None else None)  # (file sources keep the decoded frame as the result's orig_img)
+                    piece if paths is not None else None, tracked[0] if tracked is not None else None,  # (file sources keep the decoded frame as the result's orig_img)
+                    self._mask_stash(cf, streamed=True))
             if pending is not None:
                 yield from finish(pending)
             pending = item
@@ -659,3 +674,63 @@ class DetectionPredictor:
         if self.args["verbose"]:
             LOGGER.info(f"{len(results)} images: " + ", ".join(f"{len(r)} boxes" for r in results))
         return iter(results) if stream else results
+
+
+class SegmentationPredictor(DetectionPredictor):
+    """Predictor of the segmentation models — reference models/yolo/segment/predict.py:8-74 (``retina_masks`` as there, default False).
+
+    The recorded pass is the detection pass plus Proto, the per-level coefficient branches and — between the NMS and the box rescale, as
+    ops.process_mask crops with the boxes in input-image pixels — ``dy_mask_gather``.  The masks need the kept counts on the host (the
+    output holds sum(counts) masks), so ``dy_process_mask`` is launched where the counts are read back anyway: one launch per batch, still
+    one synchronisation.  The prototypes and the side buffer live in the recorded plan and are overwritten by its next replay; a streamed
+    run, whose device works a batch ahead, therefore takes stream-ordered copies of both (and of the counts the kernel bounds its reads by)
+    behind the batch's launches, where the detection rows are copied too; a single call assembles from the plan's own buffers."""
+
+    def __init__(self, model, overrides: Optional[dict] = None):
+        a = overrides or {}
+        for k in ("tile", "augment"):  # before anything touches the device
+            if a.get(k) not in (None, False):
+                raise NotImplementedError(f"{k}: not built for segmentation models")
+        super().__init__(model, overrides)
+        self.args["task"] = "segment"
+
+    def preprocess(self, im) -> torch.Tensor:
+        out = super().preprocess(im)
+        if self.args["retina_masks"] and isinstance(self.letterbox_info, list):
+            raise NotImplementedError("retina_masks with sources of different shapes in one batch: the masks of a batch share one size")
+        return out
+
+    def make_tracker(self):
+        raise NotImplementedError("track: tracking is not built for segmentation models")
+
+    def _record_masks(self, cf: CompiledForward, aux) -> None:
+        if not (isinstance(aux, tuple) and len(aux) == 3):
+            raise RuntimeError("SegmentationPredictor needs a model whose head is Segment")
+        _, levels, protos = aux
+        cf.protos = protos
+        cf.side = H.mask_gather(cf.nms, levels=levels)
+
+    def _mask_stash(self, cf: CompiledForward, streamed: bool):
+        if streamed:
+            return cf.protos.clone(), cf.side.clone(), cf.nms.count.clone()
+        return cf.protos, cf.side, cf.nms.count
+
+    def _masks_for(self, stash, counts, rows, im, info) -> list:
+        protos, side, count = stash
+        n, _, mh, mw = protos.shape
+        ih, iw = int(im.shape[2]), int(im.shape[3])
+        if self.args["retina_masks"]:
+            h0, w0 = (info[0], info[1]) if info else (ih, iw)
+            # scale_masks (utils/ops.py:732-753): the letterbox-free window of the proto grid, resized to the original image
+            gain = min(mh / h0, mw / w0)
+            pad_w, pad_h = (mw - w0 * gain) / 2, (mh - h0 * gain) / 2
+            top, left = int(pad_h), int(pad_w)
+            win = (top, left, int(mh - pad_h) - top, int(mw - pad_w) - left)
+            allm = H.process_mask(protos, side, count, counts, (h0, w0), windows=[win] * n, crop_rows=rows)
+        else:
+            allm = H.process_mask(protos, side, count, counts, (ih, iw), ratio=(mw / iw, mh / ih))
+        out, o = [], 0
+        for k in counts:
+            out.append(allm[o : o + k] if k else None)
+            o += k
+        return out

@@ -1,8 +1,8 @@
 """Result containers (reference: ultralytics/engine/results.py: ``Results``, ``Boxes`` :1004).
 
-Only the tensor-view surface the detection path fills is kept (boxes); plotting / saving /
-masks / keypoints are out of scope.  ``Boxes`` wraps the (n, 6) rows [x1, y1, x2, y2, conf, cls]
-that ``dy_nms`` + ``dy_scale_boxes`` produced on the device.
+Only the tensor-view surface the detection and segmentation paths fill is kept (boxes, masks); plotting /
+saving / keypoints are out of scope.  ``Boxes`` wraps the (n, 6) rows [x1, y1, x2, y2, conf, cls]
+that ``dy_nms`` + ``dy_scale_boxes`` produced on the device, ``Masks`` the (n, H, W) bytes of ``dy_process_mask``.
 """
 from __future__ import annotations
 
@@ -85,14 +85,35 @@ class Boxes(BaseTensor):
         return xywh
 
 
-class Results:
-    """Per-image result — reference results.py (`Results`): orig_img, orig_shape, boxes, names, path, speed."""
+class Masks(BaseTensor):
+    """Instance masks of one image — reference results.py:1222-1280.  ``data``: (n, H, W) uint8, 0 / 1, on the device the pass ran on
+    (the reference holds float 0.0 / 1.0 there; one byte per pixel is what ``dy_process_mask`` writes and a quarter of the memory).
+    H x W is the input image (letterboxed size) or, with ``retina_masks``, the original image.  ``xy`` / ``xyn`` (polygon outlines) need
+    ``cv2.findContours`` (ops.masks2segments, utils/ops.py:810-836), which this package does not depend on."""
 
-    def __init__(self, orig_img, path, names, boxes=None, speed=None, orig_shape=None):
+    def __init__(self, masks, orig_shape):
+        if masks.ndim == 2:
+            masks = masks[None, :]
+        super().__init__(masks, orig_shape)
+
+    @property
+    def xy(self):
+        raise NotImplementedError("Masks.xy: polygon outlines need cv2.findContours, which this package does not depend on; use .data")
+
+    @property
+    def xyn(self):
+        raise NotImplementedError("Masks.xyn: polygon outlines need cv2.findContours, which this package does not depend on; use .data")
+
+
+class Results:
+    """Per-image result — reference results.py (`Results`): orig_img, orig_shape, boxes, masks, names, path, speed."""
+
+    def __init__(self, orig_img, path, names, boxes=None, speed=None, orig_shape=None, masks=None):
         self._orig_img = orig_img
         self.orig_shape = tuple(orig_shape) if orig_shape is not None else tuple(orig_img.shape[:2])
         self.boxes = Boxes(boxes, self.orig_shape) if boxes is not None else None
-        self.masks = self.probs = self.keypoints = self.obb = None
+        self.masks = Masks(masks, self.orig_shape) if masks is not None else None
+        self.probs = self.keypoints = self.obb = None
         self.speed = speed if speed is not None else {"preprocess": None, "inference": None, "postprocess": None}
         self.names = names
         self.path = path
@@ -112,21 +133,25 @@ class Results:
     def cpu(self):
         r = Results(self._orig_img, self.path, self.names, None, self.speed, self.orig_shape)
         r.boxes = self.boxes.cpu() if self.boxes is not None else None
+        r.masks = self.masks.cpu() if self.masks is not None else None
         return r
 
     def numpy(self):
         r = Results(self._orig_img, self.path, self.names, None, self.speed, self.orig_shape)
         r.boxes = self.boxes.numpy() if self.boxes is not None else None
+        r.masks = self.masks.numpy() if self.masks is not None else None
         return r
 
     def to(self, *args, **kwargs):
         r = Results(self._orig_img, self.path, self.names, None, self.speed, self.orig_shape)
         r.boxes = self.boxes.to(*args, **kwargs) if self.boxes is not None else None
+        r.masks = self.masks.to(*args, **kwargs) if self.masks is not None else None
         return r
 
     def __getitem__(self, idx):
         r = Results(self._orig_img, self.path, self.names, None, self.speed, self.orig_shape)
         r.boxes = self.boxes[idx] if self.boxes is not None else None
+        r.masks = self.masks[idx] if self.masks is not None else None
         return r
 
     # ---- text forms of a detection result (reference results.py:633-666 verbose, :668-757 save_txt, :759-823 summary, :906-940 to_json) ----

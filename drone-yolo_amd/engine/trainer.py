@@ -63,7 +63,7 @@ CFG_FLOAT_KEYS = frozenset({"warmup_epochs", "box", "cls", "dfl", "time", "batch
 CFG_FRACTION_KEYS = frozenset({"lr0", "lrf", "momentum", "weight_decay", "warmup_momentum", "warmup_bias_lr", "conf", "iou", "hsv_h", "hsv_s", "hsv_v",
                                "translate", "scale", "perspective", "flipud", "fliplr", "mosaic"})  # 0.0 <= v <= 1.0
 CFG_INT_KEYS = frozenset({"epochs", "patience", "seed", "max_det", "nbs", "close_mosaic", "track_streams"})
-CFG_BOOL_KEYS = frozenset({"save", "verbose", "single_cls", "half", "agnostic_nms", "stream", "amp", "multi_scale", "device_augment", "device_match", "device_track"})
+CFG_BOOL_KEYS = frozenset({"save", "verbose", "single_cls", "half", "agnostic_nms", "stream", "amp", "multi_scale", "device_augment", "device_match", "device_track", "retina_masks"})
 
 
 def check_cfg(cfg: dict, hard: bool = True) -> None:

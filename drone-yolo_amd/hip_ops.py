@@ -1103,6 +1103,124 @@ def scale_boxes_(bufs: NmsBuffers, params: torch.Tensor) -> None:
             keep=(bufs, params))
 
 
+# ---- instance segmentation: Proto's transposed convolution, coefficient gather, mask assembly ------------------------------------
+NM = 32  # mask coefficients per detection the kernels are built for (Segment's default nm)
+
+
+def deconv2x2_as_conv1x1(weight: torch.Tensor, bias: Optional[torch.Tensor]):
+    """nn.ConvTranspose2d(cin, cout, 2, 2, 0) weights (cin, cout, 2, 2) -> the (4 * cout, cin, 1, 1) weights and (4 * cout) bias of the 1x1
+    convolution whose output ``depth_to_space2`` turns into the transposed convolution's: row (a * 2 + b) * cout + o = W[:, o, a, b]."""
+    cin, cout, kh, kw = weight.shape
+    if (kh, kw) != (2, 2):
+        raise ValueError("deconv2x2_as_conv1x1: a 2 x 2 kernel is expected")
+    w = weight.detach().float().permute(2, 3, 1, 0).reshape(4 * cout, cin, 1, 1).contiguous()
+    b = torch.zeros(cout, device=weight.device) if bias is None else bias.detach().float()
+    return w, b.repeat(4)
+
+
+def depth_to_space2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(n, 4c, h, w) -> (n, c, 2h, 2w), out[:, o, 2y + a, 2x + b] = x[:, (a * 2 + b) * c + o, y, x] (``dy_depth_to_space2_nhwc``)."""
+    require_device(x, "depth_to_space2 input")
+    n, c4, h, w = x.shape
+    if c4 % 4:
+        raise ValueError("depth_to_space2: the channel count must be a multiple of 4")
+    c = c4 // 4
+    if out is None:
+        out = alloc_nhwc(n, c, 2 * h, 2 * w, x.dtype, x.device)
+    elif tuple(out.shape) != (n, c, 2 * h, 2 * w) or out.dtype != x.dtype:
+        raise ValueError(f"depth_to_space2: out has shape {tuple(out.shape)}/{out.dtype}, expected {(n, c, 2 * h, 2 * w)}/{x.dtype}")
+    xp, lds = view_params(x)
+    op, ldd = view_params(out)
+    _launch(lib().dy_depth_to_space2_nhwc, (xp, op, n, h, w, c, lds, ldd, dy_dtype(x.dtype)), keep=(x, out))
+    return out
+
+
+def conv_transpose2x2(x: torch.Tensor, pc: PackedConv, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ConvTranspose2d(k=2, s=2, p=0): ``pc`` = PackedConv of ``deconv2x2_as_conv1x1``'s weights; the 1x1 GEMM, then the depth-to-space."""
+    return depth_to_space2(conv2d(x, pc), out=out)
+
+
+def mask_gather(bufs: NmsBuffers, levels: Optional[Sequence[torch.Tensor]] = None, pred: Optional[torch.Tensor] = None, nc: int = 0,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The kept rows' unscaled boxes and mask coefficients -> (N, max_det, 4 + 32) fp32 (``dy_mask_gather``; call it behind ``nms`` and in
+    front of ``scale_boxes_``).  ``levels``: the per-level fp32 NHWC coefficient maps (N, 32, h_i, w_i) of Segment.cv4; or ``pred``: the
+    (N, 4 + nc + 32, A) prediction tensor.  Rows beyond the counts are left as they are."""
+    d = _lib.MaskGatherDesc()
+    n, md = bufs.batch, bufs.max_det
+    if out is None:
+        out = torch.zeros((n, md, 4 + NM), dtype=torch.float32, device=bufs.out.device)
+    elif tuple(out.shape) != (n, md, 4 + NM) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("mask_gather: out must be a contiguous fp32 (N, max_det, 36) tensor")
+    d.rows, d.counts, d.index, d.out = bufs.out.data_ptr(), bufs.count.data_ptr(), bufs.index.data_ptr(), out.data_ptr()
+    d.batch, d.max_det, d.nm, d.anchors = n, md, NM, bufs.anchors
+    keep = [d, bufs, out]
+    if (levels is None) == (pred is None):
+        raise ValueError("mask_gather: give either the per-level coefficient maps or the prediction tensor")
+    if pred is not None:
+        require_device(pred, "prediction")
+        if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.dim() != 3 or pred.shape[0] != n or pred.shape[2] != bufs.anchors \
+                or pred.shape[1] != 4 + nc + NM:
+            raise ValueError("mask_gather: pred must be a contiguous fp32 (N, 4 + nc + 32, A) tensor")
+        d.pred, d.pred_ch, d.pred_c0 = pred.data_ptr(), pred.shape[1], 4 + nc
+        keep.append(pred)
+    else:
+        if len(levels) > _lib.DY_MAX_LEVELS:
+            raise ValueError("mask_gather: too many levels")
+        for i, t in enumerate(levels):
+            require_device(t, "coefficient map")
+            if t.dtype != torch.float32 or t.shape[0] != n or t.shape[1] != NM:
+                raise ValueError("mask_gather: coefficient maps must be fp32 (N, 32, h, w) NHWC views")
+            d.level[i], d.ld[i] = view_params(t)
+            d.h[i], d.w[i] = t.shape[2], t.shape[3]
+        d.n_levels = len(levels)
+        keep.extend(levels)
+    _launch(lib().dy_mask_gather, (C.byref(d),), keep=keep)
+    return out
+
+
+def process_mask(protos: torch.Tensor, side: torch.Tensor, count: torch.Tensor, counts_host: Sequence[int], out_hw: Tuple[int, int],
+                 ratio: Tuple[float, float] = (1.0, 1.0), windows: Optional[Sequence[Sequence[int]]] = None,
+                 crop_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The masks of a batch in one ``dy_process_mask`` launch: uint8 (sum(counts), oh, ow), freshly allocated.
+    ``protos``: fp32 NHWC view (N, 32, mh, mw); ``side``: ``mask_gather``'s output; ``count``: the device counts and ``counts_host`` their
+    values on the host (the predictor reads them back anyway); ``ratio`` = (mw / iw, mh / ih): proto pixels per input-image pixel, for the
+    crop at proto resolution (ops.process_mask).  ``crop_rows`` (the rows after ``scale_boxes_``) switches to the retina form
+    (ops.process_mask_native): resize ``windows[b]`` = (top, left, sh, sw) of the grid to (oh, ow), crop there."""
+    require_device(protos, "protos")
+    n, nm, mh, mw = protos.shape
+    if protos.dtype != torch.float32 or side.dtype != torch.float32 or not side.is_contiguous() or side.shape[0] != n or side.shape[2] != 4 + nm:
+        raise ValueError("process_mask: protos must be fp32 (N, nm, mh, mw), side a contiguous fp32 (N, max_det, 4 + nm) tensor")
+    md = side.shape[1]
+    counts_host = [int(k) for k in counts_host]
+    if len(counts_host) != n or any(k < 0 or k > md for k in counts_host):
+        raise ValueError("process_mask: counts_host must hold one count in [0, max_det] per image")
+    total = sum(counts_host)
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    out = torch.empty((total, oh, ow), dtype=torch.uint8, device=protos.device)
+    d = _lib.ProcessMaskDesc()
+    d.protos, d.ld_p = view_params(protos)
+    d.batch, d.max_det, d.nm, d.mh, d.mw, d.oh, d.ow, d.total = n, md, nm, mh, mw, oh, ow, total
+    d.ratio_x, d.ratio_y = float(ratio[0]), float(ratio[1])
+    if nm != NM:
+        raise NotImplementedError(f"process_mask: {nm} mask coefficients; dy_process_mask is built for {NM}")
+    if total == 0:
+        return out
+    offs = [0]
+    for k in counts_host:
+        offs.append(offs[-1] + k)
+    win = [list(map(int, w)) for w in windows] if windows is not None else [[0, 0, mh, mw]] * n
+    if len(win) != n:
+        raise ValueError("process_mask: one window per image")
+    table = torch.tensor(offs + [v for w in win for v in w], dtype=torch.int32).to(protos.device, non_blocking=True)
+    d.side, d.counts, d.offsets, d.window, d.out = side.data_ptr(), count.data_ptr(), table.data_ptr(), table[n + 1 :].data_ptr(), out.data_ptr()
+    if crop_rows is not None:
+        if crop_rows.dtype != torch.float32 or tuple(crop_rows.shape) != (n, md, 6) or not crop_rows.is_contiguous():
+            raise ValueError("process_mask: crop_rows must be the contiguous fp32 (N, max_det, 6) rows")
+        d.crop_rows, d.crop_at_output = crop_rows.data_ptr(), 1
+    _launch(lib().dy_process_mask, (C.byref(d),), keep=(d, protos, side, count, table, out, crop_rows))
+    return out
+
+
 def val_match(bufs: NmsBuffers, tbox: torch.Tensor, tcls: torch.Tensor, timg: torch.Tensor, iouv: Sequence[float], clip_wh: Tuple[float, float],
               single_cls: bool = False, want_best: bool = False):
     """The validator's matching (``BaseValidator.match_predictions`` on ``box_iou``, predictions clipped to ``clip_wh``) of a whole batch

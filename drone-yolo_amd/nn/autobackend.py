@@ -34,9 +34,9 @@ class AutoBackend(nn.Module):
 
                 model, _ = load_reference_checkpoint(w)
             elif w.endswith((".yaml", ".yml")):
-                from .tasks import DetectionModel
+                from .tasks import DetectionModel, SegmentationModel, guess_model_task
 
-                model = DetectionModel(w, verbose=False)
+                model = (SegmentationModel if guess_model_task(w) == "segment" else DetectionModel)(w, verbose=False)
             else:
                 raise NotImplementedError(f"'{w}': exported formats (onnx, engine, ...) are outside the accelerated path; give a module, *.pt or *.yaml")
         model = model.to(device)
@@ -54,7 +54,9 @@ class AutoBackend(nn.Module):
         self.names = model.names
         self.pt = self.nn_module = True
         self.jit = self.onnx = self.engine = self.triton = False
-        self.batch, self.task, self.end2end = batch, "detect", getattr(model, "end2end", False)
+        from .tasks import guess_model_task
+
+        self.batch, self.task, self.end2end = batch, guess_model_task(model), getattr(model, "end2end", False)
 
     def forward(self, im: torch.Tensor, augment: bool = False, visualize: bool = False, embed=None):
         """fp32 NCHW image batch on the device -> (decoded (N, 4 + nc, A) fp32, raw maps or None)."""

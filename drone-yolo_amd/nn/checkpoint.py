@@ -60,6 +60,7 @@ def _own_classes() -> Dict[str, type]:
 
     out = {n: getattr(M, n) for n in dir(M) if isinstance(getattr(M, n), type)}
     out["DetectionModel"] = T.DetectionModel
+    out["SegmentationModel"] = T.SegmentationModel
     out["BaseModel"] = T.BaseModel
     return out
 
@@ -123,11 +124,11 @@ def read_checkpoint_dict(path: str) -> Dict[str, Any]:
 
 
 def load_reference_checkpoint(path: str, verbose: bool = False):
-    """A ``DetectionModel`` of this package carrying the checkpoint's architecture and weights."""
-    from .tasks import DetectionModel
+    """A ``DetectionModel`` (``SegmentationModel`` when the yaml's head is Segment) of this package carrying the checkpoint's architecture and weights."""
+    from .tasks import DetectionModel, SegmentationModel, guess_model_task
 
     yaml_d, sd, meta = read_reference_checkpoint(path)
-    model = DetectionModel(dict(yaml_d), ch=yaml_d.get("ch", 3), nc=yaml_d.get("nc"), verbose=verbose)
+    model = (SegmentationModel if guess_model_task(dict(yaml_d)) == "segment" else DetectionModel)(dict(yaml_d), ch=yaml_d.get("ch", 3), nc=yaml_d.get("nc"), verbose=verbose)
     own = model.state_dict()
     missing = [k for k in own if k not in sd]
     extra = [k for k in sd if k not in own]
@@ -144,7 +145,8 @@ def load_reference_checkpoint(path: str, verbose: bool = False):
 _REF_PATHS = {"Conv": "ultralytics.nn.modules.conv", "DWConv": "ultralytics.nn.modules.conv", "Concat": "ultralytics.nn.modules.conv",
               "DFL": "ultralytics.nn.modules.block", "SPPF": "ultralytics.nn.modules.block", "C2f": "ultralytics.nn.modules.block",
               "Bottleneck": "ultralytics.nn.modules.block", "RepVGGBlock": "ultralytics.nn.modules.block", "SEBlock": "ultralytics.nn.modules.block",
-              "Detect": "ultralytics.nn.modules.head", "DetectionModel": "ultralytics.nn.tasks", "BaseModel": "ultralytics.nn.tasks"}
+              "Detect": "ultralytics.nn.modules.head", "DetectionModel": "ultralytics.nn.tasks", "BaseModel": "ultralytics.nn.tasks",
+              "Proto": "ultralytics.nn.modules.block", "Segment": "ultralytics.nn.modules.head", "SegmentationModel": "ultralytics.nn.tasks"}
 _DROP_ATTRS = ("_packed", "_block_cache", "_tail_cache", "_front_cache", "_first_cache", "_stem2_cache", "_sig_tensors", "_weights_epoch", "_place", "_srcs", "_virtual", "_skip", "_front",
                "_consumers0", "_out_ch", "_cum_stride", "criterion", "train_dtype", "args", "fused_nms", "fuse_tail")
 

@@ -1,6 +1,6 @@
 """Block-level modules of the Drone-YOLO path (reference: ultralytics/nn/modules/block.py).
 
-``DFL`` (:58-76), ``SPPF`` (:172-191), ``C2f`` (:227-249), ``Bottleneck`` (:337-350) and the fork's
+``DFL`` (:58-76), ``Proto`` (:80-97), ``SPPF`` (:172-191), ``C2f`` (:227-249), ``Bottleneck`` (:337-350) and the fork's
 own ``conv_bn`` / ``SEBlock`` / ``RepVGGBlock`` (:1365-1490).  chunk / cat inside C2f and SPPF are
 done by construction: every producer writes its channel slice of one NHWC buffer.
 """
@@ -12,7 +12,7 @@ import torch.nn as nn
 from ... import hip_ops as H
 from .conv import Conv, _PackedMixin, _train_forward, fold_conv_bn
 
-__all__ = ("DFL", "SPPF", "C2f", "Bottleneck", "RepVGGBlock", "SEBlock", "conv_bn")
+__all__ = ("DFL", "Proto", "SPPF", "C2f", "Bottleneck", "RepVGGBlock", "SEBlock", "conv_bn")
 
 
 class DFL(nn.Module):
@@ -30,6 +30,51 @@ class DFL(nn.Module):
 
     def forward(self, x):
         raise RuntimeError("DFL is fused into Detect's decode kernel (dy_detect_decode); call Detect instead")
+
+
+class Proto(_PackedMixin, nn.Module):
+    """Mask prototypes of the segmentation models — reference block.py:80-97: cv1 3x3, ``upsample`` = ConvTranspose2d(c_, c_, 2, 2, 0,
+    bias=True), cv2 3x3, cv3 1x1; same state-dict keys.
+
+    The transposed convolution (kernel = stride = 2: every output pixel has ONE input pixel) runs as a 1x1 convolution c_ -> 4 c_ on the
+    repacked weights plus ``dy_depth_to_space2_nhwc`` (``H.deconv2x2_as_conv1x1``).  ``cv3`` writes the prototypes in fp32, NHWC, in true
+    units whatever the storage type and activation domain of the pass: the mask assembly (``dy_process_mask``) reads them as they are.
+    """
+
+    def __init__(self, c1, c_=256, c2=32):
+        super().__init__()
+        self.cv1 = Conv(c1, c_, k=3)
+        self.upsample = nn.ConvTranspose2d(c_, c_, 2, 2, 0, bias=True)
+        self.cv2 = Conv(c_, c_, k=3)
+        self.cv3 = Conv(c_, c2)
+
+    def _pack(self, dtype, device, cin_pad=None) -> H.PackedConv:
+        """The pack of ``upsample`` (this module's only own launch besides its Conv children) as a 1x1 convolution."""
+        w, b = H.deconv2x2_as_conv1x1(self.upsample.weight, self.upsample.bias)
+        w, b, act = H.domain_fold(w, b, False)  # scaled input -> scaled output: the bias carries the domain's factor
+        return H.PackedConv(w, b, 1, 0, 1, act, dtype, device)
+
+    def _packed_cv3(self, x: torch.Tensor) -> H.PackedConv:
+        """cv3 packed to LEAVE the scaled activation domain: weights / log2 e on the scaled input, the plain SiLU on the true
+        pre-activation (SiLU is not homogeneous, so unlike the Detect tails the activation itself must run in true units)."""
+        cache = self.cv3._pack_cache()
+        key = ("proto_out", x.dtype, x.device, H.scaled_domain())
+        pc = cache.get(key)
+        if pc is None:
+            w, b = fold_conv_bn(self.cv3.conv.weight, self.cv3.conv.bias, self.cv3.bn)
+            if H.scaled_domain():
+                w = w / H.LOG2E
+            pc = cache[key] = H.PackedConv(w, b, 1, 0, 1, H.DY_ACT_SILU if isinstance(self.cv3.act, nn.SiLU) else H.DY_ACT_NONE, x.dtype, x.device,
+                                           for_out_f32=True)
+        return pc
+
+    def forward(self, x):
+        if self.training:
+            raise NotImplementedError("Proto: training a segmentation model (v8SegmentationLoss) is not built; prediction only")
+        t = self.cv1(x)
+        t = H.conv_transpose2x2(t, self._packed_for(t))
+        t = self.cv2(t)
+        return H.conv2d(t, self._packed_cv3(t), out_f32=True)
 
 
 class Bottleneck(nn.Module):

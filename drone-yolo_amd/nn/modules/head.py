@@ -1,4 +1,4 @@
-"""Detect head of the Drone-YOLO path (reference: ultralytics/nn/modules/head.py:21-172)."""
+"""Detect and Segment heads of the Drone-YOLO path (reference: ultralytics/nn/modules/head.py:21-197)."""
 from __future__ import annotations
 
 import math
@@ -7,10 +7,10 @@ import torch
 import torch.nn as nn
 
 from ... import hip_ops as H
-from .block import DFL
+from .block import DFL, Proto
 from .conv import Conv, DWConv, PlainConv2d
 
-__all__ = ("Detect",)
+__all__ = ("Detect", "Segment")
 
 
 class Detect(nn.Module):
@@ -276,3 +276,47 @@ class Detect(nn.Module):
             a[-1].invalidate_packed()
             b[-1].invalidate_packed()
         self._tail_cache = None
+
+
+class Segment(Detect):
+    """YOLO Segment head — reference head.py:175-197: Detect plus ``proto`` (the mask prototypes of the first level) and, per level, the
+    mask-coefficient branch ``cv4`` = Conv(x, c4, 3), Conv(c4, c4, 3), Conv2d(c4, nm, 1); same constructor and state-dict keys.
+
+    Eval forward returns the reference's ``(cat([y, mc], 1), (feats, mc, p))``: y the decoded (N, 4 + nc, A), mc (N, nm, A), p
+    (N, nm, mh, mw) fp32 in true units (an NHWC view).  On the predictor's fast path (``fuse_tail``) nothing is concatenated: the
+    Detect kernels produce y and the candidate list as for a detection model and the return is ``(y, (None, levels, p))`` with ``levels``
+    the per-level fp32 NHWC coefficient maps (N, nm, h_i, w_i) that ``dy_mask_gather`` reads.  The box and class branches go through
+    every fusion of ``Detect`` unchanged.
+    """
+
+    def __init__(self, nc=80, nm=32, npr=256, ch=()):
+        super().__init__(nc, ch)
+        self.nm = nm
+        self.npr = npr
+        self.proto = Proto(ch[0], self.npr, self.nm)
+        c4 = max(ch[0] // 4, self.nm)
+        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), PlainConv2d(c4, self.nm, 1)) for x in ch)
+
+    def coefficient_maps(self, x):
+        """cv4 of every level: fp32 NHWC (N, nm, h_i, w_i), true units (the plain last conv leaves the scaled domain like the Detect tails)."""
+        out = []
+        for i in range(self.nl):
+            n, _, h, w = x[i].shape
+            buf = H.alloc_nhwc(n, self.nm, h, w, torch.float32, x[i].device, ld=(self.nm + 3) // 4 * 4)
+            out.append(self._run(self.cv4[i], x[i], buf))
+        return out
+
+    def forward(self, x):
+        if self.training:
+            raise NotImplementedError("Segment: training a segmentation model (v8SegmentationLoss) is not built; prediction only")
+        if any(t.dtype == H.FP8 for t in x):
+            raise NotImplementedError("Segment is built for the 16-bit, split-float16 and fp32 storage types")
+        x = list(x)
+        p = self.proto(x[0])
+        levels = self.coefficient_maps(x)
+        y, feats = Detect.forward(self, x)
+        if self.fuse_tail:
+            return y, (None, levels, p)
+        bs = p.shape[0]
+        mc = torch.cat([t.reshape(bs, self.nm, -1) for t in levels], 2)  # (layout glue of the module-level return only)
+        return torch.cat([y, mc], 1), (feats, mc, p)

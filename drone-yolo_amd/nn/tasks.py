@@ -33,7 +33,7 @@ from .. import hip_ops as H
 from ..utils import LOGGER
 from ..utils.ops import make_divisible
 from ..utils.torch_utils import initialize_weights
-from .modules import SPPF, Bottleneck, C2f, Concat, Conv, Detect, DWConv, RepVGGBlock, Upsample
+from .modules import SPPF, Bottleneck, C2f, Concat, Conv, Detect, DWConv, Proto, RepVGGBlock, Segment, Upsample
 from .modules.block import DFL
 from .modules.conv import PlainConv2d
 
@@ -41,7 +41,7 @@ CFG_DIR = Path(__file__).resolve().parents[1] / "cfg"
 
 _MODULES = {
     "Conv": Conv, "DWConv": DWConv, "RepVGGBlock": RepVGGBlock, "C2f": C2f, "SPPF": SPPF, "Bottleneck": Bottleneck,
-    "Concat": Concat, "Detect": Detect, "nn.Upsample": Upsample,
+    "Concat": Concat, "Detect": Detect, "Segment": Segment, "nn.Upsample": Upsample,
 }  # fmt: skip
 _BASE_MODULES = frozenset({Conv, DWConv, RepVGGBlock, C2f, SPPF, Bottleneck})
 _REPEAT_MODULES = frozenset({C2f})
@@ -106,8 +106,10 @@ def parse_model(d: dict, ch: int, verbose: bool = True):
                 n = 1
         elif m is Concat:
             c2 = sum(ch[x] for x in f)
-        elif m is Detect:
+        elif m in (Detect, Segment):
             args.append([ch[x] for x in f])
+            if m is Segment:  # the proto channels follow the width multiple (tasks.py:1058-1064)
+                args[2] = make_divisible(min(args[2], max_channels) * width, 8)
             m.legacy = legacy
         else:
             c2 = ch[f]
@@ -245,7 +247,7 @@ class BaseModel(nn.Module):
         if ok is None:
             ok = os.environ.get("DYOLO_L2E", "1") != "0" and isinstance(self.model[0], (Conv, RepVGGBlock)) and not isinstance(self.model[0], DWConv)
             known = (Conv, RepVGGBlock, C2f, SPPF, Bottleneck, Concat, Upsample, Detect, nn.Sequential, nn.ModuleList, PlainConv2d, nn.Conv2d, nn.BatchNorm2d,
-                     nn.SiLU, nn.Identity, nn.MaxPool2d, DFL)
+                     nn.SiLU, nn.Identity, nn.MaxPool2d, DFL, Proto, Segment, nn.ConvTranspose2d)
             ok = ok and all(isinstance(m, known) for m in self.model.modules())
             if ok:
                 self.model[0]._raw_input = True
@@ -515,6 +517,38 @@ class DetectionModel(BaseModel):
         from ..utils.loss import v8DetectionLoss
 
         return v8DetectionLoss(self)
+
+
+class SegmentationModel(DetectionModel):
+    """YOLO segmentation model — reference tasks.py:403-412.  Prediction only: the mask loss (v8SegmentationLoss) is not built."""
+
+    def __init__(self, cfg="yolov8s-p2-repvgg-seg.yaml", ch=3, nc=None, verbose=True):
+        super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
+
+    def init_criterion(self):
+        raise NotImplementedError("train: the segmentation loss (v8SegmentationLoss) is not built; segmentation models predict only")
+
+    def _predict_augment(self, x, image_dtype=None):
+        raise NotImplementedError("augment=True is not built for segmentation models")
+
+    def forward_train(self, img, dtype=None):
+        raise NotImplementedError("train: segmentation models predict only")
+
+
+def guess_model_task(model) -> str:
+    """'segment' or 'detect' from a YAML dict (its head's last module), a module graph (its head class) or a file name ('-seg') —
+    reference tasks.py:1127-1190, for the two tasks built here."""
+    if isinstance(model, dict):
+        with contextlib.suppress(Exception):
+            return "segment" if str(model["head"][-1][-2]).lower() == "segment" else "detect"
+    if isinstance(model, nn.Module):
+        if any(isinstance(m, Segment) for m in model.modules()):
+            return "segment"
+        y = getattr(model, "yaml", None)
+        return guess_model_task(y) if isinstance(y, dict) else "detect"
+    if isinstance(model, (str, Path)):
+        return "segment" if "-seg" in Path(model).stem else "detect"
+    return "detect"
 
 
 def _module_out_channels(m: nn.Module) -> int:

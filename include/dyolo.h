@@ -846,6 +846,64 @@ int64_t dy_track_workspace_bytes(int32_t streams, int32_t max_tracks, int32_t ma
 int32_t dy_track_reset(void* state, int32_t streams, int32_t max_tracks, dy_stream_t stream);
 int32_t dy_track_step(const dy_track_desc* d, dy_stream_t stream);
 
+/* ---- instance segmentation: Proto's transposed convolution, the mask-coefficient gather, mask assembly ---------------------
+ * dy_depth_to_space2_nhwc: the layout half of nn.ConvTranspose2d(c, c, 2, 2, 0) inside Proto (nn/modules/block.py:80-97).  A k = 2,
+ * s = 2, p = 0 transposed convolution is a 1x1 convolution cin -> 4 * cout (GEMM row (a * 2 + b) * cout + o = W[:, o, a, b], the bias
+ * repeated four times; dy_conv2d_nhwc) followed by this permutation: src (n, h, w, 4c) -> dst (n, 2h, 2w, c),
+ *   dst[n, 2y + a, 2x + b, o] = src[n, y, x, (a * 2 + b) * c + o].
+ * A pure move of 16-byte chunks, so it serves DY_BF16 / DY_F16 / DY_F32 / DY_F16X2 alike (DY_FP8: DY_ERR_INVALID_ARG); c % 8 != 0:
+ * DY_ERR_UNSUPPORTED.  Pitches in elements, views 16-byte aligned. */
+int32_t dy_depth_to_space2_nhwc(const void* src, void* dst, int32_t n, int32_t h, int32_t w, int32_t c, int32_t ld_src, int32_t ld_dst,
+                                int32_t dtype, dy_stream_t stream);
+
+/* dy_mask_gather: behind dy_nms and IN FRONT of dy_scale_boxes (ops.process_mask crops with the boxes in input-image pixels,
+ * models/yolo/segment/predict.py:66-74).  For every kept row r < counts[b] of image b: out[b, r, 0:4] = rows[b, r, 0:4] and
+ * out[b, r, 4:4+nm] = the nm mask coefficients of anchor index[b, r] — what `pred[:, 6:]` holds in the reference after
+ * non_max_suppression(nc=...) (utils/ops.py:181-332).  Two sources: per-level fp32 NHWC buffers level[i] (batch, h[i], w[i], nm) with pitch
+ * ld[i] (the outputs of Segment.cv4[i], nn/modules/head.py:175-197; anchors are numbered level by level, row-major), or — pred != NULL —
+ * a (batch, pred_ch, anchors) fp32 prediction tensor whose channels pred_c0 .. pred_c0 + nm - 1 are the coefficients.  Rows >= counts[b]
+ * are neither read nor written; an index outside [0, anchors) writes zeros.  nm != 32: DY_ERR_UNSUPPORTED. */
+typedef struct dy_mask_gather_desc {
+  const float* rows;      /* (batch, max_det, 6) dy_nms out, unscaled */
+  const int32_t* counts;  /* (batch) */
+  const int32_t* index;   /* (batch, max_det) dy_nms out_index */
+  const float* level[DY_MAX_LEVELS];
+  int32_t h[DY_MAX_LEVELS], w[DY_MAX_LEVELS], ld[DY_MAX_LEVELS];
+  int32_t n_levels;
+  const float* pred;
+  int32_t pred_ch, pred_c0, anchors;
+  int32_t batch, max_det, nm;
+  float* out; /* (batch, max_det, 4 + nm) */
+} dy_mask_gather_desc;
+int32_t dy_mask_gather(const dy_mask_gather_desc* d, dy_stream_t stream);
+
+/* dy_process_mask: the masks of a whole batch in one launch.  Replaces ops.process_mask(..., upsample=True) (utils/ops.py:679-709: matmul,
+ * crop_mask :660-676, F.interpolate bilinear, gt) and, with crop_at_output, ops.process_mask_native + scale_masks (:712-753): dot product,
+ * crop, blend and threshold per output pixel, no (n, mh, mw) intermediate.
+ * protos: fp32 NHWC (batch, mh, mw, nm), pitch ld_p, 16-byte aligned.  side: the dy_mask_gather output.  counts (batch); offsets
+ * (batch + 1): exclusive prefix of counts — detection t of the output belongs to the image b with offsets[b] <= t < offsets[b + 1], row
+ * t - offsets[b]; a t that belongs to no image, or whose row is >= counts[b] or >= max_det, gets a zero mask and reads nothing.
+ * window: int32 (batch, 4) top, left, sh, sw per image: the part of the proto grid that is resized (clamped into the grid on the device).
+ * out: uint8 (total, oh, ow), 0 / 1, 8-byte aligned; every byte is written.  Per output pixel (y, x) of a detection:
+ *   src = (dst + 0.5) * (s / o) - 0.5 clamped at 0, i0 = floor(src), i1 = min(i0 + 1, s - 1)  (PyTorch bilinear, align_corners = False),
+ *   corner value v = sum_k coef[k] * proto[top + yy, left + xx, k] in fp32, blend of the four corners, mask = blend > 0.
+ * crop_at_output == 0: a corner counts as 0 unless bx1 <= xx < bx2 and by1 <= yy < by2 with (bx, by) = the side buffer's box times
+ *   ratio_x / ratio_y (= mw / iw, mh / ih as fp32).  crop_at_output == 1: no corner crop; the mask is also 0 unless x1 <= x < x2 and
+ *   y1 <= y < y2 for crop_rows[b, r, 0:4] (fp32 (batch, max_det, 6): the rows after dy_scale_boxes).
+ * total == 0 returns DY_OK without a launch.  nm != 32: DY_ERR_UNSUPPORTED. */
+typedef struct dy_process_mask_desc {
+  const float* protos;
+  const float* side;
+  const int32_t* counts;
+  const int32_t* offsets;
+  const int32_t* window;
+  const float* crop_rows;
+  int32_t batch, max_det, nm, mh, mw, ld_p, oh, ow, total, crop_at_output;
+  float ratio_x, ratio_y;
+  uint8_t* out;
+} dy_process_mask_desc;
+int32_t dy_process_mask(const dy_process_mask_desc* d, dy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
