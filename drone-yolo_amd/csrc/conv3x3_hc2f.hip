@@ -8,17 +8,14 @@
 // pipe idle, and y_last — a quarter / a third of the concat buffer — is written and read back (0.42 GB per block at B = 256, 80 x 80).
 // Here y_last never leaves the CU and the two limits overlap.
 //
-// The 3x3 part is conv3x3_hreg.hip's / conv3x3_hhead.hip's: a wave holds the weights of its 16-cout fragment in 72 registers, the halo
-// patch of a 32-channel chunk (10 x 18 pixels, 64-byte pixel pitch, 16-byte part index XOR-ed with ((column >> 1) & 3)) is filled by
-// buffer-addressed LDS-DMA, tiles are 8 x 16 pixels, workgroups are persistent and walk XCD-contiguous tiles, zeros come from the
-// descriptor's range check.  The tail follows conv3x3_hhead: the tile's 3x3 output is rounded to the storage type exactly where the
+// The 3x3 part is the family's stride-1 form (hreg_core.h: HrS1).  The tail follows conv3x3_hhead: the tile's 3x3 output is rounded to the storage type exactly where the
 // layer-by-layer path rounds it and laid down in the `mid` image ([chunk 2][row 8][pixel 16] x 64 B, the halo's part swizzle); the 1x1
 // then runs on MFMAs with K over the NOP leading 64-channel groups of the concat buffer and `mid` (C2f.cv2's input order: buffer
 // channels first, the fused 3x3's output last).
 //
 // A tile is 2 (+ 1 with RES) + NOP items through one two-stage ring of 16 KB stages: the two halo chunks, then the CENTRE pixels of each operand
 // group (128 pixels x 64 channels = 16 KB, DMA'd straight into mid's format).  Every item issues the next item's DMA first and ends
-// with the full drain + barrier of the family (counted waits were not safe there, conv3x3_hreg.hip).  The 1x1's weight fragments are
+// with the full drain + barrier of the family (hreg_core.h: the drain rule).  The 1x1's weight fragments are
 // not resident (48 / 64 KB): a wave streams the 1 KB blocks of its two 16-cout fragments per item from L2, requested at the end of the
 // item before, in front of the drain that covers them.  With RES (shortcut) y_prev's image gets an item of its own behind the halo chunks:
 // it has landed when the item starts, and the 3x3's epilogue runs there and reads the residual from LDS in accumulator layout (no per-lane
@@ -29,6 +26,7 @@
 // (Two passes of 16 channels at three workgroups per CU need every operand of the tile resident at once, which costs the ring its
 // overlap with the next tile; not built.)
 #include "common_hip.h"
+#include "hreg_core.h"
 
 namespace DY_NS {
 
@@ -45,8 +43,8 @@ struct Hc2fArgs {
   int tilesX, tilesY, nSpatial;
 };
 
-constexpr int kHcTH = 8, kHcTW = 16, kHcHH = 10, kHcHW = 24;
-constexpr int kHcStage = 16 * 1024;
+constexpr int kHcTH = HrS1::TH, kHcTW = HrS1::TW;
+constexpr int kHcStage = HrS1::kStage;
 constexpr int kHcMid = 2 * kHcTH * kHcTW * 64;  // 16 KB: [chunk][row][pixel] x 64 B, the format of an operand stage too
 
 template <typename T, int NOP, bool RES>
@@ -60,28 +58,21 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hc2f_kernel(const Hc2fArgs p) 
   const int lq = lane >> 4, lr = lane & 15;
 
   const int G = (int)gridDim.x;
-  const int sb = ((int)blockIdx.x & 7) * (G >> 3) + ((int)blockIdx.x >> 3);  // XCD-contiguous tile order (the host makes G a multiple of 8)
-  const int myTiles = sb < p.nSpatial ? (p.nSpatial - sb + G - 1) / G : 0;
+  const int sb = hr_block(G, 1).sb;
+  const int myTiles = hr_my_tiles(p.nSpatial, sb, G);
   if (myTiles <= 0) return;
   const int nItems = myTiles * NIT;
 
   // ---- register-resident weights: the wave's 16-cout fragment of the 3x3 ----
   u32x4 wreg[NCH][9];
-  {
-    const u32x4* wg = reinterpret_cast<const u32x4*>(p.w3);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-#pragma unroll
-      for (int t = 0; t < 9; ++t) wreg[c][t] = wg[((c * 9 + t) * 4 + wave) * 64 + lane];
-  }
+  hr_load_wreg<NCH>(wreg, reinterpret_cast<const u32x4*>(p.w3), wave, lane);
   const f32x4 bias3 = *reinterpret_cast<const f32x4*>(p.b3 + wave * 16 + lq * 4);
   f32x4 bias1[2];  // the wave's output channels: fragments 2 wave, 2 wave + 1 (32 wave .. + 31)
 #pragma unroll
   for (int f = 0; f < 2; ++f) bias1[f] = *reinterpret_cast<const f32x4*>(p.b1 + (wave * 2 + f) * 16 + lq * 4);
 
   // ---- 1x1 weights: streamed per item.  k-group g (32 channels), fragment j: the 1 KB block (g * 8 + j) of the image ----
-  constexpr unsigned kOob = 0xfffffff0u;
-  constexpr int kVmcnt0 = 0x0f70;  // s_waitcnt vmcnt(0) alone
+  constexpr unsigned kOob = kHrOob;
   const __amdgpu_buffer_rsrc_t w1rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w1), 0, (NOP + 1) * 2 * NF1 * 1024, 0x00020000);
   u32x4 w1a[2][2], w1m[2][2];  // [k-group of the 64-channel group][fragment]: the item's operand group / `mid`
   auto load_w1 = [&](u32x4 (&w)[2][2], int group) {
@@ -97,49 +88,35 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hc2f_kernel(const Hc2fArgs p) 
   auto group_of_kind = [](int kind) constexpr { return (RES && kind == NCH) ? NOP - 1 : kind - NCH - NRI; };
 
   // ---- loaders ----
-  constexpr int NDMA = 4;  // every wave issues 4 wave-instructions per item (1 KB each: w, w + 4, w + 8, w + 12)
-  // halo (conv3x3_hreg.hip): descriptor shifted back by one image row + one pixel, lane-constant offsets + a scalar tile offset
+  constexpr int NDMA = HrS1::NDMA;  // every wave issues 4 wave-instructions per item (1 KB each: w, w + 4, w + 8, w + 12), halo and operand alike
   const unsigned pre = (unsigned)((p.W + 1) * p.ldt) * 2u;
   const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.t)) - pre, 0, p.t_bytes + pre, 0x00020000);
   const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.buf), 0, p.b_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
   unsigned rel[NDMA];   // halo: ((hy W + hx) ldt + part') * 2
   unsigned orel[NDMA];  // operand: block i = k * 4 + wave is (chunk i >> 3, row i & 7): ((row W + pixel) ldb + chunk * 32 + part' * 8) * 2
+  hr_halo_rel<HrS1>(rel, wave, lane, p.W, p.ldt, 2u, 2u * EPC);
 #pragma unroll
   for (int k = 0; k < NDMA; ++k) {
-    const int s = (k * 4 + wave) * 64 + lane;
-    const int pix = s >> 2, part = s & 3;
-    const int hy = pix / kHcHW, hx = pix - hy * kHcHW;
-    const bool dead = hx >= kHcTW + 2 || hy >= kHcHH;
-    rel[k] = dead ? kOob : (unsigned)((hy * p.W + hx) * p.ldt + (part ^ ((hx >> 1) & 3)) * EPC) * 2u;
     const int i = k * 4 + wave, px = lane >> 2;
-    orel[k] = (unsigned)(((i & 7) * p.W + px) * p.ldb + (i >> 3) * 4 * EPC + (part ^ ((px >> 1) & 3)) * EPC) * 2u;
+    orel[k] = (unsigned)(((i & 7) * p.W + px) * p.ldb + (i >> 3) * 4 * EPC + ((lane & 3) ^ ((px >> 1) & 3)) * EPC) * 2u;
   }
   unsigned voff[NDMA];
   unsigned l_base_t = 0, l_base_b = 0;
   int l_y0 = 0, l_x0 = 0;
   int l_tile = sb, l_item = 0;
   auto setup_tile = [&](int tile) {
-    const int tx = tile % p.tilesX;
-    const int r = tile / p.tilesX;
-    const int ty = r % p.tilesY, n = r / p.tilesY;
-    const int y0 = ty * kHcTH, x0 = tx * kHcTW;
+    const HrTile t = hr_tile(tile, p.tilesX, p.tilesY);
+    const int y0 = t.ty * kHcTH, x0 = t.tx * kHcTW;
     l_y0 = y0, l_x0 = x0;
-    l_base_t = (unsigned)(((n * p.H + y0) * p.W + x0) * p.ldt) * 2u;
-    l_base_b = (unsigned)(((n * p.H + y0) * p.W + x0) * p.ldb) * 2u;
-    const bool interior = y0 > 0 && y0 + kHcTH + 1 <= p.H && x0 > 0 && x0 + kHcTW + 1 <= p.W;  // wave-uniform
-    if (interior) {
+    l_base_t = (unsigned)(((t.n * p.H + y0) * p.W + x0) * p.ldt) * 2u;
+    l_base_b = (unsigned)(((t.n * p.H + y0) * p.W + x0) * p.ldb) * 2u;
+    if (hr_interior<HrS1>(y0, x0, p.H, p.W)) {
 #pragma unroll
       for (int k = 0; k < NDMA; ++k) voff[k] = rel[k];
-    } else {
-      const int l4 = lane >> 2;
+    } else {  // the mask again, on border tiles only
 #pragma unroll
-      for (int k = 0; k < NDMA; ++k) {
-        const int pix = (k * 4 + wave) * 16 + l4;
-        const int hy = pix / kHcHW, hx = pix - hy * kHcHW;
-        const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
-        voff[k] = ((unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W) ? rel[k] : kOob;
-      }
+      for (int k = 0; k < NDMA; ++k) voff[k] = hr_halo_inside<HrS1>(k, wave, lane, y0, x0, p.H, p.W) ? rel[k] : kOob;
     }
   };
   // DMA of the loader's item into `stage`, then advance the loader.  `kind` is the item's place in its tile (a compile-time constant at
@@ -148,10 +125,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hc2f_kernel(const Hc2fArgs p) 
     if (l_item >= nItems) return;  // (wave-uniform)
     unsigned char* sa = smem + stage * kHcStage;
     if (kind < NCH) {
-      const unsigned soff = l_base_t + (unsigned)kind * (4u * EPC * (unsigned)sizeof(T));
-#pragma unroll
-      for (int k = 0; k < NDMA; ++k)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(trs, (__attribute__((address_space(3))) void*)(sa + (k * 4 + wave) * 1024), 16, (int)voff[k], (int)soff, 0, 0);
+      hr_issue<NDMA>(trs, sa, wave, voff, l_base_t + (unsigned)kind * (4u * EPC * (unsigned)sizeof(T)));
     } else {
       const unsigned soff = l_base_b + (unsigned)group_of_kind(kind) * (64u * (unsigned)sizeof(T));
       const bool whole = l_y0 + kHcTH <= p.H && l_x0 + kHcTW <= p.W;  // wave-uniform
@@ -159,7 +133,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hc2f_kernel(const Hc2fArgs p) 
       for (int k = 0; k < NDMA; ++k) {
         unsigned vo = orel[k];
         if (!whole) vo = (l_y0 + ((k * 4 + wave) & 7) < p.H && l_x0 + (lane >> 2) < p.W) ? vo : kOob;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(brs, (__attribute__((address_space(3))) void*)(sa + (k * 4 + wave) * 1024), 16, (int)vo, (int)soff, 0, 0);
+        hr_issue1(brs, sa, k, wave, vo, soff);
       }
     }
     ++l_item;
@@ -170,28 +144,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hc2f_kernel(const Hc2fArgs p) 
   };
 
   int lane_base[3];
-#pragma unroll
-  for (int q = 0; q < 3; ++q) lane_base[q] = (lr + q) * 64 + ((lq ^ (((lr + q) >> 1) & 3)) * 16);
+  HrS1::lane_base(lane_base, lr, lq);
 
   f32x4 acc[kHcTH];       // 3x3: 16 couts x (8 rows x 16 pixels)
   f32x4 acc1[2][kHcTH];   // 1x1: 2 x 16 couts x (8 rows x 16 pixels)
 
-  auto compute3 = [&](const unsigned char* sa, int c) {
-#pragma unroll
-    for (int iy = 0; iy < kHcHH; ++iy) {
-      u32x4 a[3];
-#pragma unroll
-      for (int q = 0; q < 3; ++q) a[q] = *reinterpret_cast<const u32x4*>(sa + lane_base[q] + iy * (kHcHW * 64));
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        const int o = iy - r;
-        if (o >= 0 && o < kHcTH) {
-#pragma unroll
-          for (int q = 0; q < 3; ++q) acc[o] = Elem<T>::mma(wreg[c][r * 3 + q], a[q], acc[o]);
-        }
-      }
-    }
-  };
   // 1x1 over one 64-channel operand image (a ring stage or `mid`): one fragment read feeds both of the wave's cout fragments
   auto gemm1 = [&](const unsigned char* img, const u32x4 (&w)[2][2]) {
 #pragma unroll
@@ -205,87 +162,24 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hc2f_kernel(const Hc2fArgs p) 
       }
   };
 
-  typedef __attribute__((ext_vector_type(4))) T t4;
-  // a result lane of the 3x3 holds channels wave * 16 + lq * 4 .. + 3 of pixel (o, lr): 8 bytes of `mid` / of an operand image
-  const int mid_w = (wave >> 1) * (kHcTH * kHcTW * 64) + lr * 64 + ((((wave & 1) * 2 + (lq >> 1)) ^ ((lr >> 1) & 3)) * 16) + (lq & 1) * 8;  // + o * 1024
+  const int mid_w = hr_mid_offset(wave, lr, lq, kHcTH * kHcTW * 64);  // + o * 1024
   // the 3x3's epilogue: SiLU (+ y_prev from its operand image `resimg`), ONE rounding to the storage type, into `mid`
-  auto tail_mid = [&](const unsigned char* resimg) {
-#pragma unroll
-    for (int o = 0; o < kHcTH; ++o) {
-      float v[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = silu_f32(acc[o][e]);
-      if constexpr (RES) {
-        const t4 rr = __builtin_bit_cast(t4, *reinterpret_cast<const u32x2*>(resimg + mid_w + o * (kHcTW * 64)));
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += Elem<T>::to_f32(rr[e]);
-      }
-      t4 ov;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) ov[e] = Elem<T>::from_f32(v[e]);
-      *reinterpret_cast<u32x2*>(mid + mid_w + o * (kHcTW * 64)) = __builtin_bit_cast(u32x2, ov);
-    }
-  };
+  auto tail_mid = [&](const unsigned char* resimg) { hr_tail_mid<T, kHcTH, RES>(acc, mid + mid_w, resimg + mid_w); };
 
-  // output: 16-byte pieces as conv3x3_hreg's (v_permlane16_swap between the rows of a pair): quarter lq stores channels
-  // f * 16 + 8 (lq >> 1) .. + 7 of the wave's 32, row o + (lq & 1), column lr
+  // output: quarter lq stores channels f * 16 + 8 (lq >> 1) .. + 7 of the wave's 32, row o + (lq & 1), column lr
   unsigned lane_out[kHcTH / 2];
-#pragma unroll
-  for (int o = 0; o < kHcTH; o += 2) lane_out[o / 2] = (unsigned)(((o + (lq & 1)) * p.W + lr) * p.ldy + wave * 32 + (lq >> 1) * 8) * (unsigned)sizeof(T);
+  hr_lane_out<kHcTH>(lane_out, lr, lq, p.W, p.ldy, wave * 32 + (lq >> 1) * 8, (unsigned)sizeof(T));
   auto epilogue = [&](int tile) {
-    const int tx = tile % p.tilesX;
-    const int r = tile / p.tilesX;
-    const int ty = r % p.tilesY, n = r / p.tilesY;
-    const int y0 = ty * kHcTH, x0 = tx * kHcTW;
-    const unsigned out_base = (unsigned)(((n * p.H + y0) * p.W + x0) * p.ldy) * (unsigned)sizeof(T);  // scalar
-    const bool whole = y0 + kHcTH <= p.H && x0 + kHcTW <= p.W;                                         // wave-uniform
-    // The tile's eight 16-byte stores per lane leave back to back AFTER all of the epilogue's vector arithmetic, and nothing but the item's
-    // drain follows them (conv3x3_hreg's epilogue has that shape by itself: one fragment, then the barrier).  First form: fragment 0's stores,
-    // then fragment 1's SiLU.  The vector code behind a store re-used its data registers, and now and then — two workgroups per CU, several
-    // tiles per workgroup — the store sent the NEW content of one register in lanes 12..15 of every row of 16: a few wrong 4-byte pieces per
-    // thousand tiles, NaNs among them (always the last store in front of the arithmetic).
-    u32x4 st[2][kHcTH / 2];
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      u32x2 pk[kHcTH];
-#pragma unroll
-      for (int o = 0; o < kHcTH; ++o) {
-        t4 ov;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) ov[e] = Elem<T>::from_f32(silu_f32(acc1[f][o][e] + bias1[f][e]));  // (bias last, as conv1x1_stream adds it)
-        pk[o] = __builtin_bit_cast(u32x2, ov);
-      }
-#pragma unroll
-      for (int o = 0; o < kHcTH; o += 2) {
-        const auto sx = __builtin_amdgcn_permlane16_swap(pk[o][0], pk[o + 1][0], false, false);
-        const auto sy = __builtin_amdgcn_permlane16_swap(pk[o][1], pk[o + 1][1], false, false);
-        st[f][o / 2] = u32x4{sx[0], sy[0], sx[1], sy[1]};
-      }
-    }
-    unsigned off[kHcTH / 2];
-#pragma unroll
-    for (int o = 0; o < kHcTH; o += 2) {
-      off[o / 2] = lane_out[o / 2];
-      if (!whole) off[o / 2] = (y0 + o + (lq & 1) < p.H && x0 + lr < p.W) ? off[o / 2] : kOob;
-    }
-    // (the empty asm statements pin every operand of the stores in front of them: no arithmetic is scheduled or sunk between the stores)
-#pragma unroll
-    for (int f = 0; f < 2; ++f)
-#pragma unroll
-      for (int h = 0; h < kHcTH / 2; ++h) asm volatile("" : "+v"(st[f][h]));
-#pragma unroll
-    for (int h = 0; h < kHcTH / 2; ++h) asm volatile("" : "+v"(off[h]));
-#pragma unroll
-    for (int f = 0; f < 2; ++f)
-#pragma unroll
-      for (int h = 0; h < kHcTH / 2; ++h)
-        __builtin_amdgcn_raw_buffer_store_b128(st[f][h], yrs, off[h], (int)(out_base + (unsigned)f * (16u * (unsigned)sizeof(T))), 0);
+    const HrTile t = hr_tile(tile, p.tilesX, p.tilesY);
+    const int y0 = t.ty * kHcTH, x0 = t.tx * kHcTW;
+    const unsigned out_base = (unsigned)(((t.n * p.H + y0) * p.W + x0) * p.ldy) * (unsigned)sizeof(T);  // scalar
+    hr_out_1x1<T, kHcTH>(acc1, bias1, lane_out, yrs, out_base, y0, x0, p.H, p.W, lr, lq);
   };
 
   // ---- item pipeline: two stages, the next item's DMA in flight during this item's MFMAs, one drain + barrier per item ----
   setup_tile(l_tile);
   issue_dma(0, 0);
-  __builtin_amdgcn_s_waitcnt(kVmcnt0);
+  __builtin_amdgcn_s_waitcnt(kHrVmcnt0);
   __syncthreads();
   int c_tile = sb;
   int stage = 0;  // (where NIT is odd an item kind changes its stage from tile to tile)
@@ -299,7 +193,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hc2f_kernel(const Hc2fArgs p) 
 #pragma unroll
           for (int o = 0; o < kHcTH; ++o) acc[o] = bias3;
         }
-        compute3(sa, kind);
+        hr_rows_s1<T, NCH>(acc, wreg, sa, lane_base, kind);
         if (kind == NCH - 1) load_w1(w1a, 0);  // (for the tile's first operand item: covered by this item's drain — and by the residual item's)
       } else if (RES && kind == NCH) {
         tail_mid(sa);  // this item's image is y_prev.  `mid` is published by this item's barrier and read in the tile's last item.
@@ -318,15 +212,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hc2f_kernel(const Hc2fArgs p) 
           if (j == NOP - 2) load_w1(w1m, NOP);
         } else {
           gemm1(mid, w1m);
-          // (the tile's last MFMAs have retired before the epilogue's vector code reads their accumulators, whatever the scheduler does around here)
-          __builtin_amdgcn_sched_barrier(0);
-          asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-          __builtin_amdgcn_sched_barrier(0);
+          hr_settle_mfma();
           epilogue(c_tile);
           c_tile += G;
         }
       }
-      __builtin_amdgcn_s_waitcnt(kVmcnt0);  // (the builtin: the compiler then knows that the streamed weight registers are valid)
+      __builtin_amdgcn_s_waitcnt(kHrVmcnt0);  // (the builtin: the compiler then knows that the streamed weight registers are valid)
       __syncthreads();  // next item's image complete and visible; `mid` written; the output stores retired
       stage ^= 1;
     }
@@ -335,9 +226,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hc2f_kernel(const Hc2fArgs p) 
 
 template <typename T>
 static int launch_hc2f(const Hc2fArgs& a, int nop, bool res, hipStream_t st) {
-  int grid = 256 * 2;  // two 256-thread workgroups per CU (136 weight + accumulator registers per lane)
-  if (a.nSpatial < grid) grid = a.nSpatial;
-  grid = (grid + 7) / 8 * 8;
+  const int grid = hr_grid(2, a.nSpatial, 1);  // two 256-thread workgroups per CU (136 weight + accumulator registers per lane)
   const dim3 g((unsigned)grid), b(256);
   if (nop == 2) {
     if (res) hipLaunchKernelGGL((conv3x3_hc2f_kernel<T, 2, true>), g, b, 0, st, a);

@@ -10,11 +10,9 @@
 // Why: the 3x3's output has one consumer, the 1x1, and layer by layer it is written to HBM and read straight back by a launch that runs
 // at the copy rate (conv1x1_stream) while the matrix pipe idles.  Here `mid` never leaves the CU.
 //
-// The 3x3 part is conv3x3_hreg_s2_kernel's (conv3x3_hreg.hip): 4 x 16 output tile, 9 x 33 halo as two column-parity planes in the 64-byte
-// pitch swizzled image, 24 KB stages filled by buffer-addressed LDS-DMA (lane-constant offsets + a scalar tile offset, zeros from the
-// descriptor's range check), a wave's weights in registers (72 per 16-cout fragment; with C3 = 128 a wave holds fragments `wave` and
-// `wave + 4`: one workgroup stages the halo once where the layer-by-layer launch staged it in two), persistent workgroups in
-// XCD-contiguous tile order.  Each accumulator is summed as there: from the bias, then chunk, halo row, kernel row, column.
+// The 3x3 part is the family's stride-2 form (hreg_core.h: HrS2), a wave's weights in registers (72 per 16-cout fragment; with C3 = 128 a
+// wave holds fragments `wave` and `wave + 4`: one workgroup stages the halo once where the layer-by-layer launch staged it in two).
+// Each accumulator is summed as in conv3x3_hreg_s2_kernel: from the bias, then chunk, halo row, kernel row, column.
 // The hand-over is conv3x3_hc2f.hip's `mid` image: SiLU, ONE rounding to the storage type, [chunk C3 / 32][row 4][pixel 16] x 64 B with the
 // halo's part swizzle.  The 1x1 runs on MFMAs with a wave owning two 16-cout fragments and the tile's 4 rows, K ascending from a zero
 // accumulator, bias last (conv1x1_stream's summation): the launch computes what its two launches compute, bit for bit.  Its weights are
@@ -24,9 +22,10 @@
 // Items of a tile: the two halo chunks, then (form B) the CENTRE pixels of the two 64-channel groups of `other` (64 pixels x 64 channels
 // = 8 KB, DMA'd straight into mid's format).  Form A: ring of two stages, the DMA one item ahead; `mid` is published by a barrier of its
 // own inside the tile's second item and the 1x1 follows it.  Form B: ring of three stages, two items ahead; `mid` is published by the
-// barrier that ends the second item and read in the third.  Every item ends with the family's full drain + barrier (counted waits were
-// not safe there, conv3x3_hreg.hip), and all output stores of a tile leave back to back behind the epilogue's arithmetic (conv3x3_hc2f.hip).
+// barrier that ends the second item and read in the third.  Every item ends with the family's full drain + barrier, and all output stores
+// of a tile leave back to back behind the epilogue's arithmetic (hreg_core.h: the drain rule, the store rule).
 #include "common_hip.h"
+#include "hreg_core.h"
 
 namespace DY_NS {
 
@@ -43,8 +42,7 @@ struct HdownArgs {
   int tilesX, tilesY, nSpatial;
 };
 
-constexpr int kHdTH = 4, kHdTW = 16, kHdHH = 9, kHdPitch = 40, kHdPlaneB = 24;  // conv3x3_hreg_s2_kernel's tile and halo image
-constexpr int kHdStage = 24 * 1024;          // 9 x 40 slots x 64 B = 23,040 B, padded to 24 wave-instructions (6 per wave)
+constexpr int kHdTH = HrS2::TH, kHdTW = HrS2::TW, kHdStage = HrS2::kStage;
 constexpr int kHdChunk = kHdTH * kHdTW * 64;  // 4 KB: one 32-channel chunk of `mid` / of an operand image
 
 template <typename T, int C3, int NOG>
@@ -70,22 +68,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hdown_kernel(const HdownArgs p
   const int Ho = (p.H - 1) / 2 + 1, Wo = (p.W - 1) / 2 + 1;
 
   const int G = (int)gridDim.x;
-  const int sb = ((int)blockIdx.x & 7) * (G >> 3) + ((int)blockIdx.x >> 3);  // XCD-contiguous tile order (the host makes G a multiple of 8)
-  const int myTiles = sb < p.nSpatial ? (p.nSpatial - sb + G - 1) / G : 0;
+  const int sb = hr_block(G, 1).sb;
+  const int myTiles = hr_my_tiles(p.nSpatial, sb, G);
   if (myTiles <= 0) return;
   const int nItems = myTiles * NIT;
 
   // ---- register-resident weights: the wave's fragments of the 3x3 (`wave` of every 64-cout tile) and of the 1x1 (2 wave, 2 wave + 1) ----
   u32x4 wreg[NF3][NCH][9];
-  {
-    const u32x4* wg = reinterpret_cast<const u32x4*>(p.w3);
 #pragma unroll
-    for (int f = 0; f < NF3; ++f)
-#pragma unroll
-      for (int c = 0; c < NCH; ++c)
-#pragma unroll
-        for (int t = 0; t < 9; ++t) wreg[f][c][t] = wg[(((f * NCH + c) * 9 + t) * 4 + wave) * 64 + lane];
-  }
+  for (int f = 0; f < NF3; ++f) hr_load_wreg<NCH>(wreg[f], reinterpret_cast<const u32x4*>(p.w3) + f * NCH * 9 * 4 * 64, wave, lane);
   u32x4 w1[NW1R][2];
   {
     const u32x4* wg = reinterpret_cast<const u32x4*>(p.w1);
@@ -113,32 +104,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hdown_kernel(const HdownArgs p
   if constexpr (BIAS_RES) load_bias1();
 
   // ---- loaders ----
-  constexpr unsigned kOob = 0xfffffff0u;  // >= num_records of every descriptor here (the host checks the sizes)
-  constexpr int kVmcnt0 = 0x0f70;         // s_waitcnt vmcnt(0) alone
-  constexpr int NDMA = 6;                 // halo: 6 wave-instructions per wave and item (1 KB each: w, w + 4, .., w + 20)
+  constexpr unsigned kOob = kHrOob;
+  constexpr int NDMA = HrS2::NDMA;        // halo: 6 wave-instructions per wave and item (1 KB each: w, w + 4, .., w + 20)
   constexpr int NDMO = 2;                 // operand group: 2 (block i = k * 4 + wave is chunk k, row wave)
   const unsigned pre = (unsigned)((p.W + 1) * p.ldx) * 2u;
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.x)) - pre, 0, p.x_bytes + pre, 0x00020000);
   const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(NOG ? p.other : p.x), 0, NOG ? p.o_bytes : 0u, 0x00020000);
   const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
-  // halo slot = (k * 4 + wave) * 16 + (lane >> 2) of the 9 x 40 image, part = lane & 3 (conv3x3_hreg_s2_kernel)
-  auto halo_yx = [&](int k, int& hy, int& hx) {
-    const int slot = (k * 4 + wave) * 16 + (lane >> 2);
-    hy = slot / kHdPitch;
-    const int c = slot - hy * kHdPitch;
-    const bool planeB = c >= kHdPlaneB;
-    const int ci = planeB ? c - kHdPlaneB : c;  // column index inside the plane (the swizzle key)
-    hx = planeB ? 2 * ci + 1 : 2 * ci;          // halo column
-    return ci;
-  };
   unsigned rel[NDMA];  // launch constants: ((hy W + hx) ldx + part') * 2
-#pragma unroll
-  for (int k = 0; k < NDMA; ++k) {
-    int hy, hx;
-    const int ci = halo_yx(k, hy, hx);
-    const bool dead = hy >= kHdHH || hx > 2 * kHdTW;  // stage padding, plane padding
-    rel[k] = dead ? kOob : (unsigned)((hy * p.W + hx) * p.ldx + ((lane & 3) ^ ((ci >> 1) & 3)) * EPC) * 2u;
-  }
+  hr_halo_rel<HrS2>(rel, wave, lane, p.W, p.ldx, 2u, 2u * EPC);
   unsigned orel[NDMO];  // operand: ((row Wo + pixel) ldo + chunk * 32 + part' * 8) * 2
 #pragma unroll
   for (int k = 0; k < NDMO; ++k) {
@@ -147,19 +121,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hdown_kernel(const HdownArgs p
   }
   unsigned l_base_x = 0, l_base_o = 0;
   bool l_interior = false;   // the loader's tile needs no zero padding (wave-uniform)
-  int l_gy0 = 0, l_gx0 = 0;  // input coordinates of its halo's first pixel
+  int l_y0 = 0, l_x0 = 0;    // input coordinates of the centre tap of its first output pixel
   int l_oy0 = 0, l_ox0 = 0;  // output coordinates of the loader's tile
   int l_tile = sb, l_item = 0;
   auto setup_tile = [&](int tile) {
-    const int tx = tile % p.tilesX;
-    const int r = tile / p.tilesX;
-    const int ty = r % p.tilesY, n = r / p.tilesY;
-    l_oy0 = ty * kHdTH, l_ox0 = tx * kHdTW;
-    const int y0 = 2 * l_oy0, x0 = 2 * l_ox0;  // input coordinates of the tile's first output pixel's centre tap
-    l_base_x = (unsigned)(((n * p.H + y0) * p.W + x0) * p.ldx) * 2u;
-    if constexpr (NOG > 0) l_base_o = (unsigned)(((n * Ho + l_oy0) * Wo + l_ox0) * p.ldo) * 2u;
-    l_gy0 = y0 - 1, l_gx0 = x0 - 1;
-    l_interior = y0 > 0 && y0 - 1 + kHdHH <= p.H && x0 > 0 && x0 + 2 * kHdTW <= p.W;
+    const HrTile t = hr_tile(tile, p.tilesX, p.tilesY);
+    l_oy0 = t.ty * kHdTH, l_ox0 = t.tx * kHdTW;
+    l_y0 = 2 * l_oy0, l_x0 = 2 * l_ox0;
+    l_base_x = (unsigned)(((t.n * p.H + l_y0) * p.W + l_x0) * p.ldx) * 2u;
+    if constexpr (NOG > 0) l_base_o = (unsigned)(((t.n * Ho + l_oy0) * Wo + l_ox0) * p.ldo) * 2u;
+    l_interior = hr_interior<HrS2>(l_y0, l_x0, p.H, p.W);
   };
   // DMA of the loader's item into `stage`, then advance the loader.  `kind` is the item's place in its tile (a compile-time constant at
   // every call: the loader runs exactly LA items ahead of the compute).
@@ -169,17 +140,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hdown_kernel(const HdownArgs p
     if (kind < NCH) {
       const unsigned soff = l_base_x + (unsigned)kind * (4u * EPC * (unsigned)sizeof(T));
       if (l_interior) {
-#pragma unroll
-        for (int k = 0; k < NDMA; ++k)
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void*)(sa + (k * 4 + wave) * 1024), 16, (int)rel[k], (int)soff, 0, 0);
+        hr_issue<NDMA>(xrs, sa, wave, rel, soff);
       } else {  // border tile: out-of-image slots get an out-of-range offset (zeros); worked out per item, not kept in six more registers
 #pragma unroll
-        for (int k = 0; k < NDMA; ++k) {
-          int hy, hx;
-          halo_yx(k, hy, hx);
-          const unsigned vo = ((unsigned)(l_gy0 + hy) < (unsigned)p.H && (unsigned)(l_gx0 + hx) < (unsigned)p.W) ? rel[k] : kOob;
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void*)(sa + (k * 4 + wave) * 1024), 16, (int)vo, (int)soff, 0, 0);
-        }
+        for (int k = 0; k < NDMA; ++k) hr_issue1(xrs, sa, k, wave, hr_halo_inside<HrS2>(k, wave, lane, l_y0, l_x0, p.H, p.W) ? rel[k] : kOob, soff);
       }
     } else {
       const unsigned soff = l_base_o + (unsigned)(kind - NCH) * (64u * (unsigned)sizeof(T));
@@ -188,7 +152,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hdown_kernel(const HdownArgs p
       for (int k = 0; k < NDMO; ++k) {
         unsigned vo = orel[k];
         if (!whole) vo = (l_oy0 + wave < Ho && l_ox0 + (lane >> 2) < Wo) ? vo : kOob;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ors, (__attribute__((address_space(3))) void*)(sa + (k * 4 + wave) * 1024), 16, (int)vo, (int)soff, 0, 0);
+        hr_issue1(ors, sa, k, wave, vo, soff);
       }
     }
     ++l_item;
@@ -198,35 +162,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hdown_kernel(const HdownArgs p
     }
   };
 
-  // fragment reads of halo row iy: q = 0 -> plane A column lr, q = 1 -> plane B column lr, q = 2 -> plane A column lr + 1
-  int lane_base[3];
-  lane_base[0] = lr * 64 + ((lq ^ ((lr >> 1) & 3)) * 16);  // (also: pixel lr, part lq of a `mid` / operand row)
-  lane_base[1] = (kHdPlaneB + lr) * 64 + ((lq ^ ((lr >> 1) & 3)) * 16);
-  lane_base[2] = (lr + 1) * 64 + ((lq ^ (((lr + 1) >> 1) & 3)) * 16);
+  int lane_base[3];  // ([0] also: pixel lr, part lq of a `mid` / operand row)
+  HrS2::lane_base(lane_base, lr, lq);
 
   f32x4 acc[NF3][kHdTH];  // 3x3: NF3 x 16 couts x (4 rows x 16 pixels)
   f32x4 acc1[2][kHdTH];   // 1x1: 2 x 16 couts x (4 rows x 16 pixels)
 
-  auto compute3 = [&](const unsigned char* sa, int c) {
-#pragma unroll
-    for (int iy = 0; iy < kHdHH; ++iy) {
-      u32x4 a[3];
-#pragma unroll
-      for (int q = 0; q < 3; ++q) a[q] = *reinterpret_cast<const u32x4*>(sa + lane_base[q] + iy * (kHdPitch * 64));
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        if ((iy - r) % 2 == 0) {
-          const int o = (iy - r) / 2;
-          if (iy - r >= 0 && o < kHdTH) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q)
-#pragma unroll
-              for (int f = 0; f < NF3; ++f) acc[f][o] = Elem<T>::mma(wreg[f][c][r * 3 + q], a[q], acc[f][o]);  // D[cout][pixel]
-          }
-        }
-      }
-    }
-  };
   // 1x1 over one 64-channel operand image (a ring stage or two chunks of `mid`), weights w1[g0], w1[g0 + 1]: one fragment read feeds both
   // of the wave's cout fragments
   auto gemm1 = [&](const unsigned char* img, int g0) {
@@ -253,77 +194,24 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hdown_kernel(const HdownArgs p
     for (int g = 0; g < NKM; g += 2) gemm1(mid + g * kHdChunk, g);
   };
 
-  typedef __attribute__((ext_vector_type(4))) T t4;
-  // a result lane of the 3x3 holds channels (f * 4 + wave) * 16 + lq * 4 .. + 3 of pixel (o, lr): 8 bytes of `mid`
-  const int mid_w = (wave >> 1) * kHdChunk + lr * 64 + ((((wave & 1) * 2 + (lq >> 1)) ^ ((lr >> 1) & 3)) * 16) + (lq & 1) * 8;  // + f * 2 chunks + o * 1024
+  const int mid_w = hr_mid_offset(wave, lr, lq, kHdChunk);  // + f * 2 chunks + o * 1024: fragment f holds channels (f * 4 + wave) * 16 + lq * 4 .. + 3
   // the 3x3's epilogue: SiLU, ONE rounding to the storage type, into `mid`
   auto tail_mid = [&]() {
 #pragma unroll
-    for (int f = 0; f < NF3; ++f)
-#pragma unroll
-      for (int o = 0; o < kHdTH; ++o) {
-        t4 ov;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) ov[e] = Elem<T>::from_f32(silu_f32(acc[f][o][e]));
-        *reinterpret_cast<u32x2*>(mid + mid_w + f * (2 * kHdChunk) + o * (kHdTW * 64)) = __builtin_bit_cast(u32x2, ov);
-      }
+    for (int f = 0; f < NF3; ++f) hr_tail_mid<T, kHdTH, false>(acc[f], mid + mid_w + f * (2 * kHdChunk), nullptr);
   };
 
-  // output: 16-byte pieces (v_permlane16_swap between the rows of a pair): quarter lq stores channels f * 16 + 8 (lq >> 1) .. + 7 of the
-  // wave's 32, row o + (lq & 1), column lr
+  // output: quarter lq stores channels f * 16 + 8 (lq >> 1) .. + 7 of the wave's 32, row o + (lq & 1), column lr
   unsigned lane_out[kHdTH / 2];
-#pragma unroll
-  for (int o = 0; o < kHdTH; o += 2) lane_out[o / 2] = (unsigned)(((o + (lq & 1)) * Wo + lr) * p.ldy + wave * 32 + (lq >> 1) * 8) * (unsigned)sizeof(T);
+  hr_lane_out<kHdTH>(lane_out, lr, lq, Wo, p.ldy, wave * 32 + (lq >> 1) * 8, (unsigned)sizeof(T));
   auto epilogue = [&](int tile) {
-    const int tx = tile % p.tilesX;
-    const int r = tile / p.tilesX;
-    const int ty = r % p.tilesY, n = r / p.tilesY;
-    const int y0 = ty * kHdTH, x0 = tx * kHdTW;  // output coordinates
-    const unsigned out_base = (unsigned)(((n * Ho + y0) * Wo + x0) * p.ldy) * (unsigned)sizeof(T);  // scalar
-    const bool whole = y0 + kHdTH <= Ho && x0 + kHdTW <= Wo;                                         // wave-uniform
-    // (conv3x3_hc2f.hip: the tile's stores leave back to back AFTER all of the epilogue's vector arithmetic)
-    u32x4 st[2][kHdTH / 2];
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      u32x2 pk[kHdTH];
-#pragma unroll
-      for (int o = 0; o < kHdTH; ++o) {
-        t4 ov;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) ov[e] = Elem<T>::from_f32(silu_f32(acc1[f][o][e] + bias1[f][e]));  // (bias last, as conv1x1_stream adds it)
-        pk[o] = __builtin_bit_cast(u32x2, ov);
-      }
-#pragma unroll
-      for (int o = 0; o < kHdTH; o += 2) {
-        const auto sx = __builtin_amdgcn_permlane16_swap(pk[o][0], pk[o + 1][0], false, false);
-        const auto sy = __builtin_amdgcn_permlane16_swap(pk[o][1], pk[o + 1][1], false, false);
-        st[f][o / 2] = u32x4{sx[0], sy[0], sx[1], sy[1]};
-      }
-    }
-    unsigned off[kHdTH / 2];
-#pragma unroll
-    for (int o = 0; o < kHdTH; o += 2) {
-      off[o / 2] = lane_out[o / 2];
-      if (!whole) off[o / 2] = (y0 + o + (lq & 1) < Ho && x0 + lr < Wo) ? off[o / 2] : kOob;
-    }
-    // (the empty asm statements pin every operand of the stores in front of them: no arithmetic is scheduled or sunk between the stores)
-#pragma unroll
-    for (int f = 0; f < 2; ++f)
-#pragma unroll
-      for (int h = 0; h < kHdTH / 2; ++h) asm volatile("" : "+v"(st[f][h]));
-#pragma unroll
-    for (int h = 0; h < kHdTH / 2; ++h) asm volatile("" : "+v"(off[h]));
-#pragma unroll
-    for (int f = 0; f < 2; ++f)
-#pragma unroll
-      for (int h = 0; h < kHdTH / 2; ++h)
-        __builtin_amdgcn_raw_buffer_store_b128(st[f][h], yrs, off[h], (int)(out_base + (unsigned)f * (16u * (unsigned)sizeof(T))), 0);
+    const HrTile t = hr_tile(tile, p.tilesX, p.tilesY);
+    const int y0 = t.ty * kHdTH, x0 = t.tx * kHdTW;  // output coordinates
+    const unsigned out_base = (unsigned)(((t.n * Ho + y0) * Wo + x0) * p.ldy) * (unsigned)sizeof(T);  // scalar
+    hr_out_1x1<T, kHdTH>(acc1, bias1, lane_out, yrs, out_base, y0, x0, Ho, Wo, lr, lq);
   };
   auto finish = [&](int tile) {
-    // (the tile's last MFMAs have retired before the epilogue's vector code reads their accumulators, whatever the scheduler does around here)
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
+    hr_settle_mfma();
     epilogue(tile);
   };
 
@@ -332,7 +220,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hdown_kernel(const HdownArgs p
   setup_tile(l_tile);
 #pragma unroll
   for (int i = 0; i < LA; ++i) issue_dma(i, i);
-  __builtin_amdgcn_s_waitcnt(kVmcnt0);
+  __builtin_amdgcn_s_waitcnt(kHrVmcnt0);
   __syncthreads();
   int c_tile = sb;
   int stage = 0;
@@ -348,7 +236,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hdown_kernel(const HdownArgs p
 #pragma unroll
             for (int o = 0; o < kHdTH; ++o) acc[f][o] = bias3[f];
         }
-        compute3(sa, kind);
+        hr_rows_s2<T, NF3, NCH>(acc, wreg, sa, lane_base, kind);
         if (kind == NCH - 1) {
           tail_mid();
           if constexpr (NOG == 0) {  // `mid` published inside the item: every wave reads all of its channels
@@ -371,7 +259,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hdown_kernel(const HdownArgs p
           c_tile += G;
         }
       }
-      __builtin_amdgcn_s_waitcnt(kVmcnt0);
+      __builtin_amdgcn_s_waitcnt(kHrVmcnt0);
       __syncthreads();  // the ring's next image complete and visible; `mid` written; the output stores retired
       stage = stage + 1 == NST ? 0 : stage + 1;
     }
@@ -380,9 +268,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hdown_kernel(const HdownArgs p
 
 template <typename T>
 static int launch_hdown(const HdownArgs& a, bool form_b, hipStream_t st) {
-  int grid = 256 * 2;  // two 256-thread workgroups per CU (64 / 80 KB of LDS each)
-  if (a.nSpatial < grid) grid = a.nSpatial;
-  grid = (grid + 7) / 8 * 8;
+  const int grid = hr_grid(2, a.nSpatial, 1);  // two 256-thread workgroups per CU (64 / 80 KB of LDS each)
   const dim3 g((unsigned)grid), b(256);
   if (form_b) hipLaunchKernelGGL((conv3x3_hdown_kernel<T, 64, 2>), g, b, 0, st, a);
   else hipLaunchKernelGGL((conv3x3_hdown_kernel<T, 128, 0>), g, b, 0, st, a);

@@ -14,8 +14,7 @@
 // rate and cannot get faster on its own.  Here the 3x3 output tile never leaves the CU: it is rounded to the storage type
 // exactly where the layer-by-layer path rounds it, laid down in LDS in the halo image's format, and consumed by the 1x1 MFMAs.
 //
-// The 3x3 part is conv3x3_hreg.hip's (weights of the wave's 16-cout fragment in 72 registers, swizzled 64-byte-pitch halo
-// image filled by LDS-DMA, 8 x 16 pixel tiles, three 256-thread workgroups per CU).  After the tile's two chunks:
+// The 3x3 part is the family's stride-1 form (hreg_core.h: HrS1, two stages, three 256-thread workgroups per CU).  After the tile's two chunks:
 //   1. every wave SiLUs its 16 couts x 128 pixels and writes them (8 bytes per lane) into the `mid` image
 //      [chunk 2][row 8][pixel 16] x 64 B with the halo's part swizzle; barrier;
 //   2. 1x1: the wave's A fragment(s) sit in 8 registers; B fragments are conflict-free ds_read_b128 of `mid`.
@@ -26,6 +25,7 @@
 //      one atomicAdd per wave to append the candidates (key = ~score bits << 32 | anchor, as detect_head.hip / nms.hip).
 #include "common_hip.h"
 #include "nms_ws.h"
+#include "hreg_core.h"
 
 namespace DY_NS {
 
@@ -49,8 +49,8 @@ struct HheadArgs {
   const uint8_t* cmask;
 };
 
-constexpr int kHhTH = 8, kHhTW = 16, kHhHH = 10, kHhHW = 24;
-constexpr int kHhStage = 16 * 1024, kHhStages = 2;
+constexpr int kHhTH = HrS1::TH, kHhTW = HrS1::TW;
+constexpr int kHhStage = HrS1::kStage, kHhStages = 2;
 constexpr int kHhMid = 2 * kHhTH * kHhTW * 64;  // 16 KB: the tile's 3x3 output, [chunk][row][pixel] x 64 B
 
 // Exchange between the four 16-lane quarters of a wave without touching LDS (v_permlane16_swap / v_permlane32_swap, gfx950):
@@ -91,27 +91,20 @@ __global__ __launch_bounds__(256, 3) void conv3x3_hhead_kernel(const HheadArgs p
   const int lq = lane >> 4, lr = lane & 15;
 
   const int G = (int)gridDim.x;
-  const int sb = ((int)blockIdx.x & 7) * (G >> 3) + ((int)blockIdx.x >> 3);  // XCD-contiguous tile order (guide T1)
-  const int myTiles = sb < p.nSpatial ? (p.nSpatial - sb + G - 1) / G : 0;
+  const int sb = hr_block(G, 1).sb;
+  const int myTiles = hr_my_tiles(p.nSpatial, sb, G);
   if (myTiles <= 0) return;
   const int nItems = myTiles * NCH;
 
   // ---- register-resident weights: the wave's 16-cout fragment of the 3x3 ----
   u32x4 wreg[NCH][9];
-  {
-    const u32x4* wg = reinterpret_cast<const u32x4*>(p.w3);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-#pragma unroll
-      for (int t = 0; t < 9; ++t) wreg[c][t] = wg[((c * 9 + t) * 4 + wave) * 64 + lane];
-  }
+  hr_load_wreg<NCH>(wreg, reinterpret_cast<const u32x4*>(p.w3), wave, lane);
   const f32x4 bias3 = *reinterpret_cast<const f32x4*>(p.b3 + wave * 16 + lq * 4);
   // The 1x1 fragments (2 x 16 B per lane) and its bias are re-read per tile (L2 / L1 hits): 12 registers the 3x3 loop needs more.
   // r06: they are requested at the END of the tile's last item (load_w1, in front of tail_mid), so that the item's closing drain covers
   // them.  Requested inside tail_out they were younger than the next item's halo DMA, and vmcnt retires in order: their first use made
   // every wave wait for the DMA it had just issued, once per tile.
-  constexpr unsigned kOob = 0xfffffff0u;
-  constexpr int kVmcnt0 = 0x0f70;  // s_waitcnt vmcnt(0) alone (gfx9 encoding: expcnt 7 and lgkmcnt 15 = no wait)
+  constexpr unsigned kOob = kHrOob;
   const __amdgpu_buffer_rsrc_t w1rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w1), 0, NCH * (KIND == 1 ? 4 : 1) * 1024, 0x00020000);
   const __amdgpu_buffer_rsrc_t b1rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.b1), 0, (KIND == 1 ? 64 : 16) * 4, 0x00020000);
   u32x4 w1reg[NCH];
@@ -122,54 +115,36 @@ __global__ __launch_bounds__(256, 3) void conv3x3_hhead_kernel(const HheadArgs p
     bias1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(b1rs, lq * 16, (KIND == 1 ? wave : 0) * 64, 0));
   };
 
-  // ---- halo loader (conv3x3_hreg.hip): buffer-addressed LDS-DMA, lane-constant offsets + a scalar tile offset, zeros by range check ----
-  constexpr int NDMA = 4;
+  // ---- halo loader ----
+  constexpr int NDMA = HrS1::NDMA;
   const unsigned pre = (unsigned)((p.W + 1) * p.ldx) * 2u;
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.x)) - pre, 0, p.x_bytes + pre, 0x00020000);
   unsigned rel[NDMA];
-#pragma unroll
-  for (int k = 0; k < NDMA; ++k) {
-    const int s = (k * 4 + wave) * 64 + lane;
-    const int pix = s >> 2, part = s & 3;
-    const int hy = pix / kHhHW, hx = pix - hy * kHhHW;
-    const bool dead = hx >= kHhTW + 2 || hy >= kHhHH;
-    rel[k] = dead ? kOob : (unsigned)((hy * p.W + hx) * p.ldx + (part ^ ((hx >> 1) & 3)) * EPC) * 2u;
-  }
+  hr_halo_rel<HrS1>(rel, wave, lane, p.W, p.ldx, 2u, 2u * EPC);
   unsigned voff[NDMA];
   unsigned l_base = 0;
   int l_tile = sb, l_chunk = 0, l_item = 0;
   auto setup_tile = [&](int tile) {
-    const int tx = tile % p.tilesX;
-    const int r = tile / p.tilesX;
-    const int ty = r % p.tilesY, n = r / p.tilesY;
-    const int y0 = ty * kHhTH, x0 = tx * kHhTW;
-    l_base = (unsigned)(((n * p.H + y0) * p.W + x0) * p.ldx) * 2u;
-    const bool interior = y0 > 0 && y0 + kHhTH + 1 <= p.H && x0 > 0 && x0 + kHhTW + 1 <= p.W;  // wave-uniform
-    if (interior) {
+    const HrTile t = hr_tile(tile, p.tilesX, p.tilesY);
+    const int y0 = t.ty * kHhTH, x0 = t.tx * kHhTW;
+    l_base = (unsigned)(((t.n * p.H + y0) * p.W + x0) * p.ldx) * 2u;
+    if (hr_interior<HrS1>(y0, x0, p.H, p.W)) {
 #pragma unroll
       for (int k = 0; k < NDMA; ++k) voff[k] = rel[k];
     } else {
       // the slots' halo pixels again, on border tiles only: as a table (or hoisted out of the tile loop, which the empty asm forbids) they cost
       // four registers, and the class branch is then back in scratch (8-12 bytes)
-      int l4 = lane >> 2;
-      asm volatile("" : "+v"(l4));
+      int ln = lane;
+      asm volatile("" : "+v"(ln));
 #pragma unroll
-      for (int k = 0; k < NDMA; ++k) {
-        const int pix = (k * 4 + wave) * 16 + l4;
-        const int hy = pix / kHhHW, hx = pix - hy * kHhHW;
-        const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
-        voff[k] = ((unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W) ? rel[k] : kOob;
-      }
+      for (int k = 0; k < NDMA; ++k) voff[k] = hr_halo_inside<HrS1>(k, wave, ln, y0, x0, p.H, p.W) ? rel[k] : kOob;
     }
   };
   auto issue_dma = [&](int stage) {
     unsigned char* sa = smem + stage * kHhStage;
     const bool live = l_item < nItems;
     if (live) {
-      const unsigned soff = l_base + (unsigned)l_chunk * (4u * EPC * (unsigned)sizeof(T));
-#pragma unroll
-      for (int k = 0; k < NDMA; ++k)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void*)(sa + (k * 4 + wave) * 1024), 16, (int)voff[k], (int)soff, 0, 0);
+      hr_issue<NDMA>(xrs, sa, wave, voff, l_base + (unsigned)l_chunk * (4u * EPC * (unsigned)sizeof(T)));
       ++l_item;
       if (++l_chunk == NCH) {
         l_chunk = 0;
@@ -178,50 +153,21 @@ __global__ __launch_bounds__(256, 3) void conv3x3_hhead_kernel(const HheadArgs p
       }
     } else {
 #pragma unroll
-      for (int k = 0; k < NDMA; ++k)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void*)(sa + (k * 4 + wave) * 1024), 16, (int)kOob, 0, 0, 0);
+      for (int k = 0; k < NDMA; ++k) hr_issue1(xrs, sa, k, wave, kOob, 0u);
     }
   };
 
   int lane_base[3];
-#pragma unroll
-  for (int q = 0; q < 3; ++q) lane_base[q] = (lr + q) * 64 + ((lq ^ (((lr + q) >> 1) & 3)) * 16);
+  HrS1::lane_base(lane_base, lr, lq);
 
   f32x4 acc[kHhTH];
 
-  auto compute = [&](int stg, int c) {
-    const unsigned char* sa = smem + stg * kHhStage;
-#pragma unroll
-    for (int iy = 0; iy < kHhHH; ++iy) {
-      u32x4 a[3];
-#pragma unroll
-      for (int q = 0; q < 3; ++q) a[q] = *reinterpret_cast<const u32x4*>(sa + lane_base[q] + iy * (kHhHW * 64));
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        const int o = iy - r;
-        if (o >= 0 && o < kHhTH) {
-#pragma unroll
-          for (int q = 0; q < 3; ++q) acc[o] = Elem<T>::mma(wreg[c][r * 3 + q], a[q], acc[o]);
-        }
-      }
-    }
-  };
-
   // ---- the tail of one tile ----
-  typedef __attribute__((ext_vector_type(4))) T t4;
-  const int mid_w = (wave >> 1) * (kHhTH * kHhTW * 64) + lr * 64 + ((((wave & 1) * 2 + (lq >> 1)) ^ ((lr >> 1) & 3)) * 16) + (lq & 1) * 8;  // + o * 1024
+  const int mid_w = hr_mid_offset(wave, lr, lq, kHhTH * kHhTW * 64);  // + o * 1024
   const int mid_r = lane_base[0];                                                                                                          // + c2 * 8192 + o * 1024
   // tail, part 1 (end of the tile's last item): SiLU, round to the storage type (where the layer-by-layer path rounds), into `mid`.
   // The item's closing barrier publishes it.
-  auto tail_mid = [&]() {
-#pragma unroll
-    for (int o = 0; o < kHhTH; ++o) {
-      t4 ov;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) ov[e] = Elem<T>::from_f32(silu_f32(acc[o][e]));
-      *reinterpret_cast<u32x2*>(mid + mid_w + o * (kHhTW * 64)) = __builtin_bit_cast(u32x2, ov);
-    }
-  };
+  auto tail_mid = [&]() { hr_tail_mid<T, kHhTH, false>(acc, mid + mid_w, nullptr); };
   // tail, part 2, DEFERRED to the start of the next item (after that item's DMA has been issued, before its MFMAs): the global
   // stores then have a whole item of matrix work behind them before the item's closing s_waitcnt vmcnt(0), instead of being waited
   // for right after they were issued (first version: the fused kernels cost as much as conv + separate tail kernel)
@@ -236,9 +182,8 @@ __global__ __launch_bounds__(256, 3) void conv3x3_hhead_kernel(const HheadArgs p
   // What waits a tile: the two ballot masks and the tile id (scalars), best score / class per row (4 registers), the counter's return (1).
   struct TileAt { int n, y0, x0; };
   auto tile_at = [&](int tile) {
-    const int tx = tile % p.tilesX;
-    const int r_ = tile / p.tilesX;
-    return TileAt{r_ / p.tilesY, (r_ % p.tilesY) * kHhTH, tx * kHhTW};
+    const HrTile t = hr_tile(tile, p.tilesX, p.tilesY);
+    return TileAt{t.n, t.ty * kHhTH, t.tx * kHhTW};
   };
   const unsigned img_bytes = (unsigned)((4 + p.nc) * p.A) * 4u;
   auto out_rsrc = [&](int n) { return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(p.out) + (size_t)n * img_bytes, 0, (int)img_bytes, 0x00020000); };
@@ -365,14 +310,14 @@ __global__ __launch_bounds__(256, 3) void conv3x3_hhead_kernel(const HheadArgs p
 #pragma unroll
         for (int o = 0; o < kHhTH; ++o) acc[o] = bias3;  // (only now: the accumulator registers are free during tail_out)
       }
-      compute(c & 1, c);
+      hr_rows_s1<T, NCH>(acc, wreg, smem + (c & 1) * kHhStage, lane_base, c);
       if (c == NCH - 1) {
         load_w1();  // (the accumulators' last MFMAs and the SiLU pass cover the round trip; nothing of the 3x3 loop is live beside them but acc)
         tail_mid();
         pending = c_tile;
         c_tile += G;
       }
-      __builtin_amdgcn_s_waitcnt(kVmcnt0);  // (the builtin, not an asm: the compiler then knows that load_w1's registers and the counter's return are valid)
+      __builtin_amdgcn_s_waitcnt(kHrVmcnt0);  // (the builtin, not an asm: the compiler then knows that load_w1's registers and the counter's return are valid)
       __syncthreads();  // next item's halo complete and visible; `mid` written (last chunk) / `dsm` free again; the 1x1 operands landed
     }
   }
@@ -382,9 +327,7 @@ __global__ __launch_bounds__(256, 3) void conv3x3_hhead_kernel(const HheadArgs p
 
 template <typename T>
 static int launch_hhead(const HheadArgs& a, int kind, hipStream_t st) {
-  int grid = 256 * 3;
-  if (a.nSpatial < grid) grid = a.nSpatial;
-  grid = (grid + 7) / 8 * 8;
+  const int grid = hr_grid(3, a.nSpatial, 1);
   if (kind == 1)
     hipLaunchKernelGGL((conv3x3_hhead_kernel<T, 1>), dim3((unsigned)grid), dim3(256), 0, st, a);
   else

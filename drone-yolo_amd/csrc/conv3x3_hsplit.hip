@@ -1,5 +1,5 @@
 // 3x3 stride-1 pad-1 convolution on SPLIT float16 storage (DY_F16X2, include/dyolo.h) for the narrow layers (cin 32 / 64): the
-// register-weight decomposition of conv3x3_hreg.hip, for the precision YOLO.predict runs by default (r05).
+// register-weight decomposition of the family (hreg_core.h), for the precision YOLO.predict runs by default (r05).
 //
 // Why.  The type's dense convolutions ran on the flat-K implicit GEMM (conv_gemm_fk.hip), which gathers a fresh 128-byte row per pixel
 // and TAP: every input pixel crosses the L2 -> LDS path nine times, and at 4 bytes per element that path is what bounds the layers —
@@ -21,6 +21,7 @@
 // Reference semantics: Conv (nn/modules/conv.py:37-55, BatchNorm folded), Bottleneck shortcut (block.py:337-350).
 #include "common_hip.h"
 #include "conv_args.h"
+#include "hreg_core.h"
 
 namespace dy {
 
@@ -36,8 +37,8 @@ struct HsArgs {
   unsigned x_bytes, y_bytes, r_bytes;
 };
 
-constexpr int kHsTH = 8, kHsTW = 16, kHsHH = 10, kHsHW = 24;
-constexpr int kHsImage = 16 * 1024;       // one (tile, chunk) halo image of one half: 10 x 24 x 64 = 15,360 B, padded to 16 wave-instructions
+constexpr int kHsTH = HrS1::TH, kHsTW = HrS1::TW, kHsHW = HrS1::kPitch;
+constexpr int kHsImage = HrS1::kStage;    // one (tile, chunk) halo image of one half
 constexpr int kHsStage = 2 * kHsImage;    // hi image, lo image
 constexpr unsigned kHsOob = 0xffff0000u;  // >= num_records of every descriptor here (+ 16 for the lo half stays inside 32 bits)
 
@@ -53,12 +54,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hsplit_kernel(const HsArgs p) 
   const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(RES ? p.res : p.y), 0, RES ? p.r_bytes : 0u, 0x00020000);
 
-  // block -> (cout group, spatial sequence), XCD-contiguous (conv3x3_hreg.hip)
-  const int G = (int)gridDim.x;
-  const int logical = ((int)blockIdx.x & 7) * (G >> 3) + ((int)blockIdx.x >> 3);
-  const int nt = logical % p.tilesN;
-  const int sb = logical / p.tilesN, Gs = G / p.tilesN;
-  const int myTiles = sb < p.nSpatial ? (p.nSpatial - sb + Gs - 1) / Gs : 0;
+  // block -> (cout group, spatial sequence)
+  const HrBlock blk = hr_block((int)gridDim.x, p.tilesN);
+  const int nt = blk.nt, sb = blk.sb, Gs = blk.Gs;
+  const int myTiles = hr_my_tiles(p.nSpatial, sb, Gs);
   if (myTiles <= 0) return;
   const int nItems = myTiles * NCH;
   const int co_w = nt * (NF * 16) + frag * 16;  // first cout of this wave
@@ -82,39 +81,24 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hsplit_kernel(const HsArgs p) 
 
   // ---- loader: slot s = (k * 4 + wave) * 64 + lane of the 10 x 24 x 4 image; pixel = s >> 2, LDS part = s & 3.  The same lane pattern fills
   // the hi image (source chunk 2 part') and the lo image (source chunk 2 part' + 1: 16 bytes further) ----
-  constexpr int NDMA = 4;
+  constexpr int NDMA = HrS1::NDMA;
   const unsigned pre = (unsigned)((p.W + 1) * p.ldx) * 4u;
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.x)) - pre, 0, p.x_bytes + pre, 0x00020000);
   unsigned rel[NDMA];
-#pragma unroll
-  for (int k = 0; k < NDMA; ++k) {
-    const int s = (k * 4 + wave) * 64 + lane;
-    const int pix = s >> 2, part = s & 3;
-    const int hy = pix / kHsHW, hx = pix - hy * kHsHW;
-    const bool dead = hx >= kHsTW + 2 || hy >= kHsHH;
-    rel[k] = dead ? kHsOob : (unsigned)((hy * p.W + hx) * p.ldx) * 4u + (unsigned)((part ^ ((hx >> 1) & 3)) * 32);
-  }
+  hr_halo_rel<HrS1>(rel, wave, lane, p.W, p.ldx, 4u, 32u, kHsOob);
   unsigned voff[NDMA];
   unsigned l_base = 0;
   int l_tile = sb, l_chunk = 0, l_item = 0;
   auto setup_tile = [&](int tile) {
-    const int tx = tile % p.tilesX;
-    const int r = tile / p.tilesX;
-    const int ty = r % p.tilesY, n = r / p.tilesY;
-    const int y0 = ty * kHsTH, x0 = tx * kHsTW;
-    l_base = (unsigned)(((n * p.H + y0) * p.W + x0) * p.ldx) * 4u;
-    const bool interior = y0 > 0 && y0 + kHsTH + 1 <= p.H && x0 > 0 && x0 + kHsTW + 1 <= p.W;
-    if (interior) {
+    const HrTile t = hr_tile(tile, p.tilesX, p.tilesY);
+    const int y0 = t.ty * kHsTH, x0 = t.tx * kHsTW;
+    l_base = (unsigned)(((t.n * p.H + y0) * p.W + x0) * p.ldx) * 4u;
+    if (hr_interior<HrS1>(y0, x0, p.H, p.W)) {
 #pragma unroll
       for (int k = 0; k < NDMA; ++k) voff[k] = rel[k];
-    } else {
+    } else {  // the mask again, on border tiles only
 #pragma unroll
-      for (int k = 0; k < NDMA; ++k) {
-        const int pix = ((k * 4 + wave) * 64 + lane) >> 2;
-        const int hy = pix / kHsHW, hx = pix - hy * kHsHW;
-        const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
-        voff[k] = ((unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W) ? rel[k] : kHsOob;
-      }
+      for (int k = 0; k < NDMA; ++k) voff[k] = hr_halo_inside<HrS1>(k, wave, lane, y0, x0, p.H, p.W) ? rel[k] : kHsOob;
     }
   };
   auto issue_dma = [&](int stage) {  // DMA of item (l_tile, l_chunk) into `stage`, then advance the loader; past the last item: nothing
@@ -123,9 +107,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hsplit_kernel(const HsArgs p) 
     const unsigned soff = l_base + (unsigned)l_chunk * 128u;
 #pragma unroll
     for (int k = 0; k < NDMA; ++k) {
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void*)(sa + (k * 4 + wave) * 1024), 16, (int)voff[k], (int)soff, 0, 0);
+      hr_issue1(xrs, sa, k, wave, voff[k], soff);
       // (+ 16 in the lane offset, not in the instruction's immediate: the immediate of an LDS-DMA load moves the LDS address as well)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void*)(sa + kHsImage + (k * 4 + wave) * 1024), 16, (int)(voff[k] + 16u), (int)soff, 0, 0);
+      hr_issue1(xrs, sa + kHsImage, k, wave, voff[k] + 16u, soff);
     }
     ++l_item;
     if (++l_chunk == NCH) {
@@ -137,8 +121,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hsplit_kernel(const HsArgs p) 
 
   // ---- fragment reads: pixel (row iy, column lr + q), part lq -> byte lane_base[q] + iy * 24 * 64, in the hi image and (+ kHsImage) the lo image ----
   int lane_base[3];
-#pragma unroll
-  for (int q = 0; q < 3; ++q) lane_base[q] = (lr + q) * 64 + ((lq ^ (((lr + q) >> 1) & 3)) * 16);
+  HrS1::lane_base(lane_base, lr, lq);
 
   f32x4 acc[ROWS], accl[ROWS];
 #pragma unroll
@@ -203,10 +186,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hsplit_kernel(const HsArgs p) 
   constexpr bool EARLY = RES && NCH == 1;
   u32x2 rh[RES ? ROWS : 1], rl[RES ? ROWS : 1];
   auto load_residual = [&](int tile) {
-    const int tx = tile % p.tilesX;
-    const int r = tile / p.tilesX;
-    const int ty = r % p.tilesY, n = r / p.tilesY;
-    const int xx = tx * kHsTW + lr;
+    const HrTile t = hr_tile(tile, p.tilesX, p.tilesY);
+    const int ty = t.ty, n = t.n;
+    const int xx = t.tx * kHsTW + lr;
 #pragma unroll
     for (int o = 0; o < ROWS; ++o) {
       const int yy = ty * kHsTH + row0 + o;
@@ -217,16 +199,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hsplit_kernel(const HsArgs p) 
     }
   };
   auto epilogue = [&](int tile) {
-    const int tx = tile % p.tilesX;
-    const int r = tile / p.tilesX;
-    const int ty = r % p.tilesY, n = r / p.tilesY;
-    const int y0 = ty * kHsTH, x0 = tx * kHsTW;
-    const unsigned out_base = (unsigned)(((n * p.H + y0) * p.W + x0) * p.ldy) * 4u;
+    const HrTile t = hr_tile(tile, p.tilesX, p.tilesY);
+    const int y0 = t.ty * kHsTH, x0 = t.tx * kHsTW;
+    const unsigned out_base = (unsigned)(((t.n * p.H + y0) * p.W + x0) * p.ldy) * 4u;
     const bool whole = y0 + kHsTH <= p.H && x0 + kHsTW <= p.W;
     const f32x4 bias4 = *reinterpret_cast<const f32x4*>(p.bias + co_w + lq * 4);
     const f32x4 scl4 = *reinterpret_cast<const f32x4*>(p.wscale + co_w + lq * 4);
     if constexpr (RES && !EARLY) load_residual(tile);
-    u32x2 ph[ROWS], pl[ROWS];
+    u32x2 pkh[ROWS], pkl[ROWS];
 #pragma unroll
     for (int o = 0; o < ROWS; ++o) {
       float v[4];
@@ -249,22 +229,19 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hsplit_kernel(const HsArgs p) 
         hh[e] = t;
         ll[e] = (f16_t)((x - (float)t) * kSplitScale);
       }
-      ph[o] = __builtin_bit_cast(u32x2, hh);
-      pl[o] = __builtin_bit_cast(u32x2, ll);
+      pkh[o] = __builtin_bit_cast(u32x2, hh);
+      pkl[o] = __builtin_bit_cast(u32x2, ll);
       acc[o] = f32x4{0.f, 0.f, 0.f, 0.f};
       accl[o] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
 #pragma unroll
     for (int o = 0; o < ROWS; o += 2) {
-      // v_permlane16_swap between the rows of a pair: quarter lq gets channels 8 (lq >> 1) .. + 7 of row o + (lq & 1), hi and lo alike
-      const auto hx = __builtin_amdgcn_permlane16_swap(ph[o][0], ph[o + 1][0], false, false);
-      const auto hy = __builtin_amdgcn_permlane16_swap(ph[o][1], ph[o + 1][1], false, false);
-      const auto lx = __builtin_amdgcn_permlane16_swap(pl[o][0], pl[o + 1][0], false, false);
-      const auto ly = __builtin_amdgcn_permlane16_swap(pl[o][1], pl[o + 1][1], false, false);
+      // hr_pack_pair: quarter lq gets channels 8 (lq >> 1) .. + 7 of row o + (lq & 1), hi and lo alike
+      const u32x4 sh = hr_pack_pair(pkh[o], pkh[o + 1]), sl = hr_pack_pair(pkl[o], pkl[o + 1]);
       unsigned off = (unsigned)(((row0 + o + (lq & 1)) * p.W + lr) * p.ldy) * 4u + (unsigned)((co_w >> 3) + (lq >> 1)) * 32u;
       if (!whole) off = (y0 + row0 + o + (lq & 1) < p.H && x0 + lr < p.W) ? off : kHsOob;
-      __builtin_amdgcn_raw_buffer_store_b128(u32x4{hx[0], hy[0], hx[1], hy[1]}, yrs, off, (int)out_base, 0);
-      __builtin_amdgcn_raw_buffer_store_b128(u32x4{lx[0], ly[0], lx[1], ly[1]}, yrs, off + 16u, (int)out_base, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(sh, yrs, off, (int)out_base, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(sl, yrs, off + 16u, (int)out_base, 0);
     }
   };
 
@@ -294,11 +271,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_hsplit_kernel(const HsArgs p) 
 template <int NCH, int NF>
 static int launch_hsplit(const HsArgs& a, hipStream_t st) {
   HsArgs p = a;
-  int grid = 256 * 2;  // two 256-thread workgroups per CU (64 KB of LDS each)
-  const long long nwork = (long long)p.nSpatial * p.tilesN;
-  if (nwork < grid) grid = (int)nwork;
-  const int q = 8 * p.tilesN;
-  grid = (grid + q - 1) / q * q;  // the XCD remap and the fixed cout group per block need G % (8 * tilesN) == 0
+  const int grid = hr_grid(2, (long long)p.nSpatial * p.tilesN, p.tilesN);  // two 256-thread workgroups per CU (64 KB of LDS each)
   if (p.res != nullptr) hipLaunchKernelGGL((conv3x3_hsplit_kernel<NCH, NF, true>), dim3((unsigned)grid), dim3(256), 0, st, p);
   else hipLaunchKernelGGL((conv3x3_hsplit_kernel<NCH, NF, false>), dim3((unsigned)grid), dim3(256), 0, st, p);
   return check_launch("conv3x3_hsplit_kernel");
