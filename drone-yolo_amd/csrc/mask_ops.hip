@@ -214,6 +214,8 @@ __global__ __launch_bounds__(kPmThreads) void process_mask_kernel(PmArgs a) {
       D.cx_hi = (int)ceilf(fminf(fmaxf(x2, 0.f), (float)sw)) - 1;
       D.cy_lo = (int)ceilf(fminf(fmaxf(y1, 0.f), (float)sh));
       D.cy_hi = (int)ceilf(fminf(fmaxf(y2, 0.f), (float)sh)) - 1;
+      // crop_mask compares: a NaN corner is inside no inequality, the mask is empty (fmaxf would turn a NaN x1 / y1 into column / row 0)
+      if (!(x1 == x1 && x2 == x2 && y1 == y1 && y2 == y2)) D.cx_hi = D.cx_lo - 1;
       if (D.cx_lo <= D.cx_hi && D.cy_lo <= D.cy_hi) {
         // output pixels whose corners can touch the crop: source coordinate in (c_lo - 1, c_hi + 1), one output pixel of slack each side
         const float ix = (float)a.ow / (float)sw, iy = (float)a.oh / (float)sh;

@@ -1180,13 +1180,14 @@ def mask_gather(bufs: NmsBuffers, levels: Optional[Sequence[torch.Tensor]] = Non
 
 def process_mask(protos: torch.Tensor, side: torch.Tensor, count: torch.Tensor, counts_host: Sequence[int], out_hw: Tuple[int, int],
                  ratio: Tuple[float, float] = (1.0, 1.0), windows: Optional[Sequence[Sequence[int]]] = None,
-                 crop_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """The masks of a batch in one ``dy_process_mask`` launch: uint8 (sum(counts), oh, ow), freshly allocated.
+                 crop_rows: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The masks of a batch in one ``dy_process_mask`` launch: uint8 (sum(counts), oh, ow), freshly allocated unless ``out`` is given: a
+    contiguous uint8 device tensor of sum(counts) * oh * ow elements at an 8-byte aligned address (any shape; it may be a slice of a larger
+    buffer), returned viewed as (sum(counts), oh, ow).
     ``protos``: fp32 NHWC view (N, 32, mh, mw); ``side``: ``mask_gather``'s output; ``count``: the device counts and ``counts_host`` their
     values on the host (the predictor reads them back anyway); ``ratio`` = (mw / iw, mh / ih): proto pixels per input-image pixel, for the
     crop at proto resolution (ops.process_mask).  ``crop_rows`` (the rows after ``scale_boxes_``) switches to the retina form
     (ops.process_mask_native): resize ``windows[b]`` = (top, left, sh, sw) of the grid to (oh, ow), crop there."""
-    require_device(protos, "protos")
     n, nm, mh, mw = protos.shape
     if protos.dtype != torch.float32 or side.dtype != torch.float32 or not side.is_contiguous() or side.shape[0] != n or side.shape[2] != 4 + nm:
         raise ValueError("process_mask: protos must be fp32 (N, nm, mh, mw), side a contiguous fp32 (N, max_det, 4 + nm) tensor")
@@ -1196,7 +1197,18 @@ def process_mask(protos: torch.Tensor, side: torch.Tensor, count: torch.Tensor, 
         raise ValueError("process_mask: counts_host must hold one count in [0, max_det] per image")
     total = sum(counts_host)
     oh, ow = int(out_hw[0]), int(out_hw[1])
-    out = torch.empty((total, oh, ow), dtype=torch.uint8, device=protos.device)
+    if out is not None:  # checked before anything touches the device; the kernel stores 64-bit words into out, so each clause guards memory
+        bad = ("its dtype is not uint8" if out.dtype != torch.uint8 else
+               f"it holds {out.numel()} elements, not {total} * {oh} * {ow}" if out.numel() != total * oh * ow else
+               "it is not contiguous" if not out.is_contiguous() else
+               "its address is not 8-byte aligned" if out.data_ptr() % 8 else
+               f"it is on '{out.device}', not on the prototypes' device '{protos.device}'" if not out.is_cuda or out.device != protos.device else None)
+        if bad:
+            raise ValueError(f"process_mask: out must be a contiguous, 8-byte aligned uint8 tensor of sum(counts) * oh * ow elements on the prototypes' device: {bad}")
+        out = out.view(total, oh, ow)
+    require_device(protos, "protos")
+    if out is None:
+        out = torch.empty((total, oh, ow), dtype=torch.uint8, device=protos.device)
     d = _lib.ProcessMaskDesc()
     d.protos, d.ld_p = view_params(protos)
     d.batch, d.max_det, d.nm, d.mh, d.mw, d.oh, d.ow, d.total = n, md, nm, mh, mw, oh, ow, total

@@ -890,6 +890,7 @@ int32_t dy_mask_gather(const dy_mask_gather_desc* d, dy_stream_t stream);
  * crop_at_output == 0: a corner counts as 0 unless bx1 <= xx < bx2 and by1 <= yy < by2 with (bx, by) = the side buffer's box times
  *   ratio_x / ratio_y (= mw / iw, mh / ih as fp32).  crop_at_output == 1: no corner crop; the mask is also 0 unless x1 <= x < x2 and
  *   y1 <= y < y2 for crop_rows[b, r, 0:4] (fp32 (batch, max_det, 6): the rows after dy_scale_boxes).
+ *   In both forms a NaN box corner satisfies no inequality (crop_mask's comparisons): the mask is empty.
  * total == 0 returns DY_OK without a launch.  nm != 32: DY_ERR_UNSUPPORTED. */
 typedef struct dy_process_mask_desc {
   const float* protos;

@@ -118,6 +118,21 @@ def test_new_entry_points_validate_without_gpu():
     assert h.dy_depth_to_space2_nhwc(p, p, 1, 4, 4, 12, 48, 12, L.DY_F32, None) == -2  # c % 8 != 0
     assert h.dy_depth_to_space2_nhwc(p, p, 1, 4, 4, 8, 32, 8, L.DY_FP8, None) == -1
     assert h.dy_depth_to_space2_nhwc(p, p, 1, 4, 4, 8, 24, 8, L.DY_F16, None) == -1  # source pitch below 4c
+    # process_mask(out=): every clause of the refusal, each tensor with exactly one defect (CPU tensors: the device clause comes last, so
+    # the others are reached here; a correct tensor that is merely on the CPU is refused by that last clause)
+    protos, side, count = torch.zeros(1, 32, 4, 4), torch.zeros(1, 8, 36), torch.zeros(1, dtype=torch.int32)
+    n_out = 2 * 6 * 5
+    base = torch.zeros(n_out + 16, dtype=torch.uint8)
+    lead = (-base.data_ptr()) % 8  # base[lead:] is 8-byte aligned
+    aligned, off4 = base[lead : lead + n_out], base[lead + 4 : lead + 4 + n_out]
+    assert aligned.data_ptr() % 8 == 0 and off4.data_ptr() % 8 == 4 and aligned.is_contiguous() and off4.is_contiguous()
+    strided = torch.zeros(2 * n_out + 16, dtype=torch.uint8)
+    strided = strided[(-strided.data_ptr()) % 8 :][: 2 * n_out : 2]
+    assert strided.numel() == n_out and strided.data_ptr() % 8 == 0 and not strided.is_contiguous()
+    for bad, word in ((aligned.view(torch.int8), "dtype"), (aligned[:-1], "elements"), (base[lead : lead + n_out + 8], "elements"),
+                      (strided, "contiguous"), (off4, "aligned"), (aligned, "device")):
+        with pytest.raises(ValueError, match=f"out must be .*: .*{word}"):
+            H.process_mask(protos, side, count, [2], (6, 5), out=bad)
 
 
 def test_new_struct_layouts_match_the_header(tmp_path):
