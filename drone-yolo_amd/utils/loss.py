@@ -45,12 +45,26 @@ class v8DetectionLoss:
         out[..., 1:3], out[..., 3:5] = xy - half, xy + half
         return torch.from_numpy(out)
 
+    @staticmethod
+    def check_classes(gt: torch.Tensor, nc: int) -> None:
+        """Refuse a HOST box table with a class outside [0, nc) before any launch: the kernels index the class logits of a row with it
+        unchecked.  A device table is the caller's (a graph-replayed trainer fills it from a table that went through here)."""
+        if gt.is_cuda or gt.numel() == 0:
+            return
+        c = gt.detach()[..., 0].float().numpy()
+        ok = (c >= 0) & (c < nc) & (c == np.floor(c))  # NaN fails every comparison
+        if not ok.all():
+            bad = c[~ok]
+            raise ValueError(f"detection loss: {bad.size} label(s) with a class outside [0, {nc}), e.g. {bad.flat[0]!r}")
+
     def targets_to_gt(self, batch, batch_size: int, img_hw) -> torch.Tensor:
         """The batch's labels as the (B, n_max, 5) pixel-box table on the host (``preprocess``); img_hw = (h, w) of the images."""
         imgsz = torch.tensor([float(img_hw[1]), float(img_hw[0]), float(img_hw[1]), float(img_hw[0])], dtype=torch.float32)
         targets = torch.cat((batch["batch_idx"].view(-1, 1).float().cpu(), batch["cls"].view(-1, 1).float().cpu(),
                              batch["bboxes"].float().cpu()), 1)
-        return self.preprocess(targets, batch_size, imgsz)
+        gt = self.preprocess(targets, batch_size, imgsz)
+        self.check_classes(gt, self.nc)
+        return gt
 
     def __call__(self, preds, batch):
         feats = preds[1] if isinstance(preds, tuple) else preds
@@ -61,6 +75,7 @@ class v8DetectionLoss:
         """loss, loss_items from the box table itself (host or device, zero rows = padding): what ``__call__`` does after
         ``preprocess``.  A trainer that replays the step as a hipGraph keeps ``gt`` in a static device buffer."""
         feats = preds[1] if isinstance(preds, tuple) else preds
+        self.check_classes(gt, self.nc)
         strides = [float(s) for s in self.stride]
         if any(f.requires_grad for f in feats):
             if self.topk != 10:

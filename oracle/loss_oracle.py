@@ -128,9 +128,12 @@ def dfl_loss(pred_dist: Tensor, target: Tensor, reg_max: int = 16) -> Tensor:
 
 
 def v8_detection_loss(feats: Sequence[Tensor], batch: Dict[str, Tensor], strides: Sequence[float], nc: int, reg_max: int = 16,
-                      box_gain: float = 7.5, cls_gain: float = 0.5, dfl_gain: float = 1.5, tal_topk: int = 10, return_assign=False):
+                      box_gain: float = 7.5, cls_gain: float = 0.5, dfl_gain: float = 1.5, tal_topk: int = 10, return_assign=False,
+                      targets: Tensor = None):
     """v8DetectionLoss.__call__ — loss.py:206-260.  feats: list of (B, 4*reg_max+nc, H_i, W_i) raw head outputs;
-    batch: batch_idx (N,), cls (N,) or (N,1), bboxes (N,4) normalised xywh.  Returns (loss.sum()*B, loss_items[3])."""
+    batch: batch_idx (N,), cls (N,) or (N,1), bboxes (N,4) normalised xywh.  Returns (loss.sum()*B, loss_items[3]).
+    ``targets``: the (B, n_max, 5) pixel table itself instead of ``batch`` (what ``preprocess_targets`` returns; the label-geometry
+    sweep of tests/_loss_util.py places box edges to the fp32 ulp, which normalised xywh labels cannot express)."""
     no = nc + 4 * reg_max
     B = feats[0].shape[0]
     cat = torch.cat([f.reshape(B, no, -1) for f in feats], 2)
@@ -139,7 +142,8 @@ def v8_detection_loss(feats: Sequence[Tensor], batch: Dict[str, Tensor], strides
     pred_distri = pred_distri.permute(0, 2, 1).contiguous()  # (B,A,64)
     imgsz = torch.tensor(feats[0].shape[2:], dtype=torch.float32) * float(strides[0])  # (h, w)
     anchor_points, stride_tensor = make_anchors([f.shape[2:] for f in feats], strides, 0.5)
-    targets = preprocess_targets(batch["batch_idx"].view(-1), batch["cls"].view(-1), batch["bboxes"], B, imgsz[[1, 0, 1, 0]])
+    if targets is None:
+        targets = preprocess_targets(batch["batch_idx"].view(-1), batch["cls"].view(-1), batch["bboxes"], B, imgsz[[1, 0, 1, 0]])
     gt_labels, gt_bboxes = targets.split((1, 4), 2)
     mask_gt = (gt_bboxes.sum(2, keepdim=True) > 0).float()  # loss.py:229
     # decode predicted boxes in grid units — loss.py:197-204

@@ -11,6 +11,7 @@ import torch
 
 from drone_yolo_amd import hip_ops as H
 from oracle import loss_oracle as LO
+from tests._loss_util import large_box_labels
 from tests._util import golden
 
 pytestmark = pytest.mark.gpu
@@ -28,9 +29,17 @@ def _gt(labels, bs, hw):
 
 @pytest.mark.parametrize("bs,hw,seed,n_mean", [(2, 64, 7, 6.0), (3, 160, 8, 14.0), (4, 320, 9, 40.0), (2, 160, 10, 0.01)])
 def test_loss_matches_oracle(bs, hw, seed, n_mean, device):
+    _matches_oracle(bs, hw, seed, LO.synthetic_labels(bs, seed, n_mean=n_mean), device)
+
+
+def test_loss_matches_oracle_64px_assigned(device):
+    """The 64-pixel case with a real assignment (tests/test_loss_geometry_host.py counts its positive anchors: at least 20)."""
+    _matches_oracle(2, 64, 7, large_box_labels(2, 7), device)
+
+
+def _matches_oracle(bs, hw, seed, labels, device):
     gg = torch.Generator().manual_seed(seed)
     feats = [torch.randn(bs, 74, hw // int(s), hw // int(s), generator=gg) * 1.5 for s in STRIDES]
-    labels = LO.synthetic_labels(bs, seed, n_mean=n_mean)
     total, items, asg = LO.v8_detection_loss(feats, labels, STRIDES, 10, return_assign=True)
     out, owner = H.detection_loss(_dev_feats(feats, device), _gt(labels, bs, hw), STRIDES, 10, want_owner=True)
     torch.cuda.synchronize()
@@ -81,9 +90,16 @@ def test_loss_class_api_and_empty_labels(device):
 def test_loss_gradient_matches_autograd(bs, hw, seed, n_mean, device):
     """d(loss.sum() * B)/d head outputs from the device against autograd through the oracle (itself equal to the
     reference's gradient to the last bit: oracle/make_golden.py loss_vectors), tolerance 1e-4 of the largest entry."""
+    _gradient_matches_autograd(bs, hw, seed, LO.synthetic_labels(bs, seed, n_mean=n_mean), device)
+
+
+def test_loss_gradient_matches_autograd_64px_assigned(device):
+    _gradient_matches_autograd(2, 64, 7, large_box_labels(2, 7), device)
+
+
+def _gradient_matches_autograd(bs, hw, seed, labels, device):
     gg = torch.Generator().manual_seed(seed)
     feats = [(torch.randn(bs, 74, hw // int(s), hw // int(s), generator=gg) * 1.5).requires_grad_(True) for s in STRIDES]
-    labels = LO.synthetic_labels(bs, seed, n_mean=n_mean)
     total, _ = LO.v8_detection_loss(feats, labels, STRIDES, 10)
     total.backward()
     out, _, grads = H.detection_loss(_dev_feats([f.detach() for f in feats], device), _gt(labels, bs, hw), STRIDES, 10, want_grad=True)
