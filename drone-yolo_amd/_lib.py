@@ -229,6 +229,22 @@ class ProcessMaskDesc(C.Structure):
     ]  # fmt: skip
 
 
+DY_MAP_U8, DY_MAP_I32 = 0, 1
+VAL_MASK_MAX_LABELS = 1024  # labels per image dy_val_mask_match takes (csrc/val_mask.hip: one LDS bin each)
+
+
+class ValMaskMatchDesc(C.Structure):
+    """Mirror of ``dy_val_mask_match_desc``."""
+
+    _fields_ = [
+        ("protos", _vp), ("side", _vp), ("rows", _vp), ("counts", _vp), ("map", _vp), ("tcls", _vp), ("loff", _vp), ("iouv", C.POINTER(_f32)),
+        ("batch", _i32), ("max_det", _i32), ("nm", _i32), ("mh", _i32), ("mw", _i32), ("ld_p", _i32), ("gh", _i32), ("gw", _i32),
+        ("map_dtype", _i32), ("n_labels", _i32), ("l_cap", _i32), ("n_iouv", _i32),
+        ("in_w", _i32), ("in_h", _i32), ("single_cls", _i32),
+        ("tp_m", _vp), ("best_iou", _vp), ("best_label", _vp), ("area_gt", _vp), ("inter", _vp), ("area_pred", _vp),
+    ]  # fmt: skip
+
+
 DY_AUG_FLIPLR, DY_AUG_FLIPUD, DY_AUG_HSV_OFF = 1, 2, 4
 
 
@@ -326,6 +342,7 @@ SIGNATURES = {
     "dy_depth_to_space2_nhwc": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dy_mask_gather": (_i32, [C.POINTER(MaskGatherDesc), _vp]),
     "dy_process_mask": (_i32, [C.POINTER(ProcessMaskDesc), _vp]),
+    "dy_val_mask_match": (_i32, [C.POINTER(ValMaskMatchDesc), _vp]),
 }
 
 _lib = None

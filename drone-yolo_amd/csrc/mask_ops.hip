@@ -2,6 +2,7 @@
 // the kept detections' mask coefficients behind dy_nms, and the mask assembly of a whole batch (ops.process_mask / process_mask_native
 // of the reference, utils/ops.py:660-753) in one launch.
 #include "common_hip.h"
+#include "mask_crop.h"
 
 namespace dy {
 
@@ -103,17 +104,7 @@ struct PmDet {  // workgroup-uniform state of one detection
 };
 
 __device__ __forceinline__ float pm_dot(const PmDet& D, int yy, int xx) {
-  const f32x4* p = reinterpret_cast<const f32x4*>(D.proto + (long long)yy * D.mw_ld + (long long)xx * D.ld_p);
-  float v = 0.f;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const f32x4 t = p[q];
-    v = __builtin_fmaf(D.cf[4 * q + 0], t[0], v);
-    v = __builtin_fmaf(D.cf[4 * q + 1], t[1], v);
-    v = __builtin_fmaf(D.cf[4 * q + 2], t[2], v);
-    v = __builtin_fmaf(D.cf[4 * q + 3], t[3], v);
-  }
-  return v;
+  return proto_dot32(D.cf, D.proto + (long long)yy * D.mw_ld + (long long)xx * D.ld_p);
 }
 
 struct PmCol {  // the two corner values (rows y0, y1) of one source column
@@ -210,12 +201,8 @@ __global__ __launch_bounds__(kPmThreads) void process_mask_kernel(PmArgs a) {
       // crop_mask at proto resolution: xx >= bx1 and xx < bx2 (window == whole grid in this mode, offsets taken out all the same)
       const float x1 = srow[0] * a.ratio_x - (float)left, x2 = srow[2] * a.ratio_x - (float)left;
       const float y1 = srow[1] * a.ratio_y - (float)top, y2 = srow[3] * a.ratio_y - (float)top;
-      D.cx_lo = (int)ceilf(fminf(fmaxf(x1, 0.f), (float)sw));
-      D.cx_hi = (int)ceilf(fminf(fmaxf(x2, 0.f), (float)sw)) - 1;
-      D.cy_lo = (int)ceilf(fminf(fmaxf(y1, 0.f), (float)sh));
-      D.cy_hi = (int)ceilf(fminf(fmaxf(y2, 0.f), (float)sh)) - 1;
-      // crop_mask compares: a NaN corner is inside no inequality, the mask is empty (fmaxf would turn a NaN x1 / y1 into column / row 0)
-      if (!(x1 == x1 && x2 == x2 && y1 == y1 && y2 == y2)) D.cx_hi = D.cx_lo - 1;
+      const CropWin cw = crop_window(x1, y1, x2, y2, sw, sh);  // (mask_crop.h: the NaN-corner rule lives there)
+      D.cx_lo = cw.x_lo, D.cx_hi = cw.x_hi, D.cy_lo = cw.y_lo, D.cy_hi = cw.y_hi;
       if (D.cx_lo <= D.cx_hi && D.cy_lo <= D.cy_hi) {
         // output pixels whose corners can touch the crop: source coordinate in (c_lo - 1, c_hi + 1), one output pixel of slack each side
         const float ix = (float)a.ow / (float)sw, iy = (float)a.oh / (float)sh;

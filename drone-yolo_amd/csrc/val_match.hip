@@ -20,6 +20,7 @@
 //     inter = max(min(x2) - max(x1), 0) * max(min(y2) - max(y1), 0);  iou = inter / (((w1 * h1) + (w2 * h2)) - inter + 1e-7f)
 // A pair of another class or without overlap is m = 0 exactly (0 / positive), so the division runs for overlapping same-class pairs only.
 #include "common_hip.h"
+#include "val_scan.h"
 
 #pragma clang fp contract(off)
 
@@ -122,30 +123,9 @@ __global__ __launch_bounds__(VM_THREADS) void val_match_kernel(const ValMatchArg
     __syncthreads();  // the stage is rewritten and the counter moves on in the next step
   }
 
-  for (int d = tid; d < cnt; d += VM_THREADS) {
-    const int bl = best[d];
-    float pm = -1.f;
-    if (bl >= 0)
-      for (int e = 0; e < d; ++e)
-        if (best[e] == bl) pm = fmaxf(pm, biou[e]);
-    prev[d] = pm;
-  }
-  __syncthreads();
-
-  uint8_t* tpb = p.tp + (size_t)b * p.max_det * p.n_iouv;
-  const int total = p.max_det * p.n_iouv;
-  for (int i = tid; i < total; i += VM_THREADS) {
-    const int d = i / p.n_iouv;
-    const float t = thr[i - d * p.n_iouv];
-    bool ok = false;
-    if (d < cnt) ok = best[d] >= 0 && biou[d] >= t && !(prev[d] >= t);
-    tpb[i] = ok ? 1 : 0;
-  }
-  for (int d = tid; d < p.max_det; d += VM_THREADS) {
-    const bool has = d < cnt && best[d] >= 0;
-    if (p.best_iou) p.best_iou[(size_t)b * p.max_det + d] = has ? biou[d] : 0.f;
-    if (p.best_label) p.best_label[(size_t)b * p.max_det + d] = has ? best[d] : -1;
-  }
+  // the rank scan over d' < d and the stores (val_scan.h, shared with dy_val_mask_match)
+  val_rank_scan(best, biou, prev, thr, cnt, p.max_det, p.n_iouv, p.tp + (size_t)b * p.max_det * p.n_iouv,
+                p.best_iou ? p.best_iou + (size_t)b * p.max_det : nullptr, p.best_label ? p.best_label + (size_t)b * p.max_det : nullptr, 0, tid, VM_THREADS);
 }
 
 }  // namespace dy

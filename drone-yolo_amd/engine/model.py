@@ -1,5 +1,5 @@
 """``YOLO`` / ``Model`` user API (reference: ultralytics/engine/model.py:29-1177,
-ultralytics/models/yolo/model.py:11-59) for the detection and (prediction only) segmentation tasks on the MI355X path."""
+ultralytics/models/yolo/model.py:11-59) for the detection and segmentation (prediction and validation) tasks on the MI355X path."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -182,8 +182,6 @@ class Model(nn.Module):
         ``"synthetic[:N]"`` (engine/trainer.py::load_dataset; image folders and dataset YAMLs are outside the accelerated path);
         ``batch``, ``imgsz``, ``conf``, ``iou``, ``max_det``, ``half`` / ``dtype``, ``device`` as the reference's arguments.  Returns the
         reference's ``results_dict`` (metrics/precision(B) ... metrics/mAP50-95(B), fitness) with the validation losses; kept in ``self.metrics``."""
-        if self.task == "segment":
-            raise NotImplementedError("val: mask metrics are not built; segmentation models predict only")
         from .predictor import resolve_dtype
         from .trainer import TensorLoader, load_dataset
         from .validator import DetectionValidator
@@ -192,6 +190,8 @@ class Model(nn.Module):
         args = {**{k: v for k, v in self.overrides.items() if k not in ("task", "mode")}, **kwargs}
         if args.get("data") is None:
             raise ValueError("val(): 'data' is missing (a tensor dataset: dict / .pt, or 'synthetic[:N]')")
+        if self.task == "segment":
+            return self._val_segment(validator, args)
         device = select_device(args.get("device", ""))
         data = load_dataset(args["data"], int(args.get("imgsz", 640)), self.model.yaml["nc"], int(args.get("seed", 0)))
         data = data.get("val") or data
@@ -203,6 +203,41 @@ class Model(nn.Module):
         loader = TensorLoader({k: data[k] for k in ("img", "batch_idx", "cls", "bboxes")}, int(args.get("batch") or 16), 0, 1, shuffle=False)
         try:
             self.metrics = (validator or DetectionValidator)(args)(model, loader, device, dtype)
+        finally:
+            model.train(was_training)
+        self.predictor = None  # (the pass may have re-packed weights for another storage type)
+        return self.metrics
+
+    def _val_segment(self, validator, args: dict) -> dict:
+        """``val`` of a segmentation model (reference models/yolo/segment/val.py; engine/validator.py::SegmentationValidator): box and mask
+        metrics, the masks scored on the device by ``dy_val_mask_match`` (``device_match=False``: the reference's data flow on the host).  The
+        dataset must carry ``masks``, the reference's ``overlap_mask=True`` index maps (N, gh, gw) uint8 / int32 — the prototype grid equals the
+        map's or is exactly twice it.  Returns ``SegmentMetrics``' dict (the four (B) and four (M) entries, ``fitness``), no validation loss."""
+        from .predictor import resolve_dtype
+        from .trainer import TensorLoader, load_dataset
+        from .validator import SegmentationValidator
+        from .. import hip_ops as H
+        from ..utils.torch_utils import select_device
+
+        # the dataset first: whatever it lacks is refused before a device is selected, the model moved or a validator built
+        data = load_dataset(args["data"], int(args.get("imgsz", 640)), self.model.yaml["nc"], int(args.get("seed", 0)))
+        data = data.get("val") or data
+        masks = data.get("masks")
+        if masks is None:
+            raise NotImplementedError("val: a segmentation model needs a dataset with 'masks' (the overlap index map (N, gh, gw) of every image); "
+                                      f"data={args['data'] if isinstance(args['data'], str) else type(args['data']).__name__!r} has none")
+        if not isinstance(masks, torch.Tensor) or masks.dim() != 3 or masks.shape[0] != data["img"].shape[0] or masks.dtype not in (torch.uint8, torch.int32):
+            raise NotImplementedError("val: 'masks' must be the overlap index map, uint8 / int32 (N, gh, gw) with one map per image; one binary mask per "
+                                      "label (overlap_mask=False) is not built")
+        device = select_device(args.get("device", ""))
+        dtype = resolve_dtype(args.get("dtype"), bool(args.get("half", False)), self.model)
+        if dtype == H.FP8:
+            raise NotImplementedError("val: Segment is built for the 16-bit, split-float16 and fp32 storage types")
+        was_training = self.model.training
+        model = self.model.to(device)
+        loader = TensorLoader({k: data[k] for k in ("img", "batch_idx", "cls", "bboxes", "masks")}, int(args.get("batch") or 16), 0, 1, shuffle=False)
+        try:
+            self.metrics = (validator or SegmentationValidator)(args)(model, loader, device, dtype)
         finally:
             model.train(was_training)
         self.predictor = None  # (the pass may have re-packed weights for another storage type)

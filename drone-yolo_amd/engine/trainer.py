@@ -346,7 +346,9 @@ def load_yaml_dataset(path: str, imgsz: int) -> Dict[str, torch.Tensor]:
 class TensorLoader:
     """Batches of a tensor dataset with ``DistributedSampler`` semantics (data/build.py:144: shuffle by seed + epoch, pad to a
     multiple of world size by wrapping around, rank r takes indices r::world); labels re-indexed per batch as the reference's
-    collate_fn does (``batch_idx`` = position in the batch)."""
+    collate_fn does (``batch_idx`` = position in the batch).  An image's labels are yielded contiguously and in dataset order; a dataset
+    with ``masks`` (integer (N, gh, gw), the reference's ``overlap_mask=True`` index maps of data/utils.py::polygons2masks_overlap) also
+    yields ``masks`` of the batch's images."""
 
     def __init__(self, data: Dict[str, torch.Tensor], batch: int, rank: int = 0, world: int = 1, seed: int = 0, shuffle: bool = True):
         self.d, self.batch, self.rank, self.world, self.seed, self.shuffle, self.epoch = data, max(int(batch), 1), rank, world, seed, shuffle, 0
@@ -383,8 +385,11 @@ class TensorLoader:
                 rows.append(r)
                 bi.append(torch.full((len(r),), float(j)))
             rows = torch.cat(rows) if rows else torch.zeros(0, dtype=torch.long)
-            yield dict(img=self.d["img"][take], batch_idx=torch.cat(bi) if bi else torch.zeros(0), cls=self.d["cls"][rows].view(-1, 1).float(),
+            out = dict(img=self.d["img"][take], batch_idx=torch.cat(bi) if bi else torch.zeros(0), cls=self.d["cls"][rows].view(-1, 1).float(),
                        bboxes=self.d["bboxes"][rows].float())
+            if self.d.get("masks") is not None:  # segmentation: the overlap label map of every image (value k = the image's k-th label, in the order above)
+                out["masks"] = self.d["masks"][take]
+            yield out
 
 
 class AugmentLoader(TensorLoader):

@@ -10,17 +10,20 @@ validation (``_collect_device``).  ``device_match=False`` is the reference's dat
 ``match_predictions``, ``_collect_host``); the returned numbers are the same ("Validation matching on the device").
 The validation loss is the criterion on Detect's raw maps of the same pass (validator.py:186-187).
 Tensor datasets only (dataset files / augmentation are out of scope): ``data["val"]`` — a dict in the training set's
-layout — or, when the dataset has no split, the training tensors themselves."""
+layout — or, when the dataset has no split, the training tensors themselves.
+``SegmentationValidator`` (models/yolo/segment/val.py) adds the mask statistics of a segmentation model: ``dy_val_mask_match`` behind the box
+matching, or the reference's mask branch on the host ("Segmentation validation")."""
 from __future__ import annotations
 
 from typing import Dict, Optional
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from .. import hip_ops as H
 from ..utils import ops
-from ..utils.metrics import DetMetrics, box_iou, match_predictions
+from ..utils.metrics import DetMetrics, SegmentMetrics, box_iou, mask_iou, match_predictions
 
 
 class DetectionValidator:
@@ -143,4 +146,185 @@ class DetectionValidator:
                 if len(cls):
                     tp = match_predictions(pn[:, 5], cls, box_iou(tbox, pn[:, :4]), self.iouv)
                 stats["tp"].append(tp), stats["conf"].append(pn[:, 4]), stats["pred_cls"].append(pn[:, 5]), stats["target_cls"].append(cls)
+        return nb
+
+
+# ---- segmentation: the reference's mask branch on the host (models/yolo/segment/val.py), piece by piece --------------------------------
+def host_pred_masks(proto: torch.Tensor, coef: torch.Tensor, boxes: torch.Tensor, in_hw) -> torch.Tensor:
+    """``ops.process_mask(proto, coef, boxes, shape=in_hw)`` with ``upsample=False`` (utils/ops.py:679-709) on CPU fp32 tensors: proto
+    (nm, mh, mw), coef (n, nm), boxes (n, 4) unscaled xyxy in input pixels -> float 0 / 1 masks (n, mh, mw) at PROTOTYPE resolution."""
+    c, mh, mw = proto.shape
+    ih, iw = in_hw
+    masks = (coef.float() @ proto.float().reshape(c, -1)).view(-1, mh, mw)
+    b = boxes.float().clone()
+    b[:, 0] *= mw / iw
+    b[:, 2] *= mw / iw
+    b[:, 3] *= mh / ih
+    b[:, 1] *= mh / ih
+    x1, y1, x2, y2 = torch.chunk(b[:, :, None], 4, 1)  # crop_mask (ops.py:660-676)
+    r = torch.arange(mw, dtype=x1.dtype)[None, None, :]
+    cc = torch.arange(mh, dtype=x1.dtype)[None, :, None]
+    return (masks * ((r >= x1) * (r < x2) * (cc >= y1) * (cc < y2))).gt_(0.0)
+
+
+def host_gt_masks(label_map: torch.Tensor, nl: int, proto_hw) -> torch.Tensor:
+    """The overlap label map (gh, gw) of one image -> one float 0 / 1 mask per label (nl, mh, mw): ``gt == index`` and, when the sizes differ,
+    ``F.interpolate(bilinear, align_corners=False)`` + ``gt_(0.5)`` (segment/val.py:196-203)."""
+    index = torch.arange(nl).view(nl, 1, 1) + 1
+    gt = torch.where(label_map[None].long().repeat(nl, 1, 1) == index, 1.0, 0.0)
+    if tuple(gt.shape[1:]) != tuple(proto_hw):
+        gt = F.interpolate(gt[None], tuple(proto_hw), mode="bilinear", align_corners=False)[0]
+        gt = gt.gt_(0.5)
+    return gt
+
+
+def host_mask_iou(gt: torch.Tensor, pred: torch.Tensor) -> np.ndarray:
+    """``mask_iou`` on the flattened masks: (nl, n) fp32."""
+    px = int(np.prod(gt.shape[1:]))
+    return mask_iou(gt.reshape(gt.shape[0], px).numpy(), pred.reshape(pred.shape[0], px).numpy())
+
+
+def check_mask_grids(proto_hw, map_hw) -> int:
+    """The two grid relations that occur: the label map on the prototype grid (ratio 1), or the prototype grid exactly twice the map on both
+    axes (ratio 2: the P2 models).  Anything else is refused."""
+    (mh, mw), (gh, gw) = (int(v) for v in proto_hw), (int(v) for v in map_hw)
+    if (mh, mw) == (gh, gw):
+        return 1
+    if (mh, mw) == (2 * gh, 2 * gw):
+        return 2
+    raise ValueError(f"segmentation val: the prototype grid {mh} x {mw} must equal the label map's {gh} x {gw} or be exactly twice it on both axes")
+
+
+class SegmentationValidator(DetectionValidator):
+    """``SegmentationValidator`` of the reference (models/yolo/segment/val.py): ``DetectionValidator`` plus the mask statistics ``tp_m``.
+    The model pass, the ``multi_label`` NMS (``nc=`` given: the 32 coefficient channels ride behind the classes), ``dy_mask_gather`` and the
+    box matching run as in the detection validator; with ``device_match`` the masks are scored by ``dy_val_mask_match`` on the prototypes
+    (no mask is stored, nothing in the batch loop waits for the device), without it by the reference's data flow on the host, image by
+    image (``host_pred_masks`` / ``host_gt_masks`` / ``host_mask_iou`` / ``match_predictions``).  The dataset carries ``masks``: the
+    reference's ``overlap_mask=True`` index map (N, gh, gw).  No validation loss (the segmentation criterion is not built, and the
+    reference's stand-alone ``val`` computes none): the dict holds the eight metrics and ``fitness``."""
+
+    def __init__(self, args: Optional[dict] = None):
+        super().__init__(args)
+        self.metrics = SegmentMetrics()
+        self.last_stats = None  # what the last call gathered (per-image lists on the host path, one block on the device path)
+
+    def __call__(self, model, loader, device, dtype: torch.dtype) -> Dict[str, float]:
+        model.eval()
+        nc = model.yaml["nc"]
+        stats = dict(tp=[], tp_m=[], conf=[], pred_cls=[], target_cls=[])
+        det = model.model[-1]
+        fuse_tail = getattr(det, "fuse_tail", False)
+        try:
+            (self._collect_device if self.device_match else self._collect_host)(model, loader, device, dtype, nc, stats, det)
+        finally:
+            det.fuse_tail = fuse_tail
+        self.last_stats = stats
+        out = {k: 0.0 for k in SegmentMetrics.keys + ("fitness",)}
+        if stats["tp"]:
+            cat = {k: np.concatenate(v, 0) for k, v in stats.items()}
+            if len(cat["target_cls"]):
+                self.metrics.process(cat["tp"], cat["tp_m"], cat["conf"], cat["pred_cls"], cat["target_cls"])
+                out = self.metrics.results_dict
+        return {k: round(float(v), 5) for k, v in out.items()}
+
+    @staticmethod
+    def _label_cap(loader) -> int:
+        """The largest label count of one image over the whole set: one read before the loop (it sizes the kernel's per-label outputs)."""
+        bi = loader.d["batch_idx"].reshape(-1).long()
+        if not bi.numel():
+            return 1
+        per = torch.zeros(int(loader.n), dtype=torch.long, device=bi.device).index_add_(0, bi, torch.ones_like(bi))
+        return max(int(per.max()), 1)
+
+    def _pass(self, model, batch, device, dtype, nc, det):
+        img = batch["img"].to(device)
+        x = (img.float() / 255.0) if img.dtype == torch.uint8 else img.float()
+        with torch.no_grad():
+            det.fuse_tail = False  # Segment returns (cat([y, mc]), (feats, mc, p))
+            y, aux = model._predict_once(x.contiguous(), image_dtype=dtype)
+            if not (isinstance(aux, tuple) and len(aux) == 3):
+                raise RuntimeError("SegmentationValidator needs a model whose head is Segment")
+            y = y.float().contiguous()
+            bufs = ops.non_max_suppression(y, self.conf, self.iou, nc=nc, multi_label=True, agnostic=self.agnostic, max_det=self.max_det,
+                                           return_padded=True)
+            side = H.mask_gather(bufs, pred=y, nc=nc)
+        return img.shape, bufs, side, aux[2]
+
+    def _collect_device(self, model, loader, device, dtype, nc, stats, det) -> int:
+        nb = n_img = 0
+        rows, counts, tps, tpms, tcls, timg = [], [], [], [], [], []
+        lim = {}
+        l_cap = self._label_cap(loader)
+        for batch in loader:
+            nb += 1
+            (b, _, h, w), bufs, side, protos = self._pass(model, batch, device, dtype, nc, det)
+            masks = batch["masks"].to(device)
+            check_mask_grids(protos.shape[2:], masks.shape[1:])
+            if (w, h) not in lim:
+                lim[(w, h)] = torch.tensor((w, h, w, h), dtype=torch.float32, device=device)
+            cls = batch["cls"].to(device).view(-1).float()
+            bi = batch["batch_idx"].to(device).view(-1).to(torch.int32)
+            tbox = ops.xywh2xyxy(batch["bboxes"].to(device).float()) * lim[(w, h)]
+            tbox = torch.minimum(tbox.clamp_min(0), lim[(w, h)])
+            tps.append(H.val_match(bufs, tbox, cls, bi, self.iouv, (w, h), single_cls=self.single_cls))
+            tpms.append(H.val_mask_match(bufs, protos, side, masks, cls, bi, self.iouv, (w, h), l_cap, single_cls=self.single_cls))
+            rows.append(bufs.out[..., 4:6].clone()), counts.append(bufs.count.clone())
+            tcls.append(cls), timg.append(bi + n_img)
+            n_img += b
+        if nb == 0:
+            return nb
+        rows, counts, tp, tpm = (torch.cat(v).cpu().numpy() for v in (rows, counts, tps, tpms))
+        tcls, timg = torch.cat(tcls).cpu().numpy(), torch.cat(timg).cpu().numpy().astype(np.int64)
+        keep = np.arange(self.max_det)[None, :] < counts[:, None]
+        conf, pred_cls = rows[keep][:, 0], rows[keep][:, 1]
+        if self.single_cls:
+            pred_cls = np.zeros_like(pred_cls)
+        if bool(((counts == 0) & (np.bincount(timg, minlength=len(counts))[: len(counts)] > 0)).any()):  # (as DetectionValidator._collect_device)
+            conf, pred_cls = conf.astype(np.float64), pred_cls.astype(np.float64)
+        if len(conf) or len(tcls):
+            stats["tp"].append(tp[keep].astype(bool)), stats["tp_m"].append(tpm[keep].astype(bool))
+            stats["conf"].append(conf), stats["pred_cls"].append(pred_cls)
+            stats["target_cls"].append(tcls[np.argsort(timg, kind="stable")])
+        self.last_counts = counts
+        return nb
+
+    def _collect_host(self, model, loader, device, dtype, nc, stats, det) -> int:
+        nb = 0
+        all_counts = []
+        for batch in loader:
+            nb += 1
+            (_, _, h, w), bufs, side, protos = self._pass(model, batch, device, dtype, nc, det)
+            check_mask_grids(protos.shape[2:], batch["masks"].shape[1:])
+            counts = bufs.count.cpu().tolist()
+            out, side, protos = bufs.out.cpu(), side.cpu(), protos.float().cpu().contiguous()
+            gmaps = batch["masks"].cpu()
+            bi = batch["batch_idx"].long().cpu()
+            all_counts += counts
+            for si, k in enumerate(counts):  # segment/val.py:90-133
+                sel = bi == si
+                cls = batch["cls"].cpu()[sel].view(-1).numpy()
+                bb = batch["bboxes"].cpu()[sel].float()
+                tbox = (ops.xywh2xyxy(bb) * torch.tensor((w, h, w, h), dtype=torch.float32)).numpy() if len(cls) else np.zeros((0, 4), np.float32)
+                pn = out[si, :k].clone().numpy()
+                for arr in (pn, tbox):  # scale_boxes at gain 1, pad 0: the clip to the image
+                    arr[:, [0, 2]] = arr[:, [0, 2]].clip(0, w)
+                    arr[:, [1, 3]] = arr[:, [1, 3]].clip(0, h)
+                if self.single_cls:
+                    pn[:, 5] = 0
+                tp = np.zeros((k, len(self.iouv)), dtype=bool)
+                tp_m = np.zeros((k, len(self.iouv)), dtype=bool)
+                if k == 0:
+                    if len(cls):
+                        stats["tp"].append(tp), stats["tp_m"].append(tp_m), stats["conf"].append(np.zeros(0)), stats["pred_cls"].append(np.zeros(0))
+                        stats["target_cls"].append(cls)
+                    continue
+                if len(cls):
+                    tp = match_predictions(pn[:, 5], cls, box_iou(tbox, pn[:, :4]), self.iouv)
+                    pm = host_pred_masks(protos[si], side[si, :k, 4:], side[si, :k, :4], (h, w))  # (the UNSCALED, unclipped NMS boxes)
+                    gt = host_gt_masks(gmaps[si], len(cls), protos.shape[2:])
+                    tp_m = match_predictions(pn[:, 5], cls, host_mask_iou(gt, pm), self.iouv)
+                stats["tp"].append(tp), stats["tp_m"].append(tp_m), stats["conf"].append(pn[:, 4]), stats["pred_cls"].append(pn[:, 5])
+                stats["target_cls"].append(cls)
+        self.last_counts = np.array(all_counts, dtype=np.int32)
         return nb

@@ -21,7 +21,7 @@ import warnings
 import torch
 
 from . import _lib
-from ._lib import DY_ACT_NONE, DY_ACT_SILU, DY_ACT_SILU_L2E, BnDesc, BranchDesc, C2fDesc, C2fFrontDesc, C2fTailDesc, ConvDesc, DecodeDesc, HeadDecodeDesc, LossDesc, NmsDesc, Stem2Desc, TileMergeDesc, TrackDesc, ValMatchDesc, check, lib
+from ._lib import DY_ACT_NONE, DY_ACT_SILU, DY_ACT_SILU_L2E, BnDesc, BranchDesc, C2fDesc, C2fFrontDesc, C2fTailDesc, ConvDesc, DecodeDesc, HeadDecodeDesc, LossDesc, NmsDesc, Stem2Desc, TileMergeDesc, TrackDesc, ValMaskMatchDesc, ValMatchDesc, check, lib
 
 FP8 = torch.float8_e4m3fn  # OCP e4m3fn: gfx950's fp8 (MI300's fnuz is another encoding)
 # DY_F16X2 (include/dyolo.h): split float16 pairs, x ~= hi + lo * 2^-11 — the bar-exact precision on the 16-bit MFMA.  torch has no such
@@ -1268,6 +1268,93 @@ def val_match(bufs: NmsBuffers, tbox: torch.Tensor, tcls: torch.Tensor, timg: to
     d.best_label = best_label.data_ptr() if want_best else None
     _launch(lib().dy_val_match, (C.byref(d),), keep=(d, thr, bufs, tbox, tcls, timg, tp, best_iou, best_label))
     return (tp, best_iou, best_label) if want_best else tp
+
+
+def label_offsets(timg: torch.Tensor, batch: int) -> torch.Tensor:
+    """int32 (batch + 1) exclusive prefix of the labels per image, from the image index of every label, built where ``timg`` lives without a
+    host synchronisation (``torch.bincount`` would read the largest index back)."""
+    per = torch.zeros((batch + 1,), dtype=torch.int64, device=timg.device)
+    if timg.numel():
+        per.index_add_(0, timg.reshape(-1).long() + 1, torch.ones((timg.numel(),), dtype=torch.int64, device=timg.device))
+    return per.cumsum(0).to(torch.int32)
+
+
+def val_mask_match_check(proto_hw: Tuple[int, int], map_hw: Tuple[int, int], l_cap: int, n_iouv: int) -> int:
+    """The host-side refusals of ``val_mask_match`` (no device needed): returns the grid ratio (1 or 2)."""
+    (mh, mw), (gh, gw) = proto_hw, map_hw
+    if (mh, mw) == (gh, gw):
+        ratio = 1
+    elif (mh, mw) == (2 * gh, 2 * gw):
+        ratio = 2
+    else:
+        raise ValueError(f"val_mask_match: the prototype grid {mh} x {mw} must equal the label map's {gh} x {gw} or be exactly twice it on both axes")
+    if mh * mw > 1 << 24:
+        raise ValueError(f"val_mask_match: a prototype grid of {mh} x {mw} pixels is beyond 2^24 (the pixel counts must stay exact in fp32)")
+    if l_cap > _lib.VAL_MASK_MAX_LABELS:
+        raise NotImplementedError(f"val_mask_match: {l_cap} labels in one image; dy_val_mask_match takes at most {_lib.VAL_MASK_MAX_LABELS} (one LDS bin each)")
+    if not 1 <= n_iouv <= 16:
+        raise ValueError("val_mask_match: 1..16 IoU thresholds")
+    return ratio
+
+
+def val_mask_match(bufs: NmsBuffers, protos: torch.Tensor, side: torch.Tensor, label_map: torch.Tensor, tcls: torch.Tensor, timg: torch.Tensor,
+                   iouv: Sequence[float], in_wh: Tuple[int, int], l_cap: int, single_cls: bool = False, want_best: bool = False,
+                   want_counts: bool = False):
+    """The segmentation validator's mask matching of a whole batch through ``dy_val_mask_match`` (``ops.process_mask`` at prototype
+    resolution, ``mask_iou`` against the overlap label map, ``match_predictions``); no host synchronisation.
+
+    ``bufs``: what ``nms`` returned; ``protos``: fp32 NHWC view (N, 32, mh, mw); ``side``: ``mask_gather``'s output; ``label_map``: uint8 /
+    int32 (N, gh, gw), value k >= 1 = the k-th label of the image; ``tcls`` (L,) and ``timg`` (L,): the batch's label classes and image
+    indices, image after image in map order; ``in_wh``: the network input size; ``l_cap``: a host bound on the labels per image (at most
+    1024).  Returns ``tp_m`` uint8 (N, max_det, len(iouv)); with ``want_best`` also ``best_iou`` / ``best_label`` (position in ``tcls``);
+    with ``want_counts`` also ``inter`` (N, max_det, l_cap), ``area_pred`` (N, max_det), ``area_gt`` (N, l_cap), int32.  New tensors on
+    every call; rows at or beyond ``bufs.count`` are 0 / 0 / -1."""
+    n, max_det, dev = bufs.batch, bufs.max_det, bufs.out.device
+    if protos.dim() != 4 or protos.shape[0] != n or protos.dtype != torch.float32:
+        raise ValueError("val_mask_match: protos must be an fp32 (N, nm, mh, mw) NHWC view")
+    nm, mh, mw = int(protos.shape[1]), int(protos.shape[2]), int(protos.shape[3])
+    if nm != NM:
+        raise NotImplementedError(f"val_mask_match: {nm} mask coefficients; dy_val_mask_match is built for {NM}")
+    if label_map.dim() != 3 or label_map.shape[0] != n or label_map.dtype not in (torch.uint8, torch.int32):
+        raise ValueError("val_mask_match: the label map must be uint8 or int32 (N, gh, gw)")
+    l_cap = max(int(l_cap), 1)
+    val_mask_match_check((mh, mw), (int(label_map.shape[1]), int(label_map.shape[2])), l_cap, len(iouv))
+    if side.dtype != torch.float32 or tuple(side.shape) != (n, max_det, 4 + NM) or not side.is_contiguous():
+        raise ValueError("val_mask_match: side must be the contiguous fp32 (N, max_det, 36) output of mask_gather")
+    L = int(tcls.numel())
+    if timg.numel() != L:
+        raise ValueError("val_mask_match: one image index per label class")
+    require_device(protos, "protos")
+    for t, what in ((side, "side buffer"), (label_map, "label map"), (tcls, "label"), (timg, "label")):
+        require_device(t, what)
+    label_map = label_map.contiguous()
+    tcls = tcls.reshape(-1).to(torch.float32).contiguous()
+    loff = label_offsets(timg, n)
+    thr = (C.c_float * len(iouv))(*[float(v) for v in iouv])
+    tp = torch.empty((n, max_det, len(iouv)), dtype=torch.uint8, device=dev)
+    best_iou = torch.empty((n, max_det), dtype=torch.float32, device=dev)
+    best_label = torch.empty((n, max_det), dtype=torch.int32, device=dev)
+    area_gt = torch.empty((n, l_cap), dtype=torch.int32, device=dev)
+    inter = torch.empty((n, max_det, l_cap), dtype=torch.int32, device=dev) if want_counts else None
+    area_pred = torch.empty((n, max_det), dtype=torch.int32, device=dev) if want_counts else None
+    d = ValMaskMatchDesc()
+    d.protos, d.ld_p = view_params(protos)
+    d.side, d.rows, d.counts = side.data_ptr(), bufs.out.data_ptr(), bufs.count.data_ptr()
+    d.map, d.tcls, d.loff, d.iouv = label_map.data_ptr(), (tcls.data_ptr() if L else None), loff.data_ptr(), thr
+    d.batch, d.max_det, d.nm, d.mh, d.mw, d.gh, d.gw = n, max_det, nm, mh, mw, int(label_map.shape[1]), int(label_map.shape[2])
+    d.map_dtype = _lib.DY_MAP_U8 if label_map.dtype == torch.uint8 else _lib.DY_MAP_I32
+    d.n_labels, d.l_cap, d.n_iouv = L, l_cap, len(iouv)
+    d.in_w, d.in_h, d.single_cls = int(in_wh[0]), int(in_wh[1]), int(bool(single_cls))
+    d.tp_m, d.best_iou, d.best_label, d.area_gt = tp.data_ptr(), best_iou.data_ptr(), best_label.data_ptr(), area_gt.data_ptr()
+    d.inter = inter.data_ptr() if want_counts else None
+    d.area_pred = area_pred.data_ptr() if want_counts else None
+    _launch(lib().dy_val_mask_match, (C.byref(d),), keep=(d, thr, bufs, protos, side, label_map, tcls, loff, tp, best_iou, best_label, area_gt, inter, area_pred))
+    out = (tp,)
+    if want_best:
+        out += (best_iou, best_label)
+    if want_counts:
+        out += (inter, area_pred, area_gt)
+    return out if len(out) > 1 else tp
 
 
 # ---- tracking ---------------------------------------------------------------------------------------------

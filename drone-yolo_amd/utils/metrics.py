@@ -1,4 +1,4 @@
-"""Detection metrics of the validation step (reference: ultralytics/utils/metrics.py ``box_iou`` :52-71, ``smooth`` :447-452,
+"""Detection and segmentation metrics of the validation step (reference: ultralytics/utils/metrics.py ``box_iou`` :52-71, ``mask_iou`` :137-153, ``SegmentMetrics`` :899-1030, ``smooth`` :447-452,
 ``compute_ap`` :505-534, ``ap_per_class`` :537-623, ``Metric`` :626-760; ``BaseValidator.match_predictions``, engine/validator.py:224-264).
 
 Host logic in numpy, as in the reference (its metrics leave the device too: validator.get_stats() does ``.cpu().numpy()``): a few
@@ -20,6 +20,15 @@ def box_iou(box1: np.ndarray, box2: np.ndarray, eps: float = 1e-7) -> np.ndarray
     b = box2.astype(np.float32)[None, :, :]
     inter = np.clip(np.minimum(a[..., 2:], b[..., 2:]) - np.maximum(a[..., :2], b[..., :2]), 0, None).prod(2)
     return inter / ((a[..., 2:] - a[..., :2]).prod(2) + (b[..., 2:] - b[..., :2]).prod(2) - inter + np.float32(eps))
+
+
+def mask_iou(mask1: np.ndarray, mask2: np.ndarray, eps: float = 1e-7) -> np.ndarray:
+    """(N, n) x (M, n) flattened 0 / 1 masks -> (N, M) IoU in fp32 — metrics.py:137-153: the intersection as a float matrix product,
+    ``(area1 + area2) - intersection`` and the division, each rounded to fp32 (all counts are integers below 2^24, so the sums are exact)."""
+    a, b = mask1.astype(np.float32), mask2.astype(np.float32)
+    inter = np.clip(a @ b.T, 0, None)
+    union = (a.sum(1, dtype=np.float32)[:, None] + b.sum(1, dtype=np.float32)[None]) - inter
+    return inter / (union + np.float32(eps))
 
 
 def match_predictions(pred_classes: np.ndarray, true_classes: np.ndarray, iou: np.ndarray, iouv: np.ndarray) -> np.ndarray:
@@ -111,6 +120,36 @@ class DetMetrics:
     @property
     def fitness(self) -> float:
         return float((np.array(self.mean_results()) * np.array([0.0, 0.0, 0.1, 0.9])).sum())
+
+    @property
+    def results_dict(self) -> Dict[str, float]:
+        return dict(zip(self.keys + ("fitness",), [float(v) for v in self.mean_results()] + [self.fitness]))
+
+
+class SegmentMetrics:
+    """Box and mask metrics of a segmentation model — ``SegmentMetrics`` (metrics.py:899-1030): two ``Metric`` sets, fed by ``tp`` (boxes)
+    and ``tp_m`` (masks) with the same ``conf`` / ``pred_cls`` / ``target_cls``; the same AP code as ``DetMetrics``.  ``fitness`` is the sum
+    of the two sets' fitness."""
+
+    keys = DetMetrics.keys + ("metrics/precision(M)", "metrics/recall(M)", "metrics/mAP50(M)", "metrics/mAP50-95(M)")
+
+    def __init__(self):
+        self.box, self.seg = DetMetrics(), DetMetrics()
+
+    def process(self, tp, tp_m, conf, pred_cls, target_cls) -> None:
+        self.seg.process(tp_m, conf, pred_cls, target_cls)
+        self.box.process(tp, conf, pred_cls, target_cls)
+
+    def mean_results(self):
+        return self.box.mean_results() + self.seg.mean_results()
+
+    @property
+    def ap_class_index(self):
+        return self.box.ap_class_index
+
+    @property
+    def fitness(self) -> float:
+        return self.seg.fitness + self.box.fitness
 
     @property
     def results_dict(self) -> Dict[str, float]:

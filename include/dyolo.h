@@ -905,6 +905,50 @@ typedef struct dy_process_mask_desc {
 } dy_process_mask_desc;
 int32_t dy_process_mask(const dy_process_mask_desc* d, dy_stream_t stream);
 
+/* dy_val_mask_match: the mask half of the segmentation validator for a whole batch behind dy_nms / dy_mask_gather; no host
+ * synchronisation.  Replaces, per image, ops.process_mask(proto, coef, box, shape=imgsz) (upsample = False: coef @ protos, crop_mask with the
+ * unscaled box times (mw / in_w, mh / in_h), > 0, at PROTOTYPE resolution; utils/ops.py:679-709), the expansion of the overlap label map
+ * to one binary mask per label with its F.interpolate(bilinear) + gt(0.5) to the prototype grid, mask_iou (utils/metrics.py:137-153) and
+ * BaseValidator.match_predictions (models/yolo/segment/val.py:164-208).  No mask is stored: the map gives a pixel to at most one label, so
+ * the intersections of one prediction with all labels are a histogram of the map values under its mask.
+ * protos: fp32 NHWC (batch, mh, mw, nm), pitch ld_p, 16-byte aligned; mh * mw <= 2^24 (integer counts exact in fp32).  side: the
+ * dy_mask_gather output (batch, max_det, 4 + nm).  rows / counts: the dy_nms outputs (class in column 5; row order = descending confidence).
+ * map: (batch, gh, gw) DY_MAP_U8 or DY_MAP_I32, the reference's overlap form: value k >= 1 = the k-th label of the image, 0 = background,
+ * values above the image's label count are background.  (mh, mw) == (gh, gw), or exactly (2 gh, 2 gw): then the map is read at
+ * [y >> 1, x >> 1] (the resized, thresholded one-hot masks are the 2 x 2 replication of the map).  Anything else: DY_ERR_INVALID_ARG.
+ * tcls: fp32 (n_labels) the batch's label classes, image after image; loff: int32 (batch + 1) DEVICE offsets, the labels of image b are
+ * tcls[loff[b] .. loff[b + 1]) in map order (clamped into [0, n_labels] on the device).  l_cap: HOST bound on the labels per image (it sizes
+ * inter / area_gt; an image with more uses its first l_cap); l_cap > 1024: DY_ERR_UNSUPPORTED (one 4-byte LDS bin per label).
+ * iouv: HOST array of n_iouv (1..16) thresholds, read during the call.  in_w, in_h: the network input size the boxes are in.
+ * For kept row d of image b and label l: inter = |pred & gt|, iou = inter / (((area_gt + area_pred) - inter) + 1e-7f), every operation
+ * rounded on its own (bit-equal to mask_iou); m(l, d) = iou if tcls[l] == cls[d] (cls[d] counts as 0 with single_cls, as in dy_val_match) else 0; best / biou / tp_m by
+ * dy_val_match's rule (ties to the lower label position).
+ * tp_m: uint8 (batch, max_det, n_iouv).  best_iou: fp32 (batch, max_det); best_label: int32 (batch, max_det), position in tcls, -1 when
+ * the image has no label; area_gt: int32 (batch, l_cap).  These three are REQUIRED: they carry the intermediate results between the
+ * launches.  Optional: inter int32 (batch, max_det, l_cap), area_pred int32 (batch, max_det).  Every element of every output is written;
+ * rows >= counts[b] get 0 / 0 / -1 and zero counts, labels >= the image's count zero areas. */
+#define DY_MAP_U8 0
+#define DY_MAP_I32 1
+typedef struct dy_val_mask_match_desc {
+  const float* protos;
+  const float* side;
+  const float* rows;
+  const int32_t* counts;
+  const void* map;
+  const float* tcls;
+  const int32_t* loff;
+  const float* iouv;
+  int32_t batch, max_det, nm, mh, mw, ld_p, gh, gw, map_dtype, n_labels, l_cap, n_iouv;
+  int32_t in_w, in_h, single_cls;
+  uint8_t* tp_m;
+  float* best_iou;
+  int32_t* best_label;
+  int32_t* area_gt;
+  int32_t* inter;
+  int32_t* area_pred;
+} dy_val_mask_match_desc;
+int32_t dy_val_mask_match(const dy_val_mask_match_desc* d, dy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
