@@ -22,6 +22,8 @@ from typing import Any, Dict, Tuple
 import torch
 import torch.nn as nn
 
+from .modules.packs import PACKED
+
 
 class _Placeholder:
     """Stands in for reference classes this package has no use for (their state is kept but inert)."""
@@ -147,7 +149,7 @@ _REF_PATHS = {"Conv": "ultralytics.nn.modules.conv", "DWConv": "ultralytics.nn.m
               "Bottleneck": "ultralytics.nn.modules.block", "RepVGGBlock": "ultralytics.nn.modules.block", "SEBlock": "ultralytics.nn.modules.block",
               "Detect": "ultralytics.nn.modules.head", "DetectionModel": "ultralytics.nn.tasks", "BaseModel": "ultralytics.nn.tasks",
               "Proto": "ultralytics.nn.modules.block", "Segment": "ultralytics.nn.modules.head", "SegmentationModel": "ultralytics.nn.tasks"}
-_DROP_ATTRS = ("_packed", "_block_cache", "_tail_cache", "_front_cache", "_first_cache", "_stem2_cache", "_sig_tensors", "_weights_epoch", "_place", "_srcs", "_virtual", "_skip", "_front",
+_DROP_ATTRS = (PACKED, "_sig_tensors", "_weights_epoch", "_place", "_srcs", "_virtual", "_skip", "_front",
                "_consumers0", "_out_ch", "_cum_stride", "criterion", "train_dtype", "args", "fused_nms", "fuse_tail")
 
 

@@ -10,7 +10,8 @@ import torch
 import torch.nn as nn
 
 from ... import hip_ops as H
-from .conv import Conv, _PackedMixin, _train_forward, fold_conv_bn
+from .conv import Conv, _train_forward, fold_conv_bn
+from .packs import PackOwner, _PackedMixin, packed
 
 __all__ = ("DFL", "Proto", "SPPF", "C2f", "Bottleneck", "RepVGGBlock", "SEBlock", "conv_bn")
 
@@ -57,16 +58,13 @@ class Proto(_PackedMixin, nn.Module):
     def _packed_cv3(self, x: torch.Tensor) -> H.PackedConv:
         """cv3 packed to LEAVE the scaled activation domain: weights / log2 e on the scaled input, the plain SiLU on the true
         pre-activation (SiLU is not homogeneous, so unlike the Detect tails the activation itself must run in true units)."""
-        cache = self.cv3._pack_cache()
-        key = ("proto_out", x.dtype, x.device, H.scaled_domain())
-        pc = cache.get(key)
-        if pc is None:
+        def build():
             w, b = fold_conv_bn(self.cv3.conv.weight, self.cv3.conv.bias, self.cv3.bn)
             if H.scaled_domain():
                 w = w / H.LOG2E
-            pc = cache[key] = H.PackedConv(w, b, 1, 0, 1, H.DY_ACT_SILU if isinstance(self.cv3.act, nn.SiLU) else H.DY_ACT_NONE, x.dtype, x.device,
-                                           for_out_f32=True)
-        return pc
+            return H.PackedConv(w, b, 1, 0, 1, H.DY_ACT_SILU if isinstance(self.cv3.act, nn.SiLU) else H.DY_ACT_NONE, x.dtype, x.device, for_out_f32=True)
+
+        return packed(self, "proto_out", (self.cv3,), x.dtype, x.device, build)
 
     def forward(self, x):
         if self.training:
@@ -94,7 +92,7 @@ class Bottleneck(nn.Module):
         return self.cv2(self.cv1(x), out=out, residual=x if self.add else None)
 
 
-class C2f(nn.Module):
+class C2f(PackOwner, nn.Module):
     """CSP bottleneck with 2 convolutions, 'faster' variant — reference block.py:227-249."""
 
     def __init__(self, c1, c2, n=1, shortcut=False, g=1, e=0.5):
@@ -117,25 +115,13 @@ class C2f(nn.Module):
 
     def _packed_block(self, dtype, device):
         convs = (self.cv1, self.m[0].cv1, self.m[0].cv2, self.cv2)
-        key = (dtype, str(device), H.scaled_domain(),
-               tuple((c.conv.weight.data_ptr(), c.conv.weight._version, c.bn.weight._version, c.bn.running_var._version) for c in convs))
-        cache = self.__dict__.get("_block_cache")
-        if cache is None or cache[0] != key:
-            folded = [H.domain_fold(*fold_conv_bn(c.conv.weight, c.conv.bias, c.bn), True)[:2] for c in convs]
-            cache = (key, H.PackedC2f(*folded, shortcut=self.m[0].add, dtype=dtype, device=device, act_l2e=H.scaled_domain()))
-            self.__dict__["_block_cache"] = cache
-        return cache[1]
+        return packed(self, "block", convs, dtype, device, lambda: H.PackedC2f(
+            *(c._folded()[:2] for c in convs), shortcut=self.m[0].add, dtype=dtype, device=device, act_l2e=H.scaled_domain()))
 
     def _packed_tail(self, dtype, device):
         convs = (self.m[-1].cv2, self.cv2)
-        key = (dtype, str(device), H.scaled_domain(),
-               tuple((c.conv.weight.data_ptr(), c.conv.weight._version, c.bn.weight._version, c.bn.running_var._version) for c in convs))
-        cache = self.__dict__.get("_tail_cache")
-        if cache is None or cache[0] != key:
-            folded = [H.domain_fold(*fold_conv_bn(c.conv.weight, c.conv.bias, c.bn), True)[:2] for c in convs]
-            cache = (key, H.PackedC2fTail(*folded, n=len(self.m), shortcut=self.m[-1].add, dtype=dtype, device=device, act_l2e=H.scaled_domain()))
-            self.__dict__["_tail_cache"] = cache
-        return cache[1]
+        return packed(self, "tail", convs, dtype, device, lambda: H.PackedC2fTail(
+            *(c._folded()[:2] for c in convs), n=len(self.m), shortcut=self.m[-1].add, dtype=dtype, device=device, act_l2e=H.scaled_domain()))
 
     @staticmethod
     def _down3x3(prod):
@@ -162,16 +148,13 @@ class C2f(nn.Module):
         return isinstance(self.cv1.act, nn.SiLU) and H.c2f_front_fused_supported(io[0], io[1], c_other, self.cv1.conv.out_channels, dtype, act)
 
     def _packed_front(self, prod, dtype, device):
-        srcs = list(prod.parameters()) + list(prod.buffers()) + list(self.cv1.parameters()) + list(self.cv1.buffers())
-        key = (dtype, str(device), H.scaled_domain(), tuple((t.data_ptr(), t._version) for t in srcs))
-        cache = self.__dict__.get("_front_cache")
-        if cache is None or cache[0] != key:
+        def build():
             w3, b3, act = prod._folded()
             w1, b1, act1 = self.cv1._folded()
             assert act == act1
-            cache = (key, H.PackedC2fFront((w3, b3), (w1, b1), act, dtype, device))
-            self.__dict__["_front_cache"] = cache
-        return cache[1]
+            return H.PackedC2fFront((w3, b3), (w1, b1), act, dtype, device)
+
+        return packed(self, "front", (prod, self.cv1), dtype, device, build)
 
     def _cv1(self, x, out, front, kw):
         """[y0 | y1] into ``out``: cv1 on ``x``, or — ``front`` = (producer, other Concat source or None) — the producer's stride-2 3x3 on

@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from ... import hip_ops as H
+from .packs import _PackedMixin, packed
 
 __all__ = ("autopad", "Conv", "DWConv", "Concat", "Upsample", "fold_conv_bn")
 
@@ -38,50 +39,6 @@ def fold_conv_bn(conv_weight: torch.Tensor, conv_bias: Optional[torch.Tensor], b
     scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
     b0 = torch.zeros(w.shape[0], device=w.device) if conv_bias is None else conv_bias.detach().float()
     return w * scale.view(-1, 1, 1, 1), bn.bias.detach().float() + (b0 - bn.running_mean.detach().float()) * scale
-
-
-class _PackedMixin:
-    """Lazy per-dtype cache of packed weights; dropped whenever parameters may have changed."""
-
-    def _pack_cache(self) -> dict:
-        """The per-dtype pack cache, emptied when any parameter / buffer of this module was re-homed or edited in place
-        (storage identity + torch's version counter) since the packs were made."""
-        sig = tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
-        cache = self.__dict__.get("_packed")
-        if cache is None or cache.get("__sig__") != sig:
-            cache = self.__dict__["_packed"] = {"__sig__": sig}
-        return cache
-
-    def _packed_for(self, x: torch.Tensor) -> H.PackedConv:
-        cache = self._pack_cache()
-        # an fp8 pack bakes the activation scale in; every pack the activation domain it was folded for (H.scaled_activations)
-        key = (x.dtype, x.device, x.shape[1], H.fp8_act_scale() if x.dtype == H.FP8 else None, H.scaled_domain())
-        pc = cache.get(key)
-        if pc is None:
-            pc = cache[key] = self._pack(x.dtype, x.device)
-            if pc.groups == 1 and 0 < x.shape[1] - pc.cin < H.chan_gran(x.dtype):
-                # zero-padded input channels (image input padded to one 16-byte chunk): pad the taps to match
-                pc = cache[key] = self._pack(x.dtype, x.device, cin_pad=x.shape[1])
-        return pc
-
-    def invalidate_packed(self) -> None:
-        self.__dict__.pop("_packed", None)
-
-    def train(self, mode: bool = True):
-        if mode != self.training:  # a training phase writes the parameters through raw pointers: packs made before it are stale
-            self.invalidate_packed()
-        return super().train(mode)
-
-    def _load_from_state_dict(self, *args, **kwargs):
-        self.invalidate_packed()
-        return super()._load_from_state_dict(*args, **kwargs)
-
-    def _apply(self, fn, *args, **kwargs):
-        before = [(t.data_ptr(), t.dtype, t.device) for t in list(self.parameters()) + list(self.buffers())]
-        out = super()._apply(fn, *args, **kwargs)
-        if before != [(t.data_ptr(), t.dtype, t.device) for t in list(self.parameters()) + list(self.buffers())]:
-            self.invalidate_packed()  # .to(device) / .half(): a no-op move (second predictor on the same model) keeps the packs
-        return out
 
 
 def _train_forward(m: nn.Module, fn_name: str, x, **kw):
@@ -111,14 +68,14 @@ class Conv(_PackedMixin, nn.Module):
         if not isinstance(self.act, (nn.SiLU, nn.Identity)):
             raise NotImplementedError("only SiLU / identity activations are built into the conv epilogue")
 
-    def _folded(self):
+    def _folded(self, raw_input=None):
         """(weight, bias, activation code) with BatchNorm folded in, for the activation domain in force (``H.domain_fold``)."""
         w, b = fold_conv_bn(self.conv.weight, self.conv.bias, self.bn) if hasattr(self, "bn") else (
             self.conv.weight, self.conv.bias)
         if b is None:
             b = torch.zeros(w.shape[0], device=w.device)
         # _raw_input: set by the model executor on the layer that reads the image (its input is not in the scaled domain)
-        return H.domain_fold(w, b, isinstance(self.act, nn.SiLU), raw_input=getattr(self, "_raw_input", False))
+        return H.domain_fold(w, b, isinstance(self.act, nn.SiLU), raw_input=getattr(self, "_raw_input", False) if raw_input is None else raw_input)
 
     def _pack(self, dtype, device, cin_pad=None) -> H.PackedConv:
         w, b, act = self._folded()
@@ -142,14 +99,11 @@ class Conv(_PackedMixin, nn.Module):
         """fp32 NCHW image -> this layer's NHWC output in ``dtype`` (layout cast + conv + BN + SiLU in one kernel)."""
         if self.training:
             raise NotImplementedError("Conv.forward_stem is the eval path's fused image kernel; training reads the image through model.forward_train")
-        cache = self._pack_cache()
-        key = ("stem", dtype, im.device, H.scaled_domain())
-        ps = cache.get(key)
-        if ps is None:
-            w, b = fold_conv_bn(self.conv.weight, self.conv.bias, self.bn)
-            w, b, act = H.domain_fold(w, b, isinstance(self.act, nn.SiLU), raw_input=True)  # the image is never in the scaled domain
-            ps = cache[key] = H.PackedStem(w, b, act, dtype, im.device)
-        return H.stem_conv(im, ps, out=out, mark_input=mark_input)
+        return H.stem_conv(im, self._packed_stem(dtype, im.device), out=out, mark_input=mark_input)
+
+    def _packed_stem(self, dtype, device) -> H.PackedStem:
+        """The pack of ``forward_stem`` (the image is never in the scaled domain: folded as raw input whatever ``_raw_input`` says)."""
+        return packed(self, "stem", (self,), dtype, device, lambda: H.PackedStem(*self._folded(raw_input=True), dtype, device))
 
 
 class DWConv(Conv):

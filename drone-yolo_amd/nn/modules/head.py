@@ -9,11 +9,12 @@ import torch.nn as nn
 from ... import hip_ops as H
 from .block import DFL, Proto
 from .conv import Conv, DWConv, PlainConv2d
+from .packs import PackOwner, packed
 
 __all__ = ("Detect", "Segment")
 
 
-class Detect(nn.Module):
+class Detect(PackOwner, nn.Module):
     """YOLO Detect head: per level box branch cv2 and class branch cv3, then decode.
 
     Same constructor, attributes and state-dict keys as the reference (head.py:34-61).  Forward
@@ -59,20 +60,6 @@ class Detect(nn.Module):
         self.dfl = DFL(self.reg_max) if self.reg_max > 1 else nn.Identity()
 
     @staticmethod
-    def _run(seq, x, out):
-        """Run one branch; its last (plain 1x1) conv writes fp32 logits into ``out``."""
-        mods = list(seq)
-        for m in mods[:-1]:
-            if isinstance(m, nn.Sequential):
-                for mm in m:
-                    x = mm(x)
-            else:
-                x = m(x)
-        return mods[-1](x, out=out, out_f32=True)
-
-    fuse_tail = False  # opt-in (the predictor sets it): eval returns (y, None), the raw maps are never materialised
-
-    @staticmethod
     def _run_trunk(seq, x):
         """All but the last (plain 1x1) conv of one branch."""
         for m in list(seq)[:-1]:
@@ -83,17 +70,29 @@ class Detect(nn.Module):
                 x = m(x)
         return x
 
+    @classmethod
+    def _run(cls, seq, x, out):
+        """Run one branch; its last (plain 1x1) conv writes fp32 logits into ``out``."""
+        return seq[-1](cls._run_trunk(seq, x), out=out, out_f32=True)
+
+    fuse_tail = False  # opt-in (the predictor sets it): eval returns (y, None), the raw maps are never materialised
+
     def _packed_tail(self, dtype, device):
-        tails = [s[-1] for s in self.cv2] + [s[-1] for s in self.cv3]
-        key = (dtype, str(device), H.scaled_domain(), tuple((m.weight.data_ptr(), m.weight._version, m.bias._version) for m in tails))
-        cache = getattr(self, "_tail_cache", None)
-        if cache is None or cache[0] != key:
-            # (in the scaled activation domain the tails divide by log2 e: the logits the decode reads are in true units)
-            pb = [H.pack_frag1x1(*H.domain_fold(s[-1].weight, s[-1].bias, False, raw_output=True)[:2], dtype, device) for s in self.cv2]
-            pc = [H.pack_frag1x1(*H.domain_fold(s[-1].weight, s[-1].bias, False, raw_output=True)[:2], dtype, device) for s in self.cv3]
-            cache = (key, pb, pc)
-            self._tail_cache = cache
-        return cache[1], cache[2]
+        tails = tuple(s[-1] for s in (*self.cv2, *self.cv3))
+
+        def build():  # (in the scaled activation domain the tails divide by log2 e: the logits the decode reads are in true units)
+            frags = [H.pack_frag1x1(*H.domain_fold(m.weight, m.bias, False, raw_output=True)[:2], dtype, device) for m in tails]
+            return frags[: self.nl], frags[self.nl :]
+
+        return packed(self, "tail", tails, dtype, device, build)
+
+    def _nms_kwargs(self, n, anchors):
+        """Keywords of the decode kernels' candidate filter when the predictor attached one: ``fused_nms`` = (NmsBuffers factory, conf, classes mask)."""
+        fused = getattr(self, "fused_nms", None)
+        if fused is None:
+            return {}
+        make_bufs, conf, mask = fused
+        return dict(nms_bufs=make_bufs(n, anchors), conf_thres=conf, classes_mask=mask)
 
     fuse_first = True  # run cv2[i][0] and cv3[i][0] (same input, both 3x3) as ONE convolution on the deep levels
 
@@ -113,19 +112,11 @@ class Detect(nn.Module):
                 and ca.in_channels == cb.in_channels and ca.in_channels >= 64 and (ca.out_channels + cb.out_channels) % 128 == 0
                 and ca.out_channels % 8 == 0 and isinstance(a.act, nn.SiLU) and isinstance(b.act, nn.SiLU)):
             return None
-        srcs = [ca.weight, a.bn.weight, a.bn.bias, a.bn.running_mean, a.bn.running_var, cb.weight, b.bn.weight, b.bn.bias, b.bn.running_mean, b.bn.running_var]
-        key = (dtype, str(device), H.fp8_act_scale() if dtype == H.FP8 else None, H.scaled_domain(), tuple((t.data_ptr(), t._version) for t in srcs))
-        cache = self.__dict__.setdefault("_first_cache", {})
-        hit = cache.get(i)
-        if hit is None or hit[0] != key:
-            from .conv import fold_conv_bn
+        def build():
+            (wa, ba, act), (wb, bb, _) = a._folded(), b._folded()
+            return H.PackedConv(torch.cat((wa, wb), 0), torch.cat((ba, bb), 0), 1, 1, 1, act, dtype, device)
 
-            wa, ba = fold_conv_bn(ca.weight, ca.bias, a.bn)
-            wb, bb = fold_conv_bn(cb.weight, cb.bias, b.bn)
-            ws, bs, act = H.domain_fold(torch.cat((wa, wb), 0), torch.cat((ba, bb), 0), True)
-            hit = (key, H.PackedConv(ws, bs, 1, 1, 1, act, dtype, device), ca.out_channels)
-            cache[i] = hit
-        return hit[1], hit[2]
+        return packed(self, ("first", i), (a, b), dtype, device, build), ca.out_channels
 
     def _trunks(self, i, x):
         """Outputs of the two branch trunks (all but the last 1x1 conv) of level i."""
@@ -166,12 +157,9 @@ class Detect(nn.Module):
         A = sum(t.shape[2] * t.shape[3] for t in x)
         dtype, dev = x[0].dtype, x[0].device
         pred = torch.empty((n, 4 + self.nc, A), dtype=torch.float32, device=dev)
-        fused = getattr(self, "fused_nms", None)
-        bufs, conf, mask = None, 0.25, None
-        if fused is not None:
-            make_bufs, conf, mask = fused
-            bufs = make_bufs(n, A)
-            H.nms_reset_counts(bufs)
+        nms = self._nms_kwargs(n, A)
+        if nms:
+            H.nms_reset_counts(nms["nms_bufs"])
         pb, pc = self._packed_tail(dtype, dev)
         a0 = 0
         for i in range(self.nl):
@@ -182,8 +170,7 @@ class Detect(nn.Module):
                 both = H.conv2d(x[i], pf[0])
                 tb, tc = both[:, : pf[1]], both[:, pf[1] :]
             H.detect_branch_fused(tb, self.cv2[i][1]._packed_for(tb), pb[i][0], pb[i][1], 1, self.nc, self.reg_max, float(self.stride[i]), pred, a0)
-            H.detect_branch_fused(tc, self.cv3[i][1]._packed_for(tc), pc[i][0], pc[i][1], 2, self.nc, self.reg_max, float(self.stride[i]), pred, a0,
-                                  nms_bufs=bufs, conf_thres=conf, classes_mask=mask)
+            H.detect_branch_fused(tc, self.cv3[i][1]._packed_for(tc), pc[i][0], pc[i][1], 2, self.nc, self.reg_max, float(self.stride[i]), pred, a0, **nms)
             a0 += x[i].shape[2] * x[i].shape[3]
         return pred
 
@@ -194,12 +181,7 @@ class Detect(nn.Module):
         tr = [self._trunks(i, x[i]) for i in range(self.nl)]
         xb, xc = [t[0] for t in tr], [t[1] for t in tr]
         pb, pc = self._packed_tail(xb[0].dtype, xb[0].device)
-        fused = getattr(self, "fused_nms", None)
-        kw = {}
-        if fused is not None:
-            make_bufs, conf, mask = fused
-            A = sum(f.shape[2] * f.shape[3] for f in xb)
-            kw = dict(nms_bufs=make_bufs(xb[0].shape[0], A), conf_thres=conf, classes_mask=mask)
+        kw = self._nms_kwargs(xb[0].shape[0], sum(f.shape[2] * f.shape[3] for f in xb))
         return H.detect_head_decode(xb, xc, pb, pc, [float(s) for s in self.stride], self.nc, self.reg_max, **kw)
 
     tail_dtype = torch.float16  # storage type of the Detect branches behind an fp8 trunk (DY_FP8 inputs): see _forward_fp8_trunk
@@ -221,11 +203,7 @@ class Detect(nn.Module):
             for m in list(self.cv3[i])[1:-1]:
                 tc = m(tc)
             xb.append(tb), xc.append(tc)
-        fused = getattr(self, "fused_nms", None)
-        kw = {}
-        if fused is not None:
-            make_bufs, conf, mask = fused
-            kw = dict(nms_bufs=make_bufs(xb[0].shape[0], sum(f.shape[2] * f.shape[3] for f in xb)), conf_thres=conf, classes_mask=mask)
+        kw = self._nms_kwargs(xb[0].shape[0], sum(f.shape[2] * f.shape[3] for f in xb))
         if self.fuse_tail and H.head_decode_supported(self.cv2[0][-1].in_channels, self.cv3[0][-1].in_channels, self.nc, self.reg_max, td):
             pb, pc = self._packed_tail(td, xb[0].device)
             y = H.detect_head_decode(xb, xc, pb, pc, [float(s) for s in self.stride], self.nc, self.reg_max, **kw)
@@ -259,12 +237,7 @@ class Detect(nn.Module):
             feats.append(buf)
         if self.training:
             return feats
-        fused = getattr(self, "fused_nms", None)  # set by the predictor: (NmsBuffers factory, conf, classes mask)
-        kw = {}
-        if fused is not None:
-            make_bufs, conf, mask = fused
-            A = sum(f.shape[2] * f.shape[3] for f in feats)
-            kw = dict(nms_bufs=make_bufs(feats[0].shape[0], A), conf_thres=conf, classes_mask=mask)
+        kw = self._nms_kwargs(feats[0].shape[0], sum(f.shape[2] * f.shape[3] for f in feats))
         y = H.detect_decode(feats, [float(s) for s in self.stride], self.nc, self.reg_max, **kw)
         return y if self.export else (y, feats)
 
@@ -275,7 +248,7 @@ class Detect(nn.Module):
             b[-1].bias.data[: self.nc] = math.log(5 / self.nc / (640 / float(s)) ** 2)
             a[-1].invalidate_packed()
             b[-1].invalidate_packed()
-        self._tail_cache = None
+        self.invalidate_packed()
 
 
 class Segment(Detect):

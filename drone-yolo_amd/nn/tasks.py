@@ -36,6 +36,7 @@ from ..utils.torch_utils import initialize_weights
 from .modules import SPPF, Bottleneck, C2f, Concat, Conv, Detect, DWConv, Proto, RepVGGBlock, Segment, Upsample
 from .modules.block import DFL
 from .modules.conv import PlainConv2d
+from .modules.packs import PACKED, PackOwner, packed
 
 CFG_DIR = Path(__file__).resolve().parents[1] / "cfg"
 
@@ -140,7 +141,7 @@ def _layer_stride(m: nn.Module) -> float:
     return 1.0
 
 
-class BaseModel(nn.Module):
+class BaseModel(PackOwner, nn.Module):
     """Sequential executor with a skip list — reference tasks.py:95-295."""
 
     def forward(self, x, *args, **kwargs):
@@ -374,25 +375,12 @@ class BaseModel(nn.Module):
         n, c, h, w = image.shape
         if not H.stem2_fused_supported(c, 32, c1, h, w, dtype):
             return None
-        srcs = [m0.conv.weight, m0.bn.weight, m0.bn.bias, m0.bn.running_mean, m0.bn.running_var] + list(m1.parameters()) + list(m1.buffers())
-        key = (dtype, str(image.device), H.scaled_domain(), tuple((t.data_ptr(), t._version) for t in srcs))
-        cache = self.__dict__.get("_stem2_cache")
-        if cache is None or cache[0] != key:
-            from .modules.conv import fold_conv_bn
-
-            w0, b0 = fold_conv_bn(m0.conv.weight, m0.conv.bias, m0.bn)
-            w1, b1 = (m1.rbr_reparam.weight, m1.rbr_reparam.bias) if hasattr(m1, "rbr_reparam") else m1.get_equivalent_kernel_bias()
-            w0, b0, a0 = H.domain_fold(w0, b0, True, raw_input=True)  # the image is raw; layer 1 reads layer 0's (scaled) output
-            w1, b1, a1 = H.domain_fold(w1, b1, True)
-            cache = (key, H.PackedStem2(w0, b0, a0, w1, b1, a1, dtype, image.device))
-            self.__dict__["_stem2_cache"] = cache
-        return cache[1]
+        # the image is raw whatever layer 0's ``_raw_input`` says; layer 1 reads layer 0's (scaled) output
+        return packed(self, "stem2", (m0, m1), dtype, image.device, lambda: H.PackedStem2(*m0._folded(raw_input=True), *m1._folded(), dtype, image.device))
 
     def _out_hw(self, i: int, h: int, w: int):
         s = self._cum_stride[i]
         return int(round(h / s)), int(round(w / s))
-
-    _PACK_CACHES = ("_packed", "_block_cache", "_tail_cache", "_front_cache", "_first_cache", "_stem2_cache")
 
     def drop_packed(self) -> None:
         """Forget every packed (BatchNorm-folded, device-layout) copy of the weights and advance the weights epoch that
@@ -400,8 +388,7 @@ class BaseModel(nn.Module):
         self.__dict__["_weights_epoch"] = self.__dict__.get("_weights_epoch", 0) + 1
         self.__dict__.pop("_sig_tensors", None)
         for m in self.modules():
-            for k in self._PACK_CACHES:
-                m.__dict__.pop(k, None)
+            m.__dict__.pop(PACKED, None)
 
     def weights_signature(self):
         """Changes whenever the weights a recorded pass baked in may have changed: storage identity and torch's in-place

@@ -97,13 +97,13 @@ def test_tail_matches_cpu_chain(shape, form, dtype, device):
     assert bool((wide[:, :16] == SENTINEL).all()) and bool((wide[:, 144:] == SENTINEL).all()), "the launch wrote outside its channel slice"
 
 
-def make_block(n, shortcut, seed):
+def make_block(n, shortcut, seed, c=128, wstd=0.08):
     from drone_yolo_amd.nn.modules import C2f
 
     g = torch.Generator().manual_seed(seed)
-    blk = C2f(128, 128, n=n, shortcut=shortcut).eval()
+    blk = C2f(c, c, n=n, shortcut=shortcut).eval()
     for prm in blk.parameters():
-        prm.data = torch.randn(prm.shape, generator=g) * (0.08 if prm.dim() > 1 else 0.3) + (1.0 if prm.dim() == 1 else 0.0)
+        prm.data = torch.randn(prm.shape, generator=g) * (wstd if prm.dim() > 1 else 0.3) + (1.0 if prm.dim() == 1 else 0.0)
     for m in blk.modules():
         if isinstance(m, torch.nn.BatchNorm2d):
             m.running_mean.copy_(torch.randn(m.running_mean.shape, generator=g) * 0.1)
@@ -161,3 +161,35 @@ def test_five_runs_beside_another_stream_are_bit_identical(form, dtype, device):
     check_close(back(outs[0]), case[4], dtype, f"c2f tail n={n} shortcut={shortcut} 3x33x31 beside a second stream")
     for k in range(1, 5):
         assert torch.equal(outs[k].view(torch.int16), outs[0].view(torch.int16)), f"run {k} differs from run 0"
+
+
+@pytest.mark.parametrize("c,shortcut,shape,kernel", [(64, True, (3, 16, 16), "c2f_fused_kernel"), (128, False, (2, 40, 36), KERNEL)], ids=["block-64", "tail-128"])
+def test_fused_packs_follow_a_training_phase_of_the_block_alone(c, shortcut, shape, kernel, device):
+    """A C2f used on its own: an eval pass fills the fused slot (dy_c2f_fused at 64 channels, dy_c2f_tail_fused at 128), one training-mode
+    forward moves the BatchNorm running statistics through raw pointers (torch's version counters see nothing), and back in eval mode the
+    fused launch must run on the NEW statistics, as the layer-by-layer path does: the block's own train() drops its packs.  float16, the
+    smallest shapes of test_c2f_fused_block_matches_cpu_chain_and_layerwise / test_block_fused_tail_agrees_with_layer_by_layer, their bound."""
+    dtype = torch.float16
+    blk, g = make_block(1, shortcut, shape[1], c=c, wstd=0.12 if c == 64 else 0.08)
+    b, h, w = shape
+    x = quantize(torch.randn(b, c, h, w, generator=g) + 1.0, dtype)  # per-channel mean well away from the running means (~ 0.1)
+    blk = blk.to(device)
+    xd = nhwc(x, dtype, device)
+    blk.fuse_block = True
+    blk(xd)
+    assert H.last_kernel_name().startswith(kernel), H.last_kernel_name()
+    bns = [blk.cv1.bn, blk.m[0].cv1.bn, blk.m[0].cv2.bn, blk.cv2.bn]
+    start = [bn.running_mean.clone() for bn in bns]
+    blk.train()
+    blk(xd)
+    blk.eval()
+    torch.cuda.synchronize()
+    for bn, m0 in zip(bns, start):
+        assert not torch.equal(bn.running_mean, m0), "the training forward left a running mean where it was"
+    got = blk(xd)
+    torch.cuda.synchronize()
+    assert H.last_kernel_name().startswith(kernel), H.last_kernel_name()
+    blk.fuse_block = False
+    layerwise = blk(xd)
+    torch.cuda.synchronize()
+    check_close(back(got), back(layerwise), dtype, f"C2f({c}, {c}, n=1, shortcut={shortcut}) {shape} after train() / eval(): fuse_block on vs off", extra=3.0)
