@@ -17,6 +17,7 @@ DY_BF16, DY_F16, DY_F32, DY_FP8, DY_F16X2 = 0, 1, 2, 3, 4
 DY_ACT_NONE, DY_ACT_SILU, DY_ACT_SILU_L2E = 0, 1, 2
 DY_MAX_LEVELS = 8
 DY_WLAYOUT_ROWS, DY_WLAYOUT_HALO3X3, DY_WLAYOUT_FRAG1X1 = 0, 1, 2
+DY_ROUTE_ROWS = 0  # dy_conv3x3_halo_route: the call needs the layer's DY_WLAYOUT_ROWS pack
 
 _vp, _i32, _f32, _i64 = C.c_void_p, C.c_int32, C.c_float, C.c_int64
 
@@ -274,6 +275,8 @@ SIGNATURES = {
     "dy_conv_cout_pad": (_i32, [_i32]),
     "dy_conv2d_nhwc": (_i32, [C.POINTER(ConvDesc), _vp]),
     "dy_conv_stats_written": (_i32, []),
+    "dy_conv3x3_halo_route": (_i32, [_i32, _i32, _i32, _i32, _i64, _i64, _i32, C.c_uint64, _i32, _i32, _i32]),
+    "dy_conv1x1_stream_supported": (_i32, [_i32, _i32, _i32, _i32]),
     "dy_c2f_fused_supported": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "dy_c2f_fused": (_i32, [C.POINTER(C2fDesc), _vp]),
     "dy_c2f_tail_fused_supported": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),

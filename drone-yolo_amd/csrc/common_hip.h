@@ -270,4 +270,13 @@ static inline int dtype_size_no_fp8(int dtype) { return (dtype == DY_FP8 || dtyp
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// Host setup of the row-block statistics epilogue (conv_gemm_glds.hip, conv_gemm_fk.hip; dy_conv_desc.bn_stats) before the launch: row block i
+// fills slot 1 + i, or -- more row blocks than slots -- ADDS into slot 1 + i % kStatSlots, which are zeroed here; reports the slot count.
+template <typename Args>
+static inline void stats_slots_setup(Args& p, int tilesM, hipStream_t st) {
+  p.stats_atomic = tilesM > kStatSlots ? 1 : 0;
+  if (p.stats_atomic) zero_async(p.stats, (size_t)(1 + kStatSlots) * 2 * p.Cout * sizeof(double), st);
+  note_stats(p.stats_atomic ? kStatSlots : tilesM);
+}
+
 }  // namespace DY_NS

@@ -250,14 +250,30 @@ __global__ __launch_bounds__(512) void conv1x1_stream_kernel(const Conv1Args p) 
 
 constexpr int kLds1 = 160 * 1024;
 
+// ---- what is built: ONE description for the launch below and for dy_conv1x1_stream_supported ----
+constexpr int kStreamNkg[6] = {2, 3, 4, 6, 8, 12};  // K groups (four 16-byte chunks each) the kernel is instantiated for
+constexpr bool stream_built(int nkg) {
+  for (int n : kStreamNkg)
+    if (n == nkg) return true;
+  return false;
+}
+constexpr int stream_mf(int nkg) { return nkg <= 2 ? 2 : 1; }  // 16-pixel fragments per wave: fatter variants would spill (a_cur + a_nxt + acc + b fragments)
+// 16-cout fragments per tile (0: not built).  f32_from_16: fp32 output of 16-bit storage, the Detect heads: 64 -> 64 box bins, 64 -> nc class logits
+constexpr int stream_nf(int nkg, int cout, bool f32_from_16) {
+  if (f32_from_16) return (nkg != 2 || cout > 64) ? 0 : (cout <= 16 ? 1 : 4);
+  if (cout <= 16) return nkg == 2 ? 1 : 0;
+  return cout <= 64 ? 4 : 8;
+}
+// weights of all K groups + bias + the eight waves' output staging
+constexpr int stream_lds_bytes(int nkg, int mf, int nf, int osz) { return nkg * nf * 1024 + nf * 16 * 4 + 8 * mf * 16 * (nf * 16 * osz + 16); }
+
 template <typename T, int NKG, int MF, int NF, bool OUTF32>
 static int launch_1x1(const Conv1Args& a, hipStream_t st) {
   Conv1Args p = a;
   constexpr int BN = NF * 16;
   p.tilesN = (p.Cout + BN - 1) / BN;
   p.nMT = (p.M + MF * 16 - 1) / (MF * 16);
-  const int osz = OUTF32 ? 4 : (int)sizeof(T);
-  const int smem = NKG * NF * 1024 + BN * 4 + 8 * MF * 16 * (BN * osz + 16);
+  constexpr int smem = stream_lds_bytes(NKG, MF, NF, OUTF32 ? 4 : (int)sizeof(T));
   DY_REQUIRE(smem <= kLds1, DY_ERR_UNSUPPORTED, "dy_conv2d_nhwc: FRAG1X1 tile needs %d B of LDS", smem);
   const int per_cu = kLds1 / smem >= 2 ? 2 : 1;
   int groups = (256 * per_cu) / p.tilesN;
@@ -285,34 +301,31 @@ static int launch_1x1(const Conv1Args& a, hipStream_t st) {
 
 template <typename T, int NKG>
 static int launch_1x1_nkg(const Conv1Args& a, bool out_f32, hipStream_t st) {
-  constexpr int MF = NKG <= 2 ? 2 : 1;  // fatter variants would spill (a_cur + a_nxt + acc + b fragments)
-  if (out_f32 && sizeof(T) < 4) {
-    if constexpr (NKG == 2) {  // Detect heads: 64 -> 64 box bins, 64 -> nc class logits
-      if (a.Cout <= 16) return launch_1x1<T, 2, 2, 1, true>(a, st);
-      if (a.Cout <= 64) return launch_1x1<T, 2, 2, 4, true>(a, st);
-    }
-    set_error("dy_conv2d_nhwc: FRAG1X1 fp32-output variant not built for cin %d cout %d", a.Cin, a.Cout);
-    return DY_ERR_UNSUPPORTED;
+  constexpr int MF = stream_mf(NKG);
+  const bool f32o = out_f32 && sizeof(T) < 4;
+  const int nf = stream_nf(NKG, a.Cout, f32o);
+  if constexpr (NKG == 2) {
+    if (f32o && nf == 1) return launch_1x1<T, 2, 2, 1, true>(a, st);
+    if (f32o && nf == 4) return launch_1x1<T, 2, 2, 4, true>(a, st);
+    if (nf == 1) return launch_1x1<T, 2, 2, 1, false>(a, st);
   }
-  if (a.Cout <= 16) {
-    if constexpr (NKG == 2) return launch_1x1<T, 2, 2, 1, false>(a, st);
-    set_error("dy_conv2d_nhwc: FRAG1X1 cout <= 16 only built for cin <= 2 k-groups");
-    return DY_ERR_UNSUPPORTED;
-  }
-  if (a.Cout <= 64) return launch_1x1<T, NKG, MF, 4, false>(a, st);
-  return launch_1x1<T, NKG, MF, 8, false>(a, st);
+  if (!f32o && nf == 4) return launch_1x1<T, NKG, MF, 4, false>(a, st);
+  if (!f32o && nf == 8) return launch_1x1<T, NKG, MF, 8, false>(a, st);
+  set_error("dy_conv2d_nhwc: FRAG1X1 not built for cin %d cout %d%s (dy_conv1x1_stream_supported tells); pack with DY_WLAYOUT_ROWS", a.Cin, a.Cout,
+            f32o ? " with fp32 output" : "");
+  return DY_ERR_UNSUPPORTED;
 }
 
 template <typename T>
 static int launch_1x1_dtype(const Conv1Args& a, bool out_f32, hipStream_t st) {
   const int nkg = (a.Cin + 4 * Elem<T>::EPC - 1) / (4 * Elem<T>::EPC);
-  switch (nkg) {
-    case 2: return launch_1x1_nkg<T, 2>(a, out_f32, st);
-    case 3: return launch_1x1_nkg<T, 3>(a, out_f32, st);
-    case 4: return launch_1x1_nkg<T, 4>(a, out_f32, st);
-    case 6: return launch_1x1_nkg<T, 6>(a, out_f32, st);
-    case 8: return launch_1x1_nkg<T, 8>(a, out_f32, st);
-    case 12: return launch_1x1_nkg<T, 12>(a, out_f32, st);
+  switch (stream_built(nkg) ? nkg : 0) {
+    case kStreamNkg[0]: return launch_1x1_nkg<T, kStreamNkg[0]>(a, out_f32, st);
+    case kStreamNkg[1]: return launch_1x1_nkg<T, kStreamNkg[1]>(a, out_f32, st);
+    case kStreamNkg[2]: return launch_1x1_nkg<T, kStreamNkg[2]>(a, out_f32, st);
+    case kStreamNkg[3]: return launch_1x1_nkg<T, kStreamNkg[3]>(a, out_f32, st);
+    case kStreamNkg[4]: return launch_1x1_nkg<T, kStreamNkg[4]>(a, out_f32, st);
+    case kStreamNkg[5]: return launch_1x1_nkg<T, kStreamNkg[5]>(a, out_f32, st);
     default:
       set_error("dy_conv2d_nhwc: FRAG1X1 not built for %d k-groups (cin %d); pack with DY_WLAYOUT_ROWS", nkg, a.Cin);
       return DY_ERR_UNSUPPORTED;
@@ -368,3 +381,14 @@ int conv1x1_stream_dispatch(const dy_conv_desc* d, hipStream_t st) {
 }
 
 }  // namespace DY_NS
+
+#ifndef DYOLO_L2E_BUILD
+extern "C" int32_t dy_conv1x1_stream_supported(int32_t cin, int32_t cout, int32_t dtype, int32_t out_f32) {
+  using namespace dy;
+  const int es = dtype_size_no_fp8(dtype);
+  if (es == 0 || cin <= 0 || cout <= 0 || cin % (16 / es)) return 0;
+  const int nkg = (cin + 4 * (16 / es) - 1) / (4 * (16 / es));
+  const int nf = stream_built(nkg) ? stream_nf(nkg, cout, out_f32 && es < 4) : 0;
+  return nf != 0 && stream_lds_bytes(nkg, stream_mf(nkg), nf, (out_f32 || es == 4) ? 4 : es) <= kLds1;
+}
+#endif

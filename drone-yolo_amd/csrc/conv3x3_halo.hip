@@ -650,7 +650,8 @@ static int launch_halo_dtype(const Conv3Args& a, int batch, int stride, hipStrea
   return launch_halo<T, 2, 1, 2, OUTF32>(a, batch, st);
 }
 
-int conv3x3_hreg_try(const dy_conv_desc* d, hipStream_t st);  // conv3x3_hreg.hip: weights in registers, four workgroups per CU
+int conv3x3_hreg_launch(const dy_conv_desc* d, hipStream_t st);     // conv3x3_hreg.hip: weights in registers, 64 / 128 input channels
+int conv3x3_hreg_s2_launch(const dy_conv_desc* d, hipStream_t st);  // conv3x3_hreg.hip: the 64-channel stride-2 layers
 
 // Entry used by dy_conv2d_nhwc when d->w_layout == DY_WLAYOUT_HALO3X3.
 int conv3x3_halo_dispatch(const dy_conv_desc* d, hipStream_t st) {
@@ -663,13 +664,14 @@ int conv3x3_halo_dispatch(const dy_conv_desc* d, hipStream_t st) {
              "dy_conv2d_nhwc: views must be 16-byte aligned");
   DY_REQUIRE((d->ld_y * (d->out_f32 ? 4 : es)) % 16 == 0, DY_ERR_INVALID_ARG, "dy_conv2d_nhwc: output pitch must be a multiple of 16 bytes");
   DY_REQUIRE(!d->residual || (aligned16(d->residual) && d->ld_res % 4 == 0), DY_ERR_INVALID_ARG, "dy_conv2d_nhwc: residual view misaligned");
-  DY_REQUIRE((long long)d->batch * d->h * d->w_in * d->ld_x * es < (1ll << 32) - 64, DY_ERR_UNSUPPORTED, "dy_conv2d_nhwc: input view exceeds 4 GiB (buffer descriptor range)");
-  {
-    const int rv = conv3x3_hreg_try(d, st);  // cin 32 / 64, cout % 64 == 0, 16-bit; stride 2 with cin 64 (r03)
-    if (rv <= 0) return rv;
-  }
-  DY_REQUIRE(!(d->stride == 2 && d->cin == 64 && d->cout > 32), DY_ERR_UNSUPPORTED,
-             "dy_conv2d_nhwc: a stride-2 64-channel layer in DY_WLAYOUT_HALO3X3 runs on conv3x3_hreg_s2 only (16-bit storage, no residual, views below 2 GiB)");
+  const long long xb = (long long)d->batch * d->h * d->w_in * d->ld_x * es, yb = (long long)d->batch * d->ho * d->wo * d->ld_y * (d->out_f32 ? 4 : es);
+  const int route = dy_conv3x3_halo_route(d->cin, d->cout, d->stride, d->dtype, xb, yb, d->ld_y, reinterpret_cast<uintptr_t>(d->y), d->residual != nullptr,
+                                          d->out_f32, d->x2 || d->up2x);
+  DY_REQUIRE(route != DY_ROUTE_ROWS, DY_ERR_UNSUPPORTED,
+             "dy_conv2d_nhwc: the kernels behind DY_WLAYOUT_HALO3X3 do not take this call (dy_conv3x3_halo_route tells: a gathered source, an input view "
+             "beyond 4 GiB, a call form conv3x3_hreg declines on the layers packed for it): run it on the layer's DY_WLAYOUT_ROWS pack");
+  if (route == DY_ROUTE_HREG) return conv3x3_hreg_launch(d, st);
+  if (route == DY_ROUTE_HREG_S2) return conv3x3_hreg_s2_launch(d, st);
   Conv3Args a{};
   a.x = d->x;
   a.w = d->w;
@@ -688,9 +690,8 @@ int conv3x3_halo_dispatch(const dy_conv_desc* d, hipStream_t st) {
   a.act = d->act;
   a.stats = (d->out_f32 || d->y_dtype1 || d->bnb_z) ? nullptr : d->bn_stats;  // (bnb_z: backward sums, conv3x3_hreg only)
   a.nChunks = (d->cin + 4 * epc - 1) / (4 * epc);
-  a.x_bytes = (unsigned)((long long)d->batch * d->h * d->w_in * d->ld_x * es);
+  a.x_bytes = (unsigned)xb;
   {
-    const long long yb = (long long)d->batch * d->ho * d->wo * d->ld_y * (d->out_f32 ? 4 : es);
     a.y_bytes = yb < (1ll << 32) - 64 ? (unsigned)yb : 0u;  // 0: view too large for a buffer descriptor -> PIPE variant not used
     const long long rb = d->residual ? (long long)d->batch * d->ho * d->wo * d->ld_res * es : 0;
     a.r_bytes = rb < (1ll << 32) - 64 ? (unsigned)rb : 0u;
@@ -714,3 +715,30 @@ int conv3x3_halo_dispatch(const dy_conv_desc* d, hipStream_t st) {
 }
 
 }  // namespace DY_NS
+
+#ifndef DYOLO_L2E_BUILD
+// THE routing rule of a call on a DY_WLAYOUT_HALO3X3 pack (include/dyolo.h): conv3x3_halo_dispatch switches on it, PackedConv.for_call
+// (hip_ops.py) asks it.  Host arithmetic only.
+extern "C" int32_t dy_conv3x3_halo_route(int32_t cin, int32_t cout, int32_t stride, int32_t dtype, int64_t x_bytes, int64_t y_bytes, int32_t ld_y,
+                                         uint64_t y_addr, int32_t residual, int32_t out_f32, int32_t gathered) {
+  // a second source / upsampled or dilated gather is built behind DY_WLAYOUT_ROWS only; a buffer descriptor addresses 4 GiB
+  if (gathered || x_bytes >= (1ll << 32) - 64) return DY_ROUTE_ROWS;
+  static const int off = dy::dy_ablate("DYOLO_NO_HREG");
+  // the register-weight kernels (conv3x3_hreg.hip): 16-bit storage, whole 64-cout tiles ...
+  const bool reg_shape = !off && (dtype == DY_BF16 || dtype == DY_F16) && cout % 64 == 0 && cout <= 256;
+  // ... no residual (measured slower than the halo kernel's, conv3x3_hreg.hip), 16-byte output rows, 32-bit element offsets into x
+  const bool reg_call = !residual && !out_f32 && ld_y % 8 == 0 && y_addr % 16 == 0 && x_bytes < (1ll << 31) && y_bytes < (1ll << 32) - 64;
+  // stride 2 with 64 input channels: the weight set does not fit beside the halo kernel's stride-2 tiles, conv3x3_hreg_s2 or nothing
+  if (stride == 2 && cin == 64 && cout > 32) return reg_shape && reg_call ? DY_ROUTE_HREG_S2 : DY_ROUTE_ROWS;
+  // 128 input channels are packed here for conv3x3_hreg's four-chunk form: a call form it declines runs on the virtual-flat GEMM
+  if (stride == 1 && cin == 128 && !reg_call) return DY_ROUTE_ROWS;
+  // measured (B = 256, alternating A/B against conv3x3_halo, tools/bench_conv.py): 64->64 @160 650 -> 598 us, @80 150 -> 141, @40 55 -> 42,
+  // @20 29 -> 18, 64->128 @80 285 -> 268; cin 32 (one chunk per tile: an epilogue every item) 205-250 -> 227-252: no gain, stays on
+  // the halo kernel; with a Bottleneck residual (halo -> conv3x3_hreg): 8-byte gathers 210 -> 237 @80, 16-byte pieces per row pair 187 -> 203:
+  // stays there too (r04, measured again in the model at B = 256 with the residual form at two workgroups per CU, no spills, and the loads
+  // requested a whole item earlier: 64->64 @80 178 -> 230 us, 128->128 @40 177 -> 240 us -- a wave's residual read is 64 16-byte pieces of 32
+  // pixel rows, and every in-order vmcnt wait behind it pays for that; the latency was not the cost)
+  if (stride == 1 && (cin == 64 || cin == 128) && reg_shape && reg_call) return DY_ROUTE_HREG;
+  return DY_ROUTE_HALO;
+}
+#endif

@@ -312,7 +312,7 @@ static int launch_hreg(const HregArgs& a, hipStream_t st) {
     return check_launch("conv3x3_hreg_kernel<bnb>");
   }
 #endif
-  if (p.stats) {  // conv3x3_hreg_try admits it without a residual only
+  if (p.stats) {  // (no residual here: dy_conv3x3_halo_route)
     if (nch == 1) hipLaunchKernelGGL((conv3x3_hreg_kernel<T, 1, false, true>), dim3((unsigned)grid), dim3(256), 0, st, p);
     else if (nch == 2) hipLaunchKernelGGL((conv3x3_hreg_kernel<T, 2, false, true>), dim3((unsigned)grid), dim3(256), 0, st, p);
     else hipLaunchKernelGGL((conv3x3_hreg_kernel<T, 4, false, true>), dim3((unsigned)grid), dim3(256), 0, st, p);
@@ -326,7 +326,7 @@ static int launch_hreg(const HregArgs& a, hipStream_t st) {
     if (res) hipLaunchKernelGGL((conv3x3_hreg_kernel<T, 2, true>), dim3((unsigned)grid), dim3(256), 0, st, p);
     else hipLaunchKernelGGL((conv3x3_hreg_kernel<T, 2, false>), dim3((unsigned)grid), dim3(256), 0, st, p);
   } else {
-    hipLaunchKernelGGL((conv3x3_hreg_kernel<T, 4, false>), dim3((unsigned)grid), dim3(256), 0, st, p);  // (no residual: conv3x3_hreg_try)
+    hipLaunchKernelGGL((conv3x3_hreg_kernel<T, 4, false>), dim3((unsigned)grid), dim3(256), 0, st, p);  // (no residual: dy_conv3x3_halo_route)
   }
   return check_launch("conv3x3_hreg_kernel");
 }
@@ -346,9 +346,9 @@ static int launch_hreg_s2(const HregArgs& a, hipStream_t st) {
   return check_launch("conv3x3_hreg_s2_kernel");
 }
 
-// the fields both strides fill alike: pointers, dims, the geometry's tiles, byte sizes (xb / yb: the caller has checked them)
+// the fields both strides fill alike: pointers, dims, the geometry's tiles, byte sizes of the 16-bit views (dy_conv3x3_halo_route has checked them)
 template <typename Geom>
-static HregArgs hreg_args(const dy_conv_desc* d, long long xb, long long yb) {
+static HregArgs hreg_args(const dy_conv_desc* d) {
   HregArgs a{};
   a.x = d->x, a.w = d->w, a.bias = d->bias, a.y = d->y;
   a.N = d->batch, a.H = d->h, a.W = d->w_in, a.Cin = d->cin, a.ldx = d->ld_x, a.Cout = d->cout, a.ldy = d->ld_y, a.act = d->act;
@@ -356,38 +356,20 @@ static HregArgs hreg_args(const dy_conv_desc* d, long long xb, long long yb) {
   a.tilesY = (d->ho + Geom::TH - 1) / Geom::TH;
   a.tilesN = d->cout / 64;
   a.nSpatial = d->batch * a.tilesY * a.tilesX;
-  a.x_bytes = (unsigned)xb, a.y_bytes = (unsigned)yb;
+  a.x_bytes = (unsigned)((long long)d->batch * d->h * d->w_in * d->ld_x * 2), a.y_bytes = (unsigned)((long long)d->batch * d->ho * d->wo * d->ld_y * 2);
   return a;
 }
 
-// Returns 1 when the shape is not one this kernel is built for (the caller then runs conv3x3_halo), else the launch status.
-int conv3x3_hreg_try(const dy_conv_desc* d, hipStream_t st) {
-  static const int off = dy_ablate("DYOLO_NO_HREG");
-  if (off) return 1;
-  if (!(d->dtype == DY_BF16 || d->dtype == DY_F16) || d->out_f32 || d->ksize != 3 || d->pad != 1 || d->groups > 1 || d->up2x || d->x2) return 1;
-  if (d->stride == 2) {  // the 64-channel downsampling layers (conv3x3_hreg_s2_kernel)
-    if (d->cin != 64 || d->cout % 64 != 0 || d->cout > 256 || d->residual) return 1;
-    const long long xb2 = (long long)d->batch * d->h * d->w_in * d->ld_x * 2, yb2 = (long long)d->batch * d->ho * d->wo * d->ld_y * 2;
-    if (xb2 >= (1ll << 31) || yb2 >= (1ll << 32) - 64 || d->ld_y % 8 || (reinterpret_cast<uintptr_t>(d->y) & 15)) return 1;
-    HregArgs a = hreg_args<HrS2>(d, xb2, yb2);
-    a.stats = (d->y_dtype1 || d->bnb_z) ? nullptr : d->bn_stats;
-    return d->dtype == DY_BF16 ? launch_hreg_s2<bf16_t>(a, st) : launch_hreg_s2<f16_t>(a, st);
-  }
-  if (d->stride != 1) return 1;
-  // measured (B = 256, alternating A/B against conv3x3_halo, tools/bench_conv.py): 64->64 @160 650 -> 598 us, @80 150 -> 141, @40 55 -> 42,
-  // @20 29 -> 18, 64->128 @80 285 -> 268; cin 32 (one chunk per tile: an epilogue every item) 205-250 -> 227-252: no gain, stays on
-  // the halo kernel; with a Bottleneck residual (halo -> this kernel): 8-byte gathers 210 -> 237 @80, 16-byte pieces per row pair 187 -> 203:
-  // stays there too (r04, measured again in the model at B = 256 with the residual form at two workgroups per CU, no spills, and the loads
-  // requested a whole item earlier: 64->64 @80 178 -> 230 us, 128->128 @40 177 -> 240 us -- a wave's residual read is 64 16-byte pieces of 32
-  // pixel rows, and every in-order vmcnt wait behind it pays for that; the latency was not the cost)
-  if ((d->cin != 64 && d->cin != 128) || d->cout % 64 != 0 || d->cout > 256 || d->residual) return 1;
-  if (d->ho != d->h || d->wo != d->w_in) return 1;
-  const long long xb = (long long)d->batch * d->h * d->w_in * d->ld_x * 2, yb = (long long)d->batch * d->ho * d->wo * d->ld_y * 2;
-  const long long rb = d->residual ? (long long)d->batch * d->ho * d->wo * d->ld_res * 2 : 0;
-  if (xb >= (1ll << 31) || yb >= (1ll << 32) - 64 || rb >= (1ll << 32) - 64) return 1;  // 32-bit element offsets / buffer descriptors
-  if (d->ld_y % 8 || (reinterpret_cast<uintptr_t>(d->y) & 15) || (d->residual && (d->ld_res % 8 || (reinterpret_cast<uintptr_t>(d->residual) & 15)))) return 1;  // 16-byte stores / residual loads
-  HregArgs a = hreg_args<HrS1>(d, xb, yb);
-  a.res = d->residual, a.ldres = d->ld_res, a.r_bytes = (unsigned)rb;
+// conv3x3_halo_dispatch's targets for the calls dy_conv3x3_halo_route (conv3x3_halo.hip) sends here: the route has checked the shape, the views'
+// alignment and the ranges of 32-bit element offsets / buffer descriptors.
+int conv3x3_hreg_s2_launch(const dy_conv_desc* d, hipStream_t st) {  // the 64-channel downsampling layers (conv3x3_hreg_s2_kernel)
+  HregArgs a = hreg_args<HrS2>(d);
+  a.stats = (d->y_dtype1 || d->bnb_z) ? nullptr : d->bn_stats;
+  return d->dtype == DY_BF16 ? launch_hreg_s2<bf16_t>(a, st) : launch_hreg_s2<f16_t>(a, st);
+}
+
+int conv3x3_hreg_launch(const dy_conv_desc* d, hipStream_t st) {
+  HregArgs a = hreg_args<HrS1>(d);
   a.stats = d->bn_stats;  // (at most 768 + 8 * tilesN - 1 workgroups: the slot count stays below the workspace's 1024)
   if (d->bnb_z) {
     const long long zb = (long long)d->batch * d->ho * d->wo * d->bnb_ld_z * 2;

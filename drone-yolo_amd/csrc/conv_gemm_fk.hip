@@ -614,10 +614,8 @@ static int launch_fk(const FkArgs& a, hipStream_t st, const char* name) {
 #ifndef DYOLO_L2E_BUILD  // (training convolutions carry no activation: they never come through the scaled-domain build)
     if constexpr (sizeof(T) == 2) {
       if (p.stats != nullptr) {
-        p.stats_atomic = tilesM > kStatSlots ? 1 : 0;  // (32 -> 64 1x1 stride 2 @320 at B = 64: 12,800 row blocks)
-        if (p.stats_atomic) zero_async(p.stats, (size_t)(1 + kStatSlots) * 2 * p.Cout * sizeof(double), st);
+        stats_slots_setup(p, tilesM, st);  // (atomic slots: 32 -> 64 1x1 stride 2 @320 at B = 64 has 12,800 row blocks)
         hipLaunchKernelGGL((conv_gemm_fk_kernel<T, OT, MFR, NFR, WM, WN, false, TABN, true>), dim3((unsigned)p.nblk), dim3(WM * WN * 64), 0, st, p);
-        note_stats(p.stats_atomic ? kStatSlots : tilesM);
         return check_launch(name);
       }
     }
@@ -627,7 +625,36 @@ static int launch_fk(const FkArgs& a, hipStream_t st, const char* name) {
   return check_launch(name);
 }
 
-// Tile choice: the cout tile that covers Cout with the fewest padded columns (ties: the wider one); 128 pixels.  Measured and dropped
+// What conv_gemm_fk_try and conv_gemm_fk_split fill alike, once their own preconditions hold (es: bytes per element of x and w).  False when
+// a view exceeds what a buffer descriptor addresses.  Left to the caller: wscale, stats, dbg (zero) and res_scale / out_scale (1).
+static bool fk_args(const dy_conv_desc* d, int es, FkArgs& a) {
+  a = FkArgs{};
+  a.x = d->x, a.x2 = d->x2 ? d->x2 : d->x, a.w = d->w, a.bias = d->bias, a.res = d->residual, a.y = d->y;
+  a.H = d->h, a.W = d->w_in, a.Cin = d->cin, a.ldx = d->ld_x, a.ldx2 = d->x2 ? d->ld_x2 : d->ld_x, a.split = d->x2 ? d->cin_split : d->cin;
+  a.HB = d->up2x ? d->h / 2 : d->h, a.WB = d->up2x ? d->w_in / 2 : d->w_in;
+  a.Ho = d->ho, a.Wo = d->wo, a.Cout = d->cout, a.ldy = d->ld_y, a.ldres = d->ld_res;
+  a.ks = d->ksize, a.stride = d->stride, a.pad = d->pad;
+  a.Kpad = d->k_pad, a.M = d->batch * d->ho * d->wo, a.HoWo = d->ho * d->wo, a.up2x = d->up2x;
+  a.act = d->act;
+  a.cout_pad = d->cout_pad;
+  const long long lim = (1ll << 32) - (1ll << 24);
+  const long long xb = (long long)d->batch * a.HB * a.WB * d->ld_x * es, x2b = d->x2 ? (long long)d->batch * d->h * d->w_in * d->ld_x2 * es : 0;
+  const long long wbytes = (long long)d->cout_pad * d->k_pad * es;
+  a.xb = (unsigned)xb, a.x2b = (unsigned)(d->x2 ? x2b : xb), a.wb = (unsigned)wbytes;
+  a.dCin = make_fastdiv((unsigned)d->cin);
+  a.res_scale = 1.f, a.out_scale = 1.f;
+  return xb < lim && x2b < lim && wbytes < lim;
+}
+
+// The cout tile that covers Cout with the fewest padded columns (ties: the wider one)
+static int fk_tile_width(int cout) {
+  int best = 160;
+  for (int c : {128, 80, 64})
+    if ((cout + c - 1) / c * c < (cout + best - 1) / best * best) best = c;
+  return best;
+}
+
+// Tile choice: fk_tile_width; 128 pixels.  Measured and dropped
 // (tools/fk_ab.sh, r04): 256-pixel tiles — 256 x 160 as sixteen waves of 32 x 80 (LDS-read bound in fp8: 14 ds_read_b128 per 10 MFMAs)
 // 3-12 % slower, 256 x 320 as sixteen waves of 64 x 80 (128-register cap: spills) 2x slower; two 128-pixel workgroups per CU that
 // cover for each other's barriers beat one big one; eight waves of 32 x 80 on the 128 x 160 tile, two waves of 64 x 80 on 128 x 80: +-2 %.
@@ -637,14 +664,7 @@ static int launch_fk(const FkArgs& a, hipStream_t st, const char* name) {
 template <typename T, typename OT>
 static int launch_fk_tiles(const FkArgs& a, hipStream_t st) {
   static const int force = dy_ablate("DYOLO_FK_BN");
-  const int cands[4] = {160, 128, 80, 64};
-  int best = 160;
-  long long bw = 1ll << 60;
-  for (int c : cands) {
-    const long long w = (long long)((a.Cout + c - 1) / c) * c;
-    if (w < bw) bw = w, best = c;
-  }
-  if (force) best = force;
+  int best = force ? force : fk_tile_width(a.Cout);
   const int nf = a.ks == 1 ? 0 : a.Kpad / (8 * Elem<T>::EPC) * 8;  // tap-table words
   if (nf > 768) return 1;
   if (best == 80 && nf > 128) best = 160;
@@ -686,30 +706,15 @@ int conv_gemm_fk_try(const dy_conv_desc* d, hipStream_t st) {
   if (d->x2 && (d->cin_split % bke || d->cin_split <= 0 || d->cin_split >= d->cin)) return 1;
   if (!aligned16(d->y) || (d->ld_y * oes) % 16 || (d->ld_x * es) % 16 || !aligned16(d->x)) return 1;
   if (d->residual && ((d->ld_res * es) % 16 || !aligned16(d->residual) || ydt != d->dtype)) return 1;
-  const int hb = d->up2x ? d->h / 2 : d->h, wb = d->up2x ? d->w_in / 2 : d->w_in;
-  const long long lim = (1ll << 32) - (1ll << 24);
-  const long long xb = (long long)d->batch * hb * wb * d->ld_x * es, x2b = d->x2 ? (long long)d->batch * d->h * d->w_in * d->ld_x2 * es : 0;
-  const long long wbytes = (long long)d->cout_pad * d->k_pad * es;
-  if (xb >= lim || x2b >= lim || wbytes >= lim) return 1;
+  FkArgs a;
+  if (!fk_args(d, es, a)) return 1;
   if (in8 && (!d->w_scale || !(d->act_scale > 0.f))) return 1;
   if (out8 && !(d->act_scale > 0.f)) return 1;
-
-  FkArgs a{};
-  a.x = d->x, a.x2 = d->x2 ? d->x2 : d->x, a.w = d->w, a.bias = d->bias, a.wscale = in8 ? d->w_scale : nullptr, a.res = d->residual, a.y = d->y;
-  a.H = d->h, a.W = d->w_in, a.Cin = d->cin, a.ldx = d->ld_x, a.ldx2 = d->x2 ? d->ld_x2 : d->ld_x, a.split = d->x2 ? d->cin_split : d->cin;
-  a.HB = hb, a.WB = wb;
-  a.Ho = d->ho, a.Wo = d->wo, a.Cout = d->cout, a.ldy = d->ld_y, a.ldres = d->ld_res;
-  a.ks = d->ksize, a.stride = d->stride, a.pad = d->pad;
-  a.Kpad = d->k_pad, a.M = d->batch * d->ho * d->wo, a.HoWo = d->ho * d->wo, a.up2x = d->up2x;
-  a.act = d->act;
-  a.cout_pad = d->cout_pad;
-  a.xb = (unsigned)xb, a.x2b = (unsigned)(d->x2 ? x2b : xb), a.wb = (unsigned)wbytes;
-  a.dCin = make_fastdiv((unsigned)d->cin);
   if (d->ksize == 3 && ((long long)(2 * d->w_in + 2) * d->ld_x + d->cin) * es >= (1ll << 28)) return 1;  // table words hold a 28-bit byte offset
   a.dbg = dy_ablate("DYOLO_FK_DBG");
   a.stats = (d->y_dtype1 || d->bnb_z) ? nullptr : d->bn_stats;
-  a.res_scale = in8 ? d->act_scale : 1.f;
-  a.out_scale = out8 ? 1.f / d->act_scale : 1.f;
+  if (in8) a.wscale = d->w_scale, a.res_scale = d->act_scale;
+  if (out8) a.out_scale = 1.f / d->act_scale;
   if (in8) return out8 ? launch_fk_tiles<fp8_t, fp8_t>(a, st) : launch_fk_tiles<fp8_t, f16_t>(a, st);
   if (d->dtype == DY_F16) return out8 ? launch_fk_tiles<f16_t, fp8_t>(a, st) : launch_fk_tiles<f16_t, f16_t>(a, st);
   return launch_fk_tiles<bf16_t, bf16_t>(a, st);
@@ -747,14 +752,7 @@ static int launch_fk_split_tiles(const FkArgs& a, hipStream_t st) {
   // half-empty 64-wide tile), and the tap table is sized by need (256 / 640 / 1536 words): 6 KB of table beside a 128 x 64 tile cost
   // the third workgroup of a CU (-15 %).  The x scale's 160 / 80 wide tiles keep the 16-bit kernel's shapes.
   const int words = a.ks == 1 ? 0 : a.Kpad / 32 * 8;
-  const int cands[4] = {160, 128, 80, 64};
-  int best = 160;
-  long long bw = 1ll << 60;
-  for (int c : cands) {
-    const long long w = (long long)((a.Cout + c - 1) / c) * c;
-    if (w < bw) bw = w, best = c;
-  }
-  if (a.Cout <= 32) best = 32;
+  const int best = a.Cout <= 32 ? 32 : fk_tile_width(a.Cout);
 #define DY_SPLIT_TAB(MFR, NFR, WM, WN, NAME)                                                   \
   return words <= 256 ? launch_fk<f16x2_t, OT, MFR, NFR, WM, WN, 256>(a, st, NAME)              \
          : words <= 640 ? launch_fk<f16x2_t, OT, MFR, NFR, WM, WN, 640>(a, st, NAME)            \
@@ -785,25 +783,11 @@ int conv_gemm_fk_split(const dy_conv_desc* d, hipStream_t st) {
   DY_REQUIRE(aligned16(d->y) && d->ld_y % epc == 0 && d->ld_x % epc == 0 && aligned16(d->x) && (!d->x2 || (aligned16(d->x2) && d->ld_x2 % epc == 0)), DY_ERR_INVALID_ARG,
              "dy_conv2d_nhwc: DY_F16X2 views must be 16-byte aligned");
   DY_REQUIRE(!d->residual || (!d->out_f32 && d->ld_res % epc == 0 && aligned16(d->residual)), DY_ERR_INVALID_ARG, "dy_conv2d_nhwc: DY_F16X2 residual view");
-  const int hb = d->up2x ? d->h / 2 : d->h, wb = d->up2x ? d->w_in / 2 : d->w_in;
-  const long long lim = (1ll << 32) - (1ll << 24);
-  const long long xb = (long long)d->batch * hb * wb * d->ld_x * es, x2b = d->x2 ? (long long)d->batch * d->h * d->w_in * d->ld_x2 * es : 0;
-  const long long wbytes = (long long)d->cout_pad * d->k_pad * es;
-  DY_REQUIRE(xb < lim && x2b < lim && wbytes < lim, DY_ERR_UNSUPPORTED, "dy_conv2d_nhwc: DY_F16X2 view beyond the 4 GiB a buffer descriptor addresses");
+  FkArgs a;
+  DY_REQUIRE(fk_args(d, es, a), DY_ERR_UNSUPPORTED, "dy_conv2d_nhwc: DY_F16X2 view beyond the 4 GiB a buffer descriptor addresses");
   DY_REQUIRE(d->ksize == 1 || (d->k_pad / bke * 8 <= 1536 && ((long long)(2 * d->w_in + 2) * d->ld_x + d->cin) * es < (1ll << 28)), DY_ERR_UNSUPPORTED,
              "dy_conv2d_nhwc: DY_F16X2 3x3 tap table (cin <= 680)");
-  FkArgs a{};
-  a.x = d->x, a.x2 = d->x2 ? d->x2 : d->x, a.w = d->w, a.bias = d->bias, a.wscale = d->w_scale, a.res = d->residual, a.y = d->y;
-  a.H = d->h, a.W = d->w_in, a.Cin = d->cin, a.ldx = d->ld_x, a.ldx2 = d->x2 ? d->ld_x2 : d->ld_x, a.split = d->x2 ? d->cin_split : d->cin;
-  a.HB = hb, a.WB = wb;
-  a.Ho = d->ho, a.Wo = d->wo, a.Cout = d->cout, a.ldy = d->ld_y, a.ldres = d->ld_res;
-  a.ks = d->ksize, a.stride = d->stride, a.pad = d->pad;
-  a.Kpad = d->k_pad, a.M = d->batch * d->ho * d->wo, a.HoWo = d->ho * d->wo, a.up2x = d->up2x;
-  a.act = d->act;
-  a.cout_pad = d->cout_pad;
-  a.xb = (unsigned)xb, a.x2b = (unsigned)(d->x2 ? x2b : xb), a.wb = (unsigned)wbytes;
-  a.dCin = make_fastdiv((unsigned)d->cin);
-  a.dbg = 0, a.stats = nullptr, a.res_scale = 1.f, a.out_scale = 1.f;
+  a.wscale = d->w_scale;
   return d->out_f32 ? launch_fk_split_tiles<float>(a, st) : launch_fk_split_tiles<f16x2_t>(a, st);
 }
 #else

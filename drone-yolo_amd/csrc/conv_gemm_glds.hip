@@ -632,11 +632,9 @@ static int launch_glds(const ConvArgs& a, hipStream_t st) {
       const int tilesM = (p.M + BM - 1) / BM;
       p.tilesN = (p.Cout + BN - 1) / BN;
       p.nblk = tilesM * p.tilesN;
-      p.stats_atomic = tilesM > kStatSlots ? 1 : 0;  // (64 -> 128 1x1 stride 2 @160 at B = 64: 3,200 row blocks)
-      if (p.stats_atomic) zero_async(p.stats, (size_t)(1 + kStatSlots) * 2 * p.Cout * sizeof(double), st);
+      stats_slots_setup(p, tilesM, st);  // (atomic slots: 64 -> 128 1x1 stride 2 @160 at B = 64 has 3,200 row blocks)
       auto kern = conv_gemm_glds_kernel<T, BM, BN, STAGES, WN, true>;
       hipLaunchKernelGGL(kern, dim3((unsigned)p.nblk), dim3(BM * WN), 0, st, p);
-      note_stats(p.stats_atomic ? kStatSlots : tilesM);
       return check_launch("conv_gemm_glds_kernel<stats>");
     }
   }

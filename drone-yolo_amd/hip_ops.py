@@ -428,18 +428,9 @@ def conv_pack_plan(cout: int, cin: int, k: int, stride: int, pad: int, groups: i
         kc, bn = 4 * e, (64 if cout > 32 else 32)
         nt, nch = -(-cout // bn), -(-cin // kc)
         return ConvPackPlan(_lib.DY_WLAYOUT_HALO3X3, cin, 0, cout_pad, 1, e, kc, bn, nt, nch, nt * nch * 9 * (bn // 16) * 64 * e)
-    frag = _frag1x1_plan(cout, cin, dtype, cout_pad)
-    e, bn, nkg = frag.e, frag.bn, frag.nch
-    frag_ok = nkg in (2, 3, 4, 6, 8, 12) and (cout > 16 or nkg == 2) and cin % e == 0
-    if for_out_f32 and dtype != torch.float32:
-        frag_ok = frag_ok and nkg == 2 and cout <= 64
-    if frag_ok:  # the streaming kernel's LDS footprint (conv1x1_stream.hip::launch_1x1) must fit 160 KB
-        osz = 4 if (for_out_f32 or dtype == torch.float32) else 2
-        smem = nkg * (bn // 16) * 1024 + bn * 4 + 8 * (2 if nkg <= 2 else 1) * 16 * (bn * osz + 16)
-        frag_ok = smem <= 160 * 1024
-    if (halo is None or halo) and groups == 1 and k == 1 and stride == 1 and pad == 0 and frag_ok:
+    if (halo is None or halo) and groups == 1 and k == 1 and stride == 1 and pad == 0 and L.dy_conv1x1_stream_supported(cin, cout, dy_dtype(dtype), for_out_f32):
         # streaming 1x1 kernel: fragment-ordered weights, single tap (include/dyolo.h, DY_WLAYOUT_FRAG1X1)
-        return frag
+        return _frag1x1_plan(cout, cin, dtype, cout_pad)
     return rows
 
 
@@ -599,22 +590,12 @@ class PackedConv:
         return self._rows_pack
 
     def for_call(self, x_bytes: int, y_bytes: int, ld_y: int, y_ptr: int, residual: bool, out_f32: bool, gathered: bool) -> "PackedConv":
-        """This pack, or its DY_WLAYOUT_ROWS twin when the call is outside what the special layout's kernels take (mirrors
-        csrc/conv3x3_halo.hip::conv3x3_halo_dispatch and conv3x3_hreg.hip::conv3x3_hreg_try): a second source / upsampled or dilated
-        gather, an input view beyond the 4 GiB a buffer descriptor addresses, and -- stride-2 64-channel layers, which have no kernel
-        but conv3x3_hreg_s2 behind DY_WLAYOUT_HALO3X3 -- a residual, fp32 output, an output pitch / base that rules out 16-byte
-        stores or an input view beyond 2 GiB."""
+        """This pack, or its DY_WLAYOUT_ROWS twin when the kernels behind DY_WLAYOUT_HALO3X3 do not take the call: csrc decides
+        (``dy_conv3x3_halo_route``, the rule ``dy_conv2d_nhwc`` dispatches by)."""
         if self.layout != _lib.DY_WLAYOUT_HALO3X3:
             return self
-        if gathered or x_bytes >= (1 << 32) - 64:
-            return self.rows()
-        if self.stride == 2 and self.cin == 64 and self.cout > 32:
-            if residual or out_f32 or ld_y % 8 or y_ptr % 16 or x_bytes >= (1 << 31) or y_bytes >= (1 << 32) - 64 or self.dtype == torch.float32:
-                return self.rows()
-        if self.stride == 1 and self.cin == 128:  # packed for conv3x3_hreg's four-chunk form: what it declines runs on the virtual-flat GEMM
-            if residual or out_f32 or ld_y % 8 or y_ptr % 16 or x_bytes >= (1 << 31) or y_bytes >= (1 << 32) - 64:
-                return self.rows()
-        return self
+        route = lib().dy_conv3x3_halo_route(self.cin, self.cout, self.stride, dy_dtype(self.dtype), x_bytes, y_bytes, ld_y, y_ptr, residual, out_f32, gathered)
+        return self.rows() if route == _lib.DY_ROUTE_ROWS else self
 
 
 def conv_out_hw(h: int, w: int, k: int, s: int, p: int) -> Tuple[int, int]:

@@ -211,6 +211,21 @@ int32_t dy_conv_cout_pad(int32_t cout);
 int32_t dy_conv2d_nhwc(const dy_conv_desc* d, dy_stream_t stream);
 int32_t dy_conv_stats_written(void); /* > 0: slots of d->bn_stats the last dy_conv2d_nhwc of this thread filled */
 
+/* Whether the kernels behind a special weight layout take a call is decided HERE and asked by the caller (hip_ops.py::PackedConv.for_call,
+ * conv_pack_plan); the dispatch of dy_conv2d_nhwc runs the same functions.  Both are host arithmetic: they need no device, launch nothing
+ * and never set the error string.
+ *
+ * dy_conv3x3_halo_route: which kernel a dense 3x3 pad-1 call on a DY_WLAYOUT_HALO3X3 pack runs.  x_bytes / y_bytes: extent of the input /
+ * output view (batch * rows * cols * pitch * element size), ld_y in elements, y_addr: address of the output view, residual / out_f32:
+ * 0 / 1 as in dy_conv_desc, gathered: 1 when the call has a second source (x2) or an upsampled / dilated gather (up2x != 0).
+ * DY_ROUTE_ROWS: none of them takes it -- dy_conv2d_nhwc returns DY_ERR_UNSUPPORTED, run the call on the layer's DY_WLAYOUT_ROWS pack. */
+typedef enum dy_conv_route { DY_ROUTE_ROWS = 0, DY_ROUTE_HREG = 1, DY_ROUTE_HREG_S2 = 2, DY_ROUTE_HALO = 3 } dy_conv_route;
+int32_t dy_conv3x3_halo_route(int32_t cin, int32_t cout, int32_t stride, int32_t dtype, int64_t x_bytes, int64_t y_bytes, int32_t ld_y,
+                              uint64_t y_addr, int32_t residual, int32_t out_f32, int32_t gathered);
+/* dy_conv1x1_stream_supported: 1 when the streaming kernel behind DY_WLAYOUT_FRAG1X1 is built for a dense 1x1 stride-1 layer of this
+ * shape (K groups, cout tile and LDS footprint of the build), out_f32: the layer will be called with dy_conv_desc.out_f32. */
+int32_t dy_conv1x1_stream_supported(int32_t cin, int32_t cout, int32_t dtype, int32_t out_f32);
+
 /* ---- one Detect branch from its second 3x3 convolution to the decoded output ------------------------------
  * Replaces in ONE kernel per (level, branch), 16-bit storage: Detect.forward's cv2[i][1] -> cv2[i][2] (kind 1, box) or cv3[i][1] ->
  * cv3[i][2] (kind 2, class) of the legacy v8 head (nn/modules/head.py:43-57, 64-70), each Conv = SiLU(conv + folded BatchNorm

@@ -33,6 +33,21 @@ def test_host_only_entry_points():
     assert h.dy_conv_k_pad(64, 3, L.DY_BF16) == 576 and h.dy_conv_k_pad(32, 3, L.DY_BF16) == 320
     assert h.dy_conv_k_pad(8, 3, L.DY_BF16) == 128 and h.dy_conv_k_pad(96, 1, L.DY_F32) == 96
     assert [h.dy_conv_cout_pad(c) for c in (10, 64, 65, 512)] == [64, 64, 128, 512]
+    # which kernel a call on a DY_WLAYOUT_HALO3X3 pack runs (cin, cout, stride, dtype, x bytes, y bytes, ld_y, y address, residual, out_f32,
+    # gathered): 1 conv3x3_hreg, 2 conv3x3_hreg_s2, 3 conv3x3_halo, 0 none of them -- the rows pack; no device, no error string
+    route = h.dy_conv3x3_halo_route
+    assert route(64, 64, 1, L.DY_BF16, 1 << 20, 1 << 20, 64, 4096, 0, 0, 0) == 1 and route(64, 64, 1, L.DY_BF16, 1 << 20, 1 << 20, 64, 4096, 1, 0, 0) == 3
+    assert route(64, 128, 2, L.DY_F16, 1 << 20, 1 << 20, 128, 4096, 0, 0, 0) == 2 and route(64, 128, 2, L.DY_F16, 1 << 20, 1 << 20, 132, 4096, 0, 0, 0) == L.DY_ROUTE_ROWS
+    assert route(128, 128, 1, L.DY_F16, 1 << 20, 1 << 20, 128, 4096, 1, 0, 0) == L.DY_ROUTE_ROWS and route(32, 32, 1, L.DY_F32, 1 << 20, 1 << 20, 32, 4096, 0, 0, 1) == L.DY_ROUTE_ROWS
+    assert route(32, 32, 1, L.DY_F32, (1 << 32) - 65, 1 << 20, 32, 4096, 0, 0, 0) == 3 and route(32, 32, 1, L.DY_F32, (1 << 32) - 64, 1 << 20, 32, 4096, 0, 0, 0) == L.DY_ROUTE_ROWS
+    # edges no pack reaches through for_call: cout <= 32 at stride 2 and cout beyond conv3x3_hreg's 256 / off its 64-wide tiles -> the halo kernel
+    assert route(64, 32, 2, L.DY_BF16, 1 << 20, 1 << 20, 32, 4096, 0, 0, 0) == 3 and route(64, 320, 1, L.DY_BF16, 1 << 20, 1 << 20, 320, 4096, 0, 0, 0) == 3
+    assert route(64, 96, 1, L.DY_F16, 1 << 20, 1 << 20, 96, 4096, 0, 0, 0) == 3 and route(64, 256, 1, L.DY_F16, 1 << 20, 1 << 20, 256, 4096, 0, 0, 0) == 1
+    assert route(64, 64, 1, L.DY_F32, 1 << 20, 1 << 20, 64, 4096, 0, 0, 0) == 3 and route(64, 64, 1, L.DY_BF16, 1 << 31, 1 << 20, 64, 4096, 0, 0, 0) == 3
+    # the shapes the streaming 1x1 kernel is built for (cin, cout, dtype, out_f32): 2 / 3 / 4 / 6 / 8 / 12 K groups, cout <= 16 and fp32 output with 2 only
+    ok = h.dy_conv1x1_stream_supported
+    assert [ok(c, 64, L.DY_BF16, 0) for c in (32, 64, 96, 160, 384, 416)] == [0, 1, 1, 0, 1, 0] and ok(60, 64, L.DY_BF16, 0) == 0
+    assert ok(64, 8, L.DY_F16, 0) == 1 and ok(96, 8, L.DY_F16, 0) == 0 and ok(64, 64, L.DY_F16, 1) == 1 and ok(64, 128, L.DY_F16, 1) == 0 and ok(64, 64, L.DY_FP8, 0) == 0
     assert h.dy_nms_workspace_bytes(2, 34000) == 256 + 2 * 65536 * 8 + 136192
     assert h.dy_last_error_string() is not None
 

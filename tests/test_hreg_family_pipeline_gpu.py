@@ -4,7 +4,7 @@ candidate list finished one tile late from scalar state).
 
 Convolutions: fp32 CPU convolution on dtype-rounded inputs, tolerance of tests/test_kernels_gpu.py (RTOL x scale).  Shapes: one tile
 (the pipeline's prologue is its epilogue), four tiles with one-pixel ragged edges, odd maps over several images, and 2,400 tiles over
-at most 768 workgroups (three or four tiles per workgroup, uneven remainder).  cin 32 stays on conv3x3_halo (conv3x3_hreg_try), which
+at most 768 workgroups (three or four tiles per workgroup, uneven remainder).  cin 32 stays on conv3x3_halo (dy_conv3x3_halo_route), which
 the case asserts.  Detect branches: scores / boxes against the fp32 CPU chain with the bounds of
 test_detect_branch_fused_matches_cpu_chain; the candidate list must be exactly the set that follows from the kernel's own scores.
 Repeatability: five runs beside another convolution on a second stream, bit-identical (stale halo reads were this family's failure)."""
@@ -54,7 +54,7 @@ def expected_kernel(cin, stride, act, dtype):
     if stride == 2:
         return "conv3x3_hreg_s2"
     if cin == 32:
-        return "conv3x3_halo"  # one chunk per tile measured no gain on the register-weight kernel: conv3x3_hreg_try declines it
+        return "conv3x3_halo"  # one chunk per tile measured no gain on the register-weight kernel: dy_conv3x3_halo_route declines it
     if cin == 128 and act and dtype == torch.bfloat16:
         return None  # bf16 inference packs of 128 channels stay on the virtual-flat GEMM (hip_ops.PackedConv)
     return "conv3x3_hreg_kernel"
