@@ -20,7 +20,12 @@
 // Stem buffer layout: [row 0..16][column parity][index 0..16][32 channels], i.e. stem column 2*index + parity, so that
 // the 16 pixels of a stride-2 fragment are CONSECUTIVE entries of one plane; the four 16-byte chunks of an entry are
 // XOR-swizzled by (index >> 2) & 3: conflict-free ds_read_b128 operand reads.
-// LDS 64 KiB -> two workgroups per CU: one loads its patch while the other computes.
+// LDS 66 KiB -> two workgroups per CU: one loads its patch while the other computes.
+// r10: (a) phase B takes a fragment slot's two LDS addresses from a table written once per workgroup (the slot -> stem pixel map is the same
+// in every tile; re-deriving it cost 29 of 61 vector instructions per fragment) and skips the zero-padding test on interior tiles; (b) phases B
+// and C are software-pipelined by hand (gather one round ahead, layer-1 fragments one stem row ahead): the compiler's order met two LDS
+// latencies per round.  747 -> 666 us at B = 256, every output bit the same.  The tile height is a template parameter; a 4-row tile at three
+// workgroups per CU was measured slower (S2Geo below, profiles/r10_ab_stem2.txt).
 #include "common_hip.h"
 
 namespace DY_NS {
@@ -38,21 +43,60 @@ struct Stem2Args {
   int tilesX, tilesY, ntiles;
 };
 
-constexpr int kS2TH = 8, kS2TW = 16;                              // layer-1 pixels per tile
-constexpr int kS2SH = 2 * kS2TH + 1, kS2SW = 2 * kS2TW + 1;       // 17 x 33 stem pixels
-constexpr int kS2PH = 2 * kS2SH + 1;                              // 35 input rows
+constexpr int kS2TW = 16;                                         // layer-1 pixels per tile row
+constexpr int kS2SW = 2 * kS2TW + 1;                              // 33 stem columns
 constexpr int kS2Pitch = 68;                                      // floats per patch row: 17 aligned float4
-constexpr int kS2Plane = kS2PH * kS2Pitch;
-constexpr int kS2PatchBytes = 28 * 1024;                          // 3 * 35 * 68 floats = 28560 B, padded to 28 DMA instructions of 1 KiB
 constexpr int kS2Idx = 17;                                        // entries per (row, parity) plane
-constexpr int kS2StemBytes = kS2SH * 2 * kS2Idx * 64;             // 36992
 constexpr int kS2EpPitch = 128 + 16;
-static_assert(3 * kS2Plane * 4 <= kS2PatchBytes && 128 * kS2EpPitch <= kS2StemBytes, "epilogue scratch aliases the stem buffer");
+constexpr int kS2DivSW = 1986;                                    // tt / 33 = (tt * 1986) >> 16 for tt < 561
+constexpr int kS2Div17 = 3856;                                    // i / 17 = (i * 3856) >> 16 for i < 1792
 
-template <typename T>
-__global__ __launch_bounds__(256, 2) void stem2_fused_kernel(const Stem2Args p) {
+// The geometry of a TH x 16 layer-1 tile (r10).  TABLE adds the phase-B address table behind the stem buffer.
+//   TH 8: 35 patch rows, 17 stem rows, 28 + 36.1 KB of LDS (+ 2.25 KB of table): two workgroups per CU.  DISPATCHED with the table.
+//   TH 4: 19 patch rows,  9 stem rows, 16 + 19.1 KB (+ 1.25 KB of table): three per CU.  Ablate builds only: 20 fragment slots per 64
+//         output pixels against 36 per 128 cost more than the third workgroup returns (685 against 666 us at B = 256).
+//   (TH 6, 27 patch rows, 22 DMA instructions: 108 - 208 bytes of scratch at the 168 registers of three per CU, 0.98 - 1.24 ms; with the
+//   DMA offsets recomputed per tile 693 us.  Not kept.)
+template <int TH, bool TABLE>
+struct S2Geo {
+  static_assert(TH >= 2 && TH <= 8 && TH % 2 == 0, "row stores take the tile in pairs of rows");
+  static constexpr int SH = 2 * TH + 1;                           // stem rows
+  static constexpr int PH = 2 * SH + 1;                           // input rows = 4 TH + 3
+  static constexpr int Plane = PH * kS2Pitch;
+  static constexpr int Dma = (3 * Plane * 4 + 1023) / 1024;       // LDS-DMA instructions of 1 KiB per patch ...
+  static constexpr int DmaPerWave = Dma / 4;                      // ... and per wave
+  static constexpr int PatchBytes = Dma * 1024;
+  static constexpr int StemBytes = SH * 2 * kS2Idx * 64;
+  static constexpr int Frags = (SH * kS2SW + 15) / 16;            // 16-pixel fragments of phase B
+  static constexpr int Rounds = (Frags + 3) / 4;                  // rounds of the four waves
+  static constexpr int TableBytes = TABLE ? Rounds * 64 * 4 : 0;  // one word per fragment slot and pixel
+  static constexpr int LdsBytes = PatchBytes + StemBytes + TableBytes;
+  static constexpr int DivPH = 65536 / PH + 1;                    // row / PH = (row * DivPH) >> 16
+  static constexpr int PerCU = TH == 8 ? 2 : 3;                   // workgroups per CU: LDS and registers (launch bounds below)
+  static constexpr int UnrollB = TH == 8 ? 3 : 1;                 // the loop without the table (unrolled, the three-per-CU form spills)
+  // entry 16 of an odd-column plane is never read by phase C (odd columns are 1 .. 31): slot-padding lanes of the table form write there
+  static constexpr int DumpEntry = kS2Idx + 16;
+  static constexpr bool divisions_exact() {
+    for (int i = 0; i < DmaPerWave * 4 * 64; ++i) {
+      const int row = (i * kS2Div17) >> 16;
+      if (row != i / 17 || ((row * DivPH) >> 16) != row / PH) return false;
+    }
+    for (int tt = 0; tt < SH * kS2SW; ++tt)
+      if (((tt * kS2DivSW) >> 16) != tt / kS2SW) return false;
+    return true;
+  }
+  static_assert(divisions_exact(), "reciprocal-multiply divisions of phases A and B over their whole argument range");
+  static_assert(3 * Plane * 4 <= PatchBytes && TH * kS2TW * kS2EpPitch <= StemBytes, "epilogue scratch aliases the stem buffer");
+  static_assert(LdsBytes * PerCU <= 160 * 1024 && Dma % 4 == 0, "LDS per CU; every wave issues the same number of DMA instructions");
+  static_assert(PatchBytes < 65536 && StemBytes < 65536, "a table word holds two 16-bit byte offsets: into the patch, into the stem buffer");
+};
+
+template <typename T, int TH, bool TABLE>
+__global__ __launch_bounds__(256, (S2Geo<TH, TABLE>::PerCU)) void stem2_fused_kernel(const Stem2Args p) {
   static_assert(sizeof(T) == 2, "16-bit storage only");
-  __shared__ __attribute__((aligned(16))) unsigned char smem[kS2PatchBytes + kS2StemBytes];
+  using G = S2Geo<TH, TABLE>;
+  constexpr int kS2SH = G::SH, kS2PH = G::PH, kS2Plane = G::Plane, kS2PatchBytes = G::PatchBytes, kS2StemBytes = G::StemBytes;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[G::LdsBytes];
   float* patch = reinterpret_cast<float*>(smem);
   unsigned char* stem = smem + kS2PatchBytes;
 
@@ -77,27 +121,27 @@ __global__ __launch_bounds__(256, 2) void stem2_fused_kernel(const Stem2Args p) 
   for (int e = 0; e < 8; ++e) {
     const int k = lq * 8 + e;
     const int c = k / 9, r = (k - c * 9) / 3, q = k - c * 9 - r * 3;
-    koff[e] = k < 27 ? c * kS2Plane + r * kS2Pitch + q : 0;
+    koff[e] = (k < 27 ? c * kS2Plane + r * kS2Pitch + q : 0) * (TABLE ? 4 : 1);  // (the table form adds byte offsets)
   }
-  // phase A (LDS-DMA): float4 number i = (7*wave + k)*64 + lane of the patch = row i / 17 (= c*35 + py), column group i % 17
+  // phase A (LDS-DMA): float4 number i = (DmaPerWave*wave + k)*64 + lane of the patch = row i / 17 (= c*PH + py), column group i % 17
   auto request_patch = [&](int tile) {
     int t = tile;
     const int tx = t % p.tilesX;
     t /= p.tilesX;
     const int ty = t % p.tilesY;
     const int n = t / p.tilesY;
-    const int gy0 = 4 * ty * kS2TH - 3, gx0 = 4 * tx * kS2TW - 4;
+    const int gy0 = 4 * ty * TH - 3, gx0 = 4 * tx * kS2TW - 4;
     const float* img = p.x + (size_t)n * 3 * p.H * p.W;
 #pragma unroll
-    for (int k = 0; k < 7; ++k) {
-      const int i = (wave * 7 + k) * 64 + lane;
-      const int row = (i * 3856) >> 16;         // i / 17 for i < 1792
-      const int c = (row * 1873) >> 16;         // row / 35 for row < 106
+    for (int k = 0; k < G::DmaPerWave; ++k) {
+      const int i = (wave * G::DmaPerWave + k) * 64 + lane;
+      const int row = (i * kS2Div17) >> 16;     // i / 17
+      const int c = (row * G::DivPH) >> 16;     // row / PH
       const int gy = gy0 + row - c * kS2PH, gx = gx0 + 4 * (i - row * 17);
       const bool ok = row < 3 * kS2PH && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
       const float* src = ok ? img + (size_t)(c * p.H + gy) * p.W + gx : reinterpret_cast<const float*>(g_s2zero);
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)(smem + (wave * 7 + k) * 1024), 16, 0, 0);
+                                       (__attribute__((address_space(3))) void*)(smem + (wave * G::DmaPerWave + k) * 1024), 16, 0, 0);
     }
   };
   f32x4 bias0[2];
@@ -116,6 +160,68 @@ __global__ __launch_bounds__(256, 2) void stem2_fused_kernel(const Stem2Args p) 
   } else {
     t_first = (int)blockIdx.x, t_step = (int)gridDim.x, t_end = p.ntiles;
   }
+  // Phase-B address table (r10).  Fragment slot tt = (wave + 4*round)*16 + lr is stem pixel (tt / 33, tt % 33) in every tile, so the byte
+  // offset of its window origin in the patch (low half) and of its stem-buffer entry with the swizzle applied to chunk 0 (high half) are
+  // worked out once per workgroup; the loop fetches the word and XORs the lane's chunk bits in.  Slots past the last pixel gather from the
+  // last pixel's window, as before, and write into an entry nobody reads, so the loop carries no `valid` flag.
+  const unsigned* tbl = reinterpret_cast<const unsigned*>(smem + kS2PatchBytes + kS2StemBytes) + wave * 16 + lr;
+  const unsigned lane_chunk = (unsigned)((lq >> 1) * 16 + (lq & 1) * 8);
+  if constexpr (TABLE) {
+    for (int tt = tid; tt < G::Rounds * 64; tt += 256) {
+      const bool valid = tt < kS2SH * kS2SW;
+      const int tc = valid ? tt : kS2SH * kS2SW - 1;
+      const int sy = (tc * kS2DivSW) >> 16;
+      const int sx = tc - sy * kS2SW;
+      const int idx = sx >> 1;
+      const int ent = valid ? ((sy * 2 + (sx & 1)) * kS2Idx + idx) * 64 + ((idx >> 2) & 3) * 16 : G::DumpEntry * 64;
+      reinterpret_cast<unsigned*>(smem + kS2PatchBytes + kS2StemBytes)[tt] = (unsigned)(((2 * sy) * kS2Pitch + 2 * sx + 1) * 4) | ((unsigned)ent << 16);
+    }
+  }
+  // Phase B in the table form, software-pipelined by hand: the table words of all rounds are fetched at the head of the phase and the
+  // gather of round it + 1 is issued in front of round it's MFMAs and SiLU, so that a wave meets one LDS latency per phase instead of
+  // two per round.  INTERIOR tiles (every stem pixel inside the layer-0 map) skip the zero-padding test.
+  auto stem_gather = [&](unsigned w, float (&g)[8]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) g[e] = *reinterpret_cast<const float*>(smem + ((w & 0xffffu) + (unsigned)koff[e]));
+  };
+  auto stem_finish = [&](int it, unsigned w, const float (&g)[8], int oy0, int ox0, auto interior) {
+    const u32x4 a = Chunk<T>::pack(g);
+    bool inside = true;
+    if constexpr (!decltype(interior)::value) {
+      const int tt = (wave + 4 * it) * 16 + lr;
+      const int tc = tt < kS2SH * kS2SW ? tt : kS2SH * kS2SW - 1;
+      const int sy = (tc * kS2DivSW) >> 16;
+      const int sx = tc - sy * kS2SW;
+      inside = ((unsigned)(2 * oy0 - 1 + sy) < (unsigned)p.H0) & ((unsigned)(2 * ox0 - 1 + sx) < (unsigned)p.W0);
+    }
+    const unsigned ent = (w >> 16) ^ lane_chunk;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      f32x4 acc = Elem<T>::mma(wf0[j], a, bias0[j]);
+      typedef __attribute__((ext_vector_type(4))) T t4;
+      t4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = Elem<T>::from_f32(silu_f32(acc[e]));
+      u32x2 ov = __builtin_bit_cast(u32x2, o);
+      if (!inside) ov = u32x2{0u, 0u};  // layer 1's zero padding
+      *reinterpret_cast<u32x2*>(stem + (ent ^ (unsigned)(j * 32))) = ov;
+    }
+  };
+  auto stem_phase = [&](int oy0, int ox0, auto interior) {
+    unsigned w[G::Rounds];
+#pragma unroll
+    for (int it = 0; it < G::Rounds; ++it) w[it] = tbl[it * 64];
+    float g[2][8];
+    stem_gather(w[0], g[0]);
+#pragma unroll
+    for (int it = 0; it < G::Rounds; ++it) {
+      if (it + 1 < G::Rounds) stem_gather(w[it + 1], g[(it + 1) & 1]);
+      __builtin_amdgcn_sched_barrier(0);
+      stem_finish(it, w[it], g[it & 1], oy0, ox0, interior);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
   if (t_first < t_end) request_patch(t_first);
   for (int tile = t_first; tile < t_end; tile += t_step) {
     int t = tile;
@@ -123,64 +229,105 @@ __global__ __launch_bounds__(256, 2) void stem2_fused_kernel(const Stem2Args p) 
     t /= p.tilesX;
     const int ty = t % p.tilesY;
     const int n = t / p.tilesY;
-    const int oy0 = ty * kS2TH, ox0 = tx * kS2TW;
+    const int oy0 = ty * TH, ox0 = tx * kS2TW;
 
     // ---- A: the patch was requested during the previous tile (LDS-DMA) ----
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();  // patch landed in every wave; the previous tile's row stores are done reading the scratch
+    __syncthreads();  // patch landed in every wave; the previous tile's row stores are done reading the scratch; (first tile) the table is written
 
     // ---- B: stem pixels (sy_l, sx_l) = stem row 2*oy0 - 1 + sy_l, column 2*ox0 - 1 + sx_l ----
-#pragma unroll 3
-    for (int it = 0; it < ((kS2SH * kS2SW + 15) / 16 + 3) / 4; ++it) {
-      const int tt = (wave + 4 * it) * 16 + lr;
-      const bool valid = tt < kS2SH * kS2SW;
-      const int tc = valid ? tt : kS2SH * kS2SW - 1;
-      const int sy = (tc * 1986) >> 16;  // tc / 33 for tc < 561
-      const int sx = tc - sy * kS2SW;
-      const float* org = patch + (2 * sy) * kS2Pitch + 2 * sx + 1;
-      float g[8];
+    if constexpr (TABLE) {
+      if (oy0 > 0 && ox0 > 0 && 2 * oy0 - 1 + kS2SH <= p.H0 && 2 * ox0 - 1 + kS2SW <= p.W0)  // one decision per tile and wave
+        stem_phase(oy0, ox0, std::true_type{});
+      else
+        stem_phase(oy0, ox0, std::false_type{});
+    } else {
+#pragma unroll G::UnrollB
+      for (int it = 0; it < G::Rounds; ++it) {
+        const int tt = (wave + 4 * it) * 16 + lr;
+        const bool valid = tt < kS2SH * kS2SW;
+        const int tc = valid ? tt : kS2SH * kS2SW - 1;
+        const int sy = (tc * kS2DivSW) >> 16;  // tc / 33
+        const int sx = tc - sy * kS2SW;
+        const float* org = patch + (2 * sy) * kS2Pitch + 2 * sx + 1;
+        float g[8];
 #pragma unroll
-      for (int e = 0; e < 8; ++e) g[e] = org[koff[e]];
-      const u32x4 a = Chunk<T>::pack(g);
-      const int gsy = 2 * oy0 - 1 + sy, gsx = 2 * ox0 - 1 + sx;
-      const bool inside = (unsigned)gsy < (unsigned)p.H0 && (unsigned)gsx < (unsigned)p.W0;
-      const int idx = sx >> 1;
-      unsigned char* ent = stem + ((sy * 2 + (sx & 1)) * kS2Idx + idx) * 64 + (lq & 1) * 8;
-      const int sw = (idx >> 2) & 3;
+        for (int e = 0; e < 8; ++e) g[e] = org[koff[e]];
+        const u32x4 a = Chunk<T>::pack(g);
+        const int gsy = 2 * oy0 - 1 + sy, gsx = 2 * ox0 - 1 + sx;
+        const bool inside = (unsigned)gsy < (unsigned)p.H0 && (unsigned)gsx < (unsigned)p.W0;
+        const int idx = sx >> 1;
+        unsigned char* ent = stem + ((sy * 2 + (sx & 1)) * kS2Idx + idx) * 64 + (lq & 1) * 8;
+        const int sw = (idx >> 2) & 3;
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        f32x4 acc = Elem<T>::mma(wf0[j], a, bias0[j]);
-        typedef __attribute__((ext_vector_type(4))) T t4;
-        t4 o;
+        for (int j = 0; j < 2; ++j) {
+          f32x4 acc = Elem<T>::mma(wf0[j], a, bias0[j]);
+          typedef __attribute__((ext_vector_type(4))) T t4;
+          t4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = Elem<T>::from_f32(silu_f32(acc[e]));
-        u32x2 ov = __builtin_bit_cast(u32x2, o);
-        if (!inside) ov = u32x2{0u, 0u};  // layer 1's zero padding
-        if (valid) *reinterpret_cast<u32x2*>(ent + (((j * 2 + (lq >> 1)) ^ sw) * 16)) = ov;
+          for (int e = 0; e < 4; ++e) o[e] = Elem<T>::from_f32(silu_f32(acc[e]));
+          u32x2 ov = __builtin_bit_cast(u32x2, o);
+          if (!inside) ov = u32x2{0u, 0u};  // layer 1's zero padding
+          if (valid) *reinterpret_cast<u32x2*>(ent + (((j * 2 + (lq >> 1)) ^ sw) * 16)) = ov;
+        }
       }
     }
     __syncthreads();
     if (tile + t_step < t_end) request_patch(tile + t_step);  // the patch is dead: fetch the next one under phase C
 
-    // ---- C: layer 1: every wave runs all 8 rows x 16 columns for its 16 couts ----
-    f32x4 acc[8];
+    // ---- C: layer 1: every wave runs all TH rows x 16 columns for its 16 couts ----
+    f32x4 acc[TH];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) acc[i] = bias1;
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
+    for (int i = 0; i < TH; ++i) acc[i] = bias1;
+    if constexpr (TABLE) {
+      // walked by STEM ROW, the three column fragments of row s + 1 requested in front of row s's MFMAs: an even row 2i feeds kernel
+      // row 0 of output row i and kernel row 2 of output row i - 1, an odd row kernel row 1.  Every accumulator still takes its nine
+      // taps in (r, q) order.
+      const unsigned char* cb[3];
 #pragma unroll
       for (int q = 0; q < 3; ++q) {
         const int idx = lr + (q == 2 ? 1 : 0);
-        const unsigned char* base = stem + ((r * 2 + (q == 1 ? 1 : 0)) * kS2Idx + idx) * 64 + ((lq ^ ((idx >> 2) & 3)) * 16);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)  // stem row 2*i + r
-          acc[i] = Elem<T>::mma(wf1[r * 3 + q], *reinterpret_cast<const u32x4*>(base + i * (4 * kS2Idx * 64)), acc[i]);
+        cb[q] = stem + ((q == 1 ? 1 : 0) * kS2Idx + idx) * 64 + ((lq ^ ((idx >> 2) & 3)) * 16);
       }
+      u32x4 x[2][3];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) x[0][q] = *reinterpret_cast<const u32x4*>(cb[q]);
+#pragma unroll
+      for (int s = 0; s < kS2SH; ++s) {
+        if (s + 1 < kS2SH) {
+#pragma unroll
+          for (int q = 0; q < 3; ++q) x[(s + 1) & 1][q] = *reinterpret_cast<const u32x4*>(cb[q] + (s + 1) * (2 * kS2Idx * 64));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          const u32x4 xv = x[s & 1][q];
+          if (s & 1) {
+            acc[s >> 1] = Elem<T>::mma(wf1[3 + q], xv, acc[s >> 1]);
+          } else {
+            if (s > 0) acc[(s >> 1) - 1] = Elem<T>::mma(wf1[6 + q], xv, acc[(s >> 1) - 1]);
+            if ((s >> 1) < TH) acc[s >> 1] = Elem<T>::mma(wf1[q], xv, acc[s >> 1]);
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          const int idx = lr + (q == 2 ? 1 : 0);
+          const unsigned char* base = stem + ((r * 2 + (q == 1 ? 1 : 0)) * kS2Idx + idx) * 64 + ((lq ^ ((idx >> 2) & 3)) * 16);
+#pragma unroll
+          for (int i = 0; i < TH; ++i)  // stem row 2*i + r
+            acc[i] = Elem<T>::mma(wf1[r * 3 + q], *reinterpret_cast<const u32x4*>(base + i * (4 * kS2Idx * 64)), acc[i]);
+        }
+    }
 
     // ---- epilogue: SiLU; the four waves assemble whole 128-byte pixel rows in the (then dead) stem buffer ----
     __syncthreads();  // every wave is done reading the stem buffer
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
+    for (int i = 0; i < TH; ++i) {
       typedef __attribute__((ext_vector_type(4))) T t4;
       t4 o;
 #pragma unroll
@@ -189,7 +336,7 @@ __global__ __launch_bounds__(256, 2) void stem2_fused_kernel(const Stem2Args p) 
     }
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < TH / 2; ++k) {
       const int id = k * 256 + tid;
       const int px = id >> 3, cc = id & 7;
       const int oy = oy0 + (px >> 4), ox = ox0 + (px & 15);
@@ -439,6 +586,15 @@ extern "C" int32_t dy_stem2_fused(const dy_stem2_desc* d, dy_stream_t stream) {
 #endif
 
 namespace DY_NS {
+// the dispatched form of the 16-bit kernel (numbering: stem2_entry below)
+constexpr int kS2Form = 2, kS2FormTH = 8;
+constexpr bool kS2FormTable = true;
+
+template <typename T, int TH, bool TABLE>
+static void launch_stem2(const Stem2Args& a, int grid, hipStream_t st) {
+  hipLaunchKernelGGL((stem2_fused_kernel<T, TH, TABLE>), dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
 int32_t stem2_entry(const dy_stem2_desc* d, dy_stream_t stream) {
   DY_REQUIRE(d && d->x && d->w0 && d->b0 && d->w1 && d->b1 && d->y, DY_ERR_INVALID_ARG, "dy_stem2_fused: null descriptor or pointer");
   DY_REQUIRE(dy_stem2_fused_supported(3, 32, 64, d->h, d->w, d->dtype), DY_ERR_UNSUPPORTED,
@@ -470,12 +626,21 @@ int32_t stem2_entry(const dy_stem2_desc* d, dy_stream_t stream) {
   DY_REQUIRE(!x2, DY_ERR_UNSUPPORTED, "dy_stem2_fused: DY_F16X2 runs in the reference's activation units (DY_ACT_SILU)");
 #endif
   DY_REQUIRE(!x2 || (d->w1_scale && aligned16(d->w1_scale) && d->ld_y % 8 == 0), DY_ERR_INVALID_ARG, "dy_stem2_fused: DY_F16X2 needs w1_scale (fp32[64], 16-byte aligned) and an output pitch in whole groups of 8 channels");
+  // the 16-bit kernel's form: tile height and address table (DYOLO_STEM2_FORM, ablate builds only: 1 = 8 rows, the kernel of r01-r09;
+  // 2 = 8 rows + table and hand pipeline; 3 / 4 = 4 rows, three workgroups per CU, without / with them).  The product build holds the
+  // dispatched form alone.
+  int form = kS2Form;
+#ifdef DYOLO_ABLATE
+  if (const int f = dy_ablate("DYOLO_STEM2_FORM")) form = f;
+  DY_REQUIRE(form >= 1 && form <= 4, DY_ERR_INVALID_ARG, "dy_stem2_fused: DYOLO_STEM2_FORM is 1 .. 4");
+#endif
+  const int th = x2 || form > 2 ? 4 : 8;
   a.tilesX = (a.W1 + kS2TW - 1) / kS2TW;
-  a.tilesY = (a.H1 + (x2 ? 4 : kS2TH) - 1) / (x2 ? 4 : kS2TH);
+  a.tilesY = (a.H1 + th - 1) / th;
   const long long nt = (long long)a.N * a.tilesY * a.tilesX;
   DY_REQUIRE(nt < (1ll << 31) && (long long)a.N * 3 * a.H * a.W < (1ll << 40), DY_ERR_INVALID_ARG, "dy_stem2_fused: batch too large");
   a.ntiles = (int)nt;
-  int grid = 512;  // two workgroups per CU
+  int grid = 256 * (x2 || th == 8 ? 2 : 3);  // the workgroups a CU holds (S2Geo::PerCU)
   if (grid > a.ntiles) grid = a.ntiles >= 8 ? (a.ntiles & ~7) : a.ntiles;  // (a multiple of 8 keeps the XCD-contiguous tile order)
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 #ifndef DYOLO_L2E_BUILD
@@ -484,10 +649,22 @@ int32_t stem2_entry(const dy_stem2_desc* d, dy_stream_t stream) {
     return check_launch("stem2_split_kernel");
   }
 #endif
-  if (d->dtype == DY_BF16)
-    hipLaunchKernelGGL((stem2_fused_kernel<bf16_t>), dim3((unsigned)grid), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((stem2_fused_kernel<f16_t>), dim3((unsigned)grid), dim3(256), 0, st, a);
+  const bool bf = d->dtype == DY_BF16;
+  switch (form) {
+#ifdef DYOLO_ABLATE
+#define DY_S2_FORM(F, TH, TABLE) \
+  case F:                        \
+    bf ? launch_stem2<bf16_t, TH, TABLE>(a, grid, st) : launch_stem2<f16_t, TH, TABLE>(a, grid, st); \
+    break;
+    DY_S2_FORM(1, 8, false)
+    DY_S2_FORM(2, 8, true)
+    DY_S2_FORM(3, 4, false)
+    DY_S2_FORM(4, 4, true)
+#undef DY_S2_FORM
+#endif
+    default:
+      bf ? launch_stem2<bf16_t, kS2FormTH, kS2FormTable>(a, grid, st) : launch_stem2<f16_t, kS2FormTH, kS2FormTable>(a, grid, st);
+  }
   return check_launch("stem2_fused_kernel");
 }
 }  // namespace DY_NS
