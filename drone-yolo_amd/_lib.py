@@ -102,6 +102,18 @@ class NmsDesc(C.Structure):
     ]  # fmt: skip
 
 
+class ObbDecodeDesc(C.Structure):
+    """Mirror of ``dy_obb_decode_desc``."""
+
+    _fields_ = [
+        ("level", _vp * DY_MAX_LEVELS),
+        ("h", _i32 * DY_MAX_LEVELS), ("w", _i32 * DY_MAX_LEVELS), ("ld", _i32 * DY_MAX_LEVELS),
+        ("stride", _f32 * DY_MAX_LEVELS),
+        ("n_levels", _i32), ("batch", _i32), ("nc", _i32), ("n_extra", _i32), ("anchors", _i32),
+        ("pred", _vp), ("theta", _vp),
+    ]  # fmt: skip
+
+
 class ValMatchDesc(C.Structure):
     """Mirror of ``dy_val_match_desc``."""
 
@@ -301,6 +313,11 @@ SIGNATURES = {
     "dy_nms": (_i32, [C.POINTER(NmsDesc), _vp]),
     "dy_nms_small_cap": (_i32, []),
     "dy_scale_boxes": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp]),
+    "dy_obb_decode": (_i32, [C.POINTER(ObbDecodeDesc), _vp]),
+    "dy_nms_rotated_workspace_bytes": (_i64, [_i32, _i32]),
+    "dy_nms_rotated": (_i32, [C.POINTER(NmsDesc), _vp, _vp]),
+    "dy_nms_rotated_lds_cap": (_i32, []),
+    "dy_scale_rboxes": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp]),
     "dy_val_match": (_i32, [C.POINTER(ValMatchDesc), _vp]),
     "dy_track_state_bytes": (_i64, [_i32, _i32]),
     "dy_track_workspace_bytes": (_i64, [_i32, _i32, _i32]),

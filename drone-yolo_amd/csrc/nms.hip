@@ -25,34 +25,11 @@
 // inputs:  xyxy = xy -/+ wh/2 (ops.py:432-449); boxes + cls*max_wh (ops.py:305,311);
 // area = (x2-x1)*(y2-y1); inter = max(0,xx2-xx1)*max(0,yy2-yy1);
 // suppress iff inter / (area_i + area_j - inter) > iou_thres.
-#include "common_hip.h"
-#include "nms_ws.h"
+#include "nms_core.h"
 
 #pragma clang fp contract(off)
 
 namespace dy {
-
-typedef unsigned long long u64;
-
-struct NmsArgs {
-  const float* pred;
-  int batch, nc, nch, A;  // nch = 4 + nc + n_extra rows per image
-  float conf, iou;
-  int max_det, max_nms;
-  float max_wh;
-  int agnostic;
-  const uint8_t* cmask;
-  float* out;
-  int* out_count;
-  int* out_index;
-  int* counts;          // [batch]
-  u64* keys;            // [batch][P]
-  unsigned short* cls;  // [batch][A] best class of every candidate anchor
-  int P;                // per-image key capacity (power of two >= A)
-  int SL;               // LDS sort capacity in keys (power of two)
-  int multi;            // multi_label (ops.py:286-288): a candidate is an (anchor, class) pair, key low word = anchor * nc + class
-  int cap;              // candidates an image can have: A, or A * nc with multi
-};
 
 __global__ __launch_bounds__(256) void nms_filter_kernel(const NmsArgs p) {
   const int lane = threadIdx.x & 63;
@@ -222,21 +199,7 @@ __global__ __launch_bounds__(NMS_SMALL_THREADS) void nms_small_kernel(const NmsA
   while (P2 < n) P2 <<= 1;
   for (int i = tid; i < P2; i += NMS_SMALL_THREADS) skeys[i] = i < n ? gkeys[i] : ~0ull;
   __syncthreads();
-  for (int k = 2; k <= P2; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = tid; t < (P2 >> 1); t += NMS_SMALL_THREADS) {
-        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));  // element with bit j clear
-        const int ixj = i | j;
-        const u64 x = skeys[i], y = skeys[ixj];
-        const bool up = (i & k) == 0;
-        if ((x > y) == up) {
-          skeys[i] = y;
-          skeys[ixj] = x;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  nms_bitonic_sort<NMS_SMALL_THREADS>(skeys, P2, tid);
 
   const int nn = n < p.max_nms ? n : p.max_nms;
   const float* pr = p.pred + (size_t)b * p.nch * (size_t)p.A;
@@ -322,34 +285,15 @@ __global__ __launch_bounds__(1024) void nms_suppress_kernel(const NmsArgs p) {
   int P2 = 1;
   while (P2 < n) P2 <<= 1;
   const bool in_lds = P2 <= p.SL;
-  // Bitonic sort, one compare-exchange pair per thread per pass.  The LDS and the global variant are
-  // separate loops on purpose: a pointer select between the two address spaces makes the compiler
-  // fall back to generic (flat) accesses, which were ~10x slower per pass.
-  auto bitonic = [&](auto* keys) {
-    for (int k = 2; k <= P2; k <<= 1) {
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int t = tid; t < (P2 >> 1); t += 1024) {
-          const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));  // element with bit j clear
-          const int ixj = i | j;
-          const u64 x = keys[i], y = keys[ixj];
-          const bool up = (i & k) == 0;
-          if ((x > y) == up) {
-            keys[i] = y;
-            keys[ixj] = x;
-          }
-        }
-        __syncthreads();
-      }
-    }
-  };
+  // the LDS and the global sort are separate instantiations on purpose (nms_core.h)
   if (in_lds) {
     for (int i = tid; i < P2; i += 1024) skeys[i] = i < n ? gkeys[i] : ~0ull;
     __syncthreads();
-    if (n > 1) bitonic(skeys);
+    if (n > 1) nms_bitonic_sort<1024>(skeys, P2, tid);
   } else {
     for (int i = n + tid; i < P2; i += 1024) gkeys[i] = ~0ull;
     __syncthreads();
-    bitonic(gkeys);
+    nms_bitonic_sort<1024>(gkeys, P2, tid);
   }
   if (tid >= 64) return;  // wave 0 runs the greedy scan
 
@@ -449,31 +393,21 @@ __global__ __launch_bounds__(256) void scale_boxes_kernel(float* __restrict__ bo
 static inline int next_pow2(int v) { return nms_next_pow2(v); }
 static inline size_t align_up(size_t v, size_t a) { return nms_align_up(v, a); }
 
-}  // namespace dy
-
-using namespace dy;
-
-extern "C" int64_t dy_nms_workspace_bytes(int32_t batch, int32_t anchors) {
-  if (batch <= 0 || anchors <= 0) return -1;
-  return (int64_t)nms_ws_bytes(batch, anchors);
-}
-
-extern "C" int32_t dy_nms(const dy_nms_desc* d, dy_stream_t stream) {
-  DY_REQUIRE(d && d->pred && d->out && d->out_count && d->workspace, DY_ERR_INVALID_ARG, "dy_nms: null pointer");
-  DY_REQUIRE(d->batch > 0 && d->nc > 0 && d->anchors > 0 && d->n_extra >= 0, DY_ERR_INVALID_ARG, "dy_nms: bad dims");
-  DY_REQUIRE(d->nc <= 65535, DY_ERR_UNSUPPORTED, "dy_nms: nc %d > 65535", d->nc);
+int nms_args_from_desc(const dy_nms_desc* d, const char* who, int64_t ws_extra, NmsArgs* out) {
+  DY_REQUIRE(d && d->pred && d->out && d->out_count && d->workspace, DY_ERR_INVALID_ARG, "%s: null pointer", who);
+  DY_REQUIRE(d->batch > 0 && d->nc > 0 && d->anchors > 0 && d->n_extra >= 0, DY_ERR_INVALID_ARG, "%s: bad dims", who);
+  DY_REQUIRE(d->nc <= 65535, DY_ERR_UNSUPPORTED, "%s: nc %d > 65535", who, d->nc);
   DY_REQUIRE(d->conf_thres >= 0.f && d->conf_thres <= 1.f && d->iou_thres >= 0.f && d->iou_thres <= 1.f,
-             DY_ERR_INVALID_ARG, "dy_nms: thresholds must be in [0,1] (utils/ops.py:233-234)");
-  DY_REQUIRE(d->max_det >= 1 && d->max_det <= 4096 && d->max_nms >= 1, DY_ERR_INVALID_ARG, "dy_nms: max_det must be in [1,4096]");
+             DY_ERR_INVALID_ARG, "%s: thresholds must be in [0,1] (utils/ops.py:233-234)", who);
+  DY_REQUIRE(d->max_det >= 1 && d->max_det <= 4096 && d->max_nms >= 1, DY_ERR_INVALID_ARG, "%s: max_det must be in [1,4096]", who);
   const bool multi = d->multi_label != 0 && d->nc > 1;  // (ops.py:255: multi_label &= nc > 1)
-  DY_REQUIRE(!multi || (long long)d->anchors * d->nc < (1ll << 30), DY_ERR_UNSUPPORTED, "dy_nms: multi_label with anchors * nc >= 2^30");
-  DY_REQUIRE(!(multi && d->prefiltered), DY_ERR_UNSUPPORTED, "dy_nms: the fused candidate filter is single-label; multi_label filters here");
+  DY_REQUIRE(!multi || (long long)d->anchors * d->nc < (1ll << 30), DY_ERR_UNSUPPORTED, "%s: multi_label with anchors * nc >= 2^30", who);
+  DY_REQUIRE(!(multi && d->prefiltered), DY_ERR_UNSUPPORTED, "%s: the fused candidate filter is single-label; multi_label filters here", who);
   const int wcap = multi ? d->anchors * d->nc : d->anchors;
-  const int64_t need = dy_nms_workspace_bytes(d->batch, wcap);
-  DY_REQUIRE(d->workspace_bytes >= need, DY_ERR_WORKSPACE, "dy_nms: workspace %lld < %lld bytes", (long long)d->workspace_bytes,
-             (long long)need);
-  DY_REQUIRE(aligned16(d->workspace), DY_ERR_INVALID_ARG, "dy_nms: workspace not 16-byte aligned");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t ws_need = (int64_t)nms_ws_bytes(d->batch, wcap) + ws_extra;
+  DY_REQUIRE(d->workspace_bytes >= ws_need, DY_ERR_WORKSPACE, "%s: workspace %lld < %lld bytes", who, (long long)d->workspace_bytes,
+             (long long)ws_need);
+  DY_REQUIRE(aligned16(d->workspace), DY_ERR_INVALID_ARG, "%s: workspace not 16-byte aligned", who);
 
   NmsArgs a{};
   a.pred = d->pred;
@@ -499,17 +433,38 @@ extern "C" int32_t dy_nms(const dy_nms_desc* d, dy_stream_t stream) {
   a.keys = reinterpret_cast<u64*>(w.keys);
   a.cls = w.cls;
   a.SL = a.P < 16384 ? a.P : 16384;
+  *out = a;
+  return DY_OK;
+}
 
-  if (!d->prefiltered) {
-    zero_async(a.counts, (size_t)d->batch * 4, st);
-    const long long total = (long long)d->batch * d->anchors;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    if (multi) hipLaunchKernelGGL(nms_filter_ml_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(nms_filter_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
-    const int rc = check_launch(multi ? "nms_filter_ml_kernel" : "nms_filter_kernel");
-    if (rc != DY_OK) return rc;
-  }
+int nms_launch_filter(const NmsArgs& a, bool prefiltered, hipStream_t st) {
+  if (prefiltered) return DY_OK;
+  zero_async(a.counts, (size_t)a.batch * 4, st);
+  const long long total = (long long)a.batch * a.A;
+  long long blocks = (total + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  if (a.multi) hipLaunchKernelGGL(nms_filter_ml_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(nms_filter_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  return check_launch(a.multi ? "nms_filter_ml_kernel" : "nms_filter_kernel");
+}
+
+}  // namespace dy
+
+using namespace dy;
+
+extern "C" int64_t dy_nms_workspace_bytes(int32_t batch, int32_t anchors) {
+  if (batch <= 0 || anchors <= 0) return -1;
+  return (int64_t)nms_ws_bytes(batch, anchors);
+}
+
+extern "C" int32_t dy_nms(const dy_nms_desc* d, dy_stream_t stream) {
+  NmsArgs a{};
+  const int rc0 = nms_args_from_desc(d, "dy_nms", 0, &a);
+  if (rc0 != DY_OK) return rc0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int wcap = a.cap;
+  const int rcf = nms_launch_filter(a, d->prefiltered != 0, st);
+  if (rcf != DY_OK) return rcf;
   // Both suppress kernels are launched: which of them an image belongs to (at most NMS_SMALL_CAP candidates or more) is known on
   // the device only, and the workgroups of the other kernel return in their first instructions.
   static const hipError_t attr_small = hipFuncSetAttribute((const void*)nms_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

@@ -1,5 +1,5 @@
 """``YOLO`` / ``Model`` user API (reference: ultralytics/engine/model.py:29-1177,
-ultralytics/models/yolo/model.py:11-59) for the detection and segmentation (prediction and validation) tasks on the MI355X path."""
+ultralytics/models/yolo/model.py:11-59) for the detection, segmentation (prediction and validation) and oriented-box (prediction) tasks on the MI355X path."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -8,9 +8,9 @@ from typing import List, Union
 import torch
 import torch.nn as nn
 
-from ..nn.tasks import DetectionModel, SegmentationModel, guess_model_task, yaml_model_load
+from ..nn.tasks import DetectionModel, OBBModel, SegmentationModel, guess_model_task, yaml_model_load
 from ..utils import LOGGER
-from .predictor import DetectionPredictor, SegmentationPredictor
+from .predictor import DetectionPredictor, OBBPredictor, SegmentationPredictor
 from .results import Results
 
 
@@ -27,8 +27,8 @@ class Model(nn.Module):
         self.ckpt_path = None
         self.overrides = {}
         self.task = task
-        if task not in (None, "detect", "segment"):
-            raise NotImplementedError(f"task '{task}': only 'detect' and 'segment' are on the accelerated path")
+        if task not in (None, "detect", "segment", "obb"):
+            raise NotImplementedError(f"task '{task}': only 'detect', 'segment' and 'obb' are on the accelerated path")
         model = str(model).strip()
         if Path(model).suffix in {".yaml", ".yml"}:
             self._new(model, verbose=verbose)
@@ -45,6 +45,14 @@ class Model(nn.Module):
         return {"detect": {"model": DetectionModel, "predictor": DetectionPredictor},
                 "segment": {"model": SegmentationModel, "predictor": SegmentationPredictor}}
 
+    @property
+    def predict_only_task_map(self):
+        """Tasks that have a model and a predictor and nothing else (no trainer, no validator); ``task_map`` keeps the tasks that can be scored."""
+        return {"obb": {"model": OBBModel, "predictor": OBBPredictor}}
+
+    def _task_classes(self, task: str) -> dict:
+        return {**self.task_map, **self.predict_only_task_map}[task]
+
     def _new(self, cfg: str, task=None, model=None, verbose=False) -> None:
         """Build from a YAML — reference engine/model.py:231-264."""
         cfg_dict = yaml_model_load(cfg)
@@ -53,7 +61,7 @@ class Model(nn.Module):
         if self.task is not None and self.task != found:
             raise ValueError(f"task '{self.task}' was asked for, but the head of '{cfg}' makes it a '{found}' model")
         self.task = found
-        self.model = (model or self.task_map[self.task]["model"])(cfg_dict, verbose=verbose)
+        self.model = (model or self._task_classes(self.task)["model"])(cfg_dict, verbose=verbose)
         self.overrides["model"] = self.cfg
         self.overrides["task"] = self.task
 
@@ -87,6 +95,7 @@ class Model(nn.Module):
         if source is None:
             raise ValueError("'source' is missing; the device path takes a BCHW float tensor in [0, 1]")
         self._refuse_for_segment(kwargs)
+        self._refuse_for_obb(kwargs)
         track = kwargs.get("mode") == "track"
         args = {**self.overrides, "conf": 0.1 if track else 0.25, **kwargs}
         args.pop("model", None), args.pop("task", None), args.pop("mode", None)
@@ -96,7 +105,7 @@ class Model(nn.Module):
         elif args.get("tile") is not None and int(args.get("merge_max_det", 1000)) > 1024:  # (before a predictor is built or anything is launched)
             raise ValueError(f"merge_max_det = {args['merge_max_det']} with tile in track mode: the track step takes at most 1024 detections per frame")
         if self.predictor is None or getattr(self, "_pred_args", None) != (args, track):
-            self.predictor = (predictor or self.task_map[self.task]["predictor"])(self.model, overrides=args)
+            self.predictor = (predictor or self._task_classes(self.task)["predictor"])(self.model, overrides=args)
             self._pred_args = (args, track)
         if track:
             # the tracker outlives the predictor (a predict call in between rebuilds that): persist=True goes on with its tracks and ids
@@ -134,6 +143,18 @@ class Model(nn.Module):
         if a.get("augment"):
             raise NotImplementedError("augment=True: test-time augmentation is not built for segmentation models")
 
+    def _refuse_for_obb(self, kwargs: dict) -> None:
+        """What an oriented-box model does not do, refused by argument name before a predictor is built or anything is launched."""
+        if self.task != "obb":
+            return
+        a = {**self.overrides, **kwargs}
+        if a.get("mode") == "track":
+            raise NotImplementedError("track: tracking is not built for oriented-box models")
+        if a.get("tile") is not None:
+            raise NotImplementedError("tile: tiled inference is not built for oriented-box models")
+        if a.get("augment"):
+            raise NotImplementedError("augment=True: test-time augmentation is not built for oriented-box models")
+
     def profile(self, source, **kwargs) -> list:
         """Per-layer device time of one pass over ``source`` (reference ``predict(profile=True)`` -> ``_profile_one_layer``, nn/tasks.py:171-191):
         [{layer, type, launches, ms, kernels}], see ``DetectionPredictor.profile_layers``."""
@@ -149,6 +170,8 @@ class Model(nn.Module):
 
         if self.task == "segment":
             raise NotImplementedError("train: the segmentation loss (v8SegmentationLoss) is not built; segmentation models predict only")
+        if self.task == "obb":
+            raise NotImplementedError("train: the oriented-box loss (v8OBBLoss) is not built; oriented-box models predict only")
         args = {**{k: v for k, v in self.overrides.items() if k not in ("task", "mode")}, **kwargs}
         devs = [x for x in str(args.get("device", "")).replace("cuda:", "").split(",") if x.strip() != ""]
         multi = len(devs) > 1
@@ -182,6 +205,8 @@ class Model(nn.Module):
         ``"synthetic[:N]"`` (engine/trainer.py::load_dataset; image folders and dataset YAMLs are outside the accelerated path);
         ``batch``, ``imgsz``, ``conf``, ``iou``, ``max_det``, ``half`` / ``dtype``, ``device`` as the reference's arguments.  Returns the
         reference's ``results_dict`` (metrics/precision(B) ... metrics/mAP50-95(B), fitness) with the validation losses; kept in ``self.metrics``."""
+        if self.task == "obb":
+            raise NotImplementedError("val: validation (OBBValidator, rotated matching) is not built for oriented-box models; they predict only")
         from .predictor import resolve_dtype
         from .trainer import TensorLoader, load_dataset
         from .validator import DetectionValidator

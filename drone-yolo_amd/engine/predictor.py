@@ -197,7 +197,7 @@ class DetectionPredictor:
         holder = {}
 
         def make_bufs(nb, anchors):  # Detect asks for the NMS buffers so that decode can fill the candidate list
-            holder["bufs"] = H.NmsBuffers(nb, anchors, int(a["max_det"]), self.device)
+            holder["bufs"] = self._new_nms_bufs(nb, anchors)
             return holder["bufs"]
 
         det.fused_nms = (make_bufs, float(a["conf"]), self._classes_mask)
@@ -207,19 +207,36 @@ class DetectionPredictor:
             with H.record(cf.plan):
                 y, aux = self.model._predict_once(im, image_dtype=self.dtype)
                 cf.pred = y
-                cf.nms = H.nms(y, float(a["conf"]), float(a["iou"]), max_det=int(a["max_det"]), max_nms=int(a["max_nms"]),
-                               max_wh=float(a["max_wh"]), agnostic=bool(a["agnostic_nms"]), nc=self.model.yaml["nc"],
-                               classes_mask=self._classes_mask, bufs=holder.get("bufs"), prefiltered="bufs" in holder)
+                cf.nms = self._record_nms(y, aux, holder.get("bufs"))
                 self._record_masks(cf, aux)  # (a segmentation model: the coefficient gather, in front of the box rescale)
                 # construct_result: scale_boxes(img.shape[2:], boxes, orig.shape) — tensor sources are their own
                 # original image, so gain 1 / pad 0 and the clip to (h, w) remain (detect/predict.py:59-73)
-                H.scale_boxes_(cf.nms, params)
+                self._record_scale(cf, params)
         finally:
             det.fused_nms = None
             det.fuse_tail = False
             self.model.fp8_layers = None
         cf.plan.keep.append(params)
         return cf
+
+    # ---- what a task changes in the recorded pass and in its results; the detection and segmentation tasks keep the four below as they are ----
+    def _new_nms_bufs(self, nb: int, anchors: int):
+        """The NMS buffers the Detect kernels' candidate filter fills and the NMS of ``_record_nms`` reads."""
+        return H.NmsBuffers(nb, anchors, int(self.args["max_det"]), self.device)
+
+    def _record_nms(self, y, aux, bufs):
+        """The NMS launch of the recorded pass; ``bufs``: what ``_new_nms_bufs`` made when the head's kernels filtered the candidates."""
+        a = self.args
+        return H.nms(y, float(a["conf"]), float(a["iou"]), max_det=int(a["max_det"]), max_nms=int(a["max_nms"]),
+                     max_wh=float(a["max_wh"]), agnostic=bool(a["agnostic_nms"]), nc=self.model.yaml["nc"],
+                     classes_mask=self._classes_mask, bufs=bufs, prefiltered=bufs is not None)
+
+    def _record_scale(self, cf: CompiledForward, params: torch.Tensor) -> None:
+        """construct_result's rescale of the kept rows to the original image, on the device."""
+        H.scale_boxes_(cf.nms, params)
+
+    def _result(self, img, path, names, rows, orig_shape, masks) -> Results:
+        return Results(img, path, names, boxes=rows, orig_shape=orig_shape, masks=masks)
 
     def _record_masks(self, cf: CompiledForward, aux) -> None:
         """Hook between the NMS and the box rescale of the recorded pass; the detection task launches nothing here."""
@@ -404,8 +421,8 @@ class DetectionPredictor:
         masks = self._masks_for(self._mask_stash(cf, streamed=False), counts, rows, im, info)
         for i, k in enumerate(counts):
             one = (info[i] if isinstance(info, list) else info) if info else None
-            out.append(Results(im[i], paths[i] if paths else f"image{i}.jpg", names, boxes=self._boxes_of(i, k, rows, tracked),
-                               orig_shape=(one[0], one[1]) if one else im.shape[2:], masks=masks[i]))
+            out.append(self._result(im[i], paths[i] if paths else f"image{i}.jpg", names, self._boxes_of(i, k, rows, tracked),
+                                    (one[0], one[1]) if one else im.shape[2:], masks[i]))
         return out
 
     # ---- image files and PIL images as sources (reference data/build.py:160-200 check_source / load_inference_source, data/loaders.py:284-420
@@ -490,8 +507,8 @@ class DetectionPredictor:
             masks = self._masks_for(stash, counts, rows, im, info)
             for i, k in enumerate(counts):
                 one = (info[i] if isinstance(info, list) else info) if info else None
-                r = Results(frames[i] if frames is not None else im[i], paths[i] if paths else f"image{lo + i}.jpg", names, boxes=self._boxes_of(i, k, rows, tracked),
-                            orig_shape=(one[0], one[1]) if one else im.shape[2:], masks=masks[i])
+                r = self._result(frames[i] if frames is not None else im[i], paths[i] if paths else f"image{lo + i}.jpg", names, self._boxes_of(i, k, rows, tracked),
+                                 (one[0], one[1]) if one else im.shape[2:], masks[i])
                 out.append(r)
             dt = (time.perf_counter() - t0) * 1e3 / max(len(out), 1)
             for r in out:  # host-side times per image (the device runs ahead: no synchronisation is placed around the stages)
@@ -734,3 +751,40 @@ class SegmentationPredictor(DetectionPredictor):
             out.append(allm[o : o + k] if k else None)
             o += k
         return out
+
+
+class OBBPredictor(DetectionPredictor):
+    """Predictor of the oriented-box models -- reference models/yolo/obb/predict.py:8-46.
+
+    The recorded pass is the detection pass (every Detect fusion and the fused candidate filter unchanged: the filter does not look at boxes)
+    plus the per-level angle branches and ``dy_obb_decode`` inside the head, then ``dy_nms_rotated`` in place of ``dy_nms`` and
+    ``dy_scale_rboxes`` in place of ``dy_scale_boxes``; one synchronisation per batch, and a streamed run copies the (N, max_det, 7) rows
+    behind the batch's launches as it copies detection rows.  ``Results.obb`` carries the rows; ``Results.boxes`` is None."""
+
+    def __init__(self, model, overrides: Optional[dict] = None):
+        a = overrides or {}
+        for k in ("tile", "augment"):  # before anything touches the device
+            if a.get(k) not in (None, False):
+                raise NotImplementedError(f"{k}: not built for oriented-box models")
+        super().__init__(model, overrides)
+        self.args["task"] = "obb"
+
+    def make_tracker(self):
+        raise NotImplementedError("track: tracking is not built for oriented-box models")
+
+    def _new_nms_bufs(self, nb: int, anchors: int):
+        return H.RNmsBuffers(nb, anchors, int(self.args["max_det"]), self.device)
+
+    def _record_nms(self, y, aux, bufs):
+        if not (isinstance(aux, tuple) and len(aux) == 3 and isinstance(aux[1], torch.Tensor)):
+            raise RuntimeError("OBBPredictor needs a model whose head is OBB")
+        a = self.args
+        return H.nms_rotated(y, aux[1], float(a["conf"]), float(a["iou"]), max_det=int(a["max_det"]), max_nms=int(a["max_nms"]),
+                             max_wh=float(a["max_wh"]), agnostic=bool(a["agnostic_nms"]), nc=self.model.yaml["nc"],
+                             classes_mask=self._classes_mask, bufs=bufs, prefiltered=bufs is not None)
+
+    def _record_scale(self, cf: CompiledForward, params: torch.Tensor) -> None:
+        H.scale_rboxes_(cf.nms, params)
+
+    def _result(self, img, path, names, rows, orig_shape, masks) -> Results:
+        return Results(img, path, names, obb=rows, orig_shape=orig_shape)

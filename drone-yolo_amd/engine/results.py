@@ -1,8 +1,9 @@
-"""Result containers (reference: ultralytics/engine/results.py: ``Results``, ``Boxes`` :1004).
+"""Result containers (reference: ultralytics/engine/results.py: ``Results``, ``Boxes`` :1004, ``OBB`` :1585).
 
-Only the tensor-view surface the detection and segmentation paths fill is kept (boxes, masks); plotting /
+Only the tensor-view surface the detection, segmentation and oriented-box paths fill is kept (boxes, masks, obb); plotting /
 saving / keypoints are out of scope.  ``Boxes`` wraps the (n, 6) rows [x1, y1, x2, y2, conf, cls]
-that ``dy_nms`` + ``dy_scale_boxes`` produced on the device, ``Masks`` the (n, H, W) bytes of ``dy_process_mask``.
+that ``dy_nms`` + ``dy_scale_boxes`` produced on the device, ``Masks`` the (n, H, W) bytes of ``dy_process_mask``, ``OBB`` the (n, 7) rows
+[x, y, w, h, rotation, conf, cls] of ``dy_nms_rotated`` + ``dy_scale_rboxes``.
 """
 from __future__ import annotations
 
@@ -105,15 +106,67 @@ class Masks(BaseTensor):
         raise NotImplementedError("Masks.xyn: polygon outlines need cv2.findContours, which this package does not depend on; use .data")
 
 
-class Results:
-    """Per-image result — reference results.py (`Results`): orig_img, orig_shape, boxes, masks, names, path, speed."""
+class OBB(BaseTensor):
+    """Oriented boxes of one image — reference results.py:1585-1806.  ``data``: (n, 7) [x, y, w, h, rotation, conf, cls], or (n, 8) with a
+    track id in front of conf (never produced here: tracking is not built for oriented boxes, ``id`` is None)."""
 
-    def __init__(self, orig_img, path, names, boxes=None, speed=None, orig_shape=None, masks=None):
+    def __init__(self, boxes, orig_shape):
+        if boxes.ndim == 1:
+            boxes = boxes[None, :]
+        assert boxes.shape[-1] in {7, 8}, f"expected 7 or 8 values but got {boxes.shape[-1]}"
+        super().__init__(boxes, orig_shape)
+        self.is_track = boxes.shape[-1] == 8
+
+    @property
+    def xywhr(self):
+        return self.data[:, :5]
+
+    @property
+    def conf(self):
+        return self.data[:, -2]
+
+    @property
+    def cls(self):
+        return self.data[:, -1]
+
+    @property
+    def id(self):
+        return self.data[:, -3] if self.is_track else None
+
+    @property
+    def xyxyxyxy(self):
+        """(n, 4, 2) corner points."""
+        return ops.xywhr2xyxyxyxy(self.xywhr)
+
+    @property
+    def xyxyxyxyn(self):
+        """The corner points divided by the original image's width and height."""
+        pts = self.xyxyxyxy
+        pts = pts.clone() if isinstance(pts, torch.Tensor) else np.copy(pts)
+        pts[..., 0] /= self.orig_shape[1]
+        pts[..., 1] /= self.orig_shape[0]
+        return pts
+
+    @property
+    def xyxy(self):
+        """(n, 4) axis-aligned boxes around the corner points."""
+        x, y = self.xyxyxyxy[..., 0], self.xyxyxyxy[..., 1]
+        if isinstance(x, torch.Tensor):
+            return torch.stack([x.amin(1), y.amin(1), x.amax(1), y.amax(1)], -1)
+        return np.stack([x.min(1), y.min(1), x.max(1), y.max(1)], -1)
+
+
+class Results:
+    """Per-image result — reference results.py (`Results`): orig_img, orig_shape, boxes, masks, obb, names, path, speed.  An oriented-box
+    result carries ``obb`` and no ``boxes``."""
+
+    def __init__(self, orig_img, path, names, boxes=None, speed=None, orig_shape=None, masks=None, obb=None):
         self._orig_img = orig_img
         self.orig_shape = tuple(orig_shape) if orig_shape is not None else tuple(orig_img.shape[:2])
         self.boxes = Boxes(boxes, self.orig_shape) if boxes is not None else None
         self.masks = Masks(masks, self.orig_shape) if masks is not None else None
-        self.probs = self.keypoints = self.obb = None
+        self.obb = OBB(obb, self.orig_shape) if obb is not None else None
+        self.probs = self.keypoints = None
         self.speed = speed if speed is not None else {"preprocess": None, "inference": None, "postprocess": None}
         self.names = names
         self.path = path
@@ -128,30 +181,37 @@ class Results:
         return im
 
     def __len__(self):
-        return 0 if self.boxes is None else len(self.boxes)
+        for v in (self.boxes, self.masks, self.obb):  # (the first that is there, as the reference's __len__)
+            if v is not None:
+                return len(v)
+        return 0
 
     def cpu(self):
         r = Results(self._orig_img, self.path, self.names, None, self.speed, self.orig_shape)
         r.boxes = self.boxes.cpu() if self.boxes is not None else None
         r.masks = self.masks.cpu() if self.masks is not None else None
+        r.obb = self.obb.cpu() if self.obb is not None else None
         return r
 
     def numpy(self):
         r = Results(self._orig_img, self.path, self.names, None, self.speed, self.orig_shape)
         r.boxes = self.boxes.numpy() if self.boxes is not None else None
         r.masks = self.masks.numpy() if self.masks is not None else None
+        r.obb = self.obb.numpy() if self.obb is not None else None
         return r
 
     def to(self, *args, **kwargs):
         r = Results(self._orig_img, self.path, self.names, None, self.speed, self.orig_shape)
         r.boxes = self.boxes.to(*args, **kwargs) if self.boxes is not None else None
         r.masks = self.masks.to(*args, **kwargs) if self.masks is not None else None
+        r.obb = self.obb.to(*args, **kwargs) if self.obb is not None else None
         return r
 
     def __getitem__(self, idx):
         r = Results(self._orig_img, self.path, self.names, None, self.speed, self.orig_shape)
         r.boxes = self.boxes[idx] if self.boxes is not None else None
         r.masks = self.masks[idx] if self.masks is not None else None
+        r.obb = self.obb[idx] if self.obb is not None else None
         return r
 
     # ---- text forms of a detection result (reference results.py:633-666 verbose, :668-757 save_txt, :759-823 summary, :906-940 to_json) ----
@@ -159,7 +219,7 @@ class Results:
         """'2 persons, 1 car, ' — detections per class in ascending class order; '(no detections), ' for none."""
         if len(self) == 0:
             return "(no detections), "
-        cls = torch.as_tensor(self.boxes.cls).cpu()
+        cls = torch.as_tensor((self.boxes if self.boxes is not None else self.obb).cls).cpu()
         out = ""
         for c in cls.unique():
             n = int((cls == c).sum())

@@ -1084,6 +1084,84 @@ def scale_boxes_(bufs: NmsBuffers, params: torch.Tensor) -> None:
             keep=(bufs, params))
 
 
+# ---- oriented boxes: rotated decode, ProbIoU fast NMS, regularize + scale of the kept rows ---------------------------------------
+def obb_decode(levels: Sequence[torch.Tensor], strides: Sequence[float], pred: torch.Tensor, nc: int,
+               theta: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``dy_obb_decode`` behind the Detect kernels.  ``levels``: the per-level angle logits, fp32 NHWC views (N, 1, h_i, w_i) in true units;
+    ``pred``: the decoded (N, 4 + nc(+extra), A) fp32 tensor, whose rows 0 and 1 are turned in place about the anchor points.
+    Returns ``theta`` (N, A) fp32 = (sigmoid(logit) - 0.25) * pi."""
+    require_device(pred, "prediction")
+    if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.dim() != 3 or pred.shape[1] < 4 + nc:
+        raise ValueError("obb_decode expects a contiguous fp32 (N, 4+nc, A) tensor")
+    n, ch, A = pred.shape
+    if len(levels) > _lib.DY_MAX_LEVELS or len(levels) != len(strides):
+        raise ValueError("obb_decode: one stride per level, at most DY_MAX_LEVELS levels")
+    if theta is None:
+        theta = torch.empty((n, A), dtype=torch.float32, device=pred.device)
+    elif tuple(theta.shape) != (n, A) or theta.dtype != torch.float32 or not theta.is_contiguous():
+        raise ValueError("obb_decode: theta must be a contiguous fp32 (N, A) tensor")
+    d = _lib.ObbDecodeDesc()
+    for i, t in enumerate(levels):
+        require_device(t, "angle map")
+        if t.dtype != torch.float32 or t.shape[0] != n or t.shape[1] < 1:
+            raise ValueError("obb_decode: angle maps must be fp32 (N, 1, h, w) NHWC views")
+        d.level[i], d.ld[i] = view_params(t)
+        d.h[i], d.w[i], d.stride[i] = t.shape[2], t.shape[3], float(strides[i])
+    d.n_levels, d.batch, d.nc, d.n_extra, d.anchors = len(levels), n, nc, ch - 4 - nc, A
+    d.pred, d.theta = pred.data_ptr(), theta.data_ptr()
+    _launch(lib().dy_obb_decode, (C.byref(d),), keep=(d, pred, theta, *levels))
+    return theta
+
+
+class RNmsBuffers:
+    """Persistent outputs + workspace of ``dy_nms_rotated`` for one (batch, anchors, max_det).  ``out`` (N, max_det, 7) = x, y, w, h, theta,
+    conf, cls.  The head of ``workspace`` is a ``dy_nms`` workspace, so the fused Detect candidate filters fill it as they fill
+    ``NmsBuffers.workspace``."""
+
+    def __init__(self, batch: int, anchors: int, max_det: int, device):
+        self.batch, self.anchors, self.max_det, self.cpa = batch, anchors, max_det, 1
+        nbytes = lib().dy_nms_rotated_workspace_bytes(batch, anchors)
+        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+        self.out = torch.empty((batch, max_det, 7), dtype=torch.float32, device=device)
+        self.count = torch.empty((batch,), dtype=torch.int32, device=device)
+        self.index = torch.empty((batch, max_det), dtype=torch.int32, device=device)
+
+
+def nms_rotated(pred: torch.Tensor, theta: torch.Tensor, conf_thres: float, iou_thres: float, max_det: int = 300, max_nms: int = 30000,
+                max_wh: float = 7680.0, agnostic: bool = False, nc: int = 0, classes_mask: Optional[torch.Tensor] = None,
+                bufs: Optional[RNmsBuffers] = None, prefiltered: bool = False, multi_label: bool = False) -> RNmsBuffers:
+    """Batched ProbIoU fast NMS (``dy_nms_rotated``) on (N, 4+nc(+extra), A) fp32 predictions and their (N, A) angles; results stay on the
+    device.  ``prefiltered``: ``bufs.workspace`` already holds the candidates (detect_decode(nms_bufs=bufs))."""
+    require_device(pred, "prediction")
+    require_device(theta, "angles")
+    if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.dim() != 3:
+        raise ValueError("nms_rotated expects a contiguous fp32 (N, 4+nc, A) tensor")
+    n, ch, A = pred.shape
+    if tuple(theta.shape) != (n, A) or theta.dtype != torch.float32 or not theta.is_contiguous():
+        raise ValueError("nms_rotated: theta must be a contiguous fp32 (N, A) tensor")
+    nc = nc or ch - 4
+    if bufs is None or (bufs.batch, bufs.anchors, bufs.max_det) != (n, A, max_det):
+        if prefiltered:
+            raise ValueError("nms_rotated(prefiltered=True) needs the RNmsBuffers that detect_decode filled")
+        bufs = RNmsBuffers(n, A, max_det, pred.device)
+    d = NmsDesc()
+    d.pred, d.batch, d.nc, d.n_extra, d.anchors = pred.data_ptr(), n, nc, ch - 4 - nc, A
+    d.conf_thres, d.iou_thres, d.max_det, d.max_nms = conf_thres, iou_thres, max_det, max_nms
+    d.max_wh, d.agnostic = max_wh, int(agnostic)
+    d.classes_mask = classes_mask.data_ptr() if classes_mask is not None else None
+    d.out, d.out_count, d.out_index = bufs.out.data_ptr(), bufs.count.data_ptr(), bufs.index.data_ptr()
+    d.workspace, d.workspace_bytes = bufs.workspace.data_ptr(), bufs.workspace.numel()
+    d.prefiltered, d.multi_label = int(prefiltered), int(bool(multi_label))
+    _launch(lib().dy_nms_rotated, (C.byref(d), theta.data_ptr()), keep=(d, pred, theta, bufs, classes_mask))
+    return bufs
+
+
+def scale_rboxes_(bufs: RNmsBuffers, params: torch.Tensor) -> None:
+    """In-place regularize_rboxes + scale_boxes(xywh=True) + clip_boxes of the kept rows; params: device fp32 (N,5)."""
+    _launch(lib().dy_scale_rboxes, (bufs.out.data_ptr(), bufs.count.data_ptr(), params.data_ptr(), bufs.batch, bufs.max_det),
+            keep=(bufs, params))
+
+
 # ---- instance segmentation: Proto's transposed convolution, coefficient gather, mask assembly ------------------------------------
 NM = 32  # mask coefficients per detection the kernels are built for (Segment's default nm)
 

@@ -34,9 +34,9 @@ class AutoBackend(nn.Module):
 
                 model, _ = load_reference_checkpoint(w)
             elif w.endswith((".yaml", ".yml")):
-                from .tasks import DetectionModel, SegmentationModel, guess_model_task
+                from .tasks import TASK_MODELS, guess_model_task
 
-                model = (SegmentationModel if guess_model_task(w) == "segment" else DetectionModel)(w, verbose=False)
+                model = TASK_MODELS[guess_model_task(w)](w, verbose=False)
             else:
                 raise NotImplementedError(f"'{w}': exported formats (onnx, engine, ...) are outside the accelerated path; give a module, *.pt or *.yaml")
         model = model.to(device)

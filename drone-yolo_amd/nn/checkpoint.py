@@ -63,6 +63,7 @@ def _own_classes() -> Dict[str, type]:
     out = {n: getattr(M, n) for n in dir(M) if isinstance(getattr(M, n), type)}
     out["DetectionModel"] = T.DetectionModel
     out["SegmentationModel"] = T.SegmentationModel
+    out["OBBModel"] = T.OBBModel
     out["BaseModel"] = T.BaseModel
     return out
 
@@ -126,11 +127,11 @@ def read_checkpoint_dict(path: str) -> Dict[str, Any]:
 
 
 def load_reference_checkpoint(path: str, verbose: bool = False):
-    """A ``DetectionModel`` (``SegmentationModel`` when the yaml's head is Segment) of this package carrying the checkpoint's architecture and weights."""
-    from .tasks import DetectionModel, SegmentationModel, guess_model_task
+    """A ``DetectionModel`` (``SegmentationModel`` / ``OBBModel`` when the yaml's head is Segment / OBB) of this package carrying the checkpoint's architecture and weights."""
+    from .tasks import TASK_MODELS, guess_model_task
 
     yaml_d, sd, meta = read_reference_checkpoint(path)
-    model = (SegmentationModel if guess_model_task(dict(yaml_d)) == "segment" else DetectionModel)(dict(yaml_d), ch=yaml_d.get("ch", 3), nc=yaml_d.get("nc"), verbose=verbose)
+    model = TASK_MODELS[guess_model_task(dict(yaml_d))](dict(yaml_d), ch=yaml_d.get("ch", 3), nc=yaml_d.get("nc"), verbose=verbose)
     own = model.state_dict()
     missing = [k for k in own if k not in sd]
     extra = [k for k in sd if k not in own]
@@ -148,7 +149,8 @@ _REF_PATHS = {"Conv": "ultralytics.nn.modules.conv", "DWConv": "ultralytics.nn.m
               "DFL": "ultralytics.nn.modules.block", "SPPF": "ultralytics.nn.modules.block", "C2f": "ultralytics.nn.modules.block",
               "Bottleneck": "ultralytics.nn.modules.block", "RepVGGBlock": "ultralytics.nn.modules.block", "SEBlock": "ultralytics.nn.modules.block",
               "Detect": "ultralytics.nn.modules.head", "DetectionModel": "ultralytics.nn.tasks", "BaseModel": "ultralytics.nn.tasks",
-              "Proto": "ultralytics.nn.modules.block", "Segment": "ultralytics.nn.modules.head", "SegmentationModel": "ultralytics.nn.tasks"}
+              "Proto": "ultralytics.nn.modules.block", "Segment": "ultralytics.nn.modules.head", "SegmentationModel": "ultralytics.nn.tasks",
+              "OBB": "ultralytics.nn.modules.head", "OBBModel": "ultralytics.nn.tasks"}
 _DROP_ATTRS = (PACKED, "_sig_tensors", "_weights_epoch", "_place", "_srcs", "_virtual", "_skip", "_front",
                "_consumers0", "_out_ch", "_cum_stride", "criterion", "train_dtype", "args", "fused_nms", "fuse_tail")
 

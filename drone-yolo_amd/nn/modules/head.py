@@ -1,4 +1,4 @@
-"""Detect and Segment heads of the Drone-YOLO path (reference: ultralytics/nn/modules/head.py:21-197)."""
+"""Detect, Segment and OBB heads of the Drone-YOLO path (reference: ultralytics/nn/modules/head.py:21-227)."""
 from __future__ import annotations
 
 import math
@@ -11,7 +11,7 @@ from .block import DFL, Proto
 from .conv import Conv, DWConv, PlainConv2d
 from .packs import PackOwner, packed
 
-__all__ = ("Detect", "Segment")
+__all__ = ("Detect", "Segment", "OBB")
 
 
 class Detect(PackOwner, nn.Module):
@@ -293,3 +293,62 @@ class Segment(Detect):
         bs = p.shape[0]
         mc = torch.cat([t.reshape(bs, self.nm, -1) for t in levels], 2)  # (layout glue of the module-level return only)
         return torch.cat([y, mc], 1), (feats, mc, p)
+
+
+class OBB(Detect):
+    """YOLO OBB head — reference head.py:200-227: Detect plus, per level, the angle branch ``cv4`` = Conv(x, c4, 3), Conv(c4, c4, 3),
+    Conv2d(c4, ne, 1); same constructor ``(nc, ne=1, ch)`` and state-dict keys.
+
+    The box and class branches go through every fusion of ``Detect`` unchanged and give the axis-aligned (N, 4 + nc, A) decode; ``dy_obb_decode``
+    then turns each centre about its anchor point by the anchor's angle, which IS the reference's dist2rbox, and writes
+    theta = (sigmoid(logit) - 0.25) * pi.  Eval forward returns the reference's ``(cat([y, angle], 1), (feats, angle))``.  On the
+    predictor's fast path (``fuse_tail``) nothing is concatenated: the return is ``(y, (None, theta, levels))`` with theta (N, A) and
+    ``levels`` the per-level fp32 NHWC angle-logit maps.
+    """
+
+    ANGLE_COUT = 8  # a 1x1 convolution with ONE output channel: its pack is padded with zero rows to a width the 1x1 kernels serve; channel 0 is read
+
+    def __init__(self, nc=80, ne=1, ch=()):
+        super().__init__(nc, ch)
+        self.ne = ne
+        c4 = max(ch[0] // 4, self.ne)
+        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), PlainConv2d(c4, self.ne, 1)) for x in ch)
+
+    def _packed_angle(self, i, dtype, device):
+        m = self.cv4[i][-1]
+
+        def build():  # (like the Detect tails the plain last conv leaves the scaled activation domain: the logits are in true units)
+            w, b, act = H.domain_fold(m.weight, m.bias, False, raw_output=True)
+            pad = self.ANGLE_COUT - w.shape[0]
+            w = torch.cat((w, w.new_zeros((pad, *w.shape[1:]))), 0)
+            b = torch.cat((b, b.new_zeros(pad)), 0)
+            return H.PackedConv(w, b, 1, 0, 1, act, dtype, device, for_out_f32=True)
+
+        return packed(self, ("angle", i), (m,), dtype, device, build)
+
+    def angle_maps(self, x):
+        """cv4 of every level: fp32 NHWC views (N, 1, h_i, w_i) of the raw angle logits, true units."""
+        out = []
+        for i in range(self.nl):
+            n, _, h, w = x[i].shape
+            buf = H.alloc_nhwc(n, self.ANGLE_COUT, h, w, torch.float32, x[i].device)
+            t = self._run_trunk(self.cv4[i], x[i])
+            H.conv2d(t, self._packed_angle(i, t.dtype, t.device), out=buf, out_f32=True)
+            out.append(buf[:, :1])
+        return out
+
+    def forward(self, x):
+        if self.training:
+            raise NotImplementedError("OBB: training an oriented-box model (v8OBBLoss) is not built; prediction only")
+        if any(t.dtype == H.FP8 for t in x):
+            raise NotImplementedError("OBB is built for the 16-bit, split-float16 and fp32 storage types")
+        if self.ne != 1:
+            raise NotImplementedError("OBB: one extra parameter per box (the angle) is what the rotated decode is built for")
+        x = list(x)
+        levels = self.angle_maps(x)
+        y, feats = Detect.forward(self, x)
+        theta = H.obb_decode(levels, [float(s) for s in self.stride], y, self.nc)
+        if self.fuse_tail:
+            return y, (None, theta, levels)
+        angle = theta[:, None]
+        return torch.cat([y, angle], 1), (feats, angle)

@@ -33,7 +33,7 @@ from .. import hip_ops as H
 from ..utils import LOGGER
 from ..utils.ops import make_divisible
 from ..utils.torch_utils import initialize_weights
-from .modules import SPPF, Bottleneck, C2f, Concat, Conv, Detect, DWConv, Proto, RepVGGBlock, Segment, Upsample
+from .modules import OBB, SPPF, Bottleneck, C2f, Concat, Conv, Detect, DWConv, Proto, RepVGGBlock, Segment, Upsample
 from .modules.block import DFL
 from .modules.conv import PlainConv2d
 from .modules.packs import PACKED, PackOwner, packed
@@ -42,7 +42,7 @@ CFG_DIR = Path(__file__).resolve().parents[1] / "cfg"
 
 _MODULES = {
     "Conv": Conv, "DWConv": DWConv, "RepVGGBlock": RepVGGBlock, "C2f": C2f, "SPPF": SPPF, "Bottleneck": Bottleneck,
-    "Concat": Concat, "Detect": Detect, "Segment": Segment, "nn.Upsample": Upsample,
+    "Concat": Concat, "Detect": Detect, "Segment": Segment, "OBB": OBB, "nn.Upsample": Upsample,
 }  # fmt: skip
 _BASE_MODULES = frozenset({Conv, DWConv, RepVGGBlock, C2f, SPPF, Bottleneck})
 _REPEAT_MODULES = frozenset({C2f})
@@ -107,7 +107,7 @@ def parse_model(d: dict, ch: int, verbose: bool = True):
                 n = 1
         elif m is Concat:
             c2 = sum(ch[x] for x in f)
-        elif m in (Detect, Segment):
+        elif m in (Detect, Segment, OBB):
             args.append([ch[x] for x in f])
             if m is Segment:  # the proto channels follow the width multiple (tasks.py:1058-1064)
                 args[2] = make_divisible(min(args[2], max_channels) * width, 8)
@@ -522,19 +522,42 @@ class SegmentationModel(DetectionModel):
         raise NotImplementedError("train: segmentation models predict only")
 
 
+class OBBModel(DetectionModel):
+    """YOLO oriented-box model — reference tasks.py:392-400.  Prediction only: the rotated loss (v8OBBLoss) is not built."""
+
+    def __init__(self, cfg="yolov8s-p2-repvgg-obb.yaml", ch=3, nc=None, verbose=True):
+        super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
+
+    def init_criterion(self):
+        raise NotImplementedError("train: the oriented-box loss (v8OBBLoss) is not built; oriented-box models predict only")
+
+    def _predict_augment(self, x, image_dtype=None):
+        raise NotImplementedError("augment=True is not built for oriented-box models")
+
+    def forward_train(self, img, dtype=None):
+        raise NotImplementedError("train: oriented-box models predict only")
+
+
+TASK_MODELS = {"detect": DetectionModel, "segment": SegmentationModel, "obb": OBBModel}
+
+
 def guess_model_task(model) -> str:
-    """'segment' or 'detect' from a YAML dict (its head's last module), a module graph (its head class) or a file name ('-seg') —
-    reference tasks.py:1127-1190, for the two tasks built here."""
+    """'segment', 'obb' or 'detect' from a YAML dict (its head's last module), a module graph (its head class) or a file name ('-seg',
+    '-obb') — reference tasks.py:1127-1190, for the three tasks built here."""
     if isinstance(model, dict):
         with contextlib.suppress(Exception):
-            return "segment" if str(model["head"][-1][-2]).lower() == "segment" else "detect"
+            return {"segment": "segment", "obb": "obb"}.get(str(model["head"][-1][-2]).lower(), "detect")
     if isinstance(model, nn.Module):
-        if any(isinstance(m, Segment) for m in model.modules()):
-            return "segment"
+        for m in model.modules():
+            if isinstance(m, Segment):
+                return "segment"
+            if isinstance(m, OBB):
+                return "obb"
         y = getattr(model, "yaml", None)
         return guess_model_task(y) if isinstance(y, dict) else "detect"
     if isinstance(model, (str, Path)):
-        return "segment" if "-seg" in Path(model).stem else "detect"
+        stem = Path(model).stem
+        return "segment" if "-seg" in stem else ("obb" if "-obb" in stem else "detect")
     return "detect"
 
 

@@ -31,6 +31,34 @@ def mask_iou(mask1: np.ndarray, mask2: np.ndarray, eps: float = 1e-7) -> np.ndar
     return inter / (union + np.float32(eps))
 
 
+def _covariance_terms(boxes):
+    """(a, b, c) of the Gaussian of xywhr boxes (N, 5), each (N, 1) — metrics.py:178-195 (the centres play no part)."""
+    a, b, r = boxes[:, 2:3].pow(2) / 12, boxes[:, 3:4].pow(2) / 12, boxes[:, 4:5]
+    cos, sin = r.cos(), r.sin()
+    cos2, sin2 = cos.pow(2), sin.pow(2)
+    return a * cos2 + b * sin2, a * sin2 + b * cos2, (a - b) * cos * sin
+
+
+def batch_probiou(obb1, obb2, eps: float = 1e-7):
+    """(N, 5) x (M, 5) xywhr boxes (tensors or arrays) -> (N, M) ProbIoU tensor in the inputs' precision — metrics.py:244-275, in torch as
+    there.  It is what ``dy_nms_rotated`` (csrc/obb.hip) evaluates pair by pair on the device and what that kernel is tested against."""
+    import torch
+
+    obb1 = torch.from_numpy(obb1) if isinstance(obb1, np.ndarray) else obb1
+    obb2 = torch.from_numpy(obb2) if isinstance(obb2, np.ndarray) else obb2
+    x1, y1 = obb1[:, 0:1], obb1[:, 1:2]
+    x2, y2 = obb2[:, 0][None], obb2[:, 1][None]
+    a1, b1, c1 = _covariance_terms(obb1)
+    a2, b2, c2 = (t.squeeze(-1)[None] for t in _covariance_terms(obb2))
+    det = (a1 + a2) * (b1 + b2) - (c1 + c2).pow(2)
+    t1 = (((a1 + a2) * (y1 - y2).pow(2) + (b1 + b2) * (x1 - x2).pow(2)) / (det + eps)) * 0.25
+    t2 = (((c1 + c2) * (x2 - x1) * (y1 - y2)) / (det + eps)) * 0.5
+    t3 = (det / (4 * ((a1 * b1 - c1.pow(2)).clamp(min=0) * (a2 * b2 - c2.pow(2)).clamp(min=0)).sqrt() + eps) + eps).log() * 0.5
+    bd = (t1 + t2 + t3).clamp(eps, 100.0)
+    hd = (1.0 - (-bd).exp() + eps).sqrt()
+    return 1 - hd
+
+
 def match_predictions(pred_classes: np.ndarray, true_classes: np.ndarray, iou: np.ndarray, iouv: np.ndarray) -> np.ndarray:
     """(D,) predicted classes, (L,) target classes, (L, D) IoU -> (D, len(iouv)) bool "correct" — validator.py:224-264 (the
     non-scipy branch: per threshold, matches sorted by IoU, each detection and then each label kept once)."""

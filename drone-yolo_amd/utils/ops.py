@@ -1,7 +1,9 @@
 """Post-processing ops of the detection path (reference: ultralytics/utils/ops.py).
 
 ``non_max_suppression`` (:181-332) keeps the reference signature and return type; the work is
-done by ``dy_nms`` (filter -> sort -> greedy suppression on the device).  ``xywh2xyxy`` (:432-449),
+done by ``dy_nms`` (filter -> sort -> greedy suppression on the device), or with ``rotated=True`` by
+``dy_nms_rotated`` (the same candidate stage, then ProbIoU fast NMS).  ``regularize_rboxes`` (:791-807),
+``xywhr2xyxyxyxy`` (:572-600) and ``nms_rotated`` (:146-178) are the oriented-box helpers under the reference's names.  ``xywh2xyxy`` (:432-449),
 ``scale_boxes`` (:92-127), ``clip_boxes`` (:335-354), ``make_divisible`` (:130-143) and ``Profile``
 (:17-62) are the small host helpers around it.
 """
@@ -112,6 +114,45 @@ def scale_boxes(img1_shape, boxes, img0_shape, ratio_pad=None, padding=True, xyw
     return clip_boxes(boxes, img0_shape)
 
 
+def regularize_rboxes(rboxes):
+    """xywhr boxes with the angle brought into [0, pi/2): w and h swap where ``t % pi >= pi/2`` — reference ops.py:791-807."""
+    x, y, w, h, t = rboxes.unbind(dim=-1)
+    swap = t % math.pi >= math.pi / 2
+    w_ = torch.where(swap, h, w)
+    h_ = torch.where(swap, w, h)
+    t = t % (math.pi / 2)
+    return torch.stack([x, y, w_, h_, t], dim=-1)
+
+
+def xywhr2xyxyxyxy(x):
+    """(cx, cy, w, h, rotation) of shape (n, 5) or (b, n, 5) -> corner points (..., 4, 2), tensors or arrays — reference ops.py:572-600."""
+    cos, sin, cat, stack = (torch.cos, torch.sin, torch.cat, torch.stack) if isinstance(x, torch.Tensor) else (np.cos, np.sin, np.concatenate, np.stack)
+    ctr = x[..., :2]
+    w, h, angle = (x[..., i : i + 1] for i in range(2, 5))
+    cos_value, sin_value = cos(angle), sin(angle)
+    vec1 = cat([w / 2 * cos_value, w / 2 * sin_value], -1)
+    vec2 = cat([-h / 2 * sin_value, h / 2 * cos_value], -1)
+    pt1 = ctr + vec1 + vec2
+    pt2 = ctr + vec1 - vec2
+    pt3 = ctr - vec1 - vec2
+    pt4 = ctr - vec1 + vec2
+    return stack([pt1, pt2, pt3, pt4], -2)
+
+
+def nms_rotated(boxes, scores, threshold=0.45, use_triu=True):
+    """Indices of the xywhr ``boxes`` (n, 5) that ProbIoU fast NMS keeps, in descending score order — reference ops.py:146-178, on the
+    device through ``dy_nms_rotated``: the boxes become a one-class, one-image prediction whose class row holds the scores.
+    Scores must lie in (0, 1]; ``use_triu`` selects an export form of the same result in the reference and is accepted and ignored."""
+    H.require_device(boxes, "boxes")
+    n = boxes.shape[0]
+    if n == 0:
+        return torch.zeros((0,), dtype=torch.long, device=boxes.device)
+    pred = torch.cat((boxes[:, :4].float().t(), scores.float()[None]), 0)[None].contiguous()
+    theta = boxes[:, 4].float()[None].contiguous()
+    bufs = H.nms_rotated(pred, theta, 0.0, float(threshold), max_det=min(n, 4096), max_nms=n, agnostic=True, nc=1)
+    return bufs.index[0, : int(bufs.count[0])].long()
+
+
 def non_max_suppression(
     prediction,
     conf_thres=0.25,
@@ -133,6 +174,11 @@ def non_max_suppression(
     """Reference ops.py:181-332 on the device via ``dy_nms``: the predictor's single-label path and the validator's ``multi_label``
     path (one candidate per (anchor, class) pair above conf, ops.py:286-288; models/yolo/detect/val.py:93-106).
 
+    ``rotated=True`` (ops.py:257-258, 307-309): ``prediction`` is (N, 4 + nc + 1, A) with the angle in the last row; the boxes stay xywh, the
+    suppression is ``dy_nms_rotated``'s, the rows are (n_i, 7) [x, y, w, h, conf, cls, angle] and ``return_padded`` gives ``RNmsBuffers``
+    (whose ``out`` columns are x, y, w, h, angle, conf, cls).  ``nc`` must be given, as the reference's predictor gives it: without it the
+    reference counts the angle row as one more class AND reads it as the angle, which is not built; neither is ``multi_label``.
+
     Returns a list (one (n_i, 6) tensor [x1, y1, x2, y2, conf, cls] per image) like the reference;
     ``return_padded=True`` returns the device-resident ``NmsBuffers`` (out (N,max_det,6), count (N,),
     index (N,max_det)) without any host synchronisation.  ``max_time_img`` is accepted and ignored:
@@ -142,8 +188,12 @@ def non_max_suppression(
     assert 0 <= iou_thres <= 1, f"Invalid IoU {iou_thres}, valid values are between 0.0 and 1.0"
     if isinstance(prediction, (list, tuple)):
         prediction = prediction[0]
-    if labels or rotated or end2end or prediction.shape[-1] == 6:
-        raise NotImplementedError("labels (autolabelling) / rotated / end2end NMS variants are not on the accelerated path")
+    if labels or end2end or prediction.shape[-1] == 6:
+        raise NotImplementedError("labels (autolabelling) / end2end NMS variants are not on the accelerated path")
+    if rotated and multi_label:
+        raise NotImplementedError("multi_label NMS (the validator's) is not built for rotated boxes")
+    if rotated and not nc:
+        raise NotImplementedError("rotated NMS without nc (the reference then takes the angle row for a class as well) is not built: pass nc, the angle is the row behind the classes")
     H.require_device(prediction, "prediction")
     nc = nc or (prediction.shape[1] - 4)
     mask = None
@@ -151,6 +201,14 @@ def non_max_suppression(
         mask = torch.zeros(nc, dtype=torch.uint8)
         mask[torch.as_tensor(list(classes), dtype=torch.long)] = 1
         mask = mask.to(prediction.device)
+    if rotated:
+        if prediction.shape[1] != 4 + nc + 1:
+            raise ValueError(f"rotated NMS expects (N, 4 + nc + 1, A) with the angle in the last row, got {tuple(prediction.shape)}")
+        rb = H.nms_rotated(prediction[:, : 4 + nc].float().contiguous(), prediction[:, -1].float().contiguous(), float(conf_thres), float(iou_thres),
+                           max_det=int(max_det), max_nms=int(max_nms), max_wh=float(max_wh), agnostic=bool(agnostic), nc=int(nc), classes_mask=mask)
+        if return_padded:
+            return rb
+        return [torch.cat((rb.out[i, :k, :4], rb.out[i, :k, 5:7], rb.out[i, :k, 4:5]), 1) for i, k in enumerate(rb.count.tolist())]
     pred = prediction if (prediction.dtype == torch.float32 and prediction.is_contiguous()) else prediction.float().contiguous()
     bufs = H.nms(pred, float(conf_thres), float(iou_thres), max_det=int(max_det), max_nms=int(max_nms),
                  max_wh=float(max_wh), agnostic=bool(agnostic), nc=int(nc), classes_mask=mask, multi_label=bool(multi_label))

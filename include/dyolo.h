@@ -594,6 +594,49 @@ int32_t dy_nms_small_cap(void);
 int32_t dy_scale_boxes(float* boxes, const int32_t* counts, const float* params, int32_t batch,
                        int32_t max_det, dy_stream_t stream);
 
+/* ---- oriented boxes (the reference's `obb` task, prediction) ------------------------------------------
+ * All three are plain launches: no host synchronisation, no allocation, every argument checked before any launch, so they can be
+ * recorded in a launch plan and captured in a hipGraph.  fp32 in the reference's order of operations, contraction off; expf / logf /
+ * sinf / cosf are the device's.
+ *
+ * dy_obb_decode.  Replaces: OBB.forward's angle = (cv4(x).sigmoid() - 0.25) * pi (nn/modules/head.py:217-221) and OBB.decode_bboxes =
+ * dist2rbox (utils/tal.py), behind the Detect kernels, whose decode already wrote cx = (ax + xf) s, cy = (ay + yf) s and wh into pred:
+ *   theta[b, a] = (sigmoid(level[l][b, y, x, 0]) - 0.25) * pi
+ *   (x, y)      = a s + R(theta) ((cx, cy) - a s),  a s = ((col + 0.5) s, (row + 0.5) s)      rows 0 and 1 of pred, in place
+ * level[i]: fp32 NHWC (batch, h[i], w[i], >= 1 channels) with pixel pitch ld[i]: the raw angle logits in true units (channel 0 is read);
+ * anchors are numbered level by level, row-major.  pred: fp32 (batch, 4 + nc + n_extra, anchors); rows 2.. are not touched.
+ * theta: fp32 (batch, anchors). */
+typedef struct dy_obb_decode_desc {
+  const float* level[DY_MAX_LEVELS];
+  int32_t h[DY_MAX_LEVELS], w[DY_MAX_LEVELS], ld[DY_MAX_LEVELS];
+  float stride[DY_MAX_LEVELS];
+  int32_t n_levels, batch, nc, n_extra, anchors;
+  float* pred;
+  float* theta;
+} dy_obb_decode_desc;
+int32_t dy_obb_decode(const dy_obb_decode_desc* d, dy_stream_t stream);
+
+/* dy_nms_rotated.  Replaces: ops.non_max_suppression(..., rotated=True) on the predictor's single-label path (utils/ops.py:257-313) with
+ * nms_rotated (:146-178) and batch_probiou (utils/metrics.py:178-275).  The descriptor is dy_nms's and so is the candidate stage: the
+ * filter (or a `prefiltered` workspace of the fused Detect filter), the keys, the order (descending score, then ascending anchor) and the
+ * max_nms truncation.  Boxes are (x + c, y + c, w, h, theta[b, anchor]) with c = cls * max_wh (0 with agnostic).  Suppression is the
+ * reference's FAST NMS, not a greedy scan: in score order candidate j is kept iff NO candidate i < j of the image has
+ * probiou(i, j) >= iou_thres, whether or not i was itself suppressed; the first max_det kept are emitted.
+ * out: fp32 (batch, max_det, 7) = x, y, w, h, theta, conf, cls (the column order of OBBPredictor.construct_result); rows >= count are zero.
+ * out_count (batch); out_index: optional (batch, max_det) anchors, -1 behind the count.
+ * workspace: dy_nms_rotated_workspace_bytes(batch, anchors) bytes; its head IS a dy_nms workspace (what the fused filter fills), behind it
+ * lies the table of the images with more than dy_nms_rotated_lds_cap() candidates.  multi_label: DY_ERR_UNSUPPORTED. */
+int64_t dy_nms_rotated_workspace_bytes(int32_t batch, int32_t anchors);
+int32_t dy_nms_rotated(const dy_nms_desc* d, const float* theta, dy_stream_t stream);
+int32_t dy_nms_rotated_lds_cap(void);
+
+/* dy_scale_rboxes.  Replaces: OBBPredictor.construct_result (models/yolo/obb/predict.py:43-45) on the kept rows, in place for rows <
+ * counts[b]: ops.regularize_rboxes (utils/ops.py:791-807: w and h swap iff theta mod pi >= pi / 2, then theta mod pi / 2, Python's `%`
+ * for negative theta) and ops.scale_boxes(..., xywh=True) (:92-127): x = (x - pad_x) / gain, y = (y - pad_y) / gain, w / gain, h / gain,
+ * then clip_boxes, which clamps columns 0 and 2 to [0, clip_w] and 1 and 3 to [0, clip_h] -- the WIDTH and HEIGHT too, as the reference does.
+ * rows: fp32 (batch, max_det, 7) of dy_nms_rotated.  params: DEVICE fp32 (batch, 5) as for dy_scale_boxes. */
+int32_t dy_scale_rboxes(float* rows, const int32_t* counts, const float* params, int32_t batch, int32_t max_det, dy_stream_t stream);
+
 /* ---- validation matching on the padded NMS output ------------------------------------------------------
  * Replaces: BaseValidator.match_predictions (engine/validator.py:224-264, the non-scipy branch) and the box_iou it is fed
  * (utils/metrics.py:52-71), with the clip of the predictions to the image (_prepare_pred, models/yolo/detect/val.py:119-124), for a
