@@ -102,6 +102,15 @@ int32_t dy_dtype_size(int32_t dtype);
  * bias: fp32[cout_pad].  residual (optional, same dtype as x) is added AFTER the
  * activation.  Requirements: cin % (16/elem_size) == 0, ld_* and view bases aligned
  * to 16 bytes (vector path) — unaligned OUTPUT views fall back to scalar stores.
+ *
+ * Views.  x, x2, residual and y are VIEWS: channel slices of wider buffers (a Concat's input or output), pitches padded to 16 bytes
+ * with whatever the allocation held.  Of a view a launch reads only elements [0, c) of the view's pixels and writes only elements
+ * [0, cout) of the output's pixels, whatever the surrounding bytes hold: the channels in front of and behind the slice, the rest of
+ * the pitch and the pixels in front of the first and behind the last image may be NaN or Inf patterns and come back bit for bit
+ * (a kernel whose address range is wider than the view masks those lanes; it never multiplies them by a zero weight).  The same holds
+ * for every entry point below that takes a pitch.  Documented exceptions: dy_conv2d_wgrad_nhwc and dy_colsum READ the tail of the
+ * last 16-byte chunk of a pixel (see there); nothing writes outside its view.  tests/test_conv_containment_gpu.py and
+ * tests/test_view_containment_gpu.py hold every dispatch leaf and every such entry point to it.
  */
 typedef struct dy_conv_desc {
   const void* x;         /* input view base */
@@ -708,11 +717,15 @@ int32_t dy_detection_loss(const dy_loss_desc* d, dy_stream_t stream);
  *   d describes the FORWARD convolution (x, batch, h, w_in, cin, ld_x, ho, wo, cout, ksize, stride, pad, dtype; w / bias /
  *   y are ignored); dz: NHWC view (batch, ho, wo, cout) of `dtype`, pitch ld_dz; dw: fp32, cout*ksize*ksize*cin, ZEROED by
  *   the caller (partial sums of pixel slabs are added with fp32 atomics).  ld_x / ld_dz must cover cin / cout rounded up to one
- *   16-byte chunk (the padding is read but only reaches entries that are never written).
+ *   16-byte chunk: the padding is read but only reaches entries that are never written, so those elements need be neither zero nor
+ *   finite — the product is an outer product over channels summed over PIXELS, and a pad channel of x (dz) is a column (row) of dw
+ *   that is dropped; NaN there leaves every written entry as it is (tests/test_view_containment_gpu.py, the "tails" cases: the 3x3,
+ *   1x1, generic and image-stem kernels).
  * Input gradient: dx = conv_transpose(dz, w) is run through dy_conv2d_nhwc itself on re-packed weights
  *   (w'[ci][2-r][2-q][co] = w[co][r][q][ci], stride 1; stride-2 layers read dz through `dil2`, a zero-dilated gather).
  * dy_colsum: out[c] += sum over rows of z[row][c] (bias gradient of the plain Detect convolutions); out zeroed by the caller;
- *   z 16-byte aligned, pitch a multiple of 16 bytes covering c rounded up to one chunk. */
+ *   z 16-byte aligned, pitch a multiple of 16 bytes covering c rounded up to one chunk: the tail of the last chunk is read, but only
+ *   channels < c are summed, so it may hold anything, NaN included. */
 int32_t dy_conv2d_wgrad_nhwc(const dy_conv_desc* d, const void* dz, int32_t ld_dz, float* dw, dy_stream_t stream);
 /* The same with a caller-owned workspace (device memory, 16-byte aligned, at least dy_conv2d_wgrad_workspace_bytes(d, ld_dz) bytes;
  * NULL / too small: the call behaves as dy_conv2d_wgrad_nhwc).  The 3x3 kernel (16-bit storage) then STORES each pixel slab's partial
