@@ -22,9 +22,8 @@
 //   3. box: a lane holds 4 of a side's 16 bins of one pixel; the softmax expectation is reduced over the four lane quarters with
 //      two xor-shuffles; the four sides meet through 2 KB of LDS and 256 threads write (cx, w) / (cy, h) of the 128 pixels;
 //      class: sigmoid per class, first arg-max over the quarters by shuffles (lowest class wins ties, as cls.max(1)), ballot +
-//      one atomicAdd per wave to append the candidates (key = ~score bits << 32 | anchor, as detect_head.hip / nms.hip).
-#include "common_hip.h"
-#include "nms_ws.h"
+//      one atomicAdd per wave to append the candidates (the key of detect_row.h's wave_append, stored by hand a tile later).
+#include "detect_row.h"
 #include "hreg_core.h"
 
 namespace DY_NS {
@@ -41,12 +40,7 @@ struct HheadArgs {
   unsigned x_bytes;
   float stride;
   int tilesX, tilesY, nSpatial;
-  int* counts;
-  unsigned long long* keys;
-  unsigned short* cls;
-  int P;
-  float conf;
-  const uint8_t* cmask;
+  FilterSink f;  // NMS candidate filter of the class branch (optional)
 };
 
 constexpr int kHhTH = HrS1::TH, kHhTW = HrS1::TW;
@@ -189,7 +183,7 @@ __global__ __launch_bounds__(256, 3) void conv3x3_hhead_kernel(const HheadArgs p
   auto out_rsrc = [&](int n) { return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(p.out) + (size_t)n * img_bytes, 0, (int)img_bytes, 0x00020000); };
   unsigned cm_bits = 0xffffu;  // classes_mask as bits (nc <= 16): no byte load behind the DMA in the filter
   if constexpr (KIND == 2) {
-    if (p.keys != nullptr && p.cmask != nullptr) cm_bits = (unsigned)__ballot(lane < p.nc && p.cmask[lane < p.nc ? lane : 0] != 0);
+    if (p.f.keys != nullptr && p.f.cmask != nullptr) cm_bits = (unsigned)__ballot(lane < p.nc && p.f.cmask[lane < p.nc ? lane : 0] != 0);
   }
   int pv_tile = 0, pv_base = 0;
   unsigned long long pv_mk0 = 0ull, pv_mk1 = 0ull;
@@ -198,8 +192,8 @@ __global__ __launch_bounds__(256, 3) void conv3x3_hhead_kernel(const HheadArgs p
   auto flush_keys = [&]() {
     if ((pv_mk0 | pv_mk1) != 0ull) {
       const TileAt t = tile_at(pv_tile);
-      const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(p.keys + (size_t)t.n * p.P, 0, p.P * 8, 0x00020000);
-      const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc(p.cls + (size_t)t.n * p.A, 0, p.A * 2, 0x00020000);
+      const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(p.f.keys + (size_t)t.n * p.f.P, 0, p.f.P * 8, 0x00020000);
+      const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc(p.f.cls + (size_t)t.n * p.A, 0, p.A * 2, 0x00020000);
       const int base = __builtin_amdgcn_readfirstlane(pv_base);
       const int n0 = __popcll(pv_mk0);
 #pragma unroll
@@ -283,14 +277,14 @@ __global__ __launch_bounds__(256, 3) void conv3x3_hhead_kernel(const HheadArgs p
           const int oj = __shfl_xor(bj, sh);
           if (ob > best || (ob == best && oj < bj)) best = ob, bj = oj;
         }
-        passv[j] = inside && lq == 0 && best > p.conf && ((cm_bits >> (bj & 15)) & 1u) != 0u;
+        passv[j] = inside && lq == 0 && best > p.f.conf && ((cm_bits >> (bj & 15)) & 1u) != 0u;
         pv_best[j] = best, pv_bj[j] = bj;
       }
-      if (p.keys != nullptr) {
+      if (p.f.keys != nullptr) {
         pv_mk0 = __ballot(passv[0]), pv_mk1 = __ballot(passv[1]);
         pv_tile = tile;
         const int total = __popcll(pv_mk0) + __popcll(pv_mk1);
-        if (total != 0 && lane == 0) pv_base = atomicAdd(p.counts + t.n, total);  // (value used by flush_keys, one tile later)
+        if (total != 0 && lane == 0) pv_base = atomicAdd(p.f.counts + t.n, total);  // (value used by flush_keys, one tile later)
       }
     }
   };
@@ -383,12 +377,9 @@ int32_t branch_entry(const dy_branch_desc* d, dy_stream_t stream) {
   a.x_bytes = (unsigned)((long long)d->batch * d->h * d->w * d->ld_x * 2);
   a.tilesX = (d->w + kHhTW - 1) / kHhTW, a.tilesY = (d->h + kHhTH - 1) / kHhTH;
   a.nSpatial = d->batch * a.tilesX * a.tilesY;
-  if (d->kind == 2 && d->nms_workspace) {
-    DY_REQUIRE(aligned16(d->nms_workspace) && d->nms_workspace_bytes >= (int64_t)nms_ws_bytes(d->batch, d->anchors), DY_ERR_WORKSPACE,
-               "dy_detect_branch_fused: nms_workspace too small or misaligned (need %lld bytes)", (long long)nms_ws_bytes(d->batch, d->anchors));
-    const NmsWs w = nms_ws_layout(d->nms_workspace, d->batch, d->anchors);
-    a.counts = w.counts, a.keys = w.keys, a.cls = w.cls, a.P = w.P;
-    a.conf = d->conf_thres, a.cmask = d->classes_mask;
+  if (d->kind == 2 && d->nms_workspace) {  // (the counts are zeroed once per pass, by dy_nms_reset_counts: every level's class branch appends)
+    const int rc = filter_sink_from_workspace("dy_detect_branch_fused", d->nms_workspace, d->nms_workspace_bytes, d->batch, d->anchors, d->nc, d->conf_thres, d->classes_mask, &a.f);
+    if (rc != DY_OK) return rc;
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   return d->dtype == DY_BF16 ? launch_hhead<bf16_t>(a, d->kind, st) : launch_hhead<f16_t>(a, d->kind, st);

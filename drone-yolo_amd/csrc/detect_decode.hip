@@ -1,15 +1,12 @@
-// Detect decode: DFL softmax-expectation + dist2bbox (xywh) * stride + sigmoid(cls), all levels in one
-// launch, fp32 throughout, with the NMS candidate filter optionally fused in.
-// Reference: nn/modules/head.py:100-131 (_inference), block.py:58-76 (DFL),
-// utils/tal.py:333-357 (make_anchors grid_cell_offset 0.5, dist2bbox); filter: utils/ops.py:250,290-295.
+// Detect decode of all levels in one launch, fp32 throughout, with the NMS candidate filter optionally fused in.  The decode of a
+// row and the filter's append are detect_row.h's.  Reference: nn/modules/head.py:100-131 (_inference).
 //
 // A single-wave workgroup owns 64 consecutive anchors of one (image, level).  Their head rows
 // (4*reg_max + nc logits each, pitch ld) are one contiguous span of the NHWC head buffer, so it is
 // copied to LDS with lane-linear 16-byte loads (every fetched byte is used once; a lane-per-row
 // float4 read pattern fetched ~4x the bytes) and each lane then reads its own row from LDS.
 // Writes: out[b][ch][a] — consecutive lanes are consecutive anchors, every channel row a coalesced store.
-#include "common_hip.h"
-#include "nms_ws.h"
+#include "detect_row.h"
 
 namespace dy {
 
@@ -21,13 +18,7 @@ struct DecodeArgs {
   float stride[DY_MAX_LEVELS];
   int n_levels, batch, nc, A, tilesPerImg;
   float* out;
-  // fused NMS filter (optional)
-  int* counts;
-  unsigned long long* keys;
-  unsigned short* cls;
-  int P;
-  float conf;
-  const uint8_t* cmask;
+  FilterSink f;  // fused NMS filter (optional)
 };
 
 template <int REG_MAX>
@@ -53,66 +44,12 @@ __global__ __launch_bounds__(64) void detect_decode_kernel(const DecodeArgs p) {
   const bool valid = tid < na;
   const int al = al0 + tid;
   const int a = p.a0[l] + al;
-  float best = 0.f;
-  int bj = 0;
+  RowBest rb{0.f, 0};
   if (valid) {
-    const float* r = rows + tid * ld;
     const int gy = al / p.w[l], gx = al - gy * p.w[l];
-    float dist[4];
-#pragma unroll
-    for (int side = 0; side < 4; ++side) {
-      float v[REG_MAX];
-#pragma unroll
-      for (int i = 0; i < REG_MAX; i += 4) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(r + side * REG_MAX + i);
-        v[i] = t[0], v[i + 1] = t[1], v[i + 2] = t[2], v[i + 3] = t[3];
-      }
-      float mx = v[0];
-#pragma unroll
-      for (int i = 1; i < REG_MAX; ++i) mx = fmaxf(mx, v[i]);
-      float den = 0.f, num = 0.f;
-#pragma unroll
-      for (int i = 0; i < REG_MAX; ++i) {
-        const float e = __builtin_amdgcn_exp2f((v[i] - mx) * 1.4426950408889634f);
-        den += e;
-        num += e * (float)i;
-      }
-      dist[side] = num * __builtin_amdgcn_rcpf(den);
-    }
-    const float ax = (float)gx + 0.5f, ay = (float)gy + 0.5f;
-    const float x1 = ax - dist[0], y1 = ay - dist[1], x2 = ax + dist[2], y2 = ay + dist[3];
-    const float s = p.stride[l];
-    float* o = p.out + (size_t)b * (size_t)(4 + p.nc) * p.A + a;
-    o[0] = (x1 + x2) * 0.5f * s;
-    o[(size_t)p.A] = (y1 + y2) * 0.5f * s;
-    o[(size_t)2 * p.A] = (x2 - x1) * s;
-    o[(size_t)3 * p.A] = (y2 - y1) * s;
-    const float* cl = r + 4 * REG_MAX;
-    for (int c = 0; c < p.nc; ++c) {
-      const float pr = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(cl[c] * -1.4426950408889634f));
-      o[(size_t)(4 + c) * p.A] = pr;
-      if (c == 0 || pr > best) {  // first arg-max, as cls.max(1) (ops.py:290)
-        best = pr;
-        bj = c;
-      }
-    }
+    rb = detect_decode_row<REG_MAX>(rows + tid * ld, 4 * REG_MAX, gx, gy, p.stride[l], p.out + (size_t)b * (size_t)(4 + p.nc) * p.A, a, p.A, p.nc);
   }
-  if (p.keys != nullptr) {  // fused candidate filter: one image per workgroup, so one ballot round per wave
-    bool pass = valid && best > p.conf;
-    if (pass && p.cmask) pass = p.cmask[bj] != 0;
-    const unsigned long long m = __ballot(pass);
-    if (m != 0ull) {
-      const int leader = __ffsll((long long)m) - 1;
-      int base = 0;
-      if (lane == leader) base = atomicAdd(p.counts + b, __popcll(m));
-      base = __shfl(base, leader);
-      if (pass) {
-        const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-        p.keys[(size_t)b * p.P + pos] = ((unsigned long long)(~__float_as_uint(best)) << 32) | (unsigned long long)(unsigned)a;
-        p.cls[(size_t)b * p.A + a] = (unsigned short)bj;
-      }
-    }
-  }
+  if (p.f.keys != nullptr) filter_append(p.f, lane, valid, rb, b, a, p.A);  // one image per workgroup, so one append per wave
 }
 
 }  // namespace dy
@@ -152,17 +89,9 @@ extern "C" int32_t dy_detect_decode(const dy_decode_desc* d, dy_stream_t stream)
   a.out = d->out;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (d->nms_workspace) {
-    DY_REQUIRE(d->nc <= 65535, DY_ERR_UNSUPPORTED, "dy_detect_decode: nc %d > 65535", d->nc);
-    DY_REQUIRE(aligned16(d->nms_workspace) && d->nms_workspace_bytes >= (int64_t)nms_ws_bytes(d->batch, A), DY_ERR_WORKSPACE,
-               "dy_detect_decode: nms_workspace too small or misaligned (need %lld bytes)", (long long)nms_ws_bytes(d->batch, A));
-    const NmsWs w = nms_ws_layout(d->nms_workspace, d->batch, A);
-    a.counts = w.counts;
-    a.keys = w.keys;
-    a.cls = w.cls;
-    a.P = w.P;
-    a.conf = d->conf_thres;
-    a.cmask = d->classes_mask;
-    zero_async(w.counts, (size_t)d->batch * 4, st);
+    const int rc = filter_sink_from_workspace("dy_detect_decode", d->nms_workspace, d->nms_workspace_bytes, d->batch, A, d->nc, d->conf_thres, d->classes_mask, &a.f);
+    if (rc != DY_OK) return rc;
+    zero_async(a.f.counts, (size_t)d->batch * 4, st);
   }
   const size_t smem = (size_t)kDecTile * ldmax * 4;
   DY_REQUIRE(smem <= 160 * 1024, DY_ERR_UNSUPPORTED, "dy_detect_decode: head pitch %d too large for the LDS tile", ldmax);

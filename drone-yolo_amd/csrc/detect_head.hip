@@ -2,8 +2,8 @@
 // + the NMS candidate filter, in one pass per 64-anchor tile, so the (batch, 4*reg_max + nc, A) fp32 logits never
 // reach HBM (unfused they are written once by two conv launches and read once by dy_detect_decode: 608 B per
 // anchor of traffic against 256 B of bf16 input + 56 B of output here).
-// Reference: nn/modules/head.py:43-57 (cv2[i][2], cv3[i][2]), :69-70 (cat), :100-131 (_inference),
-// block.py:58-76 (DFL), utils/tal.py:333-357 (make_anchors, dist2bbox); filter: utils/ops.py:250,290-295.
+// Reference: nn/modules/head.py:43-57 (cv2[i][2], cv3[i][2]), :69-70 (cat), :100-131 (_inference); decode and
+// filter: detect_row.h.
 //
 // One wave per workgroup; a workgroup walks kGroup consecutive 64-anchor tiles of one (image, level).
 //  * weights of both convs (DY_WLAYOUT_FRAG1X1 fragments) + biases are copied to LDS once per workgroup;
@@ -12,9 +12,8 @@
 //  * MFMA with the WEIGHTS as the A operand: D[cout][pixel], so a lane ends up with 4 consecutive output channels
 //    of one pixel -> one 16-byte LDS write into that pixel's logit row (pitch chosen bank-conflict free);
 //  * the next tile's inputs are requested right after the last MFMA, then the decode phase (one lane per anchor,
-//    identical arithmetic to detect_decode.hip) runs from LDS while those loads are in flight.
-#include "common_hip.h"
-#include "nms_ws.h"
+//    detect_row.h) runs from LDS while those loads are in flight.
+#include "detect_row.h"
 
 namespace dy {
 
@@ -32,12 +31,7 @@ struct HeadArgs {
   float stride[DY_MAX_LEVELS];
   int n_levels, batch, nc, A, groupsPerImg, nfc, mtc, pitch;  // nfc: fragments per k-group in the packed cls weights
   float* out;
-  int* counts;
-  unsigned long long* keys;
-  unsigned short* cls;
-  int P;
-  float conf;
-  const uint8_t* cmask;
+  FilterSink f;  // fused NMS filter (optional)
 };
 
 // NKB / NKC: k-groups (4 chunks of 16 B) of the box / class branch input channels.
@@ -131,70 +125,16 @@ __global__ __launch_bounds__(64) void detect_head_kernel(const HeadArgs p) {
     if (t + 1 < t_end) load_tile(t + 1);  // in flight during the decode phase
     __syncthreads();
 
-    // ---- decode phase: lane = anchor (same arithmetic as detect_decode_kernel) ----
+    // ---- decode phase: lane = anchor (detect_row.h) ----
     const int al = t * kHeadTile + lane;
     const bool valid = al < hw;
     const int a = p.a0[l] + al;
-    float best = 0.f;
-    int bj = 0;
+    RowBest rb{0.f, 0};
     if (valid) {
-      const float* r = rows + lane * pitch;
       const int gy = al / wl, gx = al - gy * wl;
-      float dist[4];
-#pragma unroll
-      for (int side = 0; side < 4; ++side) {
-        float v[REG_MAX];
-#pragma unroll
-        for (int i = 0; i < REG_MAX; i += 4) {
-          const f32x4 q = *reinterpret_cast<const f32x4*>(r + side * REG_MAX + i);
-          v[i] = q[0], v[i + 1] = q[1], v[i + 2] = q[2], v[i + 3] = q[3];
-        }
-        float mx = v[0];
-#pragma unroll
-        for (int i = 1; i < REG_MAX; ++i) mx = fmaxf(mx, v[i]);
-        float den = 0.f, num = 0.f;
-#pragma unroll
-        for (int i = 0; i < REG_MAX; ++i) {
-          const float e = __builtin_amdgcn_exp2f((v[i] - mx) * 1.4426950408889634f);
-          den += e;
-          num += e * (float)i;
-        }
-        dist[side] = num * __builtin_amdgcn_rcpf(den);
-      }
-      const float ax = (float)gx + 0.5f, ay = (float)gy + 0.5f;
-      const float x1 = ax - dist[0], y1 = ay - dist[1], x2 = ax + dist[2], y2 = ay + dist[3];
-      const float s = p.stride[l];
-      float* o = p.out + (size_t)b * (size_t)(4 + p.nc) * p.A + a;
-      o[0] = (x1 + x2) * 0.5f * s;
-      o[(size_t)p.A] = (y1 + y2) * 0.5f * s;
-      o[(size_t)2 * p.A] = (x2 - x1) * s;
-      o[(size_t)3 * p.A] = (y2 - y1) * s;
-      const float* cl = r + NB;
-      for (int c = 0; c < p.nc; ++c) {
-        const float pr = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(cl[c] * -1.4426950408889634f));
-        o[(size_t)(4 + c) * p.A] = pr;
-        if (c == 0 || pr > best) {  // first arg-max, as cls.max(1) (ops.py:290)
-          best = pr;
-          bj = c;
-        }
-      }
+      rb = detect_decode_row<REG_MAX>(rows + lane * pitch, NB, gx, gy, p.stride[l], p.out + (size_t)b * (size_t)(4 + p.nc) * p.A, a, p.A, p.nc);
     }
-    if (p.keys != nullptr) {
-      bool pass = valid && best > p.conf;
-      if (pass && p.cmask) pass = p.cmask[bj] != 0;
-      const unsigned long long m = __ballot(pass);
-      if (m != 0ull) {
-        const int leader = __ffsll((long long)m) - 1;
-        int base = 0;
-        if (lane == leader) base = atomicAdd(p.counts + b, __popcll(m));
-        base = __shfl(base, leader);
-        if (pass) {
-          const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-          p.keys[(size_t)b * p.P + pos] = ((unsigned long long)(~__float_as_uint(best)) << 32) | (unsigned long long)(unsigned)a;
-          p.cls[(size_t)b * p.A + a] = (unsigned short)bj;
-        }
-      }
-    }
+    if (p.f.keys != nullptr) filter_append(p.f, lane, valid, rb, b, a, p.A);
     __syncthreads();  // rows are rewritten by the next tile
   }
 }
@@ -307,70 +247,16 @@ __global__ __launch_bounds__(64) void detect_head_split_kernel(const HeadArgs p)
     if (t + 1 < t_end) load_tile(t + 1);
     __syncthreads();
 
-    // ---- decode phase: lane = anchor (the arithmetic of detect_head_kernel / detect_decode_kernel) ----
+    // ---- decode phase: lane = anchor (detect_row.h) ----
     const int al = t * kHeadTile + lane;
     const bool valid = al < hw;
     const int a = p.a0[l] + al;
-    float best = 0.f;
-    int bj = 0;
+    RowBest rb{0.f, 0};
     if (valid) {
-      const float* r = rows + lane * pitch;
       const int gy = al / wl, gx = al - gy * wl;
-      float dist[4];
-#pragma unroll
-      for (int side = 0; side < 4; ++side) {
-        float v[REG_MAX];
-#pragma unroll
-        for (int i = 0; i < REG_MAX; i += 4) {
-          const f32x4 q = *reinterpret_cast<const f32x4*>(r + side * REG_MAX + i);
-          v[i] = q[0], v[i + 1] = q[1], v[i + 2] = q[2], v[i + 3] = q[3];
-        }
-        float mx = v[0];
-#pragma unroll
-        for (int i = 1; i < REG_MAX; ++i) mx = fmaxf(mx, v[i]);
-        float den = 0.f, num = 0.f;
-#pragma unroll
-        for (int i = 0; i < REG_MAX; ++i) {
-          const float e = __builtin_amdgcn_exp2f((v[i] - mx) * 1.4426950408889634f);
-          den += e;
-          num += e * (float)i;
-        }
-        dist[side] = num * __builtin_amdgcn_rcpf(den);
-      }
-      const float ax = (float)gx + 0.5f, ay = (float)gy + 0.5f;
-      const float x1 = ax - dist[0], y1 = ay - dist[1], x2 = ax + dist[2], y2 = ay + dist[3];
-      const float s = p.stride[l];
-      float* o = p.out + (size_t)b * (size_t)(4 + p.nc) * p.A + a;
-      o[0] = (x1 + x2) * 0.5f * s;
-      o[(size_t)p.A] = (y1 + y2) * 0.5f * s;
-      o[(size_t)2 * p.A] = (x2 - x1) * s;
-      o[(size_t)3 * p.A] = (y2 - y1) * s;
-      const float* cl = r + NB;
-      for (int c = 0; c < p.nc; ++c) {
-        const float pr = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(cl[c] * -1.4426950408889634f));
-        o[(size_t)(4 + c) * p.A] = pr;
-        if (c == 0 || pr > best) {
-          best = pr;
-          bj = c;
-        }
-      }
+      rb = detect_decode_row<REG_MAX>(rows + lane * pitch, NB, gx, gy, p.stride[l], p.out + (size_t)b * (size_t)(4 + p.nc) * p.A, a, p.A, p.nc);
     }
-    if (p.keys != nullptr) {
-      bool pass = valid && best > p.conf;
-      if (pass && p.cmask) pass = p.cmask[bj] != 0;
-      const unsigned long long m = __ballot(pass);
-      if (m != 0ull) {
-        const int leader = __ffsll((long long)m) - 1;
-        int base = 0;
-        if (lane == leader) base = atomicAdd(p.counts + b, __popcll(m));
-        base = __shfl(base, leader);
-        if (pass) {
-          const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-          p.keys[(size_t)b * p.P + pos] = ((unsigned long long)(~__float_as_uint(best)) << 32) | (unsigned long long)(unsigned)a;
-          p.cls[(size_t)b * p.A + a] = (unsigned short)bj;
-        }
-      }
-    }
+    if (p.f.keys != nullptr) filter_append(p.f, lane, valid, rb, b, a, p.A);
     __syncthreads();
   }
 }
@@ -465,14 +351,9 @@ extern "C" int32_t dy_detect_head_decode(const dy_head_decode_desc* d, dy_stream
   a.out = d->out;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (d->nms_workspace) {
-    DY_REQUIRE(d->nc <= 65535, DY_ERR_UNSUPPORTED, "dy_detect_head_decode: nc %d > 65535", d->nc);
-    DY_REQUIRE(aligned16(d->nms_workspace) && d->nms_workspace_bytes >= (int64_t)nms_ws_bytes(d->batch, A), DY_ERR_WORKSPACE,
-               "dy_detect_head_decode: nms_workspace too small or misaligned (need %lld bytes)", (long long)nms_ws_bytes(d->batch, A));
-    const NmsWs w = nms_ws_layout(d->nms_workspace, d->batch, A);
-    a.counts = w.counts, a.keys = w.keys, a.cls = w.cls, a.P = w.P;
-    a.conf = d->conf_thres;
-    a.cmask = d->classes_mask;
-    zero_async(w.counts, (size_t)d->batch * 4, st);
+    const int rc = filter_sink_from_workspace("dy_detect_head_decode", d->nms_workspace, d->nms_workspace_bytes, d->batch, A, d->nc, d->conf_thres, d->classes_mask, &a.f);
+    if (rc != DY_OK) return rc;
+    zero_async(a.f.counts, (size_t)d->batch * 4, st);
   }
   const int nkb = (d->c_box + kc - 1) / kc, nkc = (d->c_cls + kc - 1) / kc;
   const size_t smem = (size_t)(nkb * 4 + nkc * a.nfc) * 1024 * (split ? 2 : 1) + (size_t)(4 * d->reg_max + a.mtc * 16) * 4 * (split ? 2 : 1) + (size_t)kHeadTile * pitch * 4;

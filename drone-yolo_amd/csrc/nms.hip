@@ -3,12 +3,10 @@
 //
 //   K1 nms_filter_kernel   all (image, anchor) pairs in parallel: best class score and FIRST
 //                          arg-max class (ops.py:290), keep score > conf (ops.py:250,291) and
-//                          the optional class filter (ops.py:294-295); survivors are appended
-//                          (wave-aggregated atomic) as 64-bit keys
-//                              key = (~float_bits(score) << 32) | anchor
-//                          Ascending key order == descending score, ties by ascending anchor
-//                          index == the stable descending sort torchvision's CPU kernel uses on
-//                          candidates listed in anchor order (ops.py:269 keeps anchor order).
+//                          the optional class filter (ops.py:294-295); survivors are appended as 64-bit
+//                          keys (detect_row.h, wave_append).  Ascending key order == descending score,
+//                          ties by ascending anchor index == the stable descending sort torchvision's CPU
+//                          kernel uses on candidates listed in anchor order (ops.py:269 keeps anchor order).
 //   K2 nms_suppress_kernel one workgroup per image: bitonic sort of the keys (LDS when they
 //                          fit, the global workspace otherwise), truncate to max_nms
 //                          (ops.py:301-302), then wave 0 runs the exact greedy scan in chunks of
@@ -18,14 +16,15 @@
 //                          exact because greedy NMS never revisits a kept box.  Serves the images with
 //                          more than NMS_SMALL_CAP candidates (the validator's conf 0.001, multi_label).
 //   K2s nms_small_kernel   the same for images with at most NMS_SMALL_CAP candidates, in 256 threads and
-//                          22 KB of LDS with the scan on four waves (described at the kernel).
+//                          22 KB of LDS with the scan on four waves (nms_scan.h).
 //
 // IoU and box arithmetic follow the reference operation by operation in fp32 with
 // contraction off, so that kept indices are bit-identical to the CPU path for identical
 // inputs:  xyxy = xy -/+ wh/2 (ops.py:432-449); boxes + cls*max_wh (ops.py:305,311);
 // area = (x2-x1)*(y2-y1); inter = max(0,xx2-xx1)*max(0,yy2-yy1);
 // suppress iff inter / (area_i + area_j - inter) > iou_thres.
-#include "nms_core.h"
+#include "detect_row.h"
+#include "nms_scan.h"
 
 #pragma clang fp contract(off)
 
@@ -59,23 +58,11 @@ __global__ __launch_bounds__(256) void nms_filter_kernel(const NmsArgs p) {
       if (pass && p.cmask) pass = p.cmask[bj] != 0;
     }
     // A wave's 64 consecutive (image, anchor) pairs may straddle images: peel one image per
-    // round, led by the lowest lane that still has a survivor to append.
+    // round, that of the lowest lane that still has a survivor to append (the round's leader in wave_append).
     u64 todo = __ballot(pass);
     while (todo != 0ull) {
-      const int leader = __ffsll((long long)todo) - 1;
-      const int bb = __shfl(b, leader);
-      const bool mine = pass && b == bb;
-      const u64 m = __ballot(mine);
-      int base = 0;
-      if (lane == leader) base = atomicAdd(p.counts + bb, __popcll(m));
-      base = __shfl(base, leader);
-      if (mine) {
-        const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-        const unsigned bits = __float_as_uint(best);
-        p.keys[(size_t)bb * p.P + pos] = ((u64)(~bits) << 32) | (u64)(unsigned)a;
-        p.cls[(size_t)bb * p.A + a] = (unsigned short)bj;
-      }
-      todo &= ~m;
+      const int bb = __shfl(b, __ffsll((long long)todo) - 1);
+      todo &= ~wave_append<true>(p.counts, p.keys, p.P, lane, pass && b == bb, bb, (unsigned)a, best, p.cls + (size_t)bb * p.A + a, bj);
     }
   }
 }
@@ -100,18 +87,8 @@ __global__ __launch_bounds__(256) void nms_filter_ml_kernel(const NmsArgs p) {
       if (pass && p.cmask) pass = p.cmask[c] != 0;
       u64 todo = __ballot(pass);
       while (todo != 0ull) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const int bb = __shfl(b, leader);
-        const bool mine = pass && b == bb;
-        const u64 m = __ballot(mine);
-        int base = 0;
-        if (lane == leader) base = atomicAdd(p.counts + bb, __popcll(m));
-        base = __shfl(base, leader);
-        if (mine) {
-          const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-          p.keys[(size_t)bb * p.P + pos] = ((u64)(~__float_as_uint(v)) << 32) | (u64)((unsigned)a * (unsigned)p.nc + (unsigned)c);
-        }
-        todo &= ~m;
+        const int bb = __shfl(b, __ffsll((long long)todo) - 1);
+        todo &= ~wave_append<false>(p.counts, p.keys, p.P, lane, pass && b == bb, bb, (unsigned)a * (unsigned)p.nc + (unsigned)c, v);
       }
     }
   }
@@ -132,13 +109,7 @@ __device__ __forceinline__ bool iou_gt(float ix1, float iy1, float ix2, float iy
 // suppression bit matrix and one verdict word per wave: 16,928 + 20 * max_det bytes (22,928 B at max_det 300), so that the convolution
 // workgroups of another stream fit on the same CU.  Same order, same arithmetic, same outputs as nms_suppress_kernel below:
 //   sort     bitonic in LDS, 256 threads over the P2 / 2 <= 1024 compare-exchange pairs of a pass;
-//   scan     per chunk of 64 candidates (lane = candidate, every wave holds the same 64): wave w tests them against kept boxes
-//            w, w + 4, ... and publishes a ballot of the suppressed lanes; wave w also computes rows 16 w .. 16 w + 15 of the chunk's
-//            bit matrix (row i, bit j: box i as the kept box suppresses candidate j).  After one barrier every wave ORs the four
-//            verdicts, takes row[lane] into a register and resolves the chunk in score order with bit operations only
-//            (lowest live bit t is kept; live &= ~row[t]), the same on all four waves, so no second exchange is needed.  Wave 0
-//            appends the kept boxes and writes their rows; a barrier publishes the kept list to the next chunk.
-// The next chunk's keys, classes and boxes are fetched while the current chunk is scanned.
+//   scan     nms_greedy_scan on four waves (nms_scan.h) with the policy NmsSmallScan below.
 // The count is known on the device only, so dy_nms launches both kernels and each returns at once for the images of the other.
 constexpr int NMS_SMALL_CAP = 2048;
 constexpr int NMS_SMALL_THREADS = 256;
@@ -147,37 +118,80 @@ constexpr int NMS_SMALL_FIXED_LDS = NMS_SMALL_CAP * 8 + 64 * 8 + NMS_SMALL_WAVES
 
 static inline size_t nms_small_lds_bytes(int max_det) { return (size_t)NMS_SMALL_FIXED_LDS + (size_t)max_det * 20; }
 
-struct NmsCand {  // what a lane fetches for its candidate of a chunk
+struct NmsCand {  // what a lane fetches for its candidate
   float cx, cy, w, h, score;
   int anchor, cls;
 };
 
-__device__ __forceinline__ NmsCand nms_small_fetch(const NmsArgs& p, const u64* skeys, const float* pr, int b, int i, int nn) {
-  NmsCand c{0.f, 0.f, 0.f, 0.f, 0.f, 0, 0};
-  if (i < nn) {
-    const u64 key = skeys[i];
-    c.anchor = (int)(unsigned)(key & 0xffffffffull);
-    c.score = __uint_as_float(~(unsigned)(key >> 32));
-    if (p.multi) {
-      c.cls = c.anchor % p.nc;
-      c.anchor = c.anchor / p.nc;
-    } else {
-      c.cls = (int)p.cls[(size_t)b * p.A + c.anchor];
-    }
-    c.cx = pr[c.anchor];
-    c.cy = pr[(size_t)p.A + c.anchor];
-    c.w = pr[(size_t)2 * p.A + c.anchor];
-    c.h = pr[(size_t)3 * p.A + c.anchor];
+// the candidate a key stands for: anchor (and class, with multi_label) from the low word, score from the high word, box from pred
+__device__ __forceinline__ NmsCand nms_cand(const NmsArgs& p, const float* pr, int b, u64 key) {
+  NmsCand c;
+  c.anchor = (int)(unsigned)(key & 0xffffffffull);
+  c.score = __uint_as_float(~(unsigned)(key >> 32));
+  if (p.multi) {
+    c.cls = c.anchor % p.nc;
+    c.anchor = c.anchor / p.nc;
+  } else {
+    c.cls = (int)p.cls[(size_t)b * p.A + c.anchor];
   }
+  c.cx = pr[c.anchor];
+  c.cy = pr[(size_t)p.A + c.anchor];
+  c.w = pr[(size_t)2 * p.A + c.anchor];
+  c.h = pr[(size_t)3 * p.A + c.anchor];
   return c;
 }
 
-// a value every lane holds alike, moved to scalar registers (the compiler cannot see that an LDS read is wave-uniform)
-__device__ __forceinline__ u64 nms_uniform64(u64 v) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
-  return ((u64)hi << 32) | (u64)lo;
+struct NmsBoxes {
+  float x1, y1, x2, y2;  // the output row's xyxy (ops.py:432-449)
+  ScanBox off;           // the same plus cls * max_wh (ops.py:305,311) and its area: what the IoU sees
+};
+
+__device__ __forceinline__ NmsBoxes nms_boxes(const NmsArgs& p, const NmsCand& c) {
+  NmsBoxes r;
+  const float hw = c.w / 2.f, hh = c.h / 2.f;
+  r.x1 = c.cx - hw, r.y1 = c.cy - hh, r.x2 = c.cx + hw, r.y2 = c.cy + hh;
+  const float off = p.agnostic ? 0.f : (float)c.cls * p.max_wh;
+  r.off.x1 = r.x1 + off, r.off.y1 = r.y1 + off, r.off.x2 = r.x2 + off, r.off.y2 = r.y2 + off;
+  r.off.area = (r.off.x2 - r.off.x1) * (r.off.y2 - r.off.y1);
+  r.off.cls = 0;
+  return r;
 }
+
+__device__ __forceinline__ void nms_store_row(const NmsArgs& p, float* outb, int b, int at, const NmsCand& c, const NmsBoxes& bx) {
+  float* o = outb + (size_t)at * 6;
+  o[0] = bx.x1;
+  o[1] = bx.y1;
+  o[2] = bx.x2;
+  o[3] = bx.y2;
+  o[4] = c.score;
+  o[5] = (float)c.cls;
+  if (p.out_index) p.out_index[(size_t)b * p.max_det + at] = c.anchor;
+}
+
+struct NmsSmallScan {  // nms_greedy_scan's policy: class-offset boxes, IoU, kept list = float4 boxes + areas
+  const NmsArgs& p;
+  const u64* skeys;
+  const float* pr;
+  float* outb;
+  float4* kbox;  // [max_det] offset xyxy of the kept boxes
+  float* kar;    // [max_det] their areas
+  int b;
+  typedef NmsCand Cand;
+  __device__ __forceinline__ Cand fetch(int i, int n) const { return i < n ? nms_cand(p, pr, b, skeys[i]) : Cand{0.f, 0.f, 0.f, 0.f, 0.f, 0, 0}; }
+  __device__ __forceinline__ ScanBox box(const Cand& c) const { return nms_boxes(p, c).off; }
+  __device__ __forceinline__ bool suppresses(const ScanBox& k, const ScanBox& c) const {
+    return iou_gt(k.x1, k.y1, k.x2, k.y2, k.area, c.x1, c.y1, c.x2, c.y2, c.area, p.iou);
+  }
+  __device__ __forceinline__ ScanBox kept(int k) const {
+    const float4 kb = kbox[k];
+    return ScanBox{kb.x, kb.y, kb.z, kb.w, kar[k], 0};
+  }
+  __device__ __forceinline__ void keep(int at, const Cand& c, const ScanBox& bx) const {
+    kbox[at] = make_float4(bx.x1, bx.y1, bx.x2, bx.y2);
+    kar[at] = bx.area;
+    nms_store_row(p, outb, b, at, c, nms_boxes(p, c));
+  }
+};
 
 __global__ __launch_bounds__(NMS_SMALL_THREADS) void nms_small_kernel(const NmsArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
@@ -188,11 +202,8 @@ __global__ __launch_bounds__(NMS_SMALL_THREADS) void nms_small_kernel(const NmsA
   u64* skeys = reinterpret_cast<u64*>(dyn_smem);
   u64* rows = skeys + NMS_SMALL_CAP;  // [64]
   u64* verdict = rows + 64;           // [NMS_SMALL_WAVES]
-  float4* kbox = reinterpret_cast<float4*>(dyn_smem + NMS_SMALL_FIXED_LDS);  // [max_det] offset xyxy of the kept boxes
-  float* kar = reinterpret_cast<float*>(kbox + p.max_det);                   // [max_det] their areas
+  float4* kbox = reinterpret_cast<float4*>(dyn_smem + NMS_SMALL_FIXED_LDS);
   const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const u64* gkeys = p.keys + (size_t)b * p.P;
 
   int P2 = 1;
@@ -201,74 +212,10 @@ __global__ __launch_bounds__(NMS_SMALL_THREADS) void nms_small_kernel(const NmsA
   __syncthreads();
   nms_bitonic_sort<NMS_SMALL_THREADS>(skeys, P2, tid);
 
-  const int nn = n < p.max_nms ? n : p.max_nms;
-  const float* pr = p.pred + (size_t)b * p.nch * (size_t)p.A;
   float* outb = p.out + (size_t)b * p.max_det * 6;
-  const u64 lane_bit = 1ull << lane;
-  int nk = 0;
-  NmsCand nxt = nms_small_fetch(p, skeys, pr, b, lane, nn);
-  for (int c0 = 0; c0 < nn && nk < p.max_det; c0 += 64) {
-    const NmsCand c = nxt;
-    nxt = nms_small_fetch(p, skeys, pr, b, c0 + 64 + lane, nn);
-    const bool in = c0 + lane < nn;
-    const float hw = c.w / 2.f, hh = c.h / 2.f;
-    const float x1 = c.cx - hw, y1 = c.cy - hh, x2 = c.cx + hw, y2 = c.cy + hh;
-    const float off = p.agnostic ? 0.f : (float)c.cls * p.max_wh;
-    const float ox1 = x1 + off, oy1 = y1 + off, ox2 = x2 + off, oy2 = y2 + off;
-    const float area = (ox2 - ox1) * (oy2 - oy1);
-    // this wave's share of the kept list
-    bool sup = false;
-    for (int k = wave; k < nk; k += NMS_SMALL_WAVES) {
-      const float4 kb = kbox[k];
-      sup |= iou_gt(kb.x, kb.y, kb.z, kb.w, kar[k], ox1, oy1, ox2, oy2, area, p.iou);
-    }
-    const u64 sm = __ballot(sup);
-    // this wave's 16 rows of the chunk's suppression matrix
-    u64 myrow = 0ull;
-    for (int r = 0; r < 16; ++r) {
-      const int i = wave * 16 + r;  // wave-uniform: v_readlane
-      auto bcast = [&](float v) { return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(v), i)); };
-      const u64 m = __ballot(iou_gt(bcast(ox1), bcast(oy1), bcast(ox2), bcast(oy2), bcast(area), ox1, oy1, ox2, oy2, area, p.iou));
-      if (lane == r) myrow = m;
-    }
-    if (lane < 16) rows[wave * 16 + lane] = myrow;
-    if (lane == 0) verdict[wave] = sm;
-    __syncthreads();
-    u64 dead = 0ull;
-    for (int w = 0; w < NMS_SMALL_WAVES; ++w) dead |= verdict[w];
-    const u64 row = rows[lane];
-    const unsigned row_lo = (unsigned)row, row_hi = (unsigned)(row >> 32);
-    u64 am = __ballot(in) & ~nms_uniform64(dead);  // candidates of the chunk that no earlier kept box suppresses
-    u64 km = 0ull;                                 // those the chunk keeps
-    int cnt = 0;
-    while (am != 0ull) {
-      const int t = __ffsll((long long)am) - 1;  // best live candidate of the chunk (wave-uniform)
-      km |= 1ull << t;
-      ++cnt;
-      if (nk + cnt >= p.max_det) break;
-      const u64 rt = ((u64)(unsigned)__builtin_amdgcn_readlane((int)row_hi, t) << 32) | (u64)(unsigned)__builtin_amdgcn_readlane((int)row_lo, t);
-      am &= ~(rt | (1ull << t));
-    }
-    if (wave == 0 && (km & lane_bit) != 0ull) {
-      const int at = nk + __popcll(km & (lane_bit - 1ull));
-      kbox[at] = make_float4(ox1, oy1, ox2, oy2);
-      kar[at] = area;
-      float* o = outb + (size_t)at * 6;
-      o[0] = x1;
-      o[1] = y1;
-      o[2] = x2;
-      o[3] = y2;
-      o[4] = c.score;
-      o[5] = (float)c.cls;
-      if (p.out_index) p.out_index[(size_t)b * p.max_det + at] = c.anchor;
-    }
-    nk += cnt;
-    __syncthreads();  // the kept list is complete before the next chunk reads it; rows / verdict may be rewritten
-  }
-  for (int r = nk * 6 + tid; r < p.max_det * 6; r += NMS_SMALL_THREADS) outb[r] = 0.f;
-  if (p.out_index)
-    for (int r = nk + tid; r < p.max_det; r += NMS_SMALL_THREADS) p.out_index[(size_t)b * p.max_det + r] = -1;
-  if (tid == 0) p.out_count[b] = nk;
+  const NmsSmallScan pol{p, skeys, p.pred + (size_t)b * p.nch * (size_t)p.A, outb, kbox, reinterpret_cast<float*>(kbox + p.max_det), b};
+  nms_greedy_scan<NMS_SMALL_WAVES>(pol, n < p.max_nms ? n : p.max_nms, p.max_det, rows, verdict, outb,
+                                   p.out_index ? p.out_index + (size_t)b * p.max_det : nullptr, p.out_count + b);
 }
 
 __global__ __launch_bounds__(1024) void nms_suppress_kernel(const NmsArgs p) {
@@ -310,36 +257,18 @@ __global__ __launch_bounds__(1024) void nms_suppress_kernel(const NmsArgs p) {
   for (int c0 = 0; c0 < nn && nk < p.max_det; c0 += 64) {
     const int i = c0 + lane;
     bool alive = i < nn;
-    float x1 = 0.f, y1 = 0.f, x2 = 0.f, y2 = 0.f, ox1 = 0.f, oy1 = 0.f, ox2 = 0.f, oy2 = 0.f, area = 0.f, score = 0.f;
-    int anchor = 0, cls = 0;
+    NmsCand c{0.f, 0.f, 0.f, 0.f, 0.f, 0, 0};
+    NmsBoxes bx{0.f, 0.f, 0.f, 0.f, ScanBox{0.f, 0.f, 0.f, 0.f, 0.f, 0}};
     if (alive) {
-      const u64 key = in_lds ? skeys[i] : gkeys[i];
-      anchor = (int)(unsigned)(key & 0xffffffffull);
-      score = __uint_as_float(~(unsigned)(key >> 32));
-      if (p.multi) {
-        cls = anchor % p.nc;
-        anchor = anchor / p.nc;
-      } else {
-        cls = (int)p.cls[(size_t)b * p.A + anchor];
-      }
-      const float cx = pr[anchor], cy = pr[(size_t)p.A + anchor];
-      const float hw = pr[(size_t)2 * p.A + anchor] / 2.f, hh = pr[(size_t)3 * p.A + anchor] / 2.f;
-      x1 = cx - hw;
-      y1 = cy - hh;
-      x2 = cx + hw;
-      y2 = cy + hh;
-      const float off = p.agnostic ? 0.f : (float)cls * p.max_wh;
-      ox1 = x1 + off;
-      oy1 = y1 + off;
-      ox2 = x2 + off;
-      oy2 = y2 + off;
-      area = (ox2 - ox1) * (oy2 - oy1);
+      c = nms_cand(p, pr, b, in_lds ? skeys[i] : gkeys[i]);
+      bx = nms_boxes(p, c);
       for (int k = 0; k < nk; ++k)
-        if (iou_gt(kx1[k], ky1[k], kx2[k], ky2[k], kar[k], ox1, oy1, ox2, oy2, area, p.iou)) {
+        if (iou_gt(kx1[k], ky1[k], kx2[k], ky2[k], kar[k], bx.off.x1, bx.off.y1, bx.off.x2, bx.off.y2, bx.off.area, p.iou)) {
           alive = false;
           break;
         }
     }
+    const float ox1 = bx.off.x1, oy1 = bx.off.y1, ox2 = bx.off.x2, oy2 = bx.off.y2, area = bx.off.area;
     u64 am = __ballot(alive);
     while (am != 0ull) {
       const int t = __ffsll((long long)am) - 1;  // best surviving candidate of the chunk (wave-uniform)
@@ -352,14 +281,7 @@ __global__ __launch_bounds__(1024) void nms_suppress_kernel(const NmsArgs p) {
         kx2[nk] = ox2;
         ky2[nk] = oy2;
         kar[nk] = area;
-        float* o = outb + (size_t)nk * 6;
-        o[0] = x1;
-        o[1] = y1;
-        o[2] = x2;
-        o[3] = y2;
-        o[4] = score;
-        o[5] = (float)cls;
-        if (p.out_index) p.out_index[(size_t)b * p.max_det + nk] = anchor;
+        nms_store_row(p, outb, b, nk, c, bx);
         alive = false;
       }
       ++nk;

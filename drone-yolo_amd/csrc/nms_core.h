@@ -1,5 +1,5 @@
-// The candidate stage dy_nms (nms.hip) and dy_nms_rotated (obb.hip) share: the kernel arguments, the filter launch and the key sort.
-//   key = (~float_bits(score) << 32) | anchor: ascending key order == descending score, ties by ascending anchor (nms.hip, K1).
+// The candidate stage dy_nms (nms.hip) and dy_nms_rotated (obb.hip) share: the kernel arguments, the filter launch and the key sort
+// (tile_merge.hip sorts with it too).  The keys are those of detect_row.h's wave_append.
 #pragma once
 #include "common_hip.h"
 #include "nms_ws.h"

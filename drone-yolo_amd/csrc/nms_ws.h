@@ -1,4 +1,4 @@
-// Layout of the dy_nms workspace, shared by nms.hip and the fused filter in detect_decode.hip.
+// Layout of the dy_nms workspace, shared by nms.hip and the fused Detect filters (detect_row.h, FilterSink).
 //   [counts: int32 x batch, padded to 256 B][keys: u64 x batch x P][cls: u16 x batch x anchors, padded to 256 B]
 // P = next power of two >= anchors (room for the bitonic sort's padding).
 #pragma once

@@ -7,22 +7,16 @@
 //                         compact   the rows r < counts[tile] are appended (wave-aggregated, one LDS atomic per wave) as 64-bit keys
 //                                       key = (~float_bits(score) << 32) | slot,   slot = k * max_det + r
 //                                   so that ascending key order is descending score, ties by ascending slot;
-//                         sort      bitonic, in LDS when the keys fit, in the workspace otherwise (two loops: see nms.hip on flat accesses);
-//                         scan      greedy, in chunks of 64 candidates held alike by all 16 waves (lane = candidate): wave w tests them against
-//                                   the kept boxes w, w + 16, ... and publishes a ballot; wave w also computes rows 4 w .. 4 w + 3 of the chunk's
-//                                   64 x 64 suppression bit matrix.  After one barrier every wave resolves the chunk in score order with bit
-//                                   operations (lowest live bit t is kept; live &= ~row[t]); wave 0 appends the kept boxes and writes their rows.
+//                         sort      bitonic, in LDS when the keys fit, in the workspace otherwise (two calls: see nms_core.h on flat accesses);
+//                         scan      nms_greedy_scan on 16 waves (nms_scan.h) with the policy TmScan below.
 //                       A box is the row's xyxy plus its tile's (ox, oy): one fp32 add of an integer-valued float.  Classes are compared as
 //                       integers; nothing is added to the coordinates.  All arithmetic is fp32 with contraction off, the IoU in the expression
 //                       order of nms.hip's iou_gt (the reference's), intersection over the smaller area for metric 1.
-#include "common_hip.h"
-#include "nms_ws.h"
+#include "nms_scan.h"
 
 #pragma clang fp contract(off)
 
 namespace dy {
-
-typedef unsigned long long u64;
 
 // ---- slicer -------------------------------------------------------------------------------------------------------------------------------
 template <bool VEC>
@@ -86,7 +80,6 @@ __global__ __launch_bounds__(256) void tiles_batch_kernel(const uint8_t* __restr
 // ---- merge --------------------------------------------------------------------------------------------------------------------------------
 constexpr int TM_THREADS = 1024;
 constexpr int TM_WAVES = TM_THREADS / 64;
-constexpr int TM_ROWS = 64 / TM_WAVES;                  // bit-matrix rows a wave computes per chunk
 constexpr int TM_MAX_SLOTS = 32768;                     // K * max_det
 constexpr int TM_MAX_KEEP = 4096;                       // merge_max_det
 constexpr int TM_MAX_LDS_KEYS = 16384;                  // 128 KiB of the CU's 160 KiB
@@ -111,7 +104,8 @@ struct TmCand {
   int slot, cls;
 };
 
-// box i (kept) suppresses box j: same class unless agnostic, then the overlap measure against thr
+// box i (kept) suppresses box j: same class unless agnostic, then the overlap measure against thr.  Scalars by value: every operand is
+// read ahead of the &&, so the predicate stays branch-free and the kept-list loop that calls it unrolls.
 __device__ __forceinline__ bool tm_suppresses(int metric, int agnostic, float thr, float ix1, float iy1, float ix2, float iy2, float iarea, int icls, float jx1,
                                               float jy1, float jx2, float jy2, float jarea, int jcls) {
   const float xx1 = fmaxf(ix1, jx1), yy1 = fmaxf(iy1, jy1);
@@ -123,29 +117,57 @@ __device__ __forceinline__ bool tm_suppresses(int metric, int agnostic, float th
   return (agnostic || icls == jcls) && ovr > thr;
 }
 
-__device__ __forceinline__ u64 tm_uniform64(u64 v) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
-  return ((u64)hi << 32) | (u64)lo;
-}
-
-__device__ __forceinline__ TmCand tm_fetch(const TmArgs& p, const u64* skeys, const u64* gkeys, bool in_lds, const float* frows, int i, int n) {
-  TmCand c{0.f, 0.f, 0.f, 0.f, 0.f, 0, -1};
-  if (i < n) {
-    const u64 key = in_lds ? skeys[i] : gkeys[i];
-    c.slot = (int)(unsigned)(key & 0xffffffffull);
-    c.score = __uint_as_float(~(unsigned)(key >> 32));
-    const int tile = c.slot / p.max_det;
-    const float oy = (float)p.offs[2 * tile], ox = (float)p.offs[2 * tile + 1];
-    const float* q = frows + (size_t)c.slot * 6;
-    c.x1 = q[0] + ox;
-    c.y1 = q[1] + oy;
-    c.x2 = q[2] + ox;
-    c.y2 = q[3] + oy;
-    c.cls = (int)q[5];
+struct TmScan {  // nms_greedy_scan's policy: frame-coordinate boxes, classes compared as integers, IoU or IoS, clamped rows
+  const TmArgs& p;
+  const u64* skeys;
+  const u64* gkeys;
+  const float* frows;
+  float* outb;
+  int* outi;
+  float4* kbox;  // [keep]
+  float* kar;
+  int* kcls;
+  bool in_lds;
+  typedef TmCand Cand;
+  __device__ __forceinline__ Cand fetch(int i, int n) const {
+    Cand c{0.f, 0.f, 0.f, 0.f, 0.f, 0, -1};
+    if (i < n) {
+      const u64 key = in_lds ? skeys[i] : gkeys[i];
+      c.slot = (int)(unsigned)(key & 0xffffffffull);
+      c.score = __uint_as_float(~(unsigned)(key >> 32));
+      const int tile = c.slot / p.max_det;
+      const float oy = (float)p.offs[2 * tile], ox = (float)p.offs[2 * tile + 1];
+      const float* q = frows + (size_t)c.slot * 6;
+      c.x1 = q[0] + ox;
+      c.y1 = q[1] + oy;
+      c.x2 = q[2] + ox;
+      c.y2 = q[3] + oy;
+      c.cls = (int)q[5];
+    }
+    return c;
   }
-  return c;
-}
+  __device__ __forceinline__ ScanBox box(const Cand& c) const { return ScanBox{c.x1, c.y1, c.x2, c.y2, (c.x2 - c.x1) * (c.y2 - c.y1), c.cls}; }
+  __device__ __forceinline__ bool suppresses(const ScanBox& i, const ScanBox& j) const {
+    return tm_suppresses(p.metric, p.agnostic, p.thr, i.x1, i.y1, i.x2, i.y2, i.area, i.cls, j.x1, j.y1, j.x2, j.y2, j.area, j.cls);
+  }
+  __device__ __forceinline__ ScanBox kept(int k) const {
+    const float4 kb = kbox[k];
+    return ScanBox{kb.x, kb.y, kb.z, kb.w, kar[k], kcls[k]};
+  }
+  __device__ __forceinline__ void keep(int at, const Cand& c, const ScanBox& bx) const {
+    kbox[at] = make_float4(c.x1, c.y1, c.x2, c.y2);
+    kar[at] = bx.area;
+    kcls[at] = c.cls;
+    float* o = outb + (size_t)at * 6;
+    o[0] = fminf(fmaxf(c.x1, 0.f), p.fw);
+    o[1] = fminf(fmaxf(c.y1, 0.f), p.fh);
+    o[2] = fminf(fmaxf(c.x2, 0.f), p.fw);
+    o[3] = fminf(fmaxf(c.y2, 0.f), p.fh);
+    o[4] = c.score;
+    o[5] = (float)c.cls;
+    if (outi) outi[at] = c.slot;
+  }
+};
 
 __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(const TmArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
@@ -159,7 +181,6 @@ __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(const TmArgs p) 
   const int f = blockIdx.x;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const float* frows = p.rows + (size_t)f * p.N * 6;
   const int* fcounts = p.counts + (size_t)f * p.K;
   u64* gkeys = p.keys + (size_t)f * p.P;
@@ -207,93 +228,13 @@ __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(const TmArgs p) 
     for (int i = n + tid; i < P2; i += TM_THREADS) gkeys[i] = ~0ull;
   }
   __syncthreads();
-  auto bitonic = [&](auto* keys) {
-    for (int k = 2; k <= P2; k <<= 1) {
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int t = tid; t < (P2 >> 1); t += TM_THREADS) {
-          const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));  // element with bit j clear
-          const int ixj = i | j;
-          const u64 x = keys[i], y = keys[ixj];
-          const bool up = (i & k) == 0;
-          if ((x > y) == up) {
-            keys[i] = y;
-            keys[ixj] = x;
-          }
-        }
-        __syncthreads();
-      }
-    }
-  };
-  if (in_lds) bitonic(skeys);
-  else bitonic(gkeys);
+  if (in_lds) nms_bitonic_sort<TM_THREADS>(skeys, P2, tid);
+  else nms_bitonic_sort<TM_THREADS>(gkeys, P2, tid);
 
   float* outb = p.out + (size_t)f * p.keep * 6;
   int* outi = p.out_index ? p.out_index + (size_t)f * p.keep : nullptr;
-  const u64 lane_bit = 1ull << lane;
-  int nk = 0;
-  TmCand nxt = tm_fetch(p, skeys, gkeys, in_lds, frows, lane, n);
-  for (int c0 = 0; c0 < n && nk < p.keep; c0 += 64) {
-    const TmCand c = nxt;
-    nxt = tm_fetch(p, skeys, gkeys, in_lds, frows, c0 + 64 + lane, n);
-    const bool in = c0 + lane < n;
-    const float area = (c.x2 - c.x1) * (c.y2 - c.y1);
-    // this wave's share of the kept list
-    bool sup = false;
-    for (int k = wave; k < nk; k += TM_WAVES) {
-      const float4 kb = kbox[k];
-      sup |= tm_suppresses(p.metric, p.agnostic, p.thr, kb.x, kb.y, kb.z, kb.w, kar[k], kcls[k], c.x1, c.y1, c.x2, c.y2, area, c.cls);
-    }
-    const u64 sm = __ballot(sup);
-    // this wave's rows of the chunk's suppression matrix
-    u64 myrow = 0ull;
-#pragma unroll
-    for (int r = 0; r < TM_ROWS; ++r) {
-      const int i = wave * TM_ROWS + r;  // wave-uniform: v_readlane
-      auto bcast = [&](float v) { return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(v), i)); };
-      const int icls = __builtin_amdgcn_readlane(c.cls, i);
-      const u64 m = __ballot(tm_suppresses(p.metric, p.agnostic, p.thr, bcast(c.x1), bcast(c.y1), bcast(c.x2), bcast(c.y2), bcast(area), icls, c.x1, c.y1,
-                                           c.x2, c.y2, area, c.cls));
-      if (lane == r) myrow = m;
-    }
-    if (lane < TM_ROWS) mrows[wave * TM_ROWS + lane] = myrow;
-    if (lane == 0) verdict[wave] = sm;
-    __syncthreads();
-    u64 dead = 0ull;
-    for (int w = 0; w < TM_WAVES; ++w) dead |= verdict[w];
-    const u64 row = mrows[lane];
-    const unsigned row_lo = (unsigned)row, row_hi = (unsigned)(row >> 32);
-    u64 am = __ballot(in) & ~tm_uniform64(dead);  // candidates of the chunk that no earlier kept box suppresses
-    u64 km = 0ull;                                // those the chunk keeps
-    int cnt = 0;
-    while (am != 0ull) {
-      const int t = __ffsll((long long)am) - 1;  // best live candidate of the chunk (wave-uniform)
-      km |= 1ull << t;
-      ++cnt;
-      if (nk + cnt >= p.keep) break;
-      const u64 rt = ((u64)(unsigned)__builtin_amdgcn_readlane((int)row_hi, t) << 32) | (u64)(unsigned)__builtin_amdgcn_readlane((int)row_lo, t);
-      am &= ~(rt | (1ull << t));
-    }
-    if (wave == 0 && (km & lane_bit) != 0ull) {
-      const int at = nk + __popcll(km & (lane_bit - 1ull));
-      kbox[at] = make_float4(c.x1, c.y1, c.x2, c.y2);
-      kar[at] = area;
-      kcls[at] = c.cls;
-      float* o = outb + (size_t)at * 6;
-      o[0] = fminf(fmaxf(c.x1, 0.f), p.fw);
-      o[1] = fminf(fmaxf(c.y1, 0.f), p.fh);
-      o[2] = fminf(fmaxf(c.x2, 0.f), p.fw);
-      o[3] = fminf(fmaxf(c.y2, 0.f), p.fh);
-      o[4] = c.score;
-      o[5] = (float)c.cls;
-      if (outi) outi[at] = c.slot;
-    }
-    nk += cnt;
-    __syncthreads();  // the kept list is complete before the next chunk reads it; mrows / verdict may be rewritten
-  }
-  for (int r = nk * 6 + tid; r < p.keep * 6; r += TM_THREADS) outb[r] = 0.f;
-  if (outi)
-    for (int r = nk + tid; r < p.keep; r += TM_THREADS) outi[r] = -1;
-  if (tid == 0) p.out_count[f] = nk;
+  const TmScan pol{p, skeys, gkeys, frows, outb, outi, kbox, kar, kcls, in_lds};
+  nms_greedy_scan<TM_WAVES>(pol, n, p.keep, mrows, verdict, outb, outi, p.out_count + f);
 }
 
 }  // namespace dy

@@ -911,6 +911,16 @@ def sppf_maxpool3(x: torch.Tensor, y1: torch.Tensor, y2: torch.Tensor, y3: torch
 # ---- detect decode + NMS --------------------------------------------------------------------------
 
 
+def _attach_filter(d, who: str, nms_bufs: "NmsBuffers", n: int, anchors: int, conf_thres: float, classes_mask: Optional[torch.Tensor]) -> None:
+    """Point a decode descriptor's fused NMS candidate filter at ``nms_bufs.workspace`` (then ``nms(..., prefiltered=True)`` with the
+    same buffers, conf_thres and classes_mask)."""
+    if (nms_bufs.batch, nms_bufs.anchors) != (n, anchors):
+        raise ValueError(f"{who}: nms_bufs were sized for another batch / anchor count")
+    d.nms_workspace, d.nms_workspace_bytes = nms_bufs.workspace.data_ptr(), nms_bufs.workspace.numel()
+    d.conf_thres = conf_thres
+    d.classes_mask = classes_mask.data_ptr() if classes_mask is not None else None
+
+
 def detect_decode(levels: Sequence[torch.Tensor], strides: Sequence[float], nc: int, reg_max: int,
                   out: Optional[torch.Tensor] = None, nms_bufs: Optional["NmsBuffers"] = None, conf_thres: float = 0.25,
                   classes_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -933,11 +943,7 @@ def detect_decode(levels: Sequence[torch.Tensor], strides: Sequence[float], nc: 
         out = torch.empty((n, 4 + nc, A), dtype=torch.float32, device=levels[0].device)
     d.out = out.data_ptr()
     if nms_bufs is not None:
-        if (nms_bufs.batch, nms_bufs.anchors) != (n, A):
-            raise ValueError("detect_decode: nms_bufs were sized for another batch / anchor count")
-        d.nms_workspace, d.nms_workspace_bytes = nms_bufs.workspace.data_ptr(), nms_bufs.workspace.numel()
-        d.conf_thres = conf_thres
-        d.classes_mask = classes_mask.data_ptr() if classes_mask is not None else None
+        _attach_filter(d, "detect_decode", nms_bufs, n, A, conf_thres, classes_mask)
     _launch(lib().dy_detect_decode, (C.byref(d),), keep=(d, out, nms_bufs, classes_mask, *levels))
     return out
 
@@ -971,11 +977,7 @@ def detect_branch_fused(x: torch.Tensor, pc3: "PackedConv", w1: torch.Tensor, b1
     if pred.dtype != torch.float32 or pred.shape[0] != n or pred.shape[1] != 4 + nc or not pred.is_contiguous():
         raise ValueError("detect_branch_fused: pred must be a contiguous fp32 (N, 4 + nc, A) tensor")
     if kind == 2 and nms_bufs is not None:
-        if (nms_bufs.batch, nms_bufs.anchors) != (n, pred.shape[2]):
-            raise ValueError("detect_branch_fused: nms_bufs were sized for another batch / anchor count")
-        d.nms_workspace, d.nms_workspace_bytes = nms_bufs.workspace.data_ptr(), nms_bufs.workspace.numel()
-        d.conf_thres = conf_thres
-        d.classes_mask = classes_mask.data_ptr() if classes_mask is not None else None
+        _attach_filter(d, "detect_branch_fused", nms_bufs, n, pred.shape[2], conf_thres, classes_mask)
     _launch(lib().dy_detect_branch_fused, (C.byref(d),), keep=(d, x, pc3, w1, b1, pred, nms_bufs, classes_mask))
 
 
@@ -1027,11 +1029,7 @@ def detect_head_decode(x_box: Sequence[torch.Tensor], x_cls: Sequence[torch.Tens
         out = torch.empty((n, 4 + nc, A), dtype=torch.float32, device=x_box[0].device)
     d.out = out.data_ptr()
     if nms_bufs is not None:
-        if (nms_bufs.batch, nms_bufs.anchors) != (n, A):
-            raise ValueError("detect_head_decode: nms_bufs were sized for another batch / anchor count")
-        d.nms_workspace, d.nms_workspace_bytes = nms_bufs.workspace.data_ptr(), nms_bufs.workspace.numel()
-        d.conf_thres = conf_thres
-        d.classes_mask = classes_mask.data_ptr() if classes_mask is not None else None
+        _attach_filter(d, "detect_head_decode", nms_bufs, n, A, conf_thres, classes_mask)
     _launch(lib().dy_detect_head_decode, (C.byref(d),),
             keep=(d, out, nms_bufs, classes_mask, *x_box, *x_cls, *packed_box, *packed_cls))
     return out
@@ -1040,14 +1038,33 @@ def detect_head_decode(x_box: Sequence[torch.Tensor], x_cls: Sequence[torch.Tens
 class NmsBuffers:
     """Persistent outputs + workspace of ``dy_nms`` for one (batch, anchors, max_det)."""
 
+    ROW = 6  # x1, y1, x2, y2, conf, cls
+
     def __init__(self, batch: int, anchors: int, max_det: int, device, candidates_per_anchor: int = 1):
         """``candidates_per_anchor``: nc for the validator's multi_label NMS (one candidate per (anchor, class) pair), else 1."""
         self.batch, self.anchors, self.max_det, self.cpa = batch, anchors, max_det, candidates_per_anchor
-        nbytes = lib().dy_nms_workspace_bytes(batch, anchors * candidates_per_anchor)
-        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=device)
-        self.out = torch.empty((batch, max_det, 6), dtype=torch.float32, device=device)
+        self.workspace = torch.empty((self.workspace_bytes(),), dtype=torch.uint8, device=device)
+        self.out = torch.empty((batch, max_det, self.ROW), dtype=torch.float32, device=device)
         self.count = torch.empty((batch,), dtype=torch.int32, device=device)
         self.index = torch.empty((batch, max_det), dtype=torch.int32, device=device)
+
+    def workspace_bytes(self) -> int:
+        return lib().dy_nms_workspace_bytes(self.batch, self.anchors * self.cpa)
+
+
+def _nms_desc(pred: torch.Tensor, bufs: NmsBuffers, nc: int, conf_thres: float, iou_thres: float, max_nms: int, max_wh: float, agnostic: bool,
+              classes_mask: Optional[torch.Tensor], prefiltered: bool, multi_label: bool) -> NmsDesc:
+    """The ``dy_nms_desc`` of a call on ``pred`` (N, 4 + nc (+ extra), A) into ``bufs``."""
+    n, ch, A = pred.shape
+    d = NmsDesc()
+    d.pred, d.batch, d.nc, d.n_extra, d.anchors = pred.data_ptr(), n, nc, ch - 4 - nc, A
+    d.conf_thres, d.iou_thres, d.max_det, d.max_nms = conf_thres, iou_thres, bufs.max_det, max_nms
+    d.max_wh, d.agnostic = max_wh, int(agnostic)
+    d.classes_mask = classes_mask.data_ptr() if classes_mask is not None else None
+    d.out, d.out_count, d.out_index = bufs.out.data_ptr(), bufs.count.data_ptr(), bufs.index.data_ptr()
+    d.workspace, d.workspace_bytes = bufs.workspace.data_ptr(), bufs.workspace.numel()
+    d.prefiltered, d.multi_label = int(prefiltered), int(bool(multi_label))
+    return d
 
 
 def nms(pred: torch.Tensor, conf_thres: float, iou_thres: float, max_det: int = 300, max_nms: int = 30000,
@@ -1066,14 +1083,7 @@ def nms(pred: torch.Tensor, conf_thres: float, iou_thres: float, max_det: int = 
         if prefiltered:
             raise ValueError("nms(prefiltered=True) needs the NmsBuffers that detect_decode filled")
         bufs = NmsBuffers(n, A, max_det, pred.device, candidates_per_anchor=cpa)
-    d = NmsDesc()
-    d.pred, d.batch, d.nc, d.n_extra, d.anchors = pred.data_ptr(), n, nc, ch - 4 - nc, A
-    d.conf_thres, d.iou_thres, d.max_det, d.max_nms = conf_thres, iou_thres, max_det, max_nms
-    d.max_wh, d.agnostic = max_wh, int(agnostic)
-    d.classes_mask = classes_mask.data_ptr() if classes_mask is not None else None
-    d.out, d.out_count, d.out_index = bufs.out.data_ptr(), bufs.count.data_ptr(), bufs.index.data_ptr()
-    d.workspace, d.workspace_bytes = bufs.workspace.data_ptr(), bufs.workspace.numel()
-    d.prefiltered, d.multi_label = int(prefiltered), int(bool(multi_label))
+    d = _nms_desc(pred, bufs, nc, conf_thres, iou_thres, max_nms, max_wh, agnostic, classes_mask, prefiltered, multi_label)
     _launch(lib().dy_nms, (C.byref(d),), keep=(d, pred, bufs, classes_mask))
     return bufs
 
@@ -1113,18 +1123,15 @@ def obb_decode(levels: Sequence[torch.Tensor], strides: Sequence[float], pred: t
     return theta
 
 
-class RNmsBuffers:
+class RNmsBuffers(NmsBuffers):
     """Persistent outputs + workspace of ``dy_nms_rotated`` for one (batch, anchors, max_det).  ``out`` (N, max_det, 7) = x, y, w, h, theta,
     conf, cls.  The head of ``workspace`` is a ``dy_nms`` workspace, so the fused Detect candidate filters fill it as they fill
     ``NmsBuffers.workspace``."""
 
-    def __init__(self, batch: int, anchors: int, max_det: int, device):
-        self.batch, self.anchors, self.max_det, self.cpa = batch, anchors, max_det, 1
-        nbytes = lib().dy_nms_rotated_workspace_bytes(batch, anchors)
-        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=device)
-        self.out = torch.empty((batch, max_det, 7), dtype=torch.float32, device=device)
-        self.count = torch.empty((batch,), dtype=torch.int32, device=device)
-        self.index = torch.empty((batch, max_det), dtype=torch.int32, device=device)
+    ROW = 7
+
+    def workspace_bytes(self) -> int:
+        return lib().dy_nms_rotated_workspace_bytes(self.batch, self.anchors)
 
 
 def nms_rotated(pred: torch.Tensor, theta: torch.Tensor, conf_thres: float, iou_thres: float, max_det: int = 300, max_nms: int = 30000,
@@ -1144,14 +1151,7 @@ def nms_rotated(pred: torch.Tensor, theta: torch.Tensor, conf_thres: float, iou_
         if prefiltered:
             raise ValueError("nms_rotated(prefiltered=True) needs the RNmsBuffers that detect_decode filled")
         bufs = RNmsBuffers(n, A, max_det, pred.device)
-    d = NmsDesc()
-    d.pred, d.batch, d.nc, d.n_extra, d.anchors = pred.data_ptr(), n, nc, ch - 4 - nc, A
-    d.conf_thres, d.iou_thres, d.max_det, d.max_nms = conf_thres, iou_thres, max_det, max_nms
-    d.max_wh, d.agnostic = max_wh, int(agnostic)
-    d.classes_mask = classes_mask.data_ptr() if classes_mask is not None else None
-    d.out, d.out_count, d.out_index = bufs.out.data_ptr(), bufs.count.data_ptr(), bufs.index.data_ptr()
-    d.workspace, d.workspace_bytes = bufs.workspace.data_ptr(), bufs.workspace.numel()
-    d.prefiltered, d.multi_label = int(prefiltered), int(bool(multi_label))
+    d = _nms_desc(pred, bufs, nc, conf_thres, iou_thres, max_nms, max_wh, agnostic, classes_mask, prefiltered, multi_label)
     _launch(lib().dy_nms_rotated, (C.byref(d), theta.data_ptr()), keep=(d, pred, theta, bufs, classes_mask))
     return bufs
 
