@@ -125,6 +125,12 @@ class ValMatchDesc(C.Structure):
     ]  # fmt: skip
 
 
+class ValMatchRotatedDesc(C.Structure):
+    """Mirror of ``dy_val_match_rotated_desc`` (the fields of ``dy_val_match_desc``; rows are 7 wide, tbox 8)."""
+
+    _fields_ = list(ValMatchDesc._fields_)
+
+
 class TileMergeDesc(C.Structure):
     """Mirror of ``dy_tile_merge_desc``."""
 
@@ -317,8 +323,11 @@ SIGNATURES = {
     "dy_nms_rotated_workspace_bytes": (_i64, [_i32, _i32]),
     "dy_nms_rotated": (_i32, [C.POINTER(NmsDesc), _vp, _vp]),
     "dy_nms_rotated_lds_cap": (_i32, []),
+    "dy_nms_rotated_ml_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "dy_nms_rotated_ml": (_i32, [C.POINTER(NmsDesc), _vp, _vp]),
     "dy_scale_rboxes": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp]),
     "dy_val_match": (_i32, [C.POINTER(ValMatchDesc), _vp]),
+    "dy_val_match_rotated": (_i32, [C.POINTER(ValMatchRotatedDesc), _vp]),
     "dy_track_state_bytes": (_i64, [_i32, _i32]),
     "dy_track_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "dy_track_reset": (_i32, [_vp, _i32, _i32, _vp]),

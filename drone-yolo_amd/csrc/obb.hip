@@ -6,11 +6,13 @@
 //   dy_nms_rotated    non_max_suppression(rotated=True) for the single-label path (utils/ops.py:257-313) with nms_rotated (:146-178) and
 //                     batch_probiou (utils/metrics.py:178-275).  The candidate stage (filter, keys, sort order, max_nms) is dy_nms's
 //                     (nms_core.h); the suppression is the reference's FAST NMS, not the greedy scan of nms.hip.
+//   dy_nms_rotated_ml the validator's form (multi_label: every (anchor, class) pair above conf is a candidate), an entry point of its own beside it.
 //   dy_scale_rboxes   OBBPredictor.construct_result (models/yolo/obb/predict.py:43-45): regularize_rboxes + scale_boxes(xywh=True).
 //
 // fp32 in the reference's order of operations with contraction off.  expf / logf / sinf / cosf are the device's and are not bit-equal to
 // the CPU's: kept sets agree for inputs the reference decides with a margin (tools/make_obb_golden.py records it).
 #include "nms_core.h"
+#include "probiou.h"
 
 #pragma clang fp contract(off)
 
@@ -62,39 +64,8 @@ constexpr int RNMS_LDS_CAP = 2048;  // candidates whose keys and table rows fit 
 struct RNmsArgs {
   NmsArgs n;
   const float* theta;  // [batch][A]
-  float* table;        // [batch][5][A]: the table of the images with more than RNMS_LDS_CAP candidates
+  float* table;        // [batch][5][cap]: the table of the images with more than RNMS_LDS_CAP candidates (cap = A, or A * nc with multi)
 };
-
-struct RRow {
-  float x, y, a, b, c;
-};
-
-// _get_covariance_matrix (metrics.py:178-195) of one box
-__device__ __forceinline__ RRow rnms_row(float x, float y, float w, float h, float th) {
-  const float a = (w * w) / 12.f, b = (h * h) / 12.f;
-  const float cs = cosf(th), sn = sinf(th);
-  const float cs2 = cs * cs, sn2 = sn * sn;
-  return RRow{x, y, a * cs2 + b * sn2, a * sn2 + b * cs2, ((a - b) * cs) * sn};
-}
-
-// batch_probiou(obb1 = r1, obb2 = r2) (metrics.py:259-275), term for term; the clamps keep a NaN as torch's do
-__device__ __forceinline__ float rnms_probiou(const RRow& r1, const RRow& r2) {
-  const float eps = 1e-7f;
-  const float sa = r1.a + r2.a, sb = r1.b + r2.b, sc = r1.c + r2.c;
-  const float dy = r1.y - r2.y, dx = r1.x - r2.x;
-  const float det = sa * sb - sc * sc;
-  const float den = det + eps;
-  const float t1 = ((sa * (dy * dy) + sb * (dx * dx)) / den) * 0.25f;
-  const float t2 = (((sc * (r2.x - r1.x)) * dy) / den) * 0.5f;
-  float d1 = r1.a * r1.b - r1.c * r1.c, d2 = r2.a * r2.b - r2.c * r2.c;
-  d1 = d1 < 0.f ? 0.f : d1;
-  d2 = d2 < 0.f ? 0.f : d2;
-  const float t3 = logf(det / (4.f * sqrtf(d1 * d2) + eps) + eps) * 0.5f;
-  float bd = (t1 + t2) + t3;
-  bd = bd < eps ? eps : (bd > 100.f ? 100.f : bd);
-  const float hd = sqrtf((1.f - expf(-bd)) + eps);
-  return 1.f - hd;
-}
 
 // One workgroup per image.  Sort as in nms.hip; then the five floats of every candidate (x + c, y + c and the covariance terms a, b, c)
 // are computed once into a table, in LDS for at most RNMS_LDS_CAP candidates and in the workspace for more (decided here, on the device,
@@ -102,14 +73,18 @@ __device__ __forceinline__ float rnms_probiou(const RRow& r1, const RRow& r2) {
 // candidate j against ALL table rows i < j, suppressed or not (ops.py:164-167: triu_(1), (ious >= thr).sum(0) <= 0).  A candidate's
 // verdict depends on the table alone, so there is no serial dependence between chunks; only the position of a kept row (a prefix count
 // of the kept bits) and the stop at max_det kept (ops.py:313) tie the rounds together.
-template <bool LDS>
+// MULTI (dy_nms_rotated_ml, the validator's multi_label form): a candidate is an (anchor, class) pair whose key low word is anchor * nc +
+// class; anchor and class both come from the key (the multi-label filter does not write p.cls), and the workspace table's pitch is the
+// candidate capacity A * nc.
+template <bool LDS, bool MULTI = false>
 __device__ __forceinline__ void rnms_image(const RNmsArgs& q, int b, int n, u64* skeys, float* stab, u64* kmask) {
   const NmsArgs& p = q.n;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   u64* gkeys = p.keys + (size_t)b * p.P;
-  float* gtab = q.table + (size_t)b * 5 * (size_t)p.A;
+  const int tcap = MULTI ? p.cap : p.A;
+  float* gtab = q.table + (size_t)b * 5 * (size_t)tcap;
   int P2 = 1;
   while (P2 < n) P2 <<= 1;
   if (LDS) {
@@ -122,12 +97,13 @@ __device__ __forceinline__ void rnms_image(const RNmsArgs& q, int b, int n, u64*
     nms_bitonic_sort<RNMS_THREADS>(gkeys, P2, tid);
   }
   const int nn = n < p.max_nms ? n : p.max_nms;
-  const int ts = LDS ? RNMS_LDS_CAP : p.A;  // pitch of the table's five arrays
+  const int ts = LDS ? RNMS_LDS_CAP : tcap;  // pitch of the table's five arrays
   const float* pr = p.pred + (size_t)b * p.nch * (size_t)p.A;
   const float* th = q.theta + (size_t)b * p.A;
   for (int i = tid; i < nn; i += RNMS_THREADS) {
-    const int anchor = (int)(unsigned)((LDS ? skeys[i] : gkeys[i]) & 0xffffffffull);
-    const float off = p.agnostic ? 0.f : (float)p.cls[(size_t)b * p.A + anchor] * p.max_wh;
+    const int low = (int)(unsigned)((LDS ? skeys[i] : gkeys[i]) & 0xffffffffull);
+    const int anchor = MULTI ? low / p.nc : low;
+    const float off = p.agnostic ? 0.f : (MULTI ? (float)(low % p.nc) : (float)p.cls[(size_t)b * p.A + anchor]) * p.max_wh;
     const RRow r = rnms_row(pr[anchor] + off, pr[(size_t)p.A + anchor] + off, pr[(size_t)2 * p.A + anchor], pr[(size_t)3 * p.A + anchor], th[anchor]);
     float* t = LDS ? stab : gtab;
     t[i] = r.x;
@@ -167,7 +143,8 @@ __device__ __forceinline__ void rnms_image(const RNmsArgs& q, int b, int n, u64*
       const int at = base + __popcll(km & ((1ull << lane) - 1ull));
       if (at < p.max_det) {
         const u64 key = LDS ? skeys[j] : gkeys[j];
-        const int anchor = (int)(unsigned)(key & 0xffffffffull);
+        const int low = (int)(unsigned)(key & 0xffffffffull);
+        const int anchor = MULTI ? low / p.nc : low;
         float* o = outb + (size_t)at * 7;
         o[0] = pr[anchor];
         o[1] = pr[(size_t)p.A + anchor];
@@ -175,7 +152,7 @@ __device__ __forceinline__ void rnms_image(const RNmsArgs& q, int b, int n, u64*
         o[3] = pr[(size_t)3 * p.A + anchor];
         o[4] = th[anchor];
         o[5] = __uint_as_float(~(unsigned)(key >> 32));
-        o[6] = (float)p.cls[(size_t)b * p.A + anchor];
+        o[6] = MULTI ? (float)(low % p.nc) : (float)p.cls[(size_t)b * p.A + anchor];
         if (p.out_index) p.out_index[(size_t)b * p.max_det + at] = anchor;
       }
     }
@@ -198,6 +175,17 @@ __global__ __launch_bounds__(RNMS_THREADS) void nms_rotated_kernel(const RNmsArg
   if (n > q.n.cap) n = q.n.cap;
   if (n <= RNMS_LDS_CAP) rnms_image<true>(q, b, n, skeys, stab, kmask);
   else rnms_image<false>(q, b, n, skeys, stab, kmask);
+}
+
+__global__ __launch_bounds__(RNMS_THREADS) void nms_rotated_ml_kernel(const RNmsArgs q) {
+  __shared__ u64 skeys[RNMS_LDS_CAP];
+  __shared__ float stab[5 * RNMS_LDS_CAP];
+  __shared__ u64 kmask[RNMS_WAVES];
+  const int b = blockIdx.x;
+  int n = q.n.counts[b];
+  if (n > q.n.cap) n = q.n.cap;
+  if (n <= RNMS_LDS_CAP) rnms_image<true, true>(q, b, n, skeys, stab, kmask);
+  else rnms_image<false, true>(q, b, n, skeys, stab, kmask);
 }
 
 // ---- dy_scale_rboxes --------------------------------------------------------------------------------------------------------------
@@ -288,6 +276,36 @@ extern "C" int32_t dy_nms_rotated(const dy_nms_desc* d, const float* theta, dy_s
   const int rcf = nms_launch_filter(q.n, d->prefiltered != 0, st);
   if (rcf != DY_OK) return rcf;
   hipLaunchKernelGGL(nms_rotated_kernel, dim3((unsigned)d->batch), dim3(RNMS_THREADS), 0, st, q);
+  return check_launch("nms_rotated_kernel");
+}
+
+extern "C" int64_t dy_nms_rotated_ml_workspace_bytes(int32_t batch, int32_t anchors, int32_t nc) {
+  if (batch <= 0 || anchors <= 0 || nc <= 0 || (long long)anchors * nc >= (1ll << 30)) return -1;
+  const int cap = anchors * nc;
+  return (int64_t)(rnms_table_offset(batch, cap) + (size_t)batch * 5 * (size_t)cap * 4);
+}
+
+extern "C" int32_t dy_nms_rotated_ml(const dy_nms_desc* d, const float* theta, dy_stream_t stream) {
+  DY_REQUIRE(d && theta, DY_ERR_INVALID_ARG, "dy_nms_rotated_ml: null pointer");
+  DY_REQUIRE(d->prefiltered == 0, DY_ERR_UNSUPPORTED, "dy_nms_rotated_ml: the fused candidate filter is single-label; multi_label filters here");
+  dy_nms_desc m = *d;
+  m.multi_label = 1;  // whatever the field says (nms_args_from_desc drops it again for nc == 1, ops.py:255)
+  RNmsArgs q{};
+  const bool dims = m.batch > 0 && m.anchors > 0 && m.nc > 0 && (long long)m.anchors * m.nc < (1ll << 30);
+  const int cap = dims ? m.anchors * m.nc : 0;
+  const int64_t extra = dims ? dy_nms_rotated_ml_workspace_bytes(m.batch, m.anchors, m.nc) - (int64_t)nms_ws_bytes(m.batch, cap) : 0;
+  const int rc0 = nms_args_from_desc(&m, "dy_nms_rotated_ml", extra, &q.n);
+  if (rc0 != DY_OK) return rc0;
+  q.theta = theta;
+  q.table = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(m.workspace) + rnms_table_offset(m.batch, q.n.cap));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int rcf = nms_launch_filter(q.n, false, st);
+  if (rcf != DY_OK) return rcf;
+  if (q.n.multi) {
+    hipLaunchKernelGGL(nms_rotated_ml_kernel, dim3((unsigned)m.batch), dim3(RNMS_THREADS), 0, st, q);
+    return check_launch("nms_rotated_ml_kernel");
+  }
+  hipLaunchKernelGGL(nms_rotated_kernel, dim3((unsigned)m.batch), dim3(RNMS_THREADS), 0, st, q);  // nc == 1: single-label
   return check_launch("nms_rotated_kernel");
 }
 

@@ -1,5 +1,6 @@
 """``YOLO`` / ``Model`` user API (reference: ultralytics/engine/model.py:29-1177,
-ultralytics/models/yolo/model.py:11-59) for the detection, segmentation (prediction and validation) and oriented-box (prediction) tasks on the MI355X path."""
+ultralytics/models/yolo/model.py:11-59) for the detection, segmentation (prediction and validation) and oriented-box (prediction and validation)
+tasks on the MI355X path."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -47,7 +48,7 @@ class Model(nn.Module):
 
     @property
     def predict_only_task_map(self):
-        """Tasks that have a model and a predictor and nothing else (no trainer, no validator); ``task_map`` keeps the tasks that can be scored."""
+        """Tasks without a trainer, kept apart from ``task_map``: a model, a predictor and (``_val_obb``) a validator."""
         return {"obb": {"model": OBBModel, "predictor": OBBPredictor}}
 
     def _task_classes(self, task: str) -> dict:
@@ -205,8 +206,6 @@ class Model(nn.Module):
         ``"synthetic[:N]"`` (engine/trainer.py::load_dataset; image folders and dataset YAMLs are outside the accelerated path);
         ``batch``, ``imgsz``, ``conf``, ``iou``, ``max_det``, ``half`` / ``dtype``, ``device`` as the reference's arguments.  Returns the
         reference's ``results_dict`` (metrics/precision(B) ... metrics/mAP50-95(B), fitness) with the validation losses; kept in ``self.metrics``."""
-        if self.task == "obb":
-            raise NotImplementedError("val: validation (OBBValidator, rotated matching) is not built for oriented-box models; they predict only")
         from .predictor import resolve_dtype
         from .trainer import TensorLoader, load_dataset
         from .validator import DetectionValidator
@@ -217,6 +216,8 @@ class Model(nn.Module):
             raise ValueError("val(): 'data' is missing (a tensor dataset: dict / .pt, or 'synthetic[:N]')")
         if self.task == "segment":
             return self._val_segment(validator, args)
+        if self.task == "obb":
+            return self._val_obb(validator, args)
         device = select_device(args.get("device", ""))
         data = load_dataset(args["data"], int(args.get("imgsz", 640)), self.model.yaml["nc"], int(args.get("seed", 0)))
         data = data.get("val") or data
@@ -263,6 +264,40 @@ class Model(nn.Module):
         loader = TensorLoader({k: data[k] for k in ("img", "batch_idx", "cls", "bboxes", "masks")}, int(args.get("batch") or 16), 0, 1, shuffle=False)
         try:
             self.metrics = (validator or SegmentationValidator)(args)(model, loader, device, dtype)
+        finally:
+            model.train(was_training)
+        self.predictor = None  # (the pass may have re-packed weights for another storage type)
+        return self.metrics
+
+    def _val_obb(self, validator, args: dict) -> dict:
+        """``val`` of an oriented-box model (reference models/yolo/obb/val.py; engine/validator.py::OBBValidator): the rotated ``multi_label``
+        NMS at conf 0.001 (``dy_nms_rotated_ml``) and the ProbIoU matching (``dy_val_match_rotated``) on the device, AP on the host
+        (``device_match=False``: the reference's data flow on the host).  The dataset's ``bboxes`` must be (M, 5): normalised xywh and the angle
+        in radians.  Returns ``OBBMetrics``' dict (the four (B) entries, ``fitness``), no validation loss.  ``save_json``, plots, the DOTA merge
+        (``eval_json``) and ``save_txt`` are not built."""
+        from .predictor import resolve_dtype
+        from .trainer import TensorLoader, load_dataset
+        from .validator import OBBValidator
+        from .. import hip_ops as H
+        from ..utils.torch_utils import select_device
+
+        # the dataset first: whatever it lacks is refused before a device is selected, the model moved or a validator built
+        data = load_dataset(args["data"], int(args.get("imgsz", 640)), self.model.yaml["nc"], int(args.get("seed", 0)))
+        data = data.get("val") or data
+        boxes = data["bboxes"]
+        if not isinstance(boxes, torch.Tensor) or boxes.dim() != 2 or boxes.shape[1] != 5:
+            shape = tuple(boxes.shape) if isinstance(boxes, torch.Tensor) else type(boxes).__name__
+            raise NotImplementedError(f"val: an oriented-box model needs a dataset whose 'bboxes' are (M, 5) xywhr (normalised xywh and the angle in radians); "
+                                      f"data={args['data'] if isinstance(args['data'], str) else type(args['data']).__name__!r} has {shape} (no angles)")
+        device = select_device(args.get("device", ""))
+        dtype = resolve_dtype(args.get("dtype"), bool(args.get("half", False)), self.model)
+        if dtype == H.FP8:
+            raise NotImplementedError("val: OBB is built for the 16-bit, split-float16 and fp32 storage types")
+        was_training = self.model.training
+        model = self.model.to(device)
+        loader = TensorLoader({k: data[k] for k in ("img", "batch_idx", "cls", "bboxes")}, int(args.get("batch") or 16), 0, 1, shuffle=False)
+        try:
+            self.metrics = (validator or OBBValidator)(args)(model, loader, device, dtype)
         finally:
             model.train(was_training)
         self.predictor = None  # (the pass may have re-packed weights for another storage type)

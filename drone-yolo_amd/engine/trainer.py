@@ -222,7 +222,8 @@ def synthetic_dataset(n: int, imgsz: int, seed: int, nc: int = 10) -> Dict[str, 
 
 def load_dataset(data, imgsz: int, nc: int, seed: int) -> Dict[str, torch.Tensor]:
     """``data``: a dict / a ``.pt`` file of tensors ``img`` (N,3,H,W) uint8, ``batch_idx`` (M,), ``cls`` (M,1), ``bboxes`` (M,4
-    normalised xywh) — the reference's collate layout (data/dataset.py:232-248) over the whole set — or ``"synthetic[:N]"``, or a
+    normalised xywh; (M,5) with the angle in radians for an oriented-box set, passed through as it is) — the reference's collate layout
+    (data/dataset.py:232-248) over the whole set — or ``"synthetic[:N]"``, or a
     YOLO-format dataset YAML (``load_yaml_dataset``: decoded once into the same tensor layout)."""
     if isinstance(data, dict):
         d = data

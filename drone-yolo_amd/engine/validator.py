@@ -12,7 +12,9 @@ The validation loss is the criterion on Detect's raw maps of the same pass (vali
 Tensor datasets only (dataset files / augmentation are out of scope): ``data["val"]`` — a dict in the training set's
 layout — or, when the dataset has no split, the training tensors themselves.
 ``SegmentationValidator`` (models/yolo/segment/val.py) adds the mask statistics of a segmentation model: ``dy_val_mask_match`` behind the box
-matching, or the reference's mask branch on the host ("Segmentation validation")."""
+matching, or the reference's mask branch on the host ("Segmentation validation").
+``OBBValidator`` (models/yolo/obb/val.py) scores an oriented-box model: ``dy_nms_rotated_ml`` and ``dy_val_match_rotated`` (ProbIoU), or the
+reference's data flow on the host ("Oriented-box validation")."""
 from __future__ import annotations
 
 from typing import Dict, Optional
@@ -23,7 +25,7 @@ import torch.nn.functional as F
 
 from .. import hip_ops as H
 from ..utils import ops
-from ..utils.metrics import DetMetrics, SegmentMetrics, box_iou, mask_iou, match_predictions
+from ..utils.metrics import DetMetrics, OBBMetrics, SegmentMetrics, batch_probiou, box_iou, mask_iou, match_predictions
 
 
 class DetectionValidator:
@@ -325,6 +327,137 @@ class SegmentationValidator(DetectionValidator):
                     gt = host_gt_masks(gmaps[si], len(cls), protos.shape[2:])
                     tp_m = match_predictions(pn[:, 5], cls, host_mask_iou(gt, pm), self.iouv)
                 stats["tp"].append(tp), stats["tp_m"].append(tp_m), stats["conf"].append(pn[:, 4]), stats["pred_cls"].append(pn[:, 5])
+                stats["target_cls"].append(cls)
+        self.last_counts = np.array(all_counts, dtype=np.int32)
+        return nb
+
+
+# ---- oriented boxes (models/yolo/obb/val.py) ---------------------------------------------------------------------------------------------
+def obb_labels(bboxes: torch.Tensor, w: int, h: int, lim: torch.Tensor) -> torch.Tensor:
+    """``OBBValidator._prepare_batch`` on the (L, 5) normalised xywhr labels of a batch: ``bboxes[:, :4] * (w, h, w, h)``, then
+    ``scale_boxes(xywh=True)`` at gain 1 / pad 0, which leaves ``clip_boxes`` (columns 0 and 2 to [0, w], 1 and 3 to [0, h]: the width and
+    height too).  The angle is untouched.  Elementwise fp32 torch operations: the same bits wherever ``bboxes`` lives.  ``lim``: fp32
+    (w, h, w, h) on the same device."""
+    t = bboxes.float().clone()
+    t[:, :4] = torch.minimum((t[:, :4] * lim).clamp_min(0), lim)
+    return t
+
+
+class OBBValidator(DetectionValidator):
+    """``OBBValidator`` of the reference (models/yolo/obb/val.py): ``DetectionValidator`` whose NMS is the rotated ``multi_label`` one
+    (``dy_nms_rotated_ml``: ProbIoU fast NMS over every (anchor, class) pair above conf) and whose matching is ``match_predictions`` on
+    ``batch_probiou(gt, det)``.  With ``device_match`` a batch is matched by ``dy_val_match_rotated`` behind the NMS and nothing in the batch
+    loop waits for the device; without it the matching is the reference's data flow on the host, image by image.  The dataset's ``bboxes``
+    are (M, 5) normalised xywh + the angle in radians.  No validation loss (``v8OBBLoss`` is not built, and the reference's stand-alone
+    ``val`` computes none): the dict holds the four metrics and ``fitness``."""
+
+    def __init__(self, args: Optional[dict] = None):
+        super().__init__(args)
+        self.metrics = OBBMetrics()
+        self.last_stats = None  # what the last call gathered (per-image lists on the host path, one block on the device path)
+
+    def __call__(self, model, loader, device, dtype: torch.dtype) -> Dict[str, float]:
+        model.eval()
+        nc = model.yaml["nc"]
+        stats = dict(tp=[], conf=[], pred_cls=[], target_cls=[])
+        det = model.model[-1]
+        fuse_tail = getattr(det, "fuse_tail", False)
+        try:
+            (self._collect_device if self.device_match else self._collect_host)(model, loader, device, dtype, nc, stats, det)
+        finally:
+            det.fuse_tail = fuse_tail
+        self.last_stats = stats
+        out = {k: 0.0 for k in OBBMetrics.keys + ("fitness",)}
+        if stats["tp"]:
+            cat = {k: np.concatenate(v, 0) for k, v in stats.items()}
+            if len(cat["target_cls"]):
+                self.metrics.process(cat["tp"], cat["conf"], cat["pred_cls"], cat["target_cls"])
+                out = self.metrics.results_dict
+        return {k: round(float(v), 5) for k, v in out.items()}
+
+    def _pass(self, model, batch, device, dtype, nc, det):
+        img = batch["img"].to(device)
+        x = (img.float() / 255.0) if img.dtype == torch.uint8 else img.float()
+        with torch.no_grad():
+            det.fuse_tail = False  # OBB returns (cat([y, angle], 1), (feats, angle))
+            y, aux = model._predict_once(x.contiguous(), image_dtype=dtype)
+            if not (isinstance(aux, tuple) and len(aux) == 2) or y.shape[1] != 4 + nc + 1:
+                raise RuntimeError("OBBValidator needs a model whose head is OBB")
+            y = y.float()
+            bufs = H.nms_rotated_ml(y[:, : 4 + nc].contiguous(), y[:, -1].contiguous(), self.conf, self.iou, max_det=self.max_det,
+                                    agnostic=self.agnostic, nc=nc)
+        return img.shape, bufs
+
+    def _collect_device(self, model, loader, device, dtype, nc, stats, det) -> int:
+        """Fills ``stats`` with what ``_collect_host`` gathers (image order, then row order), matched by ``dy_val_match_rotated``.  Nothing in
+        the loop waits for the device; the accumulated tensors go to the host once each after it."""
+        nb = n_img = 0
+        rows, counts, tps, tcls, timg = [], [], [], [], []
+        lim = {}
+        for batch in loader:
+            nb += 1
+            (b, _, h, w), bufs = self._pass(model, batch, device, dtype, nc, det)
+            if (w, h) not in lim:
+                lim[(w, h)] = torch.tensor((w, h, w, h), dtype=torch.float32, device=device)
+            cls = batch["cls"].to(device).view(-1).float()
+            bi = batch["batch_idx"].to(device).view(-1).to(torch.int32)
+            tbox = obb_labels(batch["bboxes"].to(device), w, h, lim[(w, h)])
+            tps.append(H.val_match_rotated(bufs, tbox, cls, bi, self.iouv, (w, h), single_cls=self.single_cls))  # (new tensors on every call)
+            rows.append(bufs.out[..., 5:7].clone()), counts.append(bufs.count.clone())  # (the NMS buffers may be reused by the next batch)
+            tcls.append(cls), timg.append(bi + n_img)
+            n_img += b
+        if nb == 0:
+            return nb
+        rows, counts, tp = (torch.cat(v).cpu().numpy() for v in (rows, counts, tps))
+        tcls, timg = torch.cat(tcls).cpu().numpy(), torch.cat(timg).cpu().numpy().astype(np.int64)
+        keep = np.arange(self.max_det)[None, :] < counts[:, None]
+        conf, pred_cls = rows[keep][:, 0], rows[keep][:, 1]
+        if self.single_cls:
+            pred_cls = np.zeros_like(pred_cls)
+        if bool(((counts == 0) & (np.bincount(timg, minlength=len(counts))[: len(counts)] > 0)).any()):  # (as DetectionValidator._collect_device)
+            conf, pred_cls = conf.astype(np.float64), pred_cls.astype(np.float64)
+        if len(conf) or len(tcls):
+            stats["tp"].append(tp[keep].astype(bool)), stats["conf"].append(conf), stats["pred_cls"].append(pred_cls)
+            stats["target_cls"].append(tcls[np.argsort(timg, kind="stable")])
+        self.last_counts = counts
+        return nb
+
+    def host_match(self, rows: np.ndarray, tbox: np.ndarray, cls: np.ndarray, w: int, h: int) -> np.ndarray:
+        """``_prepare_pred`` + ``_process_batch`` of one image on the host: ``rows`` (k, 7) = x, y, w, h, theta, conf, cls as the NMS left
+        them, ``tbox`` (L, 5) prepared labels, ``cls`` (L,) -> tp (k, len(iouv)) bool."""
+        pn = rows.copy()
+        pn[:, [0, 2]] = pn[:, [0, 2]].clip(0, w)  # scale_boxes(xywh=True) at gain 1, pad 0: the clip, on x, y, w and h
+        pn[:, [1, 3]] = pn[:, [1, 3]].clip(0, h)
+        if self.single_cls:
+            pn[:, 6] = 0
+        if not len(cls) or not len(pn):
+            return np.zeros((len(pn), len(self.iouv)), dtype=bool)
+        iou = batch_probiou(torch.from_numpy(np.ascontiguousarray(tbox, dtype=np.float32)), torch.from_numpy(np.ascontiguousarray(pn[:, :5]))).numpy()
+        return match_predictions(pn[:, 6], cls, iou, self.iouv)
+
+    def _collect_host(self, model, loader, device, dtype, nc, stats, det) -> int:
+        nb = 0
+        all_counts = []
+        for batch in loader:
+            nb += 1
+            (_, _, h, w), bufs = self._pass(model, batch, device, dtype, nc, det)
+            counts = bufs.count.cpu().tolist()
+            out = bufs.out.cpu()
+            bi = batch["batch_idx"].long().cpu()
+            all_counts += counts
+            lim = torch.tensor((w, h, w, h), dtype=torch.float32)
+            for si, k in enumerate(counts):  # detect/val.py:126-174 with obb/val.py's _prepare_batch / _prepare_pred / _process_batch
+                sel = bi == si
+                cls = batch["cls"].cpu()[sel].view(-1).numpy()
+                tbox = obb_labels(batch["bboxes"].cpu()[sel], w, h, lim).numpy()
+                pn = out[si, :k].clone().numpy()
+                if k == 0:
+                    if len(cls):
+                        stats["tp"].append(np.zeros((0, len(self.iouv)), dtype=bool)), stats["conf"].append(np.zeros(0)), stats["pred_cls"].append(np.zeros(0))
+                        stats["target_cls"].append(cls)
+                    continue
+                tp = self.host_match(pn, tbox, cls, w, h)
+                stats["tp"].append(tp), stats["conf"].append(pn[:, 5]), stats["pred_cls"].append(np.zeros_like(pn[:, 6]) if self.single_cls else pn[:, 6])
                 stats["target_cls"].append(cls)
         self.last_counts = np.array(all_counts, dtype=np.int32)
         return nb

@@ -1131,7 +1131,10 @@ class RNmsBuffers(NmsBuffers):
     ROW = 7
 
     def workspace_bytes(self) -> int:
-        return lib().dy_nms_rotated_workspace_bytes(self.batch, self.anchors)
+        """``candidates_per_anchor`` 1: ``dy_nms_rotated``'s size; nc: ``dy_nms_rotated_ml``'s (keys and table for anchors * nc candidates)."""
+        if self.cpa == 1:
+            return lib().dy_nms_rotated_workspace_bytes(self.batch, self.anchors)
+        return lib().dy_nms_rotated_ml_workspace_bytes(self.batch, self.anchors, self.cpa)
 
 
 def nms_rotated(pred: torch.Tensor, theta: torch.Tensor, conf_thres: float, iou_thres: float, max_det: int = 300, max_nms: int = 30000,
@@ -1153,6 +1156,27 @@ def nms_rotated(pred: torch.Tensor, theta: torch.Tensor, conf_thres: float, iou_
         bufs = RNmsBuffers(n, A, max_det, pred.device)
     d = _nms_desc(pred, bufs, nc, conf_thres, iou_thres, max_nms, max_wh, agnostic, classes_mask, prefiltered, multi_label)
     _launch(lib().dy_nms_rotated, (C.byref(d), theta.data_ptr()), keep=(d, pred, theta, bufs, classes_mask))
+    return bufs
+
+
+def nms_rotated_ml(pred: torch.Tensor, theta: torch.Tensor, conf_thres: float, iou_thres: float, max_det: int = 300, max_nms: int = 30000,
+                   max_wh: float = 7680.0, agnostic: bool = False, nc: int = 0, classes_mask: Optional[torch.Tensor] = None,
+                   bufs: Optional[RNmsBuffers] = None) -> RNmsBuffers:
+    """The validator's rotated NMS (``dy_nms_rotated_ml``: ``non_max_suppression(rotated=True, multi_label=True)``): every (anchor, class)
+    pair above ``conf_thres`` is a candidate, ``bufs.index`` holds the pair's anchor and column 6 of a row its class.  ``nc`` 1 is the
+    single-label form.  Results stay on the device."""
+    require_device(pred, "prediction")
+    require_device(theta, "angles")
+    if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.dim() != 3:
+        raise ValueError("nms_rotated_ml expects a contiguous fp32 (N, 4+nc, A) tensor")
+    n, ch, A = pred.shape
+    if tuple(theta.shape) != (n, A) or theta.dtype != torch.float32 or not theta.is_contiguous():
+        raise ValueError("nms_rotated_ml: theta must be a contiguous fp32 (N, A) tensor")
+    nc = nc or ch - 4
+    if bufs is None or (bufs.batch, bufs.anchors, bufs.max_det) != (n, A, max_det) or bufs.cpa != nc:
+        bufs = RNmsBuffers(n, A, max_det, pred.device, candidates_per_anchor=nc)
+    d = _nms_desc(pred, bufs, nc, conf_thres, iou_thres, max_nms, max_wh, agnostic, classes_mask, False, True)
+    _launch(lib().dy_nms_rotated_ml, (C.byref(d), theta.data_ptr()), keep=(d, pred, theta, bufs, classes_mask))
     return bufs
 
 
@@ -1326,6 +1350,46 @@ def val_match(bufs: NmsBuffers, tbox: torch.Tensor, tcls: torch.Tensor, timg: to
     d.best_iou = best_iou.data_ptr() if want_best else None
     d.best_label = best_label.data_ptr() if want_best else None
     _launch(lib().dy_val_match, (C.byref(d),), keep=(d, thr, bufs, tbox, tcls, timg, tp, best_iou, best_label))
+    return (tp, best_iou, best_label) if want_best else tp
+
+
+def val_match_rotated(bufs: RNmsBuffers, tbox: torch.Tensor, tcls: torch.Tensor, timg: torch.Tensor, iouv: Sequence[float], clip_wh: Tuple[float, float],
+                      single_cls: bool = False, want_best: bool = False):
+    """The oriented-box validator's matching (``match_predictions`` on ``batch_probiou(gt, det)``, predictions clipped as its ``_prepare_pred``
+    clips them) of a whole batch on the padded rotated-NMS output through ``dy_val_match_rotated``; no host synchronisation.
+
+    ``bufs``: what ``nms_rotated`` / ``nms_rotated_ml`` returned; ``tbox`` (L, 5): the batch's labels, xywhr in pixels / radians, already
+    scaled and clipped (padded here, on the device, to the kernel's 8 floats per label); ``tcls`` (L,), ``timg`` (L,) (any order); ``iouv``:
+    1..16 thresholds.  Returns ``tp`` uint8 (N, max_det, len(iouv)), new tensors on every call; with ``want_best`` ``(tp, best_iou fp32
+    (N, max_det), best_label int32 (N, max_det))``.  Rows at or beyond ``bufs.count`` are 0 / 0 / -1."""
+    n, max_det, dev = bufs.batch, bufs.max_det, bufs.out.device
+    if bufs.out.shape[-1] != 7:
+        raise ValueError("val_match_rotated: the NMS buffers must hold 7-column rows (RNmsBuffers)")
+    L = int(tbox.shape[0])
+    if L:
+        for t in (tbox, tcls, timg):
+            require_device(t, "label")
+        if tbox.dim() != 2 or tbox.shape[1] != 5 or tcls.numel() != L or timg.numel() != L:
+            raise ValueError("val_match_rotated: tbox must be (L, 5) xywhr with L classes and L image indices")
+        padded = torch.zeros((L, 8), dtype=torch.float32, device=dev)
+        padded[:, :5] = tbox
+        tbox = padded
+        tcls = tcls.reshape(-1).to(torch.float32).contiguous()
+        timg = timg.reshape(-1).to(torch.int32).contiguous()
+    thr = (C.c_float * len(iouv))(*[float(v) for v in iouv])
+    tp = torch.empty((n, max_det, len(iouv)), dtype=torch.uint8, device=dev)
+    best_iou = torch.empty((n, max_det), dtype=torch.float32, device=dev) if want_best else None
+    best_label = torch.empty((n, max_det), dtype=torch.int32, device=dev) if want_best else None
+    d = _lib.ValMatchRotatedDesc()
+    d.rows, d.counts = bufs.out.data_ptr(), bufs.count.data_ptr()
+    d.tbox, d.tcls, d.timg = (tbox.data_ptr(), tcls.data_ptr(), timg.data_ptr()) if L else (None, None, None)
+    d.iouv = thr
+    d.batch, d.max_det, d.n_labels, d.n_iouv = n, max_det, L, len(iouv)
+    d.clip_w, d.clip_h, d.single_cls = float(clip_wh[0]), float(clip_wh[1]), int(bool(single_cls))
+    d.tp = tp.data_ptr()
+    d.best_iou = best_iou.data_ptr() if want_best else None
+    d.best_label = best_label.data_ptr() if want_best else None
+    _launch(lib().dy_val_match_rotated, (C.byref(d),), keep=(d, thr, bufs, tbox, tcls, timg, tp, best_iou, best_label))
     return (tp, best_iou, best_label) if want_best else tp
 
 

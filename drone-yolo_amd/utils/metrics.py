@@ -182,3 +182,8 @@ class SegmentMetrics:
     @property
     def results_dict(self) -> Dict[str, float]:
         return dict(zip(self.keys + ("fitness",), [float(v) for v in self.mean_results()] + [self.fitness]))
+
+
+class OBBMetrics(DetMetrics):
+    """Metrics of an oriented-box model — ``OBBMetrics`` (metrics.py): ``DetMetrics`` under its own name.  The statistics it is fed are
+    matched on ProbIoU (``OBBValidator``); the AP code, the keys (the four (B) entries) and ``fitness`` are the detection ones."""

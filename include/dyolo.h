@@ -639,6 +639,18 @@ int64_t dy_nms_rotated_workspace_bytes(int32_t batch, int32_t anchors);
 int32_t dy_nms_rotated(const dy_nms_desc* d, const float* theta, dy_stream_t stream);
 int32_t dy_nms_rotated_lds_cap(void);
 
+/* dy_nms_rotated_ml.  Replaces: ops.non_max_suppression(..., rotated=True, multi_label=True), the validator's NMS of an oriented-box model
+ * (models/yolo/detect/val.py postprocess with task == "obb"; utils/ops.py:286-288: `i, j = torch.where(cls > conf_thres)`).  An entry point
+ * of its own beside dy_nms_rotated: every (anchor, class) pair scored above conf is a candidate, whatever d->multi_label says; nc == 1
+ * degrades to the single-label form (ops.py:255).  The candidate stage is dy_nms's multi_label one: key low word anchor * nc + class, order
+ * descending score, then ascending anchor * nc + class (the row-major order of the reference's torch.where).  Suppression, table (LDS up
+ * to dy_nms_rotated_lds_cap() candidates, the workspace beyond that, decided on the device), the stop at max_det and the outputs are
+ * dy_nms_rotated's; the class offset and column 6 of a row are the pair's class, out_index holds the pair's anchor.
+ * workspace: dy_nms_rotated_ml_workspace_bytes(batch, anchors, nc) = a dy_nms workspace of anchors * nc candidates and a table of that
+ * capacity.  prefiltered: DY_ERR_UNSUPPORTED (the fused Detect filter is single-label).  anchors * nc < 2^30. */
+int64_t dy_nms_rotated_ml_workspace_bytes(int32_t batch, int32_t anchors, int32_t nc);
+int32_t dy_nms_rotated_ml(const dy_nms_desc* d, const float* theta, dy_stream_t stream);
+
 /* dy_scale_rboxes.  Replaces: OBBPredictor.construct_result (models/yolo/obb/predict.py:43-45) on the kept rows, in place for rows <
  * counts[b]: ops.regularize_rboxes (utils/ops.py:791-807: w and h swap iff theta mod pi >= pi / 2, then theta mod pi / 2, Python's `%`
  * for negative theta) and ops.scale_boxes(..., xywh=True) (:92-127): x = (x - pad_x) / gain, y = (y - pad_y) / gain, w / gain, h / gain,
@@ -677,6 +689,36 @@ typedef struct dy_val_match_desc {
   int32_t* best_label;
 } dy_val_match_desc;
 int32_t dy_val_match(const dy_val_match_desc* d, dy_stream_t stream);
+
+/* dy_val_match_rotated.  Replaces: OBBValidator._process_batch (models/yolo/obb/val.py: match_predictions on batch_probiou(gt, det)) with
+ * the clip of its _prepare_pred, for a whole batch in one launch behind dy_nms_rotated / dy_nms_rotated_ml; no host synchronisation,
+ * capturable in a hipGraph.
+ * rows: fp32 (batch, max_det, 7) = x, y, w, h, theta, conf, cls and counts: int32 (batch) (rows >= counts[i] are not read).
+ * tbox: fp32 (n_labels, 8), 16-byte aligned: x, y, w, h, theta in pixels / radians, already scaled and clipped, and three unused floats;
+ * tcls: fp32 (n_labels); timg: int32 (n_labels), by value (any order).  n_labels = 0 with null label pointers is valid.
+ * iouv: HOST array of n_iouv (1..16) thresholds, read during the call.
+ * A detection is clipped as scale_boxes(xywh=True) at gain 1, pad 0 leaves it: x and w to [0, clip_w], y and h to [0, clip_h] (clip_boxes
+ * clamps the width and height of an xywh row too); theta is untouched and not regularized.
+ *   m(l, d) = probiou(label l, detection d) if tcls[l] == cls[d] (0 with single_cls) else 0, in fp32 in batch_probiou's order of operations
+ *   (the expression of dy_nms_rotated; the device's sinf / cosf / logf / expf are not bit-equal to the host's);
+ *   best / biou / tp by dy_val_match's rule; exact ties go to the lower position in tbox, a NaN m never becomes the best.
+ * tp: uint8 (batch, max_det, n_iouv); best_iou: optional fp32 (batch, max_det); best_label: optional int32 (batch, max_det).  Every element
+ * is written: rows >= counts[i] (and rows without a best label) get 0 / 0 / -1.  max_det <= 4096 (36 bytes of LDS per detection). */
+typedef struct dy_val_match_rotated_desc {
+  const float* rows;
+  const int32_t* counts;
+  const float* tbox;
+  const float* tcls;
+  const int32_t* timg;
+  const float* iouv;
+  int32_t batch, max_det, n_labels, n_iouv;
+  float clip_w, clip_h;
+  int32_t single_cls;
+  uint8_t* tp;
+  float* best_iou;
+  int32_t* best_label;
+} dy_val_match_rotated_desc;
+int32_t dy_val_match_rotated(const dy_val_match_rotated_desc* d, dy_stream_t stream);
 
 /* ---- training loss (forward + gradient w.r.t. the head outputs) -----------------------------------------------------
  * Replaces: v8DetectionLoss.__call__ (utils/loss.py:206-260) = TaskAlignedAssigner (utils/tal.py:14-295, topk /
