@@ -38,9 +38,10 @@ __device__ __forceinline__ u64 nms_uniform64(u64 v) {
 }
 
 // Every thread of the 64 * WAVES of the workgroup calls it, behind the barrier that ends the sort.  mrows [64] and verdict [WAVES] are
-// LDS; outb / outi (or nullptr) / out_count: the image's max_keep output rows, their indices and its count.
+// LDS; outb / outi (or nullptr) / out_count: the image's max_keep output rows, their indices and its count.  Returns the count (alike on
+// every thread; tile_merge.hip's fusion pass goes on from it).
 template <int WAVES, typename Policy>
-__device__ __forceinline__ void nms_greedy_scan(const Policy& pol, int n, int max_keep, u64* mrows, u64* verdict, float* outb, int* outi, int* out_count) {
+__device__ __forceinline__ int nms_greedy_scan(const Policy& pol, int n, int max_keep, u64* mrows, u64* verdict, float* outb, int* outi, int* out_count) {
   constexpr int THREADS = 64 * WAVES, ROWS = 64 / WAVES;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -92,6 +93,7 @@ __device__ __forceinline__ void nms_greedy_scan(const Policy& pol, int n, int ma
   if (outi)
     for (int r = nk + tid; r < max_keep; r += THREADS) outi[r] = -1;
   if (tid == 0) *out_count = nk;
+  return nk;
 }
 
 }  // namespace dy

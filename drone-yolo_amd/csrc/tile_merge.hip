@@ -12,6 +12,20 @@
 //                       A box is the row's xyxy plus its tile's (ox, oy): one fp32 add of an integer-valued float.  Classes are compared as
 //                       integers; nothing is added to the coordinates.  All arithmetic is fp32 with contraction off, the IoU in the expression
 //                       order of nms.hip's iou_gt (the reference's), intersection over the smaller area for metric 1.
+//   tile_merge_kernel<true>   dy_tile_fuse: the same compaction, sort and scan (the same kept rows, scores, classes and slots), then the
+//                       kept row absorbs what it suppressed instead of dropping it (greedy non-maximum merging):
+//                         init      kept row k: members = 1, accumulators = its own box (the scan also left its sorted position, kpos[k]);
+//                         absorb    one thread per candidate j of the sorted list: a binary search of kpos gives the kept rows ahead of j
+//                                   (a prefix of the kept list, j itself when it is kept); the FIRST of them whose own box suppresses j
+//                                   absorbs it (a walk of eight rows per step, the predicate only for rows that intersect one of the wave's
+//                                   candidates) -- integer atomics on the kept row's accumulators, so the result does not depend on order:
+//                                     union  atomic min / max of an order-preserving map of the float bits (any sign);
+//                                     wbf    64-bit adds of w = rint(score * 2^16) and w * rint(coord * 64);
+//                         write     rows with two or more members get their fused box (wbf: X / S / 64 in float64), clamped to the frame.
+//                       LDS: keys [SL] * 8 + 656 fixed + 28 bytes per kept row (float4 box, area, class, sorted position), sized by need at
+//                       launch: 4,096 keys + 1,000 kept = 60 KB, at merge_max_det 4096 the kept list takes 112 KB and 4,096 keys the rest.
+//                       The accumulators (40 bytes per kept row) do not fit beside that, so they lie in the workspace behind the keys; only
+//                       this workgroup touches its frame's, with an agent-scope fence and a barrier between the phases.
 #include "nms_scan.h"
 
 #pragma clang fp contract(off)
@@ -85,6 +99,11 @@ constexpr int TM_MAX_KEEP = 4096;                       // merge_max_det
 constexpr int TM_MAX_LDS_KEYS = 16384;                  // 128 KiB of the CU's 160 KiB
 constexpr int TM_FIXED_LDS = 64 * 8 + TM_WAVES * 8 + 16;  // bit matrix, verdict words, two counters
 constexpr int TM_KEEP_BYTES = 24;                       // float4 box, area, class per kept row
+constexpr int TM_FUSE_KEEP_BYTES = TM_KEEP_BYTES + 4;   // dy_tile_fuse: and its position in the sorted list
+constexpr int TM_ACC_WORDS = 5;                         // dy_tile_fuse: 64-bit accumulators per kept row (wbf: S, X of x1 y1 x2 y2; union: 4 x 32 bits)
+constexpr int TM_UNION = 1, TM_WBF = 2;                 // dy_tile_fuse_desc.mode
+constexpr int TM_ABSORB_STEP = 8;                       // dy_tile_fuse: kept rows a candidate is tested against per step of its walk
+constexpr int TM_WBF_MAX_SIDE = 32768;                  // wbf: members * 2^16 * (side * 64) stays below 2^53
 
 struct TmArgs {
   const float* rows;
@@ -97,6 +116,10 @@ struct TmArgs {
   int K, max_det, N, P, SL;
   float fw, fh, thr;
   int metric, agnostic, keep;
+  // dy_tile_fuse only
+  int mode;
+  int* out_members;
+  u64* acc;  // [frames][keep][TM_ACC_WORDS]
 };
 
 struct TmCand {
@@ -169,6 +192,149 @@ struct TmScan {  // nms_greedy_scan's policy: frame-coordinate boxes, classes co
   }
 };
 
+// ---- fusion (dy_tile_fuse) ----------------------------------------------------------------------------------------------------------------
+struct TmFuseCand : TmCand {
+  int pos;  // place in the sorted list
+};
+
+struct TmFuseScan : TmScan {  // TmScan, and the sorted position of every kept row
+  int* kpos;                  // [keep]
+  typedef TmFuseCand Cand;
+  __device__ __forceinline__ Cand fetch(int i, int n) const {
+    Cand c;
+    static_cast<TmCand&>(c) = TmScan::fetch(i, n);
+    c.pos = i;
+    return c;
+  }
+  __device__ __forceinline__ void keep(int at, const Cand& c, const ScanBox& bx) const {
+    TmScan::keep(at, c, bx);
+    kpos[at] = c.pos;
+  }
+};
+
+// float -> unsigned whose integer order is the float order (negative values included), and back
+__device__ __forceinline__ unsigned tm_ord(float v) {
+  const unsigned u = __float_as_uint(v);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float tm_unord(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
+
+__device__ __forceinline__ long long tm_wbf_weight(float score) { return (long long)rintf(score * 65536.f); }
+__device__ __forceinline__ long long tm_wbf_coord(float v) { return (long long)rintf(v * 64.f); }
+
+// between two phases that hand this frame's accumulators from plain stores to atomics or from atomics to loads, inside the workgroup
+__device__ __forceinline__ void tm_phase_barrier() {
+  __threadfence();
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+}
+
+// Behind the scan, every thread of the workgroup: nk rows kept out of the n sorted candidates.
+__device__ __forceinline__ void tm_fuse_tail(const TmArgs& p, const TmFuseScan& pol, int f, int n, int nk) {
+  const int tid = threadIdx.x;
+  u64* acc = p.acc + (size_t)f * p.keep * TM_ACC_WORDS;
+  int* mem = p.out_members + (size_t)f * p.keep;
+  float* outb = p.out + (size_t)f * p.keep * 6;
+
+  // init: a kept row is its own first member
+  for (int k = tid; k < p.keep; k += TM_THREADS) {
+    mem[k] = k < nk ? 1 : 0;
+    if (k >= nk) continue;
+    const float4 b = pol.kbox[k];
+    if (p.mode == TM_UNION) {
+      unsigned* a = reinterpret_cast<unsigned*>(acc + (size_t)k * TM_ACC_WORDS);
+      a[0] = tm_ord(b.x);
+      a[1] = tm_ord(b.y);
+      a[2] = tm_ord(b.z);
+      a[3] = tm_ord(b.w);
+    } else {
+      const int at = pol.kpos[k];
+      const u64 key = pol.in_lds ? pol.skeys[at] : pol.gkeys[at];
+      const long long w = tm_wbf_weight(__uint_as_float(~(unsigned)(key >> 32)));
+      u64* a = acc + (size_t)k * TM_ACC_WORDS;
+      a[0] = (u64)w;
+      a[1] = (u64)(w * tm_wbf_coord(b.x));
+      a[2] = (u64)(w * tm_wbf_coord(b.y));
+      a[3] = (u64)(w * tm_wbf_coord(b.z));
+      a[4] = (u64)(w * tm_wbf_coord(b.w));
+    }
+  }
+  tm_phase_barrier();
+
+  // absorb: candidate j goes to the first kept row ahead of it in the sorted list whose own box suppresses it
+  for (int j = tid; j < n; j += TM_THREADS) {
+    int lo = 0, hi = nk;  // lo: the kept rows with kpos < j
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (pol.kpos[mid] < j) lo = mid + 1;
+      else hi = mid;
+    }
+    if (lo < nk && pol.kpos[lo] == j) continue;  // kept itself
+    const TmCand c = pol.TmScan::fetch(j, n);
+    const ScanBox bx = pol.box(c);
+    // eight kept rows per step, their LDS reads in flight together, the exit tested once per step (a row past the prefix repeats its last).
+    // The predicate (a division) runs only where the boxes intersect at all: inter == 0 gives 0 / den > thr, false for every den and
+    // thr >= 0, and a wave whose 64 candidates all miss the kept row -- most rows of the walk -- skips it.  inter is the predicate's own
+    // w * h, so the verdict is the scan's.
+    int own = lo;
+    for (int k0 = 0; k0 < lo && own == lo; k0 += TM_ABSORB_STEP) {
+#pragma unroll
+      for (int u = TM_ABSORB_STEP - 1; u >= 0; --u) {
+        const int k = min(k0 + u, lo - 1);
+        const float4 kb = pol.kbox[k];
+        const float w = fmaxf(0.f, fminf(kb.z, bx.x2) - fmaxf(kb.x, bx.x1)), h = fmaxf(0.f, fminf(kb.w, bx.y2) - fmaxf(kb.y, bx.y1));
+        if (__ballot(w * h > 0.f) != 0ull && pol.suppresses(pol.kept(k), bx)) own = k;  // (the ballot of the active lanes: a uniform branch)
+      }
+    }
+    if (own == lo) continue;  // behind the stop at merge_max_det and matching no kept row: dropped
+    atomicAdd(mem + own, 1);
+    if (p.mode == TM_UNION) {
+      unsigned* a = reinterpret_cast<unsigned*>(acc + (size_t)own * TM_ACC_WORDS);
+      atomicMin(a + 0, tm_ord(c.x1));
+      atomicMin(a + 1, tm_ord(c.y1));
+      atomicMax(a + 2, tm_ord(c.x2));
+      atomicMax(a + 3, tm_ord(c.y2));
+    } else {
+      const long long w = tm_wbf_weight(c.score);
+      u64* a = acc + (size_t)own * TM_ACC_WORDS;
+      atomicAdd(a + 0, (u64)w);
+      atomicAdd(a + 1, (u64)(w * tm_wbf_coord(c.x1)));
+      atomicAdd(a + 2, (u64)(w * tm_wbf_coord(c.y1)));
+      atomicAdd(a + 3, (u64)(w * tm_wbf_coord(c.x2)));
+      atomicAdd(a + 4, (u64)(w * tm_wbf_coord(c.y2)));
+    }
+  }
+  tm_phase_barrier();
+
+  // write: the scan left every kept row with its own box; a row that absorbed something gets the fused one
+  for (int k = tid; k < nk; k += TM_THREADS) {
+    if (__hip_atomic_load(mem + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 2) continue;
+    float v[4];
+    if (p.mode == TM_UNION) {
+      const unsigned* a = reinterpret_cast<const unsigned*>(acc + (size_t)k * TM_ACC_WORDS);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) v[c] = tm_unord(__hip_atomic_load(a + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    } else {
+      const u64* a = acc + (size_t)k * TM_ACC_WORDS;
+      const long long s = (long long)__hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (s == 0) continue;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const long long x = (long long)__hip_atomic_load(a + 1 + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        v[c] = (float)(((double)x / (double)s) * 0.015625);
+      }
+    }
+    float* o = outb + (size_t)k * 6;
+    o[0] = fminf(fmaxf(v[0], 0.f), p.fw);
+    o[1] = fminf(fmaxf(v[1], 0.f), p.fh);
+    o[2] = fminf(fmaxf(v[2], 0.f), p.fw);
+    o[3] = fminf(fmaxf(v[3], 0.f), p.fh);
+  }
+}
+
+// FUSE = false is dy_tile_merge's kernel; FUSE = true goes on behind the scan (dy_tile_fuse): a kernel of its own, the suppress path is at
+// 115 of its 128 VGPRs
+template <bool FUSE>
 __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(const TmArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
   u64* skeys = reinterpret_cast<u64*>(dyn_smem);  // [SL]
@@ -233,8 +399,14 @@ __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(const TmArgs p) 
 
   float* outb = p.out + (size_t)f * p.keep * 6;
   int* outi = p.out_index ? p.out_index + (size_t)f * p.keep : nullptr;
-  const TmScan pol{p, skeys, gkeys, frows, outb, outi, kbox, kar, kcls, in_lds};
-  nms_greedy_scan<TM_WAVES>(pol, n, p.keep, mrows, verdict, outb, outi, p.out_count + f);
+  if constexpr (!FUSE) {
+    const TmScan pol{p, skeys, gkeys, frows, outb, outi, kbox, kar, kcls, in_lds};
+    nms_greedy_scan<TM_WAVES>(pol, n, p.keep, mrows, verdict, outb, outi, p.out_count + f);
+  } else {
+    const TmFuseScan pol{{p, skeys, gkeys, frows, outb, outi, kbox, kar, kcls, in_lds}, kcls + p.keep};
+    const int nk = nms_greedy_scan<TM_WAVES>(pol, n, p.keep, mrows, verdict, outb, outi, p.out_count + f);
+    tm_fuse_tail(p, pol, f, n, nk);
+  }
 }
 
 }  // namespace dy
@@ -262,22 +434,10 @@ extern "C" int64_t dy_tile_merge_workspace_bytes(int32_t frames, int32_t tiles, 
   return (int64_t)frames * nms_next_pow2(tiles * max_det) * 8;
 }
 
-extern "C" int32_t dy_tile_merge(const dy_tile_merge_desc* d, dy_stream_t stream) {
-  DY_REQUIRE(d && d->rows && d->counts && d->offsets_yx && d->out && d->out_count && d->workspace, DY_ERR_INVALID_ARG,
-             "dy_tile_merge: null pointer (rows / counts / offsets_yx / out / out_count / workspace)");
-  DY_REQUIRE(d->frames > 0 && d->tiles > 0 && d->max_det > 0 && d->nc > 0 && d->frame_h > 0 && d->frame_w > 0 && d->merge_max_det > 0, DY_ERR_INVALID_ARG,
-             "dy_tile_merge: bad dims (frames %d, tiles %d, max_det %d, nc %d, frame %d x %d, merge_max_det %d)", d->frames, d->tiles, d->max_det, d->nc,
-             d->frame_h, d->frame_w, d->merge_max_det);
-  DY_REQUIRE(d->metric == 0 || d->metric == 1, DY_ERR_INVALID_ARG, "dy_tile_merge: metric %d (0 = IoU, 1 = IoS)", d->metric);
-  DY_REQUIRE(d->thr >= 0.f && d->thr <= 1.f, DY_ERR_INVALID_ARG, "dy_tile_merge: thr must be in [0,1]");
-  DY_REQUIRE((long long)d->tiles * d->max_det <= TM_MAX_SLOTS, DY_ERR_UNSUPPORTED, "dy_tile_merge: tiles * max_det = %lld > %d", (long long)d->tiles * d->max_det,
-             TM_MAX_SLOTS);
-  DY_REQUIRE(d->merge_max_det <= TM_MAX_KEEP, DY_ERR_UNSUPPORTED, "dy_tile_merge: merge_max_det %d > %d", d->merge_max_det, TM_MAX_KEEP);
-  const int64_t need = dy_tile_merge_workspace_bytes(d->frames, d->tiles, d->max_det);
-  DY_REQUIRE(d->workspace_bytes >= need, DY_ERR_WORKSPACE, "dy_tile_merge: workspace %lld < %lld bytes", (long long)d->workspace_bytes, (long long)need);
-  DY_REQUIRE(aligned16(d->workspace), DY_ERR_INVALID_ARG, "dy_tile_merge: workspace not 16-byte aligned");
-
-  TmArgs a{};
+// The kernel arguments a checked descriptor describes (dy_tile_merge_desc / dy_tile_fuse_desc: the fields they share; `a` holds what only
+// the fusion has) and the launch.
+template <bool FUSE, typename Desc>
+static int tm_launch(const Desc* d, TmArgs a, const char* who, dy_stream_t stream) {
   a.rows = d->rows;
   a.counts = d->counts;
   a.offs = d->offsets_yx;
@@ -296,12 +456,59 @@ extern "C" int32_t dy_tile_merge(const dy_tile_merge_desc* d, dy_stream_t stream
   a.agnostic = d->agnostic ? 1 : 0;
   a.keep = d->merge_max_det;
   // LDS by need: the keys of every slot when they fit beside the kept list, the largest power of two that does otherwise
-  const size_t rest = (size_t)TM_FIXED_LDS + nms_align_up((size_t)a.keep * TM_KEEP_BYTES, 16);
+  const size_t rest = (size_t)TM_FIXED_LDS + nms_align_up((size_t)a.keep * (FUSE ? TM_FUSE_KEEP_BYTES : TM_KEEP_BYTES), 16);
   a.SL = a.P < TM_MAX_LDS_KEYS ? a.P : TM_MAX_LDS_KEYS;
   while ((size_t)a.SL * 8 + rest > 160 * 1024) a.SL >>= 1;
   const size_t smem = (size_t)a.SL * 8 + rest;
-  static const hipError_t attr_once = hipFuncSetAttribute((const void*)tile_merge_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  static const hipError_t attr_once = hipFuncSetAttribute((const void*)tile_merge_kernel<FUSE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   (void)attr_once;
-  hipLaunchKernelGGL(tile_merge_kernel, dim3((unsigned)d->frames), dim3(TM_THREADS), smem, reinterpret_cast<hipStream_t>(stream), a);
-  return check_launch("dy_tile_merge");
+  hipLaunchKernelGGL(tile_merge_kernel<FUSE>, dim3((unsigned)d->frames), dim3(TM_THREADS), smem, reinterpret_cast<hipStream_t>(stream), a);
+  return check_launch(who);
+}
+
+extern "C" int32_t dy_tile_merge(const dy_tile_merge_desc* d, dy_stream_t stream) {
+  DY_REQUIRE(d && d->rows && d->counts && d->offsets_yx && d->out && d->out_count && d->workspace, DY_ERR_INVALID_ARG,
+             "dy_tile_merge: null pointer (rows / counts / offsets_yx / out / out_count / workspace)");
+  DY_REQUIRE(d->frames > 0 && d->tiles > 0 && d->max_det > 0 && d->nc > 0 && d->frame_h > 0 && d->frame_w > 0 && d->merge_max_det > 0, DY_ERR_INVALID_ARG,
+             "dy_tile_merge: bad dims (frames %d, tiles %d, max_det %d, nc %d, frame %d x %d, merge_max_det %d)", d->frames, d->tiles, d->max_det, d->nc,
+             d->frame_h, d->frame_w, d->merge_max_det);
+  DY_REQUIRE(d->metric == 0 || d->metric == 1, DY_ERR_INVALID_ARG, "dy_tile_merge: metric %d (0 = IoU, 1 = IoS)", d->metric);
+  DY_REQUIRE(d->thr >= 0.f && d->thr <= 1.f, DY_ERR_INVALID_ARG, "dy_tile_merge: thr must be in [0,1]");
+  DY_REQUIRE((long long)d->tiles * d->max_det <= TM_MAX_SLOTS, DY_ERR_UNSUPPORTED, "dy_tile_merge: tiles * max_det = %lld > %d", (long long)d->tiles * d->max_det,
+             TM_MAX_SLOTS);
+  DY_REQUIRE(d->merge_max_det <= TM_MAX_KEEP, DY_ERR_UNSUPPORTED, "dy_tile_merge: merge_max_det %d > %d", d->merge_max_det, TM_MAX_KEEP);
+  const int64_t need = dy_tile_merge_workspace_bytes(d->frames, d->tiles, d->max_det);
+  DY_REQUIRE(d->workspace_bytes >= need, DY_ERR_WORKSPACE, "dy_tile_merge: workspace %lld < %lld bytes", (long long)d->workspace_bytes, (long long)need);
+  DY_REQUIRE(aligned16(d->workspace), DY_ERR_INVALID_ARG, "dy_tile_merge: workspace not 16-byte aligned");
+  return tm_launch<false>(d, TmArgs{}, "dy_tile_merge", stream);
+}
+
+extern "C" int64_t dy_tile_fuse_workspace_bytes(int32_t frames, int32_t tiles, int32_t max_det, int32_t merge_max_det) {
+  const int64_t keys = dy_tile_merge_workspace_bytes(frames, tiles, max_det);
+  if (keys < 0 || merge_max_det <= 0 || merge_max_det > TM_MAX_KEEP) return -1;
+  return keys + (int64_t)frames * merge_max_det * TM_ACC_WORDS * 8;
+}
+
+extern "C" int32_t dy_tile_fuse(const dy_tile_fuse_desc* d, dy_stream_t stream) {
+  DY_REQUIRE(d && d->rows && d->counts && d->offsets_yx && d->out && d->out_count && d->out_members && d->workspace, DY_ERR_INVALID_ARG,
+             "dy_tile_fuse: null pointer (rows / counts / offsets_yx / out / out_count / out_members / workspace)");
+  DY_REQUIRE(d->frames > 0 && d->tiles > 0 && d->max_det > 0 && d->nc > 0 && d->frame_h > 0 && d->frame_w > 0 && d->merge_max_det > 0, DY_ERR_INVALID_ARG,
+             "dy_tile_fuse: bad dims (frames %d, tiles %d, max_det %d, nc %d, frame %d x %d, merge_max_det %d)", d->frames, d->tiles, d->max_det, d->nc,
+             d->frame_h, d->frame_w, d->merge_max_det);
+  DY_REQUIRE(d->metric == 0 || d->metric == 1, DY_ERR_INVALID_ARG, "dy_tile_fuse: metric %d (0 = IoU, 1 = IoS)", d->metric);
+  DY_REQUIRE(d->mode == TM_UNION || d->mode == TM_WBF, DY_ERR_INVALID_ARG, "dy_tile_fuse: mode %d (1 = union, 2 = wbf; suppression is dy_tile_merge)", d->mode);
+  DY_REQUIRE(d->thr >= 0.f && d->thr <= 1.f, DY_ERR_INVALID_ARG, "dy_tile_fuse: thr must be in [0,1]");
+  DY_REQUIRE((long long)d->tiles * d->max_det <= TM_MAX_SLOTS, DY_ERR_UNSUPPORTED, "dy_tile_fuse: tiles * max_det = %lld > %d", (long long)d->tiles * d->max_det,
+             TM_MAX_SLOTS);
+  DY_REQUIRE(d->merge_max_det <= TM_MAX_KEEP, DY_ERR_UNSUPPORTED, "dy_tile_fuse: merge_max_det %d > %d", d->merge_max_det, TM_MAX_KEEP);
+  DY_REQUIRE(d->mode != TM_WBF || (d->frame_h <= TM_WBF_MAX_SIDE && d->frame_w <= TM_WBF_MAX_SIDE), DY_ERR_UNSUPPORTED,
+             "dy_tile_fuse: wbf on a frame of %d x %d, sides above %d are beyond its integer sums", d->frame_h, d->frame_w, TM_WBF_MAX_SIDE);
+  const int64_t need = dy_tile_fuse_workspace_bytes(d->frames, d->tiles, d->max_det, d->merge_max_det);
+  DY_REQUIRE(d->workspace_bytes >= need, DY_ERR_WORKSPACE, "dy_tile_fuse: workspace %lld < %lld bytes", (long long)d->workspace_bytes, (long long)need);
+  DY_REQUIRE(aligned16(d->workspace), DY_ERR_INVALID_ARG, "dy_tile_fuse: workspace not 16-byte aligned");
+  TmArgs a{};
+  a.mode = d->mode;
+  a.out_members = d->out_members;
+  a.acc = reinterpret_cast<u64*>(reinterpret_cast<unsigned char*>(d->workspace) + dy_tile_merge_workspace_bytes(d->frames, d->tiles, d->max_det));
+  return tm_launch<true>(d, a, "dy_tile_fuse", stream);
 }

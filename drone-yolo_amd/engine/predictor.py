@@ -93,7 +93,7 @@ class DetectionPredictor:
         a = dict(conf=0.25, iou=0.7, max_det=300, classes=None, agnostic_nms=False, half=False, dtype=None, device="",
                  verbose=False, graph=True, max_nms=30000, max_wh=7680, imgsz=640, fp8_layers=None, batch=None, augment=False,
                  tracker="bytetrack.yaml", device_track=True, track_streams=1, max_tracks=512,
-                 tile=None, tile_overlap=0.2, merge_iou=0.7, merge_metric="iou", merge_max_det=1000, retina_masks=False)
+                 tile=None, tile_overlap=0.2, merge_iou=0.7, merge_metric="iou", merge_mode="suppress", merge_max_det=1000, retina_masks=False)
         a.update(overrides or {})
         self.args = a
         if a["tile"] is not None:  # tiled inference: checked before anything touches the device
@@ -102,6 +102,8 @@ class DetectionPredictor:
                 raise ValueError(f"tile = {a['tile']} must be a positive multiple of the model's largest stride {s}")
             if str(a["merge_metric"]).lower() not in H.TILE_MERGE_METRICS:
                 raise ValueError(f"merge_metric = '{a['merge_metric']}', expected one of {sorted(H.TILE_MERGE_METRICS)}")
+            if str(a["merge_mode"]).lower() not in H.TILE_MERGE_MODES:
+                raise ValueError(f"merge_mode = '{a['merge_mode']}', expected one of {sorted(H.TILE_MERGE_MODES)}")
             if a["augment"]:
                 raise NotImplementedError("augment=True with tile: the image pyramid of test-time augmentation is not built for tiles")
             if not 0.0 <= float(a["tile_overlap"]) < 1.0 or not 0.0 <= float(a["merge_iou"]) <= 1.0 or int(a["merge_max_det"]) < 1:
@@ -601,13 +603,14 @@ class DetectionPredictor:
                 offs_d = torch.tensor(offs, dtype=torch.int32, device=self.device)
                 k = len(offs)
                 st = self._tile_state[key] = (offs_d, k, torch.empty((len(idxs) * k, 3, tile, tile), dtype=torch.float32, device=self.device),
-                                              H.TileMergeBuffers(len(idxs), k, int(a["max_det"]), int(a["merge_max_det"]), self.device))
+                                              H.TileMergeBuffers(len(idxs), k, int(a["max_det"]), int(a["merge_max_det"]), self.device,
+                                                                 fuse=str(a["merge_mode"]).lower() != "suppress"))
             offs_d, k, tiles, mbufs = st
             H.tiles_batch(stacked, offs_d, tile, out=tiles)  # a frame no larger than the tile is one tile padded with 114
             self.letterbox_info = None  # every tile is an image of its own to the pass: boxes clipped to the tile
             cf = self.forward_device(tiles)
             merged = H.tile_merge(cf.nms, offs_d, k, (hf, wf), self.model.yaml["nc"], float(a["merge_iou"]), str(a["merge_metric"]),
-                                  bool(a["agnostic_nms"]), int(a["merge_max_det"]), bufs=mbufs)
+                                  bool(a["agnostic_nms"]), int(a["merge_max_det"]), bufs=mbufs, mode=str(a["merge_mode"]))
             tracked = None
             if self.tracker is not None and hasattr(self.tracker, "bufs"):
                 tout, tcnt = self.tracker.update_batch(merged.out, merged.count)

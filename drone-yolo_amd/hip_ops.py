@@ -21,7 +21,7 @@ import warnings
 import torch
 
 from . import _lib
-from ._lib import DY_ACT_NONE, DY_ACT_SILU, DY_ACT_SILU_L2E, BnDesc, BranchDesc, C2fDesc, C2fFrontDesc, C2fTailDesc, ConvDesc, DecodeDesc, HeadDecodeDesc, LossDesc, NmsDesc, Stem2Desc, TileMergeDesc, TrackDesc, ValMaskMatchDesc, ValMatchDesc, check, lib
+from ._lib import DY_ACT_NONE, DY_ACT_SILU, DY_ACT_SILU_L2E, BnDesc, BranchDesc, C2fDesc, C2fFrontDesc, C2fTailDesc, ConvDesc, DecodeDesc, HeadDecodeDesc, LossDesc, NmsDesc, Stem2Desc, TileFuseDesc, TileMergeDesc, TrackDesc, ValMaskMatchDesc, ValMatchDesc, check, lib
 
 FP8 = torch.float8_e4m3fn  # OCP e4m3fn: gfx950's fp8 (MI300's fnuz is another encoding)
 # DY_F16X2 (include/dyolo.h): split float16 pairs, x ~= hi + lo * 2^-11 — the bar-exact precision on the 16-bit MFMA.  torch has no such
@@ -1977,9 +1977,11 @@ def tiles_batch(frames: torch.Tensor, offsets: torch.Tensor, tile: int, out: Opt
 
 class TileMergeBuffers:
     """Persistent outputs + workspace of ``dy_tile_merge`` for one (frames, tiles, max_det, merge_max_det).  ``out`` / ``count`` / ``index`` /
-    ``batch`` / ``max_det`` mean what they mean on ``NmsBuffers`` (``max_det`` = merge_max_det), so whatever reads NMS output reads this."""
+    ``batch`` / ``max_det`` mean what they mean on ``NmsBuffers`` (``max_det`` = merge_max_det), so whatever reads NMS output reads this.
+    ``fuse=True`` (or the first ``tile_merge`` call with a fusing mode) adds what ``dy_tile_fuse`` needs: ``members`` (frames, merge_max_det)
+    int32 and ``fuse_workspace``; ``members`` stays ``None`` on buffers that only ever suppress."""
 
-    def __init__(self, frames: int, tiles: int, tile_max_det: int, merge_max_det: int, device):
+    def __init__(self, frames: int, tiles: int, tile_max_det: int, merge_max_det: int, device, fuse: bool = False):
         self.batch, self.tiles, self.tile_max_det, self.max_det = int(frames), int(tiles), int(tile_max_det), int(merge_max_det)
         nbytes = lib().dy_tile_merge_workspace_bytes(self.batch, self.tiles, self.tile_max_det)
         if nbytes < 0:
@@ -1988,17 +1990,34 @@ class TileMergeBuffers:
         self.out = torch.empty((self.batch, self.max_det, 6), dtype=torch.float32, device=device)
         self.count = torch.empty((self.batch,), dtype=torch.int32, device=device)
         self.index = torch.empty((self.batch, self.max_det), dtype=torch.int32, device=device)
+        self.members: Optional[torch.Tensor] = None
+        self.fuse_workspace: Optional[torch.Tensor] = None
+        if fuse:
+            self.enable_fuse()
+
+    def enable_fuse(self) -> None:
+        """Allocate (once) ``members`` and the workspace of ``dy_tile_fuse``."""
+        if self.members is not None:
+            return
+        nbytes = lib().dy_tile_fuse_workspace_bytes(self.batch, self.tiles, self.tile_max_det, self.max_det)
+        if nbytes < 0:
+            raise ValueError(f"tile_merge: merge_max_det {self.max_det} is beyond the fusing kernel's 4096 rows per frame")
+        self.fuse_workspace = torch.empty((nbytes,), dtype=torch.uint8, device=self.out.device)
+        self.members = torch.empty((self.batch, self.max_det), dtype=torch.int32, device=self.out.device)
 
 
 _TILE_MERGE_BUFS: dict = {}
 TILE_MERGE_METRICS = {"iou": 0, "ios": 1}
+TILE_MERGE_MODES = {"suppress": 0, "union": 1, "wbf": 2}
 
 
 def tile_merge(nms_bufs, offsets: torch.Tensor, K: int, frame_hw: Tuple[int, int], nc: int, thr: float, metric=0, agnostic: bool = False,
-               merge_max_det: int = 1000, bufs: Optional[TileMergeBuffers] = None) -> TileMergeBuffers:
+               merge_max_det: int = 1000, bufs: Optional[TileMergeBuffers] = None, mode="suppress") -> TileMergeBuffers:
     """Cross-tile merge of F frames in one ``dy_tile_merge`` launch; no host synchronisation.  ``nms_bufs``: the per-tile ``NmsBuffers`` of the
     (F * K)-tile batch (rows in tile pixels, clipped to the tile) or a ``(rows, counts)`` pair; ``offsets``: device int32 (K, 2) = (y, x);
-    ``metric``: 0 / "iou" or 1 / "ios" (intersection over the smaller box).  Returns rows in frame pixels, clamped to the frame, in buffers
+    ``metric``: 0 / "iou" or 1 / "ios" (intersection over the smaller box).  ``mode``: 0 / "suppress" drops what a kept row suppresses; 1 / "union"
+    and 2 / "wbf" go through one ``dy_tile_fuse`` launch instead: the same rows are kept, each with the bounding box / the score-weighted mean
+    of itself and the rows it absorbed, and ``bufs.members`` counts them.  Returns rows in frame pixels, clamped to the frame, in buffers
     that persist per (F, K, max_det, merge_max_det): the next call with the same sizes overwrites them."""
     rows, counts = (nms_bufs.out, nms_bufs.count) if hasattr(nms_bufs, "out") else nms_bufs
     require_device(rows, "per-tile rows")
@@ -2014,18 +2033,32 @@ def tile_merge(nms_bufs, offsets: torch.Tensor, K: int, frame_hw: Tuple[int, int
         if metric.lower() not in TILE_MERGE_METRICS:
             raise ValueError(f"tile_merge: metric '{metric}', expected one of {sorted(TILE_MERGE_METRICS)}")
         metric = TILE_MERGE_METRICS[metric.lower()]
+    if isinstance(mode, str):
+        if mode.lower() not in TILE_MERGE_MODES:
+            raise ValueError(f"tile_merge: mode '{mode}', expected one of {sorted(TILE_MERGE_MODES)}")
+        mode = TILE_MERGE_MODES[mode.lower()]
+    if int(mode) not in TILE_MERGE_MODES.values():
+        raise ValueError(f"tile_merge: mode {mode}, expected 0 (suppress), 1 (union) or 2 (wbf)")
     f, md = rows.shape[0] // K, int(rows.shape[1])
     if bufs is None or (bufs.batch, bufs.tiles, bufs.tile_max_det, bufs.max_det) != (f, K, md, int(merge_max_det)) or bufs.out.device != rows.device:
         key = (rows.device, f, K, md, int(merge_max_det))
         bufs = _TILE_MERGE_BUFS.get(key)
         if bufs is None:
             bufs = _TILE_MERGE_BUFS[key] = TileMergeBuffers(f, K, md, int(merge_max_det), rows.device)
-    d = TileMergeDesc()
+    fuse = int(mode) != 0
+    if fuse:
+        bufs.enable_fuse()
+    d = TileFuseDesc() if fuse else TileMergeDesc()
     d.rows, d.counts, d.offsets_yx = rows.data_ptr(), counts.data_ptr(), offsets.data_ptr()
     d.frames, d.tiles, d.max_det, d.nc = f, K, md, int(nc)
     d.frame_h, d.frame_w = int(frame_hw[0]), int(frame_hw[1])
     d.thr, d.metric, d.agnostic, d.merge_max_det = float(thr), int(metric), int(bool(agnostic)), int(merge_max_det)
     d.out, d.out_count, d.out_index = bufs.out.data_ptr(), bufs.count.data_ptr(), bufs.index.data_ptr()
+    if fuse:
+        d.mode, d.out_members = int(mode), bufs.members.data_ptr()
+        d.workspace, d.workspace_bytes = bufs.fuse_workspace.data_ptr(), bufs.fuse_workspace.numel()
+        _launch(lib().dy_tile_fuse, (C.byref(d),), keep=(d, rows, counts, offsets, bufs))
+        return bufs
     d.workspace, d.workspace_bytes = bufs.workspace.data_ptr(), bufs.workspace.numel()
     _launch(lib().dy_tile_merge, (C.byref(d),), keep=(d, rows, counts, offsets, bufs))
     return bufs

@@ -459,6 +459,41 @@ typedef struct dy_tile_merge_desc {
 int64_t dy_tile_merge_workspace_bytes(int32_t frames, int32_t tiles, int32_t max_det);
 int32_t dy_tile_merge(const dy_tile_merge_desc* d, dy_stream_t stream);
 
+/* dy_tile_fuse: dy_tile_merge whose kept rows absorb what they suppress (greedy non-maximum merging) instead of dropping it; one launch,
+ *   one workgroup per frame, no host synchronisation.  Candidates, their frame-coordinate boxes, the order, the predicate and the kept rows
+ *   are dy_tile_merge's: out_count, out_index, conf and cls of every output row are bit-identical to dy_tile_merge on the same input, only
+ *   x1, y1, x2, y2 differ.  A candidate j that is not kept is absorbed by the kept row k of smallest index that stands before j in the
+ *   sorted order and whose OWN box (never the grown one: greedy, not transitive) suppresses j; a candidate without such a row is dropped
+ *   (only rows behind the stop at merge_max_det).  The members of a kept row are itself and the rows it absorbed.
+ *     mode 1 (union): x1, y1 = the minimum, x2, y2 = the maximum over the members (exact in fp32, independent of order).
+ *     mode 2 (wbf): a row with one member keeps its own box; otherwise, in integers (associative, bit-reproducible),
+ *       w_j = (int64) rintf(score_j * 65536.f), q_jc = (int64) rintf(coord_jc * 64.f), S = sum w_j, X_c = sum w_j * q_jc,
+ *       fused_c = (float)(((double)X_c / (double)S) * 0.015625); S == 0 keeps the row's own box.  frame_h, frame_w <= 32768
+ *       (DY_ERR_UNSUPPORTED beyond: X_c stays below 2^53).
+ *   Both are clamped to the frame like dy_tile_merge's rows.  out_members: int32 (f, merge_max_det), the number of members of every kept
+ *   row (>= 1), 0 beyond the count.  No floating-point atomic anywhere: two launches on one input give bit-identical buffers.
+ *   workspace: dy_tile_fuse_workspace_bytes(f, k, max_det, merge_max_det) bytes (the keys and 40 bytes of accumulators per output row;
+ *   -1 for sizes the entry point refuses), 16-byte aligned.  Limits and checks as dy_tile_merge, and mode; all before any launch. */
+typedef struct dy_tile_fuse_desc {
+  const float* rows;
+  const int32_t* counts;
+  const int32_t* offsets_yx;
+  int32_t frames, tiles, max_det, nc;
+  int32_t frame_h, frame_w;
+  float thr;
+  int32_t metric; /* 0 = IoU, 1 = IoS */
+  int32_t agnostic, merge_max_det;
+  int32_t mode; /* 1 = union, 2 = wbf */
+  float* out;
+  int32_t* out_count;
+  int32_t* out_index;   /* optional, as in dy_tile_merge_desc */
+  int32_t* out_members;
+  void* workspace;
+  int64_t workspace_bytes;
+} dy_tile_fuse_desc;
+int64_t dy_tile_fuse_workspace_bytes(int32_t frames, int32_t tiles, int32_t max_det, int32_t merge_max_det);
+int32_t dy_tile_fuse(const dy_tile_fuse_desc* d, dy_stream_t stream);
+
 /* ---- layout / copy ops ------------------------------------------------------ */
 
 /* Replaces: predictor preprocess `.half()/.float()` + the NCHW->device layout step

@@ -5,7 +5,7 @@ A synthetic 3840 x 2160 uint8 video, tile 1280, overlap 0.2 (eight tiles per fra
 after warm-up and is timed with device events; each figure is the median over `--rounds` rounds, with the smallest and largest beside it.
   (a) merge   the merge stage alone on the same per-tile rows (objects seen by every tile that holds them, about 30 and about 300 rows per
               tile): A = dy_rows_to_pred + dy_nms (the parent chain, one frame), B = dy_tile_merge (one frame); B8 = dy_tile_merge on eight
-              frames in one launch, per frame.
+              frames in one launch, per frame; U / W = dy_tile_fuse in mode union / wbf (one frame), U8 / W8 on eight frames, per frame.
   (b) slicer  eight frames: A = eight dy_tiles_u8_to_nchw_f32 launches, B = one dy_tiles_batch_u8_to_nchw_f32 launch; ms and GB/s written.
   (c) frames/s end to end over `--frames` frames (host clock around the whole loop, results materialised): A = TiledPredictor called frame by
               frame, B = predict(frames, tile=1280, batch=F, stream=True) for F = 1, 2, 4.
@@ -102,11 +102,20 @@ for per_tile in (30, 300):
 
     one = lambda: H.tile_merge((r1, c1), offs_d, K, (HF, WF), NC, THR, 0, False, KEEP)  # noqa: E731
     eight = lambda: H.tile_merge((rows_d, counts_d), offs_d, K, (HF, WF), NC, THR, 0, False, KEEP)  # noqa: E731
-    ts = ab({"parent": parent, "tile_merge": one, "tile_merge_x8": eight}, a.rounds)
+    fuse = lambda r, c, mode: lambda: H.tile_merge((r, c), offs_d, K, (HF, WF), NC, THR, 0, False, KEEP, mode=mode)  # noqa: E731
+    ts = ab({"parent": parent, "tile_merge": one, "tile_merge_x8": eight, "union": fuse(r1, c1, "union"), "wbf": fuse(r1, c1, "wbf"),
+             "union_x8": fuse(rows_d, counts_d, "union"), "wbf_x8": fuse(rows_d, counts_d, "wbf")}, a.rounds)
     same = bool(torch.equal(nbufs.index[0, : int(nbufs.count[0])], one().index[0, : int(nbufs.count[0])])) and int(nbufs.count[0]) == int(one().count[0])
+    kept = one().index[0].clone()
+    fused = fuse(r1, c1, "union")()
+    same_fused = bool(torch.equal(fused.index[0], kept))
     out["merge"].append({"rows_per_tile": round(float(counts[:K].mean()), 1), "kept": int(nbufs.count[0]), "same_rows_kept": same,
+                         "fuse_keeps_the_same_rows": same_fused, "absorbed": int((fused.members[0] - 1).clamp(min=0).sum()),
                          "parent_rows_to_pred_nms_ms": stat(ts["parent"]), "tile_merge_ms": stat(ts["tile_merge"]),
-                         "tile_merge_8_frames_ms_per_frame": stat([t / 8 for t in ts["tile_merge_x8"]])})
+                         "tile_merge_8_frames_ms_per_frame": stat([t / 8 for t in ts["tile_merge_x8"]]),
+                         "tile_fuse_union_ms": stat(ts["union"]), "tile_fuse_wbf_ms": stat(ts["wbf"]),
+                         "tile_fuse_union_8_frames_ms_per_frame": stat([t / 8 for t in ts["union_x8"]]),
+                         "tile_fuse_wbf_8_frames_ms_per_frame": stat([t / 8 for t in ts["wbf_x8"]])})
     print(json.dumps(out["merge"][-1]), file=sys.stderr, flush=True)
 
 # ---- (b) the slicer ---------------------------------------------------------------------------------------------------------------------------
