@@ -176,7 +176,9 @@ __global__ __launch_bounds__(64) void detect_head_split_kernel(const HeadArgs p)
     for (int i = 0; i < 2 * NKB * 4; ++i) wBh[i * 64 + lane] = gb[i * 64 + lane];
     for (int i = 0; i < 2 * NKC * p.nfc; ++i) wCh[i * 64 + lane] = gc[i * 64 + lane];
     bias[lane] = p.bb[l][lane], bias[NB + lane] = p.bb[l][NB + lane];
-    for (int i = lane; i < 2 * nbc; i += 64) bias[2 * NB + i] = p.bc[l][i];
+    // (the pack pads the bias to whole DY_WLAYOUT_FRAG1X1 tiles, 16 / 64 / 128 rows, and the scales follow THAT; the rows here stop at 16 * mtc)
+    const int skip = p.nfc * 16 - nbc;
+    for (int i = lane; i < 2 * nbc; i += 64) bias[2 * NB + i] = p.bc[l][i < nbc ? i : i + skip];
   }
   const unsigned char* xb = reinterpret_cast<const unsigned char*>(p.xb[l]) + ((size_t)b * hw * p.ldb[l]) * 4 + lq * 32;
   const unsigned char* xc = reinterpret_cast<const unsigned char*>(p.xc[l]) + ((size_t)b * hw * p.ldc[l]) * 4 + lq * 32;
