@@ -153,6 +153,17 @@ class TileFuseDesc(C.Structure):
     ]  # fmt: skip
 
 
+class TileMergeRotatedDesc(C.Structure):
+    """Mirror of ``dy_tile_merge_rotated_desc`` (``dy_tile_merge_desc`` without the metric; rows are 7 wide)."""
+
+    _fields_ = [
+        ("rows", _vp), ("counts", _vp), ("offsets_yx", _vp),
+        ("frames", _i32), ("tiles", _i32), ("max_det", _i32), ("nc", _i32), ("frame_h", _i32), ("frame_w", _i32),
+        ("thr", _f32), ("agnostic", _i32), ("merge_max_det", _i32),
+        ("out", _vp), ("out_count", _vp), ("out_index", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
+    ]  # fmt: skip
+
+
 class TrackDesc(C.Structure):
     """Mirror of ``dy_track_desc``."""
 
@@ -363,6 +374,8 @@ SIGNATURES = {
     "dy_tile_merge": (_i32, [C.POINTER(TileMergeDesc), _vp]),
     "dy_tile_fuse_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "dy_tile_fuse": (_i32, [C.POINTER(TileFuseDesc), _vp]),
+    "dy_tile_merge_rotated_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "dy_tile_merge_rotated": (_i32, [C.POINTER(TileMergeRotatedDesc), _vp]),
     "dy_upsample2x_bwd_nhwc": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dy_maxpool_bwd_nhwc": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dy_add_nhwc": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -10,7 +10,9 @@
 // The next chunk's candidates are fetched while the current one is scanned.  The scan stops at max_keep kept (exact: greedy NMS never
 // revisits a kept box); then the rows past the count are zeroed, their indices set to -1 and the count stored.
 //
-// What differs between the two kernels is the Policy (a small struct of the kernel's pointers):
+// tile_merge.hip's oriented-box merge runs the same scan with ScanBox holding a covariance row (x, y, a, b, c of probiou.h) in place of
+// x1, y1, x2, y2, area, and output rows of 7 floats (ROW).
+// What differs between the kernels is the Policy (a small struct of the kernel's pointers):
 //   Cand                                    what a lane fetches for its candidate of a chunk
 //   Cand fetch(int i, int n)                candidate i of the sorted list, zeros for i >= n
 //   ScanBox box(const Cand&)                the box the predicate sees (cls unused where classes are offsets of the coordinates)
@@ -39,8 +41,8 @@ __device__ __forceinline__ u64 nms_uniform64(u64 v) {
 
 // Every thread of the 64 * WAVES of the workgroup calls it, behind the barrier that ends the sort.  mrows [64] and verdict [WAVES] are
 // LDS; outb / outi (or nullptr) / out_count: the image's max_keep output rows, their indices and its count.  Returns the count (alike on
-// every thread; tile_merge.hip's fusion pass goes on from it).
-template <int WAVES, typename Policy>
+// every thread; tile_merge.hip's fusion pass goes on from it).  ROW: the floats of an output row (6; the oriented-box merge's rows have 7).
+template <int WAVES, int ROW = 6, typename Policy>
 __device__ __forceinline__ int nms_greedy_scan(const Policy& pol, int n, int max_keep, u64* mrows, u64* verdict, float* outb, int* outi, int* out_count) {
   constexpr int THREADS = 64 * WAVES, ROWS = 64 / WAVES;
   const int tid = threadIdx.x;
@@ -89,7 +91,7 @@ __device__ __forceinline__ int nms_greedy_scan(const Policy& pol, int n, int max
     nk += cnt;
     __syncthreads();  // the kept list is complete before the next chunk reads it; mrows / verdict may be rewritten
   }
-  for (int r = nk * 6 + tid; r < max_keep * 6; r += THREADS) outb[r] = 0.f;
+  for (int r = nk * ROW + tid; r < max_keep * ROW; r += THREADS) outb[r] = 0.f;
   if (outi)
     for (int r = nk + tid; r < max_keep; r += THREADS) outi[r] = -1;
   if (tid == 0) *out_count = nk;

@@ -26,7 +26,15 @@
 //                       launch: 4,096 keys + 1,000 kept = 60 KB, at merge_max_det 4096 the kept list takes 112 KB and 4,096 keys the rest.
 //                       The accumulators (40 bytes per kept row) do not fit beside that, so they lie in the workspace behind the keys; only
 //                       this workgroup touches its frame's, with an agent-scope fence and a barrier between the phases.
+//   tile_merge_kernel<false, true>   dy_tile_merge_rotated: the merge for oriented boxes.  Rows are the 7 columns of dy_nms_rotated (x, y, w, h,
+//                       theta, conf, cls); compaction, keys and sort are the same.  The scan's policy is TmrScan: a box is the covariance row of
+//                       probiou.h (rnms_row of the centre plus (ox, oy), w, h, theta: sinf / cosf once per candidate of a chunk, never per
+//                       pair) and the predicate rnms_probiou(kept, candidate) >= thr -- the one expression the per-tile NMS and the validator
+//                       use.  ScanBox's five floats hold x, y, a, b, c, so the kept list stays 24 bytes a row and the LDS budget above holds.
+//                       The expression's second half runs only when a ballot finds a lane that can still be suppressed: of the kept
+//                       row's class and not ruled out by its distance terms (tmr_far_bound; no verdict can change).
 #include "nms_scan.h"
+#include "probiou.h"
 
 #pragma clang fp contract(off)
 
@@ -120,6 +128,8 @@ struct TmArgs {
   int mode;
   int* out_members;
   u64* acc;  // [frames][keep][TM_ACC_WORDS]
+  // dy_tile_merge_rotated only (behind everything else: the other kernels' argument offsets stay what they were)
+  float far;  // tmr_far_bound(thr)
 };
 
 struct TmCand {
@@ -188,6 +198,103 @@ struct TmScan {  // nms_greedy_scan's policy: frame-coordinate boxes, classes co
     o[3] = fminf(fmaxf(c.y2, 0.f), p.fh);
     o[4] = c.score;
     o[5] = (float)c.cls;
+    if (outi) outi[at] = c.slot;
+  }
+};
+
+// ---- oriented boxes (dy_tile_merge_rotated) -----------------------------------------------------------------------------------------------
+struct TmrCand {
+  float x, y, w, h, th, score;  // the centre in frame coordinates
+  int slot, cls;
+};
+
+// t12 = t1 + t2 of rnms_probiou above which a pair cannot reach thr, whatever the rest of the expression gives.  rnms_probiou >= thr
+// needs bd <= B = -log(1 - (1 - thr)^2 + eps).  With det > 0 the logarithm's argument is at least eps, so t3 >= 0.5 * logf(1e-7f) > -8.06
+// and bd >= t12 - 8.06; t12 > B + 9 therefore leaves bd > B + 0.94, i.e. 1 - exp(-bd) + eps above (1 - thr)^2 by 0.61 (1 - (1 - thr)^2):
+// at least 1.2e-3 for thr >= 1e-3, four orders of magnitude above the fp32 rounding of expf, the subtraction and sqrtf (a bd beyond the clamp
+// at 100 or a NaN does not suppress either).  Below thr = 1e-3 a far pair's ProbIoU of 0 or -1.2e-7 may still reach thr: no pre-test.
+// tmr_distance_terms restates the first lines of rnms_probiou (the same operations in the same order, contraction off: the same bits, and
+// the compiler shares them with the call that follows); it serves the bound only, the verdict is rnms_probiou's.
+__device__ __forceinline__ float tmr_distance_terms(const RRow& r1, const RRow& r2, float* det_out) {
+  const float eps = 1e-7f;
+  const float sa = r1.a + r2.a, sb = r1.b + r2.b, sc = r1.c + r2.c;
+  const float dy = r1.y - r2.y, dx = r1.x - r2.x;
+  const float det = sa * sb - sc * sc;
+  const float den = det + eps;
+  const float t1 = ((sa * (dy * dy) + sb * (dx * dx)) / den) * 0.25f;
+  const float t2 = (((sc * (r2.x - r1.x)) * dy) / den) * 0.5f;
+  *det_out = det;
+  return t1 + t2;
+}
+
+static inline float tmr_far_bound(float thr) {
+  if (!(thr >= 1e-3f)) return INFINITY;
+  const double keep = (1.0 - (double)thr) * (1.0 - (double)thr);
+  return (float)(-log(1.0 - keep + 1e-7) + 9.0);
+}
+
+struct TmrScan {  // nms_greedy_scan's policy: ScanBox = {x, y, a, b, c, cls}, the covariance row of a frame-coordinate box and its class
+  const TmArgs& p;
+  const u64* skeys;
+  const u64* gkeys;
+  const float* frows;
+  float* outb;
+  int* outi;
+  float4* kbox;  // [keep]: x, y, a, b
+  float* kc;
+  int* kcls;
+  bool in_lds;
+  typedef TmrCand Cand;
+  __device__ __forceinline__ Cand fetch(int i, int n) const {
+    Cand c{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0, -1};
+    if (i < n) {
+      const u64 key = in_lds ? skeys[i] : gkeys[i];
+      c.slot = (int)(unsigned)(key & 0xffffffffull);
+      c.score = __uint_as_float(~(unsigned)(key >> 32));
+      const int tile = c.slot / p.max_det;
+      const float oy = (float)p.offs[2 * tile], ox = (float)p.offs[2 * tile + 1];
+      const float* q = frows + (size_t)c.slot * 7;
+      c.x = q[0] + ox;
+      c.y = q[1] + oy;
+      c.w = q[2];
+      c.h = q[3];
+      c.th = q[4];
+      c.cls = (int)q[6];
+    }
+    return c;
+  }
+  __device__ __forceinline__ ScanBox box(const Cand& c) const {  // once per candidate of a chunk: the only sinf / cosf of the scan
+    const RRow r = rnms_row(c.x, c.y, c.w, c.h, c.th);
+    return ScanBox{r.x, r.y, r.a, r.b, r.c, c.cls};
+  }
+  // row i (kept) suppresses row j: the class rule and rnms_probiou(i, j) >= thr, the kept row first; a NaN compares false and suppresses
+  // nothing.  i is wave-uniform at both call sites of the scan (a kept row, a row of the chunk's matrix).  What follows the distance terms
+  // (two square roots, a division, logf, expf) is issued only when some lane of the wave can still be suppressed: one of i's class (any
+  // with agnostic) whose distance terms do not already rule it out (tmr_far_bound).  A lane that is skipped has the verdict false either way.
+  __device__ __forceinline__ bool suppresses(const ScanBox& i, const ScanBox& j) const {
+    const RRow ri{i.x1, i.y1, i.x2, i.y2, i.area}, rj{j.x1, j.y1, j.x2, j.y2, j.area};
+    float det;
+    const float t12 = tmr_distance_terms(ri, rj, &det);
+    const bool open = (p.agnostic || i.cls == j.cls) && !(det > 0.f && t12 > p.far);
+    if (__ballot(open) == 0ull) return false;
+    return open && rnms_probiou(ri, rj) >= p.thr;
+  }
+  __device__ __forceinline__ ScanBox kept(int k) const {
+    const float4 kb = kbox[k];
+    return ScanBox{kb.x, kb.y, kb.z, kb.w, kc[k], kcls[k]};
+  }
+  __device__ __forceinline__ void keep(int at, const Cand& c, const ScanBox& bx) const {
+    kbox[at] = make_float4(bx.x1, bx.y1, bx.x2, bx.y2);
+    kc[at] = bx.area;
+    kcls[at] = c.cls;
+    float* o = outb + (size_t)at * 7;  // clip_boxes on an xywh row, as dy_scale_rboxes: x and w to [0, frame_w], y and h to [0, frame_h]
+    o[0] = fminf(fmaxf(c.x, 0.f), p.fw);
+    o[1] = fminf(fmaxf(c.y, 0.f), p.fh);
+    o[2] = fminf(fmaxf(c.w, 0.f), p.fw);
+    o[3] = fminf(fmaxf(c.h, 0.f), p.fh);
+    o[4] = c.th;
+    o[5] = c.score;
+    o[6] = (float)c.cls;
     if (outi) outi[at] = c.slot;
   }
 };
@@ -333,9 +440,11 @@ __device__ __forceinline__ void tm_fuse_tail(const TmArgs& p, const TmFuseScan& 
 }
 
 // FUSE = false is dy_tile_merge's kernel; FUSE = true goes on behind the scan (dy_tile_fuse): a kernel of its own, the suppress path is at
-// 115 of its 128 VGPRs
-template <bool FUSE>
+// 115 of its 128 VGPRs.  ROT = true is dy_tile_merge_rotated's: rows of 7 floats with the score in column 5, and the policy TmrScan.
+template <bool FUSE, bool ROT = false>
 __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(const TmArgs p) {
+  static_assert(!(FUSE && ROT), "fusing merges are not built for oriented boxes");
+  constexpr int ROW = ROT ? 7 : 6, SCORE = ROT ? 5 : 4;
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
   u64* skeys = reinterpret_cast<u64*>(dyn_smem);  // [SL]
   u64* mrows = skeys + p.SL;                      // [64]
@@ -347,7 +456,7 @@ __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(const TmArgs p) 
   const int f = blockIdx.x;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const float* frows = p.rows + (size_t)f * p.N * 6;
+  const float* frows = p.rows + (size_t)f * p.N * ROW;
   const int* fcounts = p.counts + (size_t)f * p.K;
   u64* gkeys = p.keys + (size_t)f * p.P;
 
@@ -375,7 +484,7 @@ __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(const TmArgs p) 
     if (j < p.N) {
       const int tile = j / p.max_det, r = j - tile * p.max_det;
       valid = r < fcounts[tile];
-      if (valid) score = frows[(size_t)j * 6 + 4];
+      if (valid) score = frows[(size_t)j * ROW + SCORE];
     }
     const u64 m = __ballot(valid);
     int base = 0;
@@ -397,9 +506,12 @@ __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(const TmArgs p) 
   if (in_lds) nms_bitonic_sort<TM_THREADS>(skeys, P2, tid);
   else nms_bitonic_sort<TM_THREADS>(gkeys, P2, tid);
 
-  float* outb = p.out + (size_t)f * p.keep * 6;
+  float* outb = p.out + (size_t)f * p.keep * ROW;
   int* outi = p.out_index ? p.out_index + (size_t)f * p.keep : nullptr;
-  if constexpr (!FUSE) {
+  if constexpr (ROT) {
+    const TmrScan pol{p, skeys, gkeys, frows, outb, outi, kbox, kar, kcls, in_lds};
+    nms_greedy_scan<TM_WAVES, 7>(pol, n, p.keep, mrows, verdict, outb, outi, p.out_count + f);
+  } else if constexpr (!FUSE) {
     const TmScan pol{p, skeys, gkeys, frows, outb, outi, kbox, kar, kcls, in_lds};
     nms_greedy_scan<TM_WAVES>(pol, n, p.keep, mrows, verdict, outb, outi, p.out_count + f);
   } else {
@@ -436,7 +548,7 @@ extern "C" int64_t dy_tile_merge_workspace_bytes(int32_t frames, int32_t tiles, 
 
 // The kernel arguments a checked descriptor describes (dy_tile_merge_desc / dy_tile_fuse_desc: the fields they share; `a` holds what only
 // the fusion has) and the launch.
-template <bool FUSE, typename Desc>
+template <bool FUSE, bool ROT = false, typename Desc>
 static int tm_launch(const Desc* d, TmArgs a, const char* who, dy_stream_t stream) {
   a.rows = d->rows;
   a.counts = d->counts;
@@ -452,7 +564,8 @@ static int tm_launch(const Desc* d, TmArgs a, const char* who, dy_stream_t strea
   a.fw = (float)d->frame_w;
   a.fh = (float)d->frame_h;
   a.thr = d->thr;
-  a.metric = d->metric;
+  if constexpr (!ROT) a.metric = d->metric;
+  if constexpr (ROT) a.far = tmr_far_bound(d->thr);
   a.agnostic = d->agnostic ? 1 : 0;
   a.keep = d->merge_max_det;
   // LDS by need: the keys of every slot when they fit beside the kept list, the largest power of two that does otherwise
@@ -460,9 +573,9 @@ static int tm_launch(const Desc* d, TmArgs a, const char* who, dy_stream_t strea
   a.SL = a.P < TM_MAX_LDS_KEYS ? a.P : TM_MAX_LDS_KEYS;
   while ((size_t)a.SL * 8 + rest > 160 * 1024) a.SL >>= 1;
   const size_t smem = (size_t)a.SL * 8 + rest;
-  static const hipError_t attr_once = hipFuncSetAttribute((const void*)tile_merge_kernel<FUSE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  static const hipError_t attr_once = hipFuncSetAttribute((const void*)tile_merge_kernel<FUSE, ROT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   (void)attr_once;
-  hipLaunchKernelGGL(tile_merge_kernel<FUSE>, dim3((unsigned)d->frames), dim3(TM_THREADS), smem, reinterpret_cast<hipStream_t>(stream), a);
+  hipLaunchKernelGGL((tile_merge_kernel<FUSE, ROT>), dim3((unsigned)d->frames), dim3(TM_THREADS), smem, reinterpret_cast<hipStream_t>(stream), a);
   return check_launch(who);
 }
 
@@ -511,4 +624,24 @@ extern "C" int32_t dy_tile_fuse(const dy_tile_fuse_desc* d, dy_stream_t stream) 
   a.out_members = d->out_members;
   a.acc = reinterpret_cast<u64*>(reinterpret_cast<unsigned char*>(d->workspace) + dy_tile_merge_workspace_bytes(d->frames, d->tiles, d->max_det));
   return tm_launch<true>(d, a, "dy_tile_fuse", stream);
+}
+
+extern "C" int64_t dy_tile_merge_rotated_workspace_bytes(int32_t frames, int32_t tiles, int32_t max_det) {
+  return dy_tile_merge_workspace_bytes(frames, tiles, max_det);  // the keys; the kept list is LDS
+}
+
+extern "C" int32_t dy_tile_merge_rotated(const dy_tile_merge_rotated_desc* d, dy_stream_t stream) {
+  DY_REQUIRE(d && d->rows && d->counts && d->offsets_yx && d->out && d->out_count && d->workspace, DY_ERR_INVALID_ARG,
+             "dy_tile_merge_rotated: null pointer (rows / counts / offsets_yx / out / out_count / workspace)");
+  DY_REQUIRE(d->frames > 0 && d->tiles > 0 && d->max_det > 0 && d->nc > 0 && d->frame_h > 0 && d->frame_w > 0 && d->merge_max_det > 0, DY_ERR_INVALID_ARG,
+             "dy_tile_merge_rotated: bad dims (frames %d, tiles %d, max_det %d, nc %d, frame %d x %d, merge_max_det %d)", d->frames, d->tiles, d->max_det,
+             d->nc, d->frame_h, d->frame_w, d->merge_max_det);
+  DY_REQUIRE(d->thr >= 0.f && d->thr <= 1.f, DY_ERR_INVALID_ARG, "dy_tile_merge_rotated: thr must be in [0,1]");
+  DY_REQUIRE((long long)d->tiles * d->max_det <= TM_MAX_SLOTS, DY_ERR_UNSUPPORTED, "dy_tile_merge_rotated: tiles * max_det = %lld > %d",
+             (long long)d->tiles * d->max_det, TM_MAX_SLOTS);
+  DY_REQUIRE(d->merge_max_det <= TM_MAX_KEEP, DY_ERR_UNSUPPORTED, "dy_tile_merge_rotated: merge_max_det %d > %d", d->merge_max_det, TM_MAX_KEEP);
+  const int64_t need = dy_tile_merge_rotated_workspace_bytes(d->frames, d->tiles, d->max_det);
+  DY_REQUIRE(d->workspace_bytes >= need, DY_ERR_WORKSPACE, "dy_tile_merge_rotated: workspace %lld < %lld bytes", (long long)d->workspace_bytes, (long long)need);
+  DY_REQUIRE(aligned16(d->workspace), DY_ERR_INVALID_ARG, "dy_tile_merge_rotated: workspace not 16-byte aligned");
+  return tm_launch<false, true>(d, TmArgs{}, "dy_tile_merge_rotated", stream);
 }

@@ -96,7 +96,7 @@ class Model(nn.Module):
         if source is None:
             raise ValueError("'source' is missing; the device path takes a BCHW float tensor in [0, 1]")
         self._refuse_for_segment(kwargs)
-        self._refuse_for_obb(kwargs)
+        self._refuse_for_obb(kwargs, source)
         track = kwargs.get("mode") == "track"
         args = {**self.overrides, "conf": 0.1 if track else 0.25, **kwargs}
         args.pop("model", None), args.pop("task", None), args.pop("mode", None)
@@ -144,15 +144,19 @@ class Model(nn.Module):
         if a.get("augment"):
             raise NotImplementedError("augment=True: test-time augmentation is not built for segmentation models")
 
-    def _refuse_for_obb(self, kwargs: dict) -> None:
-        """What an oriented-box model does not do, refused by argument name before a predictor is built or anything is launched."""
+    def _refuse_for_obb(self, kwargs: dict, source=None) -> None:
+        """What an oriented-box model does not do, refused by argument name before a predictor is built or anything is launched.  ``tile=`` is
+        built; what it does not take -- a float tensor source, an IoS metric, a fusing merge -- is refused here too, so that
+        the refusal comes before the predictor moves the model to the device."""
         if self.task != "obb":
             return
         a = {**self.overrides, **kwargs}
         if a.get("mode") == "track":
             raise NotImplementedError("track: tracking is not built for oriented-box models")
         if a.get("tile") is not None:
-            raise NotImplementedError("tile: tiled inference is not built for oriented-box models")
+            if isinstance(source, torch.Tensor) and source.dtype != torch.uint8:
+                raise NotImplementedError("tile with a float BCHW tensor: tiles are cut from uint8 pixels (HWC frames), not from a letterboxed tensor")
+            OBBPredictor.refuse_tile_args(a)
         if a.get("augment"):
             raise NotImplementedError("augment=True: test-time augmentation is not built for oriented-box models")
 

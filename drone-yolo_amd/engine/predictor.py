@@ -567,6 +567,18 @@ class DetectionPredictor:
             raise NotImplementedError("tile sources: uint8 HWC BGR frames (list of numpy arrays / uint8 NHWC tensor), image files, PIL images")
         return self._chunks(source, int(batch or len(source)))
 
+    # ---- what a task changes in the cross-tile merge: its buffers and its launch (the oriented-box task overrides both) ----
+    def _new_merge_bufs(self, frames: int, k: int):
+        """The merge buffers of ``frames`` frames of ``k`` tiles each, kept per frame shape in ``_tile_state``."""
+        a = self.args
+        return H.TileMergeBuffers(frames, k, int(a["max_det"]), int(a["merge_max_det"]), self.device, fuse=str(a["merge_mode"]).lower() != "suppress")
+
+    def _merge_tiles(self, cf: CompiledForward, offs_d: torch.Tensor, k: int, frame_hw, mbufs):
+        """The merge launch behind the recorded pass over the tiles: ``cf.nms`` holds the per-tile rows; returns ``mbufs``, filled."""
+        a = self.args
+        return H.tile_merge(cf.nms, offs_d, k, frame_hw, self.model.yaml["nc"], float(a["merge_iou"]), str(a["merge_metric"]),
+                            bool(a["agnostic_nms"]), int(a["merge_max_det"]), bufs=mbufs, mode=str(a["merge_mode"]))
+
     def _tiled_enqueue(self, lo: int, frames, paths):
         """Everything one batch of frames launches — per group of frames of one shape: the slicer, the recorded pass over the (F * K)-tile batch,
         the cross-tile merge and, in track mode, the track step — then ONE asynchronous copy of the merged (and the tracker's) counts."""
@@ -603,14 +615,12 @@ class DetectionPredictor:
                 offs_d = torch.tensor(offs, dtype=torch.int32, device=self.device)
                 k = len(offs)
                 st = self._tile_state[key] = (offs_d, k, torch.empty((len(idxs) * k, 3, tile, tile), dtype=torch.float32, device=self.device),
-                                              H.TileMergeBuffers(len(idxs), k, int(a["max_det"]), int(a["merge_max_det"]), self.device,
-                                                                 fuse=str(a["merge_mode"]).lower() != "suppress"))
+                                              self._new_merge_bufs(len(idxs), k))
             offs_d, k, tiles, mbufs = st
             H.tiles_batch(stacked, offs_d, tile, out=tiles)  # a frame no larger than the tile is one tile padded with 114
             self.letterbox_info = None  # every tile is an image of its own to the pass: boxes clipped to the tile
             cf = self.forward_device(tiles)
-            merged = H.tile_merge(cf.nms, offs_d, k, (hf, wf), self.model.yaml["nc"], float(a["merge_iou"]), str(a["merge_metric"]),
-                                  bool(a["agnostic_nms"]), int(a["merge_max_det"]), bufs=mbufs, mode=str(a["merge_mode"]))
+            merged = self._merge_tiles(cf, offs_d, k, (hf, wf), mbufs)
             tracked = None
             if self.tracker is not None and hasattr(self.tracker, "bufs"):
                 tout, tcnt = self.tracker.update_batch(merged.out, merged.count)
@@ -641,7 +651,7 @@ class DetectionPredictor:
                 img = frames[i]
                 if isinstance(img, torch.Tensor):
                     img = img.cpu().numpy()
-                out[i] = Results(img, paths[i] if paths else f"image{lo + i}.jpg", names, boxes=self._boxes_of(j, counts[j], rows, tracked), orig_shape=hw)
+                out[i] = self._result(img, paths[i] if paths else f"image{lo + i}.jpg", names, self._boxes_of(j, counts[j], rows, tracked), hw, None)
         dt = (time.perf_counter() - t0) * 1e3 / max(len(out), 1)
         for r in out:
             r.speed = {"preprocess": 0.0, "inference": t_inf, "postprocess": dt}
@@ -762,13 +772,26 @@ class OBBPredictor(DetectionPredictor):
     The recorded pass is the detection pass (every Detect fusion and the fused candidate filter unchanged: the filter does not look at boxes)
     plus the per-level angle branches and ``dy_obb_decode`` inside the head, then ``dy_nms_rotated`` in place of ``dy_nms`` and
     ``dy_scale_rboxes`` in place of ``dy_scale_boxes``; one synchronisation per batch, and a streamed run copies the (N, max_det, 7) rows
-    behind the batch's launches as it copies detection rows.  ``Results.obb`` carries the rows; ``Results.boxes`` is None."""
+    behind the batch's launches as it copies detection rows.  ``Results.obb`` carries the rows; ``Results.boxes`` is None.
+
+    ``tile=``: the tiled loop is the detection task's; the cross-tile merge is ``dy_tile_merge_rotated`` -- greedy suppression
+    at ``merge_iou`` as a ProbIoU threshold.  An IoS-like measure and fusing merges are not built for rotated boxes."""
+
+    @staticmethod
+    def refuse_tile_args(a: dict) -> None:
+        """What ``tile=`` does not do for oriented boxes, refused by argument name (also by ``YOLO.predict``, before a predictor is built)."""
+        if a.get("tile") is None:
+            return
+        if str(a.get("merge_metric", "iou")).lower() != "iou":
+            raise NotImplementedError(f"merge_metric = '{a['merge_metric']}': the oriented-box tile merge compares with ProbIoU (merge_metric='iou' only)")
+        if str(a.get("merge_mode", "suppress")).lower() != "suppress":
+            raise NotImplementedError(f"merge_mode = '{a['merge_mode']}': fusing merges are not built for oriented boxes (merge_mode='suppress' only)")
 
     def __init__(self, model, overrides: Optional[dict] = None):
         a = overrides or {}
-        for k in ("tile", "augment"):  # before anything touches the device
-            if a.get(k) not in (None, False):
-                raise NotImplementedError(f"{k}: not built for oriented-box models")
+        if a.get("augment") not in (None, False):  # before anything touches the device
+            raise NotImplementedError("augment: not built for oriented-box models")
+        self.refuse_tile_args(a)
         super().__init__(model, overrides)
         self.args["task"] = "obb"
 
@@ -791,3 +814,11 @@ class OBBPredictor(DetectionPredictor):
 
     def _result(self, img, path, names, rows, orig_shape, masks) -> Results:
         return Results(img, path, names, obb=rows, orig_shape=orig_shape)
+
+    def _new_merge_bufs(self, frames: int, k: int):
+        return H.RTileMergeBuffers(frames, k, int(self.args["max_det"]), int(self.args["merge_max_det"]), self.device)
+
+    def _merge_tiles(self, cf: CompiledForward, offs_d: torch.Tensor, k: int, frame_hw, mbufs):
+        a = self.args
+        return H.tile_merge_rotated(cf.nms, offs_d, k, frame_hw, self.model.yaml["nc"], float(a["merge_iou"]), bool(a["agnostic_nms"]),
+                                    int(a["merge_max_det"]), bufs=mbufs)

@@ -1981,13 +1981,15 @@ class TileMergeBuffers:
     ``fuse=True`` (or the first ``tile_merge`` call with a fusing mode) adds what ``dy_tile_fuse`` needs: ``members`` (frames, merge_max_det)
     int32 and ``fuse_workspace``; ``members`` stays ``None`` on buffers that only ever suppress."""
 
+    ROW = 6  # x1, y1, x2, y2, conf, cls
+
     def __init__(self, frames: int, tiles: int, tile_max_det: int, merge_max_det: int, device, fuse: bool = False):
         self.batch, self.tiles, self.tile_max_det, self.max_det = int(frames), int(tiles), int(tile_max_det), int(merge_max_det)
         nbytes = lib().dy_tile_merge_workspace_bytes(self.batch, self.tiles, self.tile_max_det)
         if nbytes < 0:
             raise ValueError(f"tile_merge: {tiles} tiles x max_det {tile_max_det} is beyond the kernel's 32768 slots per frame")
         self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=device)
-        self.out = torch.empty((self.batch, self.max_det, 6), dtype=torch.float32, device=device)
+        self.out = torch.empty((self.batch, self.max_det, self.ROW), dtype=torch.float32, device=device)
         self.count = torch.empty((self.batch,), dtype=torch.int32, device=device)
         self.index = torch.empty((self.batch, self.max_det), dtype=torch.int32, device=device)
         self.members: Optional[torch.Tensor] = None
@@ -2061,6 +2063,56 @@ def tile_merge(nms_bufs, offsets: torch.Tensor, K: int, frame_hw: Tuple[int, int
         return bufs
     d.workspace, d.workspace_bytes = bufs.workspace.data_ptr(), bufs.workspace.numel()
     _launch(lib().dy_tile_merge, (C.byref(d),), keep=(d, rows, counts, offsets, bufs))
+    return bufs
+
+
+class RTileMergeBuffers(TileMergeBuffers):
+    """``TileMergeBuffers`` of ``dy_tile_merge_rotated``: ``out`` (frames, merge_max_det, 7) = x, y, w, h, theta, conf, cls; ``out`` / ``count`` /
+    ``index`` / ``batch`` / ``max_det`` mean what they mean on ``RNmsBuffers``.  The workspace is ``dy_tile_merge``'s (the sort keys)."""
+
+    ROW = 7
+
+    def __init__(self, frames: int, tiles: int, tile_max_det: int, merge_max_det: int, device):
+        super().__init__(frames, tiles, tile_max_det, merge_max_det, device)
+
+    def enable_fuse(self) -> None:
+        raise NotImplementedError("tile_merge_rotated: fusing merges (union / wbf) are not built for oriented boxes")
+
+
+_RTILE_MERGE_BUFS: dict = {}
+
+
+def tile_merge_rotated(nms_bufs, offsets: torch.Tensor, K: int, frame_hw: Tuple[int, int], nc: int, thr: float, agnostic: bool = False,
+                       merge_max_det: int = 1000, bufs: Optional[RTileMergeBuffers] = None) -> RTileMergeBuffers:
+    """Cross-tile merge of F frames of oriented boxes in one ``dy_tile_merge_rotated`` launch; no host synchronisation.  ``nms_bufs``: the
+    per-tile ``RNmsBuffers`` of the (F * K)-tile batch (rows x, y, w, h, theta, conf, cls in tile pixels) or a ``(rows, counts)`` pair;
+    ``offsets``: device int32 (K, 2) = (y, x); ``thr``: the ProbIoU at or above which a kept row of the same class (any class with
+    ``agnostic``) suppresses a candidate -- greedily, as ``tile_merge`` does.  Returns rows in frame pixels, centre and size clamped to the
+    frame, in buffers that persist per (F, K, max_det, merge_max_det): the next call with the same sizes overwrites them."""
+    rows, counts = (nms_bufs.out, nms_bufs.count) if hasattr(nms_bufs, "out") else nms_bufs
+    require_device(rows, "per-tile rows")
+    require_device(counts, "per-tile counts")
+    require_device(offsets, "tile offsets")
+    K = int(K)
+    if rows.dtype != torch.float32 or rows.dim() != 3 or rows.shape[2] != 7 or not rows.is_contiguous() or rows.shape[0] % K or counts.dtype != torch.int32 \
+            or counts.numel() != rows.shape[0] or not counts.is_contiguous():
+        raise ValueError(f"tile_merge_rotated: rows must be contiguous fp32 (F * {K}, max_det, 7) with as many int32 counts")
+    if offsets.dtype != torch.int32 or tuple(offsets.shape) != (K, 2) or not offsets.is_contiguous():
+        raise ValueError(f"tile_merge_rotated: offsets must be a contiguous int32 ({K}, 2) device tensor")
+    f, md = rows.shape[0] // K, int(rows.shape[1])
+    if bufs is None or bufs.ROW != 7 or (bufs.batch, bufs.tiles, bufs.tile_max_det, bufs.max_det) != (f, K, md, int(merge_max_det)) or bufs.out.device != rows.device:
+        key = (rows.device, f, K, md, int(merge_max_det))
+        bufs = _RTILE_MERGE_BUFS.get(key)
+        if bufs is None:
+            bufs = _RTILE_MERGE_BUFS[key] = RTileMergeBuffers(f, K, md, int(merge_max_det), rows.device)
+    d = _lib.TileMergeRotatedDesc()
+    d.rows, d.counts, d.offsets_yx = rows.data_ptr(), counts.data_ptr(), offsets.data_ptr()
+    d.frames, d.tiles, d.max_det, d.nc = f, K, md, int(nc)
+    d.frame_h, d.frame_w = int(frame_hw[0]), int(frame_hw[1])
+    d.thr, d.agnostic, d.merge_max_det = float(thr), int(bool(agnostic)), int(merge_max_det)
+    d.out, d.out_count, d.out_index = bufs.out.data_ptr(), bufs.count.data_ptr(), bufs.index.data_ptr()
+    d.workspace, d.workspace_bytes = bufs.workspace.data_ptr(), bufs.workspace.numel()
+    _launch(lib().dy_tile_merge_rotated, (C.byref(d),), keep=(d, rows, counts, offsets, bufs))
     return bufs
 
 

@@ -494,6 +494,40 @@ typedef struct dy_tile_fuse_desc {
 int64_t dy_tile_fuse_workspace_bytes(int32_t frames, int32_t tiles, int32_t max_det, int32_t merge_max_det);
 int32_t dy_tile_fuse(const dy_tile_fuse_desc* d, dy_stream_t stream);
 
+/* dy_tile_merge_rotated: the cross-tile merge of f frames for oriented boxes; one launch, one workgroup per frame, no host synchronisation.
+ *   rows: fp32 (f*k, max_det, 7) = x, y, w, h, theta, conf, cls and counts: int32 (f*k): the per-tile dy_nms_rotated + dy_scale_rboxes
+ *   outputs, in tile pixels; offsets_yx (k, 2) DEVICE int32 as for dy_tile_merge.  Candidates are the rows r < min(counts[tile], max_det)
+ *   (a negative count is 0), slot = k'*max_det + r.  Order: descending conf, ties by ascending slot (key = ~bits(conf) << 32 | slot).
+ *   A candidate's box is (x + ox, y + oy, w, h, theta): one fp32 add of an integer-valued float each; its covariance row (x, y, a, b, c of
+ *   csrc/probiou.h's rnms_row) is computed once per candidate, never per pair.  A kept row i suppresses candidate j when
+ *     (agnostic || cls_i == cls_j) && rnms_probiou(row_i, row_j) >= thr        (the kept row first; a NaN does not suppress)
+ *   with the one ProbIoU expression of dy_nms_rotated and dy_val_match_rotated, fp32 without contraction.  Classes are compared as integers
+ *   and NOTHING is added to the coordinates (dy_nms_rotated's max_wh class offset would cost ProbIoU its low bits at frame coordinates of
+ *   several thousand pixels).  GREEDY, not fast: a candidate is tested only against rows that were kept, so a row that only a dropped
+ *   duplicate overlaps survives -- dy_tile_merge's rule; dy_nms_rotated reproduces the reference's fast NMS, in which a suppressed row still
+ *   suppresses, and the reference has no slicer to follow here.  The scan stops at merge_max_det kept rows.
+ *   out: fp32 (f, merge_max_det, 7) in the input column order; x and w clamped to [0, frame_w], y and h to [0, frame_h] (clip_boxes on xywh
+ *   rows, as dy_scale_rboxes); theta, conf, cls copied; rows >= count are zero.  out_count: int32 (f).  out_index: optional int32
+ *   (f, merge_max_det): the slot of every kept row, -1 beyond the count; or NULL.  workspace: dy_tile_merge_rotated_workspace_bytes(f, k,
+ *   max_det) bytes, 16-byte aligned (-1 for sizes the entry point refuses).  Limits: k * max_det <= 32768 and merge_max_det <= 4096
+ *   (DY_ERR_UNSUPPORTED beyond), thr in [0, 1], DY_ERR_WORKSPACE for a short workspace; every argument is checked before any launch. */
+typedef struct dy_tile_merge_rotated_desc {
+  const float* rows;
+  const int32_t* counts;
+  const int32_t* offsets_yx;
+  int32_t frames, tiles, max_det, nc;
+  int32_t frame_h, frame_w;
+  float thr; /* ProbIoU */
+  int32_t agnostic, merge_max_det;
+  float* out;
+  int32_t* out_count;
+  int32_t* out_index;
+  void* workspace;
+  int64_t workspace_bytes;
+} dy_tile_merge_rotated_desc;
+int64_t dy_tile_merge_rotated_workspace_bytes(int32_t frames, int32_t tiles, int32_t max_det);
+int32_t dy_tile_merge_rotated(const dy_tile_merge_rotated_desc* d, dy_stream_t stream);
+
 /* ---- layout / copy ops ------------------------------------------------------ */
 
 /* Replaces: predictor preprocess `.half()/.float()` + the NCHW->device layout step

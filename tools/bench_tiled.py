@@ -1,5 +1,5 @@
 """Times tiled inference on 4K frames (GPU box): the parent's per-frame stages against the batched slicer and the one-launch merge.
-usage: python tools/bench_tiled.py [--rounds 10] [--frames 24] [--scale s] [--dtype float16] [--tile 1280] [--overlap 0.2]
+usage: python tools/bench_tiled.py [--rounds 10] [--frames 24] [--scale s] [--dtype float16] [--tile 1280] [--overlap 0.2] [--obb]
 
 A synthetic 3840 x 2160 uint8 video, tile 1280, overlap 0.2 (eight tiles per frame).  Every comparison alternates A and B in one process
 after warm-up and is timed with device events; each figure is the median over `--rounds` rounds, with the smallest and largest beside it.
@@ -9,6 +9,9 @@ after warm-up and is timed with device events; each figure is the median over `-
   (b) slicer  eight frames: A = eight dy_tiles_u8_to_nchw_f32 launches, B = one dy_tiles_batch_u8_to_nchw_f32 launch; ms and GB/s written.
   (c) frames/s end to end over `--frames` frames (host clock around the whole loop, results materialised): A = TiledPredictor called frame by
               frame, B = predict(frames, tile=1280, batch=F, stream=True) for F = 1, 2, 4.
+--obb: oriented boxes.  (a) gains R = dy_tile_merge_rotated (one frame) and R8 (eight frames, per frame) on the same objects as xywh rows with
+an angle each -- the same counts, so the difference to B / B8 is the price of the ProbIoU predicate; (c) runs the `-obb` model of the scale
+through predict(frames, tile=..., batch=F, stream=True) only (TiledPredictor is the detection task's).
 Prints one JSON line."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -23,6 +26,7 @@ ap.add_argument("--dtype", default="float16")
 ap.add_argument("--tile", type=int, default=1280)
 ap.add_argument("--overlap", type=float, default=0.2)
 ap.add_argument("--no-e2e", action="store_true")
+ap.add_argument("--obb", action="store_true")
 a = ap.parse_args()
 assert torch.cuda.is_available(), "tools/bench_tiled.py needs an MI355X"
 dev = torch.device("cuda", 0)
@@ -103,8 +107,15 @@ for per_tile in (30, 300):
     one = lambda: H.tile_merge((r1, c1), offs_d, K, (HF, WF), NC, THR, 0, False, KEEP)  # noqa: E731
     eight = lambda: H.tile_merge((rows_d, counts_d), offs_d, K, (HF, WF), NC, THR, 0, False, KEEP)  # noqa: E731
     fuse = lambda r, c, mode: lambda: H.tile_merge((r, c), offs_d, K, (HF, WF), NC, THR, 0, False, KEEP, mode=mode)  # noqa: E731
-    ts = ab({"parent": parent, "tile_merge": one, "tile_merge_x8": eight, "union": fuse(r1, c1, "union"), "wbf": fuse(r1, c1, "wbf"),
-             "union_x8": fuse(rows_d, counts_d, "union"), "wbf_x8": fuse(rows_d, counts_d, "wbf")}, a.rounds)
+    fns = {"parent": parent, "tile_merge": one, "tile_merge_x8": eight, "union": fuse(r1, c1, "union"), "wbf": fuse(r1, c1, "wbf"),
+           "union_x8": fuse(rows_d, counts_d, "union"), "wbf_x8": fuse(rows_d, counts_d, "wbf")}
+    if a.obb:  # the same objects as x, y, w, h, theta, conf, cls: the angle of a row follows its score, so the views of an object share it
+        x1, y1, x2, y2, sc, cl = rows_d.unbind(2)
+        rrows_d = torch.stack(((x1 + x2) / 2, (y1 + y2) / 2, x2 - x1, y2 - y1, sc.round(decimals=1) * 1.5, sc, cl), 2).contiguous()
+        rr1 = rrows_d[:K].contiguous()
+        fns["rotated"] = lambda: H.tile_merge_rotated((rr1, c1), offs_d, K, (HF, WF), NC, THR, False, KEEP)  # noqa: E731
+        fns["rotated_x8"] = lambda: H.tile_merge_rotated((rrows_d, counts_d), offs_d, K, (HF, WF), NC, THR, False, KEEP)  # noqa: E731
+    ts = ab(fns, a.rounds)
     same = bool(torch.equal(nbufs.index[0, : int(nbufs.count[0])], one().index[0, : int(nbufs.count[0])])) and int(nbufs.count[0]) == int(one().count[0])
     kept = one().index[0].clone()
     fused = fuse(r1, c1, "union")()
@@ -116,6 +127,9 @@ for per_tile in (30, 300):
                          "tile_fuse_union_ms": stat(ts["union"]), "tile_fuse_wbf_ms": stat(ts["wbf"]),
                          "tile_fuse_union_8_frames_ms_per_frame": stat([t / 8 for t in ts["union_x8"]]),
                          "tile_fuse_wbf_8_frames_ms_per_frame": stat([t / 8 for t in ts["wbf_x8"]])})
+    if a.obb:
+        out["merge"][-1].update({"tile_merge_rotated_ms": stat(ts["rotated"]), "tile_merge_rotated_8_frames_ms_per_frame": stat([t / 8 for t in ts["rotated_x8"]]),
+                                 "rotated_kept": int(fns["rotated"]().count[0])})
     print(json.dumps(out["merge"][-1]), file=sys.stderr, flush=True)
 
 # ---- (b) the slicer ---------------------------------------------------------------------------------------------------------------------------
@@ -140,11 +154,11 @@ del tiles8, tv
 if not a.no_e2e:
     from drone_yolo_amd.utils.parity import seeded_state_dict
 
-    yolo = D.YOLO(f"yolov8{a.scale}-p2-repvgg.yaml")
+    yolo = D.YOLO(f"yolov8{a.scale}-p2-repvgg{'-obb' if a.obb else ''}.yaml")
     yolo.model.load_state_dict(seeded_state_dict(yolo.model.state_dict(), 5, cls_bias=-1.2))
     video = [np.ascontiguousarray(f) for f in np.random.default_rng(2).integers(0, 256, (a.frames, HF, WF, 3), dtype=np.uint8)]
     common = dict(conf=0.25, iou=0.7, dtype=a.dtype, device=0)
-    tp = TiledPredictor(yolo.model, tile=a.tile, overlap=a.overlap, merge_iou=THR, merge_max_det=KEEP, **common)
+    tp = None if a.obb else TiledPredictor(yolo.model, tile=a.tile, overlap=a.overlap, merge_iou=THR, merge_max_det=KEEP, **common)
 
     def per_frame():
         return [len(tp(f)) for f in video]
@@ -153,6 +167,8 @@ if not a.no_e2e:
         return [len(r) for r in yolo.predict(video, tile=a.tile, tile_overlap=a.overlap, merge_iou=THR, merge_max_det=KEEP, batch=F, stream=True, **common)]
 
     runs = {"TiledPredictor_per_frame": per_frame, "predict_batch1": lambda: batched(1), "predict_batch2": lambda: batched(2), "predict_batch4": lambda: batched(4)}
+    if a.obb:
+        runs.pop("TiledPredictor_per_frame")
     fps = {k: [] for k in runs}
     boxes = {}
     for k, fn in runs.items():  # warm-up: records and captures every pass
@@ -165,5 +181,5 @@ if not a.no_e2e:
             fn()
             torch.cuda.synchronize()
             fps[k].append(a.frames / (time.perf_counter() - t0))
-    out["end_to_end"] = {"frames": a.frames, "scale": a.scale, "dtype": a.dtype, "rounds": rounds, "boxes": boxes, "frames_per_s": {k: stat(v) for k, v in fps.items()}}
+    out["end_to_end"] = {"frames": a.frames, "scale": a.scale, "obb": a.obb, "dtype": a.dtype, "rounds": rounds, "boxes": boxes, "frames_per_s": {k: stat(v) for k, v in fps.items()}}
 print(json.dumps(out))
