@@ -125,10 +125,7 @@ class ValMatchDesc(C.Structure):
     ]  # fmt: skip
 
 
-class ValMatchRotatedDesc(C.Structure):
-    """Mirror of ``dy_val_match_rotated_desc`` (the fields of ``dy_val_match_desc``; rows are 7 wide, tbox 8)."""
-
-    _fields_ = list(ValMatchDesc._fields_)
+ValMatchRotatedDesc = ValMatchDesc  # dy_val_match_rotated_desc is a typedef of dy_val_match_desc (rows are 7 wide, tbox 8)
 
 
 class TileMergeDesc(C.Structure):

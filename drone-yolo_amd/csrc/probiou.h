@@ -1,4 +1,4 @@
-// ProbIoU of two oriented boxes, shared by the rotated NMS (obb.hip) and the validator's rotated matching (val_match_rotated.hip): one
+// ProbIoU of two oriented boxes, shared by the rotated NMS (obb.hip) and the validator's rotated matching (val_match.hip, the VmRotated policy): one
 // expression, so a pair scores the same in both.  fp32 in the reference's order of operations; the including file keeps
 // `#pragma clang fp contract(off)` in force (the pragma below covers this header's functions wherever it is included).
 #pragma once

@@ -1,5 +1,5 @@
-// The second half of the validator's match rule, shared by dy_val_match (val_match.hip: box IoU) and dy_val_mask_match (val_mask.hip: mask
-// IoU).  With best(d) / biou(d) of an image's kept rows in LDS (rows in descending confidence, so "e < d" is "ranked higher"):
+// The second half of the validator's match rule, shared by dy_val_match / dy_val_match_rotated (val_match.hip: box IoU / ProbIoU) and
+// dy_val_mask_match (val_mask.hip: mask IoU).  With best(d) / biou(d) of an image's kept rows in LDS (rows in descending confidence, so "e < d" is "ranked higher"):
 //     tp[d][i] = biou(d) >= thr[i] and no e < d has best(e) == best(d) and biou(e) >= thr[i]
 // Every element of tp / best_iou / best_label of the image is written; rows >= cnt (or without a label) get 0 / 0 / -1.
 #pragma once

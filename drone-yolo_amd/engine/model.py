@@ -48,7 +48,7 @@ class Model(nn.Module):
 
     @property
     def predict_only_task_map(self):
-        """Tasks without a trainer, kept apart from ``task_map``: a model, a predictor and (``_val_obb``) a validator."""
+        """Tasks without a trainer, kept apart from ``task_map``: a model, a predictor and (``val``) a validator."""
         return {"obb": {"model": OBBModel, "predictor": OBBPredictor}}
 
     def _task_classes(self, task: str) -> dict:
@@ -205,107 +205,74 @@ class Model(nn.Module):
 
     def val(self, validator=None, **kwargs) -> dict:
         """Reference engine/model.py:620-656 (``Model.val``): the model's own weights scored on a dataset by the task's validator
-        (models/yolo/detect/val.py; engine/validator.py here: the model pass, the ``multi_label`` NMS at conf 0.001 and the matching of detections
-        to labels on the device, AP on the host; ``device_match=False`` matches on the host as the reference does, with the same result).  ``data``: a tensor dataset — a dict / ``.pt`` in the training layout, its ``"val"`` split when it has one — or
-        ``"synthetic[:N]"`` (engine/trainer.py::load_dataset; image folders and dataset YAMLs are outside the accelerated path);
-        ``batch``, ``imgsz``, ``conf``, ``iou``, ``max_det``, ``half`` / ``dtype``, ``device`` as the reference's arguments.  Returns the
-        reference's ``results_dict`` (metrics/precision(B) ... metrics/mAP50-95(B), fitness) with the validation losses; kept in ``self.metrics``."""
+        (engine/validator.py here): the model pass, the ``multi_label`` NMS at conf 0.001 and the matching of detections to labels on the
+        device, AP on the host; ``device_match=False`` matches on the host as the reference does, with the same result.  ``data``: a tensor
+        dataset — a dict / ``.pt`` in the training layout, its ``"val"`` split when it has one — or ``"synthetic[:N]"``
+        (engine/trainer.py::load_dataset; image folders and dataset YAMLs are outside the accelerated path); ``batch``, ``imgsz``, ``conf``,
+        ``iou``, ``max_det``, ``half`` / ``dtype``, ``device`` as the reference's arguments.  The result is kept in ``self.metrics``.
+
+        detect (models/yolo/detect/val.py; ``DetectionValidator``, ``dy_val_match``): the reference's ``results_dict``
+        (metrics/precision(B) ... metrics/mAP50-95(B), fitness) with the validation losses.
+        segment (models/yolo/segment/val.py; ``SegmentationValidator``): box and mask metrics, the masks scored by ``dy_val_mask_match``.  The
+        dataset must carry ``masks``, the reference's ``overlap_mask=True`` index maps (N, gh, gw) uint8 / int32 — the prototype grid equals
+        the map's or is exactly twice it.  ``SegmentMetrics``' dict (the four (B) and four (M) entries, ``fitness``), no validation loss.
+        obb (models/yolo/obb/val.py; ``OBBValidator``): the rotated ``multi_label`` NMS (``dy_nms_rotated_ml``) and the ProbIoU matching
+        (``dy_val_match_rotated``).  The dataset's ``bboxes`` must be (M, 5): normalised xywh and the angle in radians.  ``OBBMetrics``' dict
+        (the four (B) entries, ``fitness``), no validation loss.  ``save_json``, plots, the DOTA merge (``eval_json``) and ``save_txt`` are
+        not built."""
         from .predictor import resolve_dtype
         from .trainer import TensorLoader, load_dataset
-        from .validator import DetectionValidator
+        from . import validator as V
+        from .. import hip_ops as H
         from ..utils.torch_utils import select_device
 
         args = {**{k: v for k, v in self.overrides.items() if k not in ("task", "mode")}, **kwargs}
         if args.get("data") is None:
             raise ValueError("val(): 'data' is missing (a tensor dataset: dict / .pt, or 'synthetic[:N]')")
-        if self.task == "segment":
-            return self._val_segment(validator, args)
-        if self.task == "obb":
-            return self._val_obb(validator, args)
-        device = select_device(args.get("device", ""))
+        # per task: the dataset check, the head's name when FP8 storage is refused (None: whatever is not a storage type of the training path
+        # falls back to fp32, the pass returns the raw maps for the loss), the loader keys, the validator
+        keys = ("img", "batch_idx", "cls", "bboxes")
+        check, fp8_refused, keys, default = {"detect": (None, None, keys, V.DetectionValidator),
+                                             "segment": (self._check_val_masks, "Segment", keys + ("masks",), V.SegmentationValidator),
+                                             "obb": (self._check_val_xywhr, "OBB", keys, V.OBBValidator)}[self.task]
+        # the dataset first: whatever it lacks is refused before a device is selected, the model moved or a validator built
         data = load_dataset(args["data"], int(args.get("imgsz", 640)), self.model.yaml["nc"], int(args.get("seed", 0)))
         data = data.get("val") or data
+        if check is not None:
+            check(data, repr(args["data"] if isinstance(args["data"], str) else type(args["data"]).__name__))
+        device = select_device(args.get("device", ""))
         dtype = resolve_dtype(args.get("dtype"), bool(args.get("half", False)), self.model)
-        if dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            dtype = torch.float32  # (the validator's pass returns the raw maps for the loss: the storage types of the training path)
+        if fp8_refused is None and dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            dtype = torch.float32
+        elif fp8_refused is not None and dtype == H.FP8:
+            raise NotImplementedError(f"val: {fp8_refused} is built for the 16-bit, split-float16 and fp32 storage types")
         was_training = self.model.training
         model = self.model.to(device)
-        loader = TensorLoader({k: data[k] for k in ("img", "batch_idx", "cls", "bboxes")}, int(args.get("batch") or 16), 0, 1, shuffle=False)
+        loader = TensorLoader({k: data[k] for k in keys}, int(args.get("batch") or 16), 0, 1, shuffle=False)
         try:
-            self.metrics = (validator or DetectionValidator)(args)(model, loader, device, dtype)
+            self.metrics = (validator or default)(args)(model, loader, device, dtype)
         finally:
             model.train(was_training)
         self.predictor = None  # (the pass may have re-packed weights for another storage type)
         return self.metrics
 
-    def _val_segment(self, validator, args: dict) -> dict:
-        """``val`` of a segmentation model (reference models/yolo/segment/val.py; engine/validator.py::SegmentationValidator): box and mask
-        metrics, the masks scored on the device by ``dy_val_mask_match`` (``device_match=False``: the reference's data flow on the host).  The
-        dataset must carry ``masks``, the reference's ``overlap_mask=True`` index maps (N, gh, gw) uint8 / int32 — the prototype grid equals the
-        map's or is exactly twice it.  Returns ``SegmentMetrics``' dict (the four (B) and four (M) entries, ``fitness``), no validation loss."""
-        from .predictor import resolve_dtype
-        from .trainer import TensorLoader, load_dataset
-        from .validator import SegmentationValidator
-        from .. import hip_ops as H
-        from ..utils.torch_utils import select_device
-
-        # the dataset first: whatever it lacks is refused before a device is selected, the model moved or a validator built
-        data = load_dataset(args["data"], int(args.get("imgsz", 640)), self.model.yaml["nc"], int(args.get("seed", 0)))
-        data = data.get("val") or data
+    @staticmethod
+    def _check_val_masks(data: dict, name: str) -> None:
         masks = data.get("masks")
         if masks is None:
             raise NotImplementedError("val: a segmentation model needs a dataset with 'masks' (the overlap index map (N, gh, gw) of every image); "
-                                      f"data={args['data'] if isinstance(args['data'], str) else type(args['data']).__name__!r} has none")
+                                      f"data={name} has none")
         if not isinstance(masks, torch.Tensor) or masks.dim() != 3 or masks.shape[0] != data["img"].shape[0] or masks.dtype not in (torch.uint8, torch.int32):
             raise NotImplementedError("val: 'masks' must be the overlap index map, uint8 / int32 (N, gh, gw) with one map per image; one binary mask per "
                                       "label (overlap_mask=False) is not built")
-        device = select_device(args.get("device", ""))
-        dtype = resolve_dtype(args.get("dtype"), bool(args.get("half", False)), self.model)
-        if dtype == H.FP8:
-            raise NotImplementedError("val: Segment is built for the 16-bit, split-float16 and fp32 storage types")
-        was_training = self.model.training
-        model = self.model.to(device)
-        loader = TensorLoader({k: data[k] for k in ("img", "batch_idx", "cls", "bboxes", "masks")}, int(args.get("batch") or 16), 0, 1, shuffle=False)
-        try:
-            self.metrics = (validator or SegmentationValidator)(args)(model, loader, device, dtype)
-        finally:
-            model.train(was_training)
-        self.predictor = None  # (the pass may have re-packed weights for another storage type)
-        return self.metrics
 
-    def _val_obb(self, validator, args: dict) -> dict:
-        """``val`` of an oriented-box model (reference models/yolo/obb/val.py; engine/validator.py::OBBValidator): the rotated ``multi_label``
-        NMS at conf 0.001 (``dy_nms_rotated_ml``) and the ProbIoU matching (``dy_val_match_rotated``) on the device, AP on the host
-        (``device_match=False``: the reference's data flow on the host).  The dataset's ``bboxes`` must be (M, 5): normalised xywh and the angle
-        in radians.  Returns ``OBBMetrics``' dict (the four (B) entries, ``fitness``), no validation loss.  ``save_json``, plots, the DOTA merge
-        (``eval_json``) and ``save_txt`` are not built."""
-        from .predictor import resolve_dtype
-        from .trainer import TensorLoader, load_dataset
-        from .validator import OBBValidator
-        from .. import hip_ops as H
-        from ..utils.torch_utils import select_device
-
-        # the dataset first: whatever it lacks is refused before a device is selected, the model moved or a validator built
-        data = load_dataset(args["data"], int(args.get("imgsz", 640)), self.model.yaml["nc"], int(args.get("seed", 0)))
-        data = data.get("val") or data
+    @staticmethod
+    def _check_val_xywhr(data: dict, name: str) -> None:
         boxes = data["bboxes"]
         if not isinstance(boxes, torch.Tensor) or boxes.dim() != 2 or boxes.shape[1] != 5:
             shape = tuple(boxes.shape) if isinstance(boxes, torch.Tensor) else type(boxes).__name__
             raise NotImplementedError(f"val: an oriented-box model needs a dataset whose 'bboxes' are (M, 5) xywhr (normalised xywh and the angle in radians); "
-                                      f"data={args['data'] if isinstance(args['data'], str) else type(args['data']).__name__!r} has {shape} (no angles)")
-        device = select_device(args.get("device", ""))
-        dtype = resolve_dtype(args.get("dtype"), bool(args.get("half", False)), self.model)
-        if dtype == H.FP8:
-            raise NotImplementedError("val: OBB is built for the 16-bit, split-float16 and fp32 storage types")
-        was_training = self.model.training
-        model = self.model.to(device)
-        loader = TensorLoader({k: data[k] for k in ("img", "batch_idx", "cls", "bboxes")}, int(args.get("batch") or 16), 0, 1, shuffle=False)
-        try:
-            self.metrics = (validator or OBBValidator)(args)(model, loader, device, dtype)
-        finally:
-            model.train(was_training)
-        self.predictor = None  # (the pass may have re-packed weights for another storage type)
-        return self.metrics
+                                      f"data={name} has {shape} (no angles)")
 
     def fuse(self):
         self.model.fuse()

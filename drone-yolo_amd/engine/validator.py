@@ -11,6 +11,9 @@ validation (``_collect_device``).  ``device_match=False`` is the reference's dat
 The validation loss is the criterion on Detect's raw maps of the same pass (validator.py:186-187).
 Tensor datasets only (dataset files / augmentation are out of scope): ``data["val"]`` — a dict in the training set's
 layout — or, when the dataset has no split, the training tensors themselves.
+
+``DetectionValidator`` owns the call, both collect loops and the final assembly; a task differs in its class data (``stat_keys``,
+``metrics_cls``, ``val_loss``) and four hooks: ``_nms`` (the task's half of the pass), ``_labels``, ``_match_device`` and ``_match_host``.
 ``SegmentationValidator`` (models/yolo/segment/val.py) adds the mask statistics of a segmentation model: ``dy_val_mask_match`` behind the box
 matching, or the reference's mask branch on the host ("Segmentation validation").
 ``OBBValidator`` (models/yolo/obb/val.py) scores an oriented-box model: ``dy_nms_rotated_ml`` and ``dy_val_match_rotated`` (ProbIoU), or the
@@ -29,6 +32,10 @@ from ..utils.metrics import DetMetrics, OBBMetrics, SegmentMetrics, batch_probio
 
 
 class DetectionValidator:
+    stat_keys = ("tp",)  # what the matchers return, per detection; conf, pred_cls and target_cls follow in ``stats``
+    metrics_cls = DetMetrics
+    val_loss = True  # the criterion on the raw maps of the same pass: ``val/*_loss`` in the dict
+
     def __init__(self, args: Optional[dict] = None):
         a = dict(conf=None, iou=0.7, max_det=300, single_cls=False, agnostic_nms=False, device_match=True)
         a.update({k: v for k, v in (args or {}).items() if k in a})
@@ -38,68 +45,102 @@ class DetectionValidator:
         self.single_cls = bool(a["single_cls"])
         self.device_match = bool(a["device_match"])  # package extension (cfg/default.yaml): matching through dy_val_match
         self.iouv = np.linspace(0.5, 0.95, 10)  # detect/val.py:37
-        self.metrics = DetMetrics()
+        self.metrics = self.metrics_cls()
+        self.last_stats = None  # what the last call gathered (per-image lists on the host path, one block on the device path)
+        self.last_counts = None  # and the kept rows of every image, int32
 
     def __call__(self, model, loader, device, dtype: torch.dtype) -> Dict[str, float]:
-        """``model``: the DetectionModel carrying the weights to evaluate (the trainer loads the EMA copy), put in eval mode here and
+        """``model``: the model carrying the weights to evaluate (the trainer loads the EMA copy), put in eval mode here and
         left there; ``loader``: batches in the training layout (uint8 images + normalised xywh labels).  Returns the reference's
-        ``results_dict`` + ``val/*_loss`` + ``fitness``, rounded to 5 digits (validator.py:204-207)."""
+        ``results_dict`` (+ ``val/*_loss`` with ``val_loss``) + ``fitness``, rounded to 5 digits (validator.py:204-207)."""
         model.eval()
         nc = model.yaml["nc"]
-        stats = dict(tp=[], conf=[], pred_cls=[], target_cls=[])
-        loss = torch.zeros(3, device=device)
-        if getattr(model, "criterion", None) is None:
+        stats = {k: [] for k in (*self.stat_keys, "conf", "pred_cls", "target_cls")}
+        loss = torch.zeros(3, device=device) if self.val_loss else None
+        if self.val_loss and getattr(model, "criterion", None) is None:
             model.criterion = model.init_criterion()
         det = model.model[-1]
         fuse_tail = getattr(det, "fuse_tail", False)
         try:
-            return self._evaluate(model, loader, device, dtype, nc, stats, loss, det)
+            nb = (self._collect_device if self.device_match else self._collect_host)(model, loader, device, dtype, nc, stats, loss, det)
         finally:
             det.fuse_tail = fuse_tail  # (a predictor that shares the model keeps its fused tail: ADVICE r4)
-
-    def _evaluate(self, model, loader, device, dtype, nc, stats, loss, det) -> Dict[str, float]:
-        nb = (self._collect_device if self.device_match else self._collect_host)(model, loader, device, dtype, nc, stats, loss, det)
-        out = {k: 0.0 for k in DetMetrics.keys + ("fitness",)}
+        self.last_stats = stats
+        out = {k: 0.0 for k in self.metrics_cls.keys + ("fitness",)}
         if stats["tp"]:
             cat = {k: np.concatenate(v, 0) for k, v in stats.items()}
             if len(cat["target_cls"]):
-                self.metrics.process(cat["tp"], cat["conf"], cat["pred_cls"], cat["target_cls"])
+                self.metrics.process(*cat.values())
                 out = self.metrics.results_dict
-        vl = (loss / max(nb, 1)).cpu().tolist()
-        out.update({"val/box_loss": vl[0], "val/cls_loss": vl[1], "val/dfl_loss": vl[2]})
+        if self.val_loss:
+            vl = (loss / max(nb, 1)).cpu().tolist()
+            out.update({"val/box_loss": vl[0], "val/cls_loss": vl[1], "val/dfl_loss": vl[2]})
         return {k: round(float(v), 5) for k, v in out.items()}
 
+    # ---- the task's hooks ----------------------------------------------------------------------------------------------------
+    def _nms(self, y, aux, nc, batch):
+        """The task's half of the pass: the head's outputs -> the padded NMS buffers and the tensors the matchers need besides."""
+        return ops.non_max_suppression(y, self.conf, self.iou, nc=nc, multi_label=True, agnostic=self.agnostic, max_det=self.max_det, return_padded=True), ()
+
+    def _labels(self, bboxes: torch.Tensor, w: int, h: int, lim: torch.Tensor) -> torch.Tensor:
+        """_prepare_batch (detect/val.py:108-117) on normalised xywh labels: xyxy in pixels, then ops.scale_boxes to the original image — for a
+        tensor dataset gain 1, pad 0 and the clip to the image (ops.py:92-127, 335-354).  Elementwise fp32 torch operations: the same bits
+        wherever ``bboxes`` lives.  ``lim``: fp32 (w, h, w, h) on the same device."""
+        return torch.minimum((ops.xywh2xyxy(bboxes.float()) * lim).clamp_min(0), lim)
+
+    def _match_device(self, bufs, tbox, cls, bi, wh, extras) -> Dict[str, torch.Tensor]:
+        return dict(tp=H.val_match(bufs, tbox, cls, bi, self.iouv, wh, single_cls=self.single_cls))  # (new tensors on every call)
+
+    def _match_host(self, pn: np.ndarray, tbox: np.ndarray, cls: np.ndarray, wh, extras, si: int) -> Dict[str, np.ndarray]:
+        """One image with labels and rows: ``pn`` as ``_clipped`` leaves them."""
+        return dict(tp=match_predictions(pn[:, 5], cls, box_iou(tbox, pn[:, :4]), self.iouv))
+
+    # ---- the pass and the two loops ------------------------------------------------------------------------------------------
+    def _pass(self, model, batch, device, dtype, nc, det, loss):
+        img = batch["img"].to(device)
+        x = (img.float() / 255.0) if img.dtype == torch.uint8 else img.float()  # detect/val.py:49-52
+        with torch.no_grad():
+            det.fuse_tail = False  # the head returns (y, aux) with its raw maps: Detect's feats, Segment's (feats, mc, p), OBB's (feats, angle)
+            y, aux = model._predict_once(x.contiguous(), image_dtype=dtype)
+            if self.val_loss:
+                loss += model.criterion(aux, batch)[1]  # validator.py:186-187: loss items of the same pass
+            bufs, extras = self._nms(y, aux, nc, batch)
+        return img.shape, bufs, extras
+
+    def _clipped(self, rows: np.ndarray, w: int, h: int) -> np.ndarray:
+        """_prepare_pred (detect/val.py:119-124): ops.scale_boxes at gain 1, pad 0 is the clip, columns 0 and 2 to [0, w], 1 and 3 to [0, h]
+        (of an xywh row the width and height too); class 0 with ``single_cls``."""
+        pn = rows.copy()
+        pn[:, [0, 2]] = pn[:, [0, 2]].clip(0, w)
+        pn[:, [1, 3]] = pn[:, [1, 3]].clip(0, h)
+        if self.single_cls:
+            pn[:, -1] = 0
+        return pn
+
     def _collect_device(self, model, loader, device, dtype, nc, stats, loss, det) -> int:
-        """``device_match``: fills ``stats`` with what ``_collect_host`` gathers (image order, then row order), matched by ``dy_val_match``.
+        """``device_match``: fills ``stats`` with what ``_collect_host`` gathers (image order, then row order), matched on the device.
         Nothing in the loop waits for the device; the accumulated tensors go to the host once each after it."""
         nb = n_img = 0
-        rows, counts, tps, tcls, timg = [], [], [], [], []
+        rows, counts, tcls, timg = [], [], [], []
+        tps = {k: [] for k in self.stat_keys}
         lim = {}
         for batch in loader:
             nb += 1
-            img = batch["img"].to(device)
-            b, _, h, w = img.shape
-            x = (img.float() / 255.0) if img.dtype == torch.uint8 else img.float()  # detect/val.py:49-52
-            with torch.no_grad():
-                det.fuse_tail = False  # the raw maps are needed for the loss: Detect returns (y, feats)
-                y, feats = model._predict_once(x.contiguous(), image_dtype=dtype)
-                loss += model.criterion(feats, batch)[1]  # validator.py:186-187: loss items of the same pass
-                bufs = ops.non_max_suppression(y, self.conf, self.iou, nc=nc, multi_label=True, agnostic=self.agnostic, max_det=self.max_det,
-                                               return_padded=True)
+            (b, _, h, w), bufs, extras = self._pass(model, batch, device, dtype, nc, det, loss)
             if (w, h) not in lim:
                 lim[(w, h)] = torch.tensor((w, h, w, h), dtype=torch.float32, device=device)
-            # the labels as _collect_host prepares them, in the same elementwise fp32 arithmetic (the same bits): scale to pixels, clip to the image
             cls = batch["cls"].to(device).view(-1).float()
             bi = batch["batch_idx"].to(device).view(-1).to(torch.int32)
-            tbox = ops.xywh2xyxy(batch["bboxes"].to(device).float()) * lim[(w, h)]
-            tbox = torch.minimum(tbox.clamp_min(0), lim[(w, h)])
-            tps.append(H.val_match(bufs, tbox, cls, bi, self.iouv, (w, h), single_cls=self.single_cls))  # (new tensors on every call)
-            rows.append(bufs.out[..., 4:6].clone()), counts.append(bufs.count.clone())  # (the NMS buffers may be reused by the next batch)
+            tbox = self._labels(batch["bboxes"].to(device), w, h, lim[(w, h)])
+            for k, v in self._match_device(bufs, tbox, cls, bi, (w, h), extras).items():
+                tps[k].append(v)
+            rows.append(bufs.out[..., bufs.ROW - 2 :].clone()), counts.append(bufs.count.clone())  # (the NMS buffers may be reused by the next batch)
             tcls.append(cls), timg.append(bi + n_img)
             n_img += b
         if nb == 0:
             return nb
-        rows, counts, tp = (torch.cat(v).cpu().numpy() for v in (rows, counts, tps))
+        rows, counts = torch.cat(rows).cpu().numpy(), torch.cat(counts).cpu().numpy()
+        tps = {k: torch.cat(v).cpu().numpy() for k, v in tps.items()}
         tcls, timg = torch.cat(tcls).cpu().numpy(), torch.cat(timg).cpu().numpy().astype(np.int64)
         keep = np.arange(self.max_det)[None, :] < counts[:, None]
         conf, pred_cls = rows[keep][:, 0], rows[keep][:, 1]
@@ -110,44 +151,44 @@ class DetectionValidator:
         if bool(((counts == 0) & (np.bincount(timg, minlength=len(counts))[: len(counts)] > 0)).any()):
             conf, pred_cls = conf.astype(np.float64), pred_cls.astype(np.float64)
         if len(conf) or len(tcls):
-            stats["tp"].append(tp[keep].astype(bool)), stats["conf"].append(conf), stats["pred_cls"].append(pred_cls)
+            for k, v in tps.items():
+                stats[k].append(v[keep].astype(bool))
+            stats["conf"].append(conf), stats["pred_cls"].append(pred_cls)
             stats["target_cls"].append(tcls[np.argsort(timg, kind="stable")])
+        self.last_counts = counts
         return nb
 
     def _collect_host(self, model, loader, device, dtype, nc, stats, loss, det) -> int:
+        """``device_match=False``: detect/val.py:126-174 image by image on CPU arrays; one read-back of the counts and the rows per batch."""
         nb = 0
+        all_counts = []
         for batch in loader:
             nb += 1
-            img = batch["img"].to(device)
-            b, _, h, w = img.shape
-            x = (img.float() / 255.0) if img.dtype == torch.uint8 else img.float()  # detect/val.py:49-52
-            with torch.no_grad():
-                det.fuse_tail = False  # the raw maps are needed for the loss: Detect returns (y, feats)
-                y, feats = model._predict_once(x.contiguous(), image_dtype=dtype)
-                loss += model.criterion(feats, batch)[1]  # validator.py:186-187: loss items of the same pass
-                preds = ops.non_max_suppression(y, self.conf, self.iou, nc=nc, multi_label=True, agnostic=self.agnostic, max_det=self.max_det)
+            (_, _, h, w), bufs, extras = self._pass(model, batch, device, dtype, nc, det, loss)
+            counts = bufs.count.cpu().tolist()
+            out = bufs.out.cpu()
+            extras = tuple(t.cpu() for t in extras)
             bi = batch["batch_idx"].long().cpu()
-            for si, pred in enumerate(preds):  # detect/val.py:126-174
+            all_counts += counts
+            lim = torch.tensor((w, h, w, h), dtype=torch.float32)
+            for si, k in enumerate(counts):
                 sel = bi == si
                 cls = batch["cls"].cpu()[sel].view(-1).numpy()
-                bb = batch["bboxes"].cpu()[sel].float()  # (a dataset held on the device: the scaling below is host arithmetic)
-                tbox = (ops.xywh2xyxy(bb) * torch.tensor((w, h, w, h), dtype=torch.float32)).numpy() if len(cls) else np.zeros((0, 4), np.float32)
-                pn = pred.cpu().numpy()
-                # _prepare_batch / _prepare_pred (detect/val.py:108-124): labels and predictions go through ops.scale_boxes to the original
-                # image — for a tensor dataset that is gain 1, pad 0 and the clip to the image (ops.py:92-127, 335-354)
-                for arr in (pn, tbox):
-                    arr[:, [0, 2]] = arr[:, [0, 2]].clip(0, w)
-                    arr[:, [1, 3]] = arr[:, [1, 3]].clip(0, h)
-                if self.single_cls:
-                    pn[:, 5] = 0
-                tp = np.zeros((len(pn), len(self.iouv)), dtype=bool)
-                if len(pn) == 0:
+                tps = {key: np.zeros((k, len(self.iouv)), dtype=bool) for key in self.stat_keys}
+                if k == 0:
                     if len(cls):
-                        stats["tp"].append(tp), stats["conf"].append(np.zeros(0)), stats["pred_cls"].append(np.zeros(0)), stats["target_cls"].append(cls)
+                        for key, v in tps.items():
+                            stats[key].append(v)
+                        stats["conf"].append(np.zeros(0)), stats["pred_cls"].append(np.zeros(0)), stats["target_cls"].append(cls)
                     continue
+                pn = self._clipped(out[si, :k].numpy(), w, h)
                 if len(cls):
-                    tp = match_predictions(pn[:, 5], cls, box_iou(tbox, pn[:, :4]), self.iouv)
-                stats["tp"].append(tp), stats["conf"].append(pn[:, 4]), stats["pred_cls"].append(pn[:, 5]), stats["target_cls"].append(cls)
+                    tbox = self._labels(batch["bboxes"].cpu()[sel], w, h, lim).numpy()  # (a dataset held on the device: host arithmetic)
+                    tps = self._match_host(pn, tbox, cls, (w, h), extras, si)
+                for key in self.stat_keys:
+                    stats[key].append(tps[key])
+                stats["conf"].append(pn[:, -2]), stats["pred_cls"].append(pn[:, -1]), stats["target_cls"].append(cls)
+        self.last_counts = np.array(all_counts, dtype=np.int32)
         return nb
 
 
@@ -206,29 +247,9 @@ class SegmentationValidator(DetectionValidator):
     reference's ``overlap_mask=True`` index map (N, gh, gw).  No validation loss (the segmentation criterion is not built, and the
     reference's stand-alone ``val`` computes none): the dict holds the eight metrics and ``fitness``."""
 
-    def __init__(self, args: Optional[dict] = None):
-        super().__init__(args)
-        self.metrics = SegmentMetrics()
-        self.last_stats = None  # what the last call gathered (per-image lists on the host path, one block on the device path)
-
-    def __call__(self, model, loader, device, dtype: torch.dtype) -> Dict[str, float]:
-        model.eval()
-        nc = model.yaml["nc"]
-        stats = dict(tp=[], tp_m=[], conf=[], pred_cls=[], target_cls=[])
-        det = model.model[-1]
-        fuse_tail = getattr(det, "fuse_tail", False)
-        try:
-            (self._collect_device if self.device_match else self._collect_host)(model, loader, device, dtype, nc, stats, det)
-        finally:
-            det.fuse_tail = fuse_tail
-        self.last_stats = stats
-        out = {k: 0.0 for k in SegmentMetrics.keys + ("fitness",)}
-        if stats["tp"]:
-            cat = {k: np.concatenate(v, 0) for k, v in stats.items()}
-            if len(cat["target_cls"]):
-                self.metrics.process(cat["tp"], cat["tp_m"], cat["conf"], cat["pred_cls"], cat["target_cls"])
-                out = self.metrics.results_dict
-        return {k: round(float(v), 5) for k, v in out.items()}
+    stat_keys = ("tp", "tp_m")
+    metrics_cls = SegmentMetrics
+    val_loss = False
 
     @staticmethod
     def _label_cap(loader) -> int:
@@ -239,97 +260,30 @@ class SegmentationValidator(DetectionValidator):
         per = torch.zeros(int(loader.n), dtype=torch.long, device=bi.device).index_add_(0, bi, torch.ones_like(bi))
         return max(int(per.max()), 1)
 
-    def _pass(self, model, batch, device, dtype, nc, det):
-        img = batch["img"].to(device)
-        x = (img.float() / 255.0) if img.dtype == torch.uint8 else img.float()
-        with torch.no_grad():
-            det.fuse_tail = False  # Segment returns (cat([y, mc]), (feats, mc, p))
-            y, aux = model._predict_once(x.contiguous(), image_dtype=dtype)
-            if not (isinstance(aux, tuple) and len(aux) == 3):
-                raise RuntimeError("SegmentationValidator needs a model whose head is Segment")
-            y = y.float().contiguous()
-            bufs = ops.non_max_suppression(y, self.conf, self.iou, nc=nc, multi_label=True, agnostic=self.agnostic, max_det=self.max_det,
-                                           return_padded=True)
-            side = H.mask_gather(bufs, pred=y, nc=nc)
-        return img.shape, bufs, side, aux[2]
+    def _collect_device(self, model, loader, *rest) -> int:
+        self._l_cap = self._label_cap(loader)
+        return super()._collect_device(model, loader, *rest)
 
-    def _collect_device(self, model, loader, device, dtype, nc, stats, det) -> int:
-        nb = n_img = 0
-        rows, counts, tps, tpms, tcls, timg = [], [], [], [], [], []
-        lim = {}
-        l_cap = self._label_cap(loader)
-        for batch in loader:
-            nb += 1
-            (b, _, h, w), bufs, side, protos = self._pass(model, batch, device, dtype, nc, det)
-            masks = batch["masks"].to(device)
-            check_mask_grids(protos.shape[2:], masks.shape[1:])
-            if (w, h) not in lim:
-                lim[(w, h)] = torch.tensor((w, h, w, h), dtype=torch.float32, device=device)
-            cls = batch["cls"].to(device).view(-1).float()
-            bi = batch["batch_idx"].to(device).view(-1).to(torch.int32)
-            tbox = ops.xywh2xyxy(batch["bboxes"].to(device).float()) * lim[(w, h)]
-            tbox = torch.minimum(tbox.clamp_min(0), lim[(w, h)])
-            tps.append(H.val_match(bufs, tbox, cls, bi, self.iouv, (w, h), single_cls=self.single_cls))
-            tpms.append(H.val_mask_match(bufs, protos, side, masks, cls, bi, self.iouv, (w, h), l_cap, single_cls=self.single_cls))
-            rows.append(bufs.out[..., 4:6].clone()), counts.append(bufs.count.clone())
-            tcls.append(cls), timg.append(bi + n_img)
-            n_img += b
-        if nb == 0:
-            return nb
-        rows, counts, tp, tpm = (torch.cat(v).cpu().numpy() for v in (rows, counts, tps, tpms))
-        tcls, timg = torch.cat(tcls).cpu().numpy(), torch.cat(timg).cpu().numpy().astype(np.int64)
-        keep = np.arange(self.max_det)[None, :] < counts[:, None]
-        conf, pred_cls = rows[keep][:, 0], rows[keep][:, 1]
-        if self.single_cls:
-            pred_cls = np.zeros_like(pred_cls)
-        if bool(((counts == 0) & (np.bincount(timg, minlength=len(counts))[: len(counts)] > 0)).any()):  # (as DetectionValidator._collect_device)
-            conf, pred_cls = conf.astype(np.float64), pred_cls.astype(np.float64)
-        if len(conf) or len(tcls):
-            stats["tp"].append(tp[keep].astype(bool)), stats["tp_m"].append(tpm[keep].astype(bool))
-            stats["conf"].append(conf), stats["pred_cls"].append(pred_cls)
-            stats["target_cls"].append(tcls[np.argsort(timg, kind="stable")])
-        self.last_counts = counts
-        return nb
+    def _nms(self, y, aux, nc, batch):
+        if not (isinstance(aux, tuple) and len(aux) == 3):  # Segment returns (cat([y, mc]), (feats, mc, p))
+            raise RuntimeError("SegmentationValidator needs a model whose head is Segment")
+        y = y.float().contiguous()
+        bufs, _ = super()._nms(y, aux, nc, batch)
+        side, protos, masks = H.mask_gather(bufs, pred=y, nc=nc), aux[2], batch["masks"]
+        check_mask_grids(protos.shape[2:], masks.shape[1:])
+        return bufs, (side, protos, masks)
 
-    def _collect_host(self, model, loader, device, dtype, nc, stats, det) -> int:
-        nb = 0
-        all_counts = []
-        for batch in loader:
-            nb += 1
-            (_, _, h, w), bufs, side, protos = self._pass(model, batch, device, dtype, nc, det)
-            check_mask_grids(protos.shape[2:], batch["masks"].shape[1:])
-            counts = bufs.count.cpu().tolist()
-            out, side, protos = bufs.out.cpu(), side.cpu(), protos.float().cpu().contiguous()
-            gmaps = batch["masks"].cpu()
-            bi = batch["batch_idx"].long().cpu()
-            all_counts += counts
-            for si, k in enumerate(counts):  # segment/val.py:90-133
-                sel = bi == si
-                cls = batch["cls"].cpu()[sel].view(-1).numpy()
-                bb = batch["bboxes"].cpu()[sel].float()
-                tbox = (ops.xywh2xyxy(bb) * torch.tensor((w, h, w, h), dtype=torch.float32)).numpy() if len(cls) else np.zeros((0, 4), np.float32)
-                pn = out[si, :k].clone().numpy()
-                for arr in (pn, tbox):  # scale_boxes at gain 1, pad 0: the clip to the image
-                    arr[:, [0, 2]] = arr[:, [0, 2]].clip(0, w)
-                    arr[:, [1, 3]] = arr[:, [1, 3]].clip(0, h)
-                if self.single_cls:
-                    pn[:, 5] = 0
-                tp = np.zeros((k, len(self.iouv)), dtype=bool)
-                tp_m = np.zeros((k, len(self.iouv)), dtype=bool)
-                if k == 0:
-                    if len(cls):
-                        stats["tp"].append(tp), stats["tp_m"].append(tp_m), stats["conf"].append(np.zeros(0)), stats["pred_cls"].append(np.zeros(0))
-                        stats["target_cls"].append(cls)
-                    continue
-                if len(cls):
-                    tp = match_predictions(pn[:, 5], cls, box_iou(tbox, pn[:, :4]), self.iouv)
-                    pm = host_pred_masks(protos[si], side[si, :k, 4:], side[si, :k, :4], (h, w))  # (the UNSCALED, unclipped NMS boxes)
-                    gt = host_gt_masks(gmaps[si], len(cls), protos.shape[2:])
-                    tp_m = match_predictions(pn[:, 5], cls, host_mask_iou(gt, pm), self.iouv)
-                stats["tp"].append(tp), stats["tp_m"].append(tp_m), stats["conf"].append(pn[:, 4]), stats["pred_cls"].append(pn[:, 5])
-                stats["target_cls"].append(cls)
-        self.last_counts = np.array(all_counts, dtype=np.int32)
-        return nb
+    def _match_device(self, bufs, tbox, cls, bi, wh, extras) -> Dict[str, torch.Tensor]:
+        side, protos, masks = extras
+        tpm = H.val_mask_match(bufs, protos, side, masks.to(bufs.out.device), cls, bi, self.iouv, wh, self._l_cap, single_cls=self.single_cls)
+        return dict(super()._match_device(bufs, tbox, cls, bi, wh, extras), tp_m=tpm)
+
+    def _match_host(self, pn, tbox, cls, wh, extras, si) -> Dict[str, np.ndarray]:  # segment/val.py:90-133
+        side, protos, gmaps = extras
+        k = len(pn)
+        pm = host_pred_masks(protos[si], side[si, :k, 4:], side[si, :k, :4], (wh[1], wh[0]))  # (the UNSCALED, unclipped NMS boxes)
+        gt = host_gt_masks(gmaps[si], len(cls), protos.shape[2:])
+        return dict(super()._match_host(pn, tbox, cls, wh, extras, si), tp_m=match_predictions(pn[:, 5], cls, host_mask_iou(gt, pm), self.iouv))
 
 
 # ---- oriented boxes (models/yolo/obb/val.py) ---------------------------------------------------------------------------------------------
@@ -351,113 +305,26 @@ class OBBValidator(DetectionValidator):
     are (M, 5) normalised xywh + the angle in radians.  No validation loss (``v8OBBLoss`` is not built, and the reference's stand-alone
     ``val`` computes none): the dict holds the four metrics and ``fitness``."""
 
-    def __init__(self, args: Optional[dict] = None):
-        super().__init__(args)
-        self.metrics = OBBMetrics()
-        self.last_stats = None  # what the last call gathered (per-image lists on the host path, one block on the device path)
+    metrics_cls = OBBMetrics
+    val_loss = False
+    _labels = staticmethod(obb_labels)
 
-    def __call__(self, model, loader, device, dtype: torch.dtype) -> Dict[str, float]:
-        model.eval()
-        nc = model.yaml["nc"]
-        stats = dict(tp=[], conf=[], pred_cls=[], target_cls=[])
-        det = model.model[-1]
-        fuse_tail = getattr(det, "fuse_tail", False)
-        try:
-            (self._collect_device if self.device_match else self._collect_host)(model, loader, device, dtype, nc, stats, det)
-        finally:
-            det.fuse_tail = fuse_tail
-        self.last_stats = stats
-        out = {k: 0.0 for k in OBBMetrics.keys + ("fitness",)}
-        if stats["tp"]:
-            cat = {k: np.concatenate(v, 0) for k, v in stats.items()}
-            if len(cat["target_cls"]):
-                self.metrics.process(cat["tp"], cat["conf"], cat["pred_cls"], cat["target_cls"])
-                out = self.metrics.results_dict
-        return {k: round(float(v), 5) for k, v in out.items()}
+    def _nms(self, y, aux, nc, batch):
+        if not (isinstance(aux, tuple) and len(aux) == 2) or y.shape[1] != 4 + nc + 1:  # OBB returns (cat([y, angle], 1), (feats, angle))
+            raise RuntimeError("OBBValidator needs a model whose head is OBB")
+        y = y.float()
+        return H.nms_rotated_ml(y[:, : 4 + nc].contiguous(), y[:, -1].contiguous(), self.conf, self.iou, max_det=self.max_det, agnostic=self.agnostic, nc=nc), ()
 
-    def _pass(self, model, batch, device, dtype, nc, det):
-        img = batch["img"].to(device)
-        x = (img.float() / 255.0) if img.dtype == torch.uint8 else img.float()
-        with torch.no_grad():
-            det.fuse_tail = False  # OBB returns (cat([y, angle], 1), (feats, angle))
-            y, aux = model._predict_once(x.contiguous(), image_dtype=dtype)
-            if not (isinstance(aux, tuple) and len(aux) == 2) or y.shape[1] != 4 + nc + 1:
-                raise RuntimeError("OBBValidator needs a model whose head is OBB")
-            y = y.float()
-            bufs = H.nms_rotated_ml(y[:, : 4 + nc].contiguous(), y[:, -1].contiguous(), self.conf, self.iou, max_det=self.max_det,
-                                    agnostic=self.agnostic, nc=nc)
-        return img.shape, bufs
+    def _match_device(self, bufs, tbox, cls, bi, wh, extras) -> Dict[str, torch.Tensor]:
+        return dict(tp=H.val_match_rotated(bufs, tbox, cls, bi, self.iouv, wh, single_cls=self.single_cls))  # (new tensors on every call)
 
-    def _collect_device(self, model, loader, device, dtype, nc, stats, det) -> int:
-        """Fills ``stats`` with what ``_collect_host`` gathers (image order, then row order), matched by ``dy_val_match_rotated``.  Nothing in
-        the loop waits for the device; the accumulated tensors go to the host once each after it."""
-        nb = n_img = 0
-        rows, counts, tps, tcls, timg = [], [], [], [], []
-        lim = {}
-        for batch in loader:
-            nb += 1
-            (b, _, h, w), bufs = self._pass(model, batch, device, dtype, nc, det)
-            if (w, h) not in lim:
-                lim[(w, h)] = torch.tensor((w, h, w, h), dtype=torch.float32, device=device)
-            cls = batch["cls"].to(device).view(-1).float()
-            bi = batch["batch_idx"].to(device).view(-1).to(torch.int32)
-            tbox = obb_labels(batch["bboxes"].to(device), w, h, lim[(w, h)])
-            tps.append(H.val_match_rotated(bufs, tbox, cls, bi, self.iouv, (w, h), single_cls=self.single_cls))  # (new tensors on every call)
-            rows.append(bufs.out[..., 5:7].clone()), counts.append(bufs.count.clone())  # (the NMS buffers may be reused by the next batch)
-            tcls.append(cls), timg.append(bi + n_img)
-            n_img += b
-        if nb == 0:
-            return nb
-        rows, counts, tp = (torch.cat(v).cpu().numpy() for v in (rows, counts, tps))
-        tcls, timg = torch.cat(tcls).cpu().numpy(), torch.cat(timg).cpu().numpy().astype(np.int64)
-        keep = np.arange(self.max_det)[None, :] < counts[:, None]
-        conf, pred_cls = rows[keep][:, 0], rows[keep][:, 1]
-        if self.single_cls:
-            pred_cls = np.zeros_like(pred_cls)
-        if bool(((counts == 0) & (np.bincount(timg, minlength=len(counts))[: len(counts)] > 0)).any()):  # (as DetectionValidator._collect_device)
-            conf, pred_cls = conf.astype(np.float64), pred_cls.astype(np.float64)
-        if len(conf) or len(tcls):
-            stats["tp"].append(tp[keep].astype(bool)), stats["conf"].append(conf), stats["pred_cls"].append(pred_cls)
-            stats["target_cls"].append(tcls[np.argsort(timg, kind="stable")])
-        self.last_counts = counts
-        return nb
+    def _match_host(self, pn, tbox, cls, wh, extras, si) -> Dict[str, np.ndarray]:
+        iou = batch_probiou(torch.from_numpy(np.ascontiguousarray(tbox, dtype=np.float32)), torch.from_numpy(np.ascontiguousarray(pn[:, :5]))).numpy()
+        return dict(tp=match_predictions(pn[:, 6], cls, iou, self.iouv))
 
     def host_match(self, rows: np.ndarray, tbox: np.ndarray, cls: np.ndarray, w: int, h: int) -> np.ndarray:
         """``_prepare_pred`` + ``_process_batch`` of one image on the host: ``rows`` (k, 7) = x, y, w, h, theta, conf, cls as the NMS left
         them, ``tbox`` (L, 5) prepared labels, ``cls`` (L,) -> tp (k, len(iouv)) bool."""
-        pn = rows.copy()
-        pn[:, [0, 2]] = pn[:, [0, 2]].clip(0, w)  # scale_boxes(xywh=True) at gain 1, pad 0: the clip, on x, y, w and h
-        pn[:, [1, 3]] = pn[:, [1, 3]].clip(0, h)
-        if self.single_cls:
-            pn[:, 6] = 0
-        if not len(cls) or not len(pn):
-            return np.zeros((len(pn), len(self.iouv)), dtype=bool)
-        iou = batch_probiou(torch.from_numpy(np.ascontiguousarray(tbox, dtype=np.float32)), torch.from_numpy(np.ascontiguousarray(pn[:, :5]))).numpy()
-        return match_predictions(pn[:, 6], cls, iou, self.iouv)
-
-    def _collect_host(self, model, loader, device, dtype, nc, stats, det) -> int:
-        nb = 0
-        all_counts = []
-        for batch in loader:
-            nb += 1
-            (_, _, h, w), bufs = self._pass(model, batch, device, dtype, nc, det)
-            counts = bufs.count.cpu().tolist()
-            out = bufs.out.cpu()
-            bi = batch["batch_idx"].long().cpu()
-            all_counts += counts
-            lim = torch.tensor((w, h, w, h), dtype=torch.float32)
-            for si, k in enumerate(counts):  # detect/val.py:126-174 with obb/val.py's _prepare_batch / _prepare_pred / _process_batch
-                sel = bi == si
-                cls = batch["cls"].cpu()[sel].view(-1).numpy()
-                tbox = obb_labels(batch["bboxes"].cpu()[sel], w, h, lim).numpy()
-                pn = out[si, :k].clone().numpy()
-                if k == 0:
-                    if len(cls):
-                        stats["tp"].append(np.zeros((0, len(self.iouv)), dtype=bool)), stats["conf"].append(np.zeros(0)), stats["pred_cls"].append(np.zeros(0))
-                        stats["target_cls"].append(cls)
-                    continue
-                tp = self.host_match(pn, tbox, cls, w, h)
-                stats["tp"].append(tp), stats["conf"].append(pn[:, 5]), stats["pred_cls"].append(np.zeros_like(pn[:, 6]) if self.single_cls else pn[:, 6])
-                stats["target_cls"].append(cls)
-        self.last_counts = np.array(all_counts, dtype=np.int32)
-        return nb
+        if not len(cls) or not len(rows):
+            return np.zeros((len(rows), len(self.iouv)), dtype=bool)
+        return self._match_host(self._clipped(rows, w, h), tbox, cls, (w, h), (), 0)["tp"]

@@ -1137,18 +1137,24 @@ class RNmsBuffers(NmsBuffers):
         return lib().dy_nms_rotated_ml_workspace_bytes(self.batch, self.anchors, self.cpa)
 
 
+def _check_rotated_pred(who: str, pred: torch.Tensor, theta: torch.Tensor) -> Tuple[int, int, int]:
+    """The ``pred`` / ``theta`` checks of ``nms_rotated`` and ``nms_rotated_ml``; returns ``pred.shape``."""
+    require_device(pred, "prediction")
+    require_device(theta, "angles")
+    if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.dim() != 3:
+        raise ValueError(f"{who} expects a contiguous fp32 (N, 4+nc, A) tensor")
+    n, ch, A = pred.shape
+    if tuple(theta.shape) != (n, A) or theta.dtype != torch.float32 or not theta.is_contiguous():
+        raise ValueError(f"{who}: theta must be a contiguous fp32 (N, A) tensor")
+    return n, ch, A
+
+
 def nms_rotated(pred: torch.Tensor, theta: torch.Tensor, conf_thres: float, iou_thres: float, max_det: int = 300, max_nms: int = 30000,
                 max_wh: float = 7680.0, agnostic: bool = False, nc: int = 0, classes_mask: Optional[torch.Tensor] = None,
                 bufs: Optional[RNmsBuffers] = None, prefiltered: bool = False, multi_label: bool = False) -> RNmsBuffers:
     """Batched ProbIoU fast NMS (``dy_nms_rotated``) on (N, 4+nc(+extra), A) fp32 predictions and their (N, A) angles; results stay on the
     device.  ``prefiltered``: ``bufs.workspace`` already holds the candidates (detect_decode(nms_bufs=bufs))."""
-    require_device(pred, "prediction")
-    require_device(theta, "angles")
-    if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.dim() != 3:
-        raise ValueError("nms_rotated expects a contiguous fp32 (N, 4+nc, A) tensor")
-    n, ch, A = pred.shape
-    if tuple(theta.shape) != (n, A) or theta.dtype != torch.float32 or not theta.is_contiguous():
-        raise ValueError("nms_rotated: theta must be a contiguous fp32 (N, A) tensor")
+    n, ch, A = _check_rotated_pred("nms_rotated", pred, theta)
     nc = nc or ch - 4
     if bufs is None or (bufs.batch, bufs.anchors, bufs.max_det) != (n, A, max_det):
         if prefiltered:
@@ -1165,13 +1171,7 @@ def nms_rotated_ml(pred: torch.Tensor, theta: torch.Tensor, conf_thres: float, i
     """The validator's rotated NMS (``dy_nms_rotated_ml``: ``non_max_suppression(rotated=True, multi_label=True)``): every (anchor, class)
     pair above ``conf_thres`` is a candidate, ``bufs.index`` holds the pair's anchor and column 6 of a row its class.  ``nc`` 1 is the
     single-label form.  Results stay on the device."""
-    require_device(pred, "prediction")
-    require_device(theta, "angles")
-    if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.dim() != 3:
-        raise ValueError("nms_rotated_ml expects a contiguous fp32 (N, 4+nc, A) tensor")
-    n, ch, A = pred.shape
-    if tuple(theta.shape) != (n, A) or theta.dtype != torch.float32 or not theta.is_contiguous():
-        raise ValueError("nms_rotated_ml: theta must be a contiguous fp32 (N, A) tensor")
+    n, ch, A = _check_rotated_pred("nms_rotated_ml", pred, theta)
     nc = nc or ch - 4
     if bufs is None or (bufs.batch, bufs.anchors, bufs.max_det) != (n, A, max_det) or bufs.cpa != nc:
         bufs = RNmsBuffers(n, A, max_det, pred.device, candidates_per_anchor=nc)
@@ -1316,24 +1316,13 @@ def process_mask(protos: torch.Tensor, side: torch.Tensor, count: torch.Tensor, 
     return out
 
 
-def val_match(bufs: NmsBuffers, tbox: torch.Tensor, tcls: torch.Tensor, timg: torch.Tensor, iouv: Sequence[float], clip_wh: Tuple[float, float],
-              single_cls: bool = False, want_best: bool = False):
-    """The validator's matching (``BaseValidator.match_predictions`` on ``box_iou``, predictions clipped to ``clip_wh``) of a whole batch
-    on the padded NMS output through ``dy_val_match``; no host synchronisation.
-
-    ``bufs``: what ``nms`` returned; ``tbox`` (L, 4): the batch's label boxes, xyxy in pixels, clipped; ``tcls`` (L,) their classes and
-    ``timg`` (L,) the image each belongs to (any order; converted here, on the device, to the fp32 / int32 the kernel reads); ``iouv``:
-    1..16 thresholds (host values, rounded to fp32 as the host comparison rounds them).  Returns ``tp`` uint8 (N, max_det, len(iouv)),
-    new tensors on every call; with ``want_best`` ``(tp, best_iou fp32 (N, max_det), best_label int32 (N, max_det))``.  Rows at or
-    beyond ``bufs.count`` are 0 / 0 / -1."""
+def _val_match(fn, bufs: NmsBuffers, tbox: torch.Tensor, tcls: torch.Tensor, timg: torch.Tensor, iouv: Sequence[float],
+               clip_wh: Tuple[float, float], single_cls: bool, want_best: bool):
+    """The launch behind ``val_match`` / ``val_match_rotated``: ``tbox`` as the kernel reads it (fp32, contiguous, on the device); ``tcls`` /
+    ``timg`` are converted here to fp32 / int32."""
     n, max_det, dev = bufs.batch, bufs.max_det, bufs.out.device
     L = int(tbox.shape[0])
     if L:
-        for t in (tbox, tcls, timg):
-            require_device(t, "label")
-        if tbox.dim() != 2 or tbox.shape[1] != 4 or tcls.numel() != L or timg.numel() != L:
-            raise ValueError("val_match: tbox must be (L, 4) with L classes and L image indices")
-        tbox = tbox.to(torch.float32).contiguous()
         tcls = tcls.reshape(-1).to(torch.float32).contiguous()
         timg = timg.reshape(-1).to(torch.int32).contiguous()
     thr = (C.c_float * len(iouv))(*[float(v) for v in iouv])
@@ -1349,8 +1338,34 @@ def val_match(bufs: NmsBuffers, tbox: torch.Tensor, tcls: torch.Tensor, timg: to
     d.tp = tp.data_ptr()
     d.best_iou = best_iou.data_ptr() if want_best else None
     d.best_label = best_label.data_ptr() if want_best else None
-    _launch(lib().dy_val_match, (C.byref(d),), keep=(d, thr, bufs, tbox, tcls, timg, tp, best_iou, best_label))
+    _launch(fn, (C.byref(d),), keep=(d, thr, bufs, tbox, tcls, timg, tp, best_iou, best_label))
     return (tp, best_iou, best_label) if want_best else tp
+
+
+def _check_labels(who: str, what: str, cols: int, tbox: torch.Tensor, tcls: torch.Tensor, timg: torch.Tensor) -> int:
+    """The label checks of ``val_match`` / ``val_match_rotated``; returns L."""
+    L = int(tbox.shape[0])
+    if L:
+        for t in (tbox, tcls, timg):
+            require_device(t, "label")
+        if tbox.dim() != 2 or tbox.shape[1] != cols or tcls.numel() != L or timg.numel() != L:
+            raise ValueError(f"{who}: tbox must be (L, {cols}){what} with L classes and L image indices")
+    return L
+
+
+def val_match(bufs: NmsBuffers, tbox: torch.Tensor, tcls: torch.Tensor, timg: torch.Tensor, iouv: Sequence[float], clip_wh: Tuple[float, float],
+              single_cls: bool = False, want_best: bool = False):
+    """The validator's matching (``BaseValidator.match_predictions`` on ``box_iou``, predictions clipped to ``clip_wh``) of a whole batch
+    on the padded NMS output through ``dy_val_match``; no host synchronisation.
+
+    ``bufs``: what ``nms`` returned; ``tbox`` (L, 4): the batch's label boxes, xyxy in pixels, clipped; ``tcls`` (L,) their classes and
+    ``timg`` (L,) the image each belongs to (any order; converted here, on the device, to the fp32 / int32 the kernel reads); ``iouv``:
+    1..16 thresholds (host values, rounded to fp32 as the host comparison rounds them).  Returns ``tp`` uint8 (N, max_det, len(iouv)),
+    new tensors on every call; with ``want_best`` ``(tp, best_iou fp32 (N, max_det), best_label int32 (N, max_det))``.  Rows at or
+    beyond ``bufs.count`` are 0 / 0 / -1."""
+    if _check_labels("val_match", "", 4, tbox, tcls, timg):
+        tbox = tbox.to(torch.float32).contiguous()
+    return _val_match(lib().dy_val_match, bufs, tbox, tcls, timg, iouv, clip_wh, single_cls, want_best)
 
 
 def val_match_rotated(bufs: RNmsBuffers, tbox: torch.Tensor, tcls: torch.Tensor, timg: torch.Tensor, iouv: Sequence[float], clip_wh: Tuple[float, float],
@@ -1362,35 +1377,14 @@ def val_match_rotated(bufs: RNmsBuffers, tbox: torch.Tensor, tcls: torch.Tensor,
     scaled and clipped (padded here, on the device, to the kernel's 8 floats per label); ``tcls`` (L,), ``timg`` (L,) (any order); ``iouv``:
     1..16 thresholds.  Returns ``tp`` uint8 (N, max_det, len(iouv)), new tensors on every call; with ``want_best`` ``(tp, best_iou fp32
     (N, max_det), best_label int32 (N, max_det))``.  Rows at or beyond ``bufs.count`` are 0 / 0 / -1."""
-    n, max_det, dev = bufs.batch, bufs.max_det, bufs.out.device
     if bufs.out.shape[-1] != 7:
         raise ValueError("val_match_rotated: the NMS buffers must hold 7-column rows (RNmsBuffers)")
-    L = int(tbox.shape[0])
+    L = _check_labels("val_match_rotated", " xywhr", 5, tbox, tcls, timg)
     if L:
-        for t in (tbox, tcls, timg):
-            require_device(t, "label")
-        if tbox.dim() != 2 or tbox.shape[1] != 5 or tcls.numel() != L or timg.numel() != L:
-            raise ValueError("val_match_rotated: tbox must be (L, 5) xywhr with L classes and L image indices")
-        padded = torch.zeros((L, 8), dtype=torch.float32, device=dev)
+        padded = torch.zeros((L, 8), dtype=torch.float32, device=bufs.out.device)
         padded[:, :5] = tbox
         tbox = padded
-        tcls = tcls.reshape(-1).to(torch.float32).contiguous()
-        timg = timg.reshape(-1).to(torch.int32).contiguous()
-    thr = (C.c_float * len(iouv))(*[float(v) for v in iouv])
-    tp = torch.empty((n, max_det, len(iouv)), dtype=torch.uint8, device=dev)
-    best_iou = torch.empty((n, max_det), dtype=torch.float32, device=dev) if want_best else None
-    best_label = torch.empty((n, max_det), dtype=torch.int32, device=dev) if want_best else None
-    d = _lib.ValMatchRotatedDesc()
-    d.rows, d.counts = bufs.out.data_ptr(), bufs.count.data_ptr()
-    d.tbox, d.tcls, d.timg = (tbox.data_ptr(), tcls.data_ptr(), timg.data_ptr()) if L else (None, None, None)
-    d.iouv = thr
-    d.batch, d.max_det, d.n_labels, d.n_iouv = n, max_det, L, len(iouv)
-    d.clip_w, d.clip_h, d.single_cls = float(clip_wh[0]), float(clip_wh[1]), int(bool(single_cls))
-    d.tp = tp.data_ptr()
-    d.best_iou = best_iou.data_ptr() if want_best else None
-    d.best_label = best_label.data_ptr() if want_best else None
-    _launch(lib().dy_val_match_rotated, (C.byref(d),), keep=(d, thr, bufs, tbox, tcls, timg, tp, best_iou, best_label))
-    return (tp, best_iou, best_label) if want_best else tp
+    return _val_match(lib().dy_val_match_rotated, bufs, tbox, tcls, timg, iouv, clip_wh, single_cls, want_best)
 
 
 def label_offsets(timg: torch.Tensor, batch: int) -> torch.Tensor:

@@ -760,33 +760,15 @@ typedef struct dy_val_match_desc {
 int32_t dy_val_match(const dy_val_match_desc* d, dy_stream_t stream);
 
 /* dy_val_match_rotated.  Replaces: OBBValidator._process_batch (models/yolo/obb/val.py: match_predictions on batch_probiou(gt, det)) with
- * the clip of its _prepare_pred, for a whole batch in one launch behind dy_nms_rotated / dy_nms_rotated_ml; no host synchronisation,
- * capturable in a hipGraph.
- * rows: fp32 (batch, max_det, 7) = x, y, w, h, theta, conf, cls and counts: int32 (batch) (rows >= counts[i] are not read).
- * tbox: fp32 (n_labels, 8), 16-byte aligned: x, y, w, h, theta in pixels / radians, already scaled and clipped, and three unused floats;
- * tcls: fp32 (n_labels); timg: int32 (n_labels), by value (any order).  n_labels = 0 with null label pointers is valid.
- * iouv: HOST array of n_iouv (1..16) thresholds, read during the call.
+ * the clip of its _prepare_pred, behind dy_nms_rotated / dy_nms_rotated_ml.  dy_val_match's descriptor, rule and outputs, except:
+ * rows: fp32 (batch, max_det, 7) = x, y, w, h, theta, conf, cls.
+ * tbox: fp32 (n_labels, 8), 16-byte aligned: x, y, w, h, theta in pixels / radians, already scaled and clipped, and three unused floats.
  * A detection is clipped as scale_boxes(xywh=True) at gain 1, pad 0 leaves it: x and w to [0, clip_w], y and h to [0, clip_h] (clip_boxes
  * clamps the width and height of an xywh row too); theta is untouched and not regularized.
  *   m(l, d) = probiou(label l, detection d) if tcls[l] == cls[d] (0 with single_cls) else 0, in fp32 in batch_probiou's order of operations
- *   (the expression of dy_nms_rotated; the device's sinf / cosf / logf / expf are not bit-equal to the host's);
- *   best / biou / tp by dy_val_match's rule; exact ties go to the lower position in tbox, a NaN m never becomes the best.
- * tp: uint8 (batch, max_det, n_iouv); best_iou: optional fp32 (batch, max_det); best_label: optional int32 (batch, max_det).  Every element
- * is written: rows >= counts[i] (and rows without a best label) get 0 / 0 / -1.  max_det <= 4096 (36 bytes of LDS per detection). */
-typedef struct dy_val_match_rotated_desc {
-  const float* rows;
-  const int32_t* counts;
-  const float* tbox;
-  const float* tcls;
-  const int32_t* timg;
-  const float* iouv;
-  int32_t batch, max_det, n_labels, n_iouv;
-  float clip_w, clip_h;
-  int32_t single_cls;
-  uint8_t* tp;
-  float* best_iou;
-  int32_t* best_label;
-} dy_val_match_rotated_desc;
+ *   (the expression of dy_nms_rotated; the device's sinf / cosf / logf / expf are not bit-equal to the host's); a NaN m never becomes the
+ *   best, and a row without a best label gets 0 / 0 / -1.  36 bytes of LDS per detection. */
+typedef dy_val_match_desc dy_val_match_rotated_desc;
 int32_t dy_val_match_rotated(const dy_val_match_rotated_desc* d, dy_stream_t stream);
 
 /* ---- training loss (forward + gradient w.r.t. the head outputs) -----------------------------------------------------

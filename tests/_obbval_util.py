@@ -120,6 +120,48 @@ def match_inputs(name, seed):
     return _gen(seed, **MATCH_CASES[name])
 
 
+def _grid_labels(n, pitch=60.0):
+    """n 20 x 10 boxes of mixed angles on a grid ``pitch`` px apart: every pair of different boxes scores below 0.01."""
+    i = np.arange(n)
+    return np.stack((40.0 + pitch * (i % 17), 40.0 + pitch * (i // 17), np.full(n, 20.0), np.full(n, 10.0), (i % 7) * 0.4 - 0.7), 1).astype(np.float32)
+
+
+def full_stage_case():
+    """A stage filled exactly to capacity: 257 labels of one class, all of image 0 and in order (the first step stages 256 entries, the second
+    one); detections = exact copies of labels 0, 255 and 256, and a second copy of label 256 ranked below the first.  No seed: every same-class
+    pair is above 0.99 or below 0.01."""
+    lab = _grid_labels(257)
+    rows = np.zeros((1, 4, 7), np.float32)
+    rows[0, :, :5] = lab[[0, 255, 256, 256]]
+    rows[0, :, 5], rows[0, :, 6] = (0.9, 0.8, 0.7, 0.6), 1.0
+    return dict(rows=rows, counts=np.array([4], np.int32), tbox=lab, tcls=np.ones(257, np.float32), timg=np.zeros(257, np.int32), clip=(1100, 1040),
+                max_det=4, single_cls=False)
+
+
+def bound_case():
+    """The LDS layout at its upper bound: max_det 4096, all rows kept, 5 labels.  The first five detections are copies of the labels, the rest
+    far-away boxes of a class no label has."""
+    lab = _grid_labels(5)
+    rng = np.random.default_rng(0)
+    rows = np.zeros((1, 4096, 7), np.float32)
+    rows[0, :, :5] = np.stack((rng.uniform(500, 1000, 4096), rng.uniform(500, 1000, 4096), rng.uniform(8, 60, 4096), rng.uniform(6, 40, 4096),
+                               rng.uniform(-0.7, 2.3, 4096)), 1)
+    rows[0, :, 5], rows[0, :, 6] = np.linspace(0.99, 0.01, 4096), 2.0
+    rows[0, :5, :5], rows[0, :5, 6] = lab, (0.0, 1.0, 0.0, 1.0, 0.0)
+    return dict(rows=rows, counts=np.array([4096], np.int32), tbox=lab, tcls=np.array([0.0, 1.0, 0.0, 1.0, 0.0], np.float32), timg=np.zeros(5, np.int32),
+                clip=(1100, 1040), max_det=4096, single_cls=False)
+
+
+def expect64(c):
+    """``rule64`` on a one-image case whose labels are in image order: tp (max_det, T), best_label (max_det,), and the float64 scores of the
+    same-class pairs."""
+    cnt = int(c["counts"][0])
+    i64 = probiou64(c["tbox"], clip_xywhr(c["rows"][0, :cnt, :5], *c["clip"]))
+    same = c["tcls"][:, None] == c["rows"][0, :cnt, 6][None]
+    tp, best, _ = rule64(np.where(same, i64, 0.0))
+    return tp, best, i64[same]
+
+
 def rule64(m, iouv=IOUV):
     """The restated match rule on a class-masked (L, D) matrix (NaN: never the best): tp (D, T) bool, best (D,) position among the L labels
     (-1: none), biou (D,)."""

@@ -21,7 +21,7 @@ from oracle import drone_yolo_oracle as O
 from tests import _obbval_util as V
 from tests._util import golden, load_yaml, meta, split_rows
 from tests.test_model_gpu import RTOL as _RTOL
-from tests.test_obbval_host import MATCH_NAMES, e2e_fixture, match_case, unpack
+from tests.test_obbval_host import MATCH_NAMES, e2e_fixture, match_case, seedless_case, unpack
 
 pytestmark = pytest.mark.gpu
 X2 = H.F16X2
@@ -123,6 +123,21 @@ def test_val_match_rotated_replayed_from_a_captured_graph(name, device):
     assert all(torch.equal(a.view(torch.uint8), b.view(torch.uint8)) for a, b in zip(outs, eager)), "the replay did not give the new rows' result"
     if c["counts"].max() > 1 and name != "degenerate":
         assert not torch.equal(first[1], eager[1]), "the new rows must score differently"
+
+
+@pytest.mark.parametrize("name", ["full_stage", "bound"])
+def test_val_match_rotated_full_stage_and_layout_bound(name, device):
+    """A stage filled exactly to capacity (257 labels at a step of 256) and the largest dynamic LDS request (max_det 4096: 36 bytes per
+    detection), against the float64 rule; the outputs start poisoned, so every element is written."""
+    c, tp64, best64 = seedless_case(name)
+    tp, bi, bl, clean = _guarded(c, device)
+    assert H.last_kernel_name() == "val_match_rotated_kernel" and clean
+    tpn, bin_, bln = tp.cpu().numpy()[0], bi.cpu().numpy()[0], bl.cpu().numpy()[0]
+    assert np.array_equal(bln, best64), "best_label is not the float64 argmax"
+    assert np.array_equal(tpn, tp64.astype(np.uint8))
+    hit = tp64.any(1)
+    dup = np.zeros_like(hit) if name == "bound" else np.arange(4) == 3  # (the second copy scores as the first and loses the label)
+    assert (bin_[hit | dup] > 0.99).all() and not bin_[~(hit | dup)].any()
 
 
 def test_no_labels_and_argument_checks(device):

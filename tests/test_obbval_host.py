@@ -108,6 +108,30 @@ def test_match_cases_are_what_they_are_for(g):
     assert c["single_cls"] and not c["tcls"].any() and e["tp64"].any() and np.array_equal(c["rows"], match_case("few")[0]["rows"])
 
 
+@functools.lru_cache(maxsize=None)
+def seedless_case(name):
+    """(inputs, float64 tp, float64 best label) of the full-stage / layout-bound cases: computed once, shared, not modified."""
+    c = dict(full_stage=V.full_stage_case, bound=V.bound_case)[name]()
+    tp, best, scores = V.expect64(c)
+    assert ((scores > 0.99) | (scores < 0.01)).all(), "every threshold is decided by a margin thousands of times the recorded M"
+    return c, tp, best
+
+
+def test_full_stage_and_bound_cases_are_what_they_are_for():
+    c, tp, best = seedless_case("full_stage")
+    assert len(c["tbox"]) == 257 and not c["timg"].any() and (c["tcls"] == 1).all() and c["counts"].tolist() == [4] and c["max_det"] == 4
+    d = c["tbox"][:, None, :2] - c["tbox"][None, :, :2]
+    assert np.sqrt((d ** 2).sum(-1))[~np.eye(257, dtype=bool)].min() >= 60 and len(np.unique(c["tbox"][:, 4])) > 3
+    assert best.tolist() == [0, 255, 256, 256] and tp[:3].all() and not tp[3].any()
+    c, tp, best = seedless_case("bound")
+    assert c["max_det"] == 4096 and c["counts"].tolist() == [4096] and len(c["tbox"]) == 5 and not np.isin(c["rows"][0, 5:, 6], c["tcls"]).any()
+    assert best[:5].tolist() == [0, 1, 2, 3, 4] and tp[:5].all() and not tp[5:].any()
+    v = OBBValidator()
+    for name in ("full_stage", "bound"):  # the validator's host arithmetic (fp32) gives the same verdicts
+        c, tp, _ = seedless_case(name)
+        assert np.array_equal(v.host_match(c["rows"][0], c["tbox"], c["tcls"], *c["clip"]), tp)
+
+
 @pytest.mark.parametrize("name", list(V.NMS_CASES))
 def test_nms_fixture_conditions_hold_at_the_stored_seed(g, name):
     counts, anchors, nc, _, kw, _ = V.NMS_CASES[name]

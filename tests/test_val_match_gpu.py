@@ -57,17 +57,23 @@ def batch_case(seed=11, COUNTS=COUNTS, NLAB=NLAB, MAX_DET=MAX_DET):
     tbox, tcls, timg = np.concatenate(tbox), np.concatenate(tcls), np.concatenate(timg)
     perm = rng.permutation(len(tbox))  # batch layout: labels belong to images by value, in no order
     tbox, tcls, timg = tbox[perm], tcls[perm], timg[perm]
-    exp_tp = np.zeros((len(COUNTS), MAX_DET, len(IOUV)), bool)
-    exp_iou = np.zeros((len(COUNTS), MAX_DET), np.float32)
-    exp_lab = np.full((len(COUNTS), MAX_DET), -1, np.int64)
+    return dict(rows=rows, counts=np.array(COUNTS, np.int32), tbox=tbox, tcls=tcls, timg=timg, **host_expect(rows, COUNTS, tbox, tcls, timg))
+
+
+def host_expect(rows, counts, tbox, tcls, timg, clip=(CLIP_W, CLIP_H)):
+    """The host's tp / best_iou / best_label (``box_iou`` + ``match_predictions`` on the clipped rows) and the class-masked IoU of every image."""
+    n, max_det = rows.shape[:2]
+    exp_tp = np.zeros((n, max_det, len(IOUV)), bool)
+    exp_iou = np.zeros((n, max_det), np.float32)
+    exp_lab = np.full((n, max_det), -1, np.int64)
     masked = []
-    for i, cnt in enumerate(COUNTS):
+    for i, cnt in enumerate(counts):
         where = np.nonzero(timg == i)[0]
         if cnt == 0 or len(where) == 0:
             continue
         pn = rows[i, :cnt].copy()
-        pn[:, [0, 2]] = pn[:, [0, 2]].clip(0, CLIP_W)
-        pn[:, [1, 3]] = pn[:, [1, 3]].clip(0, CLIP_H)
+        pn[:, [0, 2]] = pn[:, [0, 2]].clip(0, clip[0])
+        pn[:, [1, 3]] = pn[:, [1, 3]].clip(0, clip[1])
         iou = box_iou(tbox[where], pn[:, :4])
         exp_tp[i, :cnt] = match_predictions(pn[:, 5], tcls[where], iou, IOUV)
         m = iou * (tcls[where][:, None] == pn[:, 5])
@@ -75,7 +81,36 @@ def batch_case(seed=11, COUNTS=COUNTS, NLAB=NLAB, MAX_DET=MAX_DET):
         exp_iou[i, :cnt] = m.max(0)
         exp_lab[i, :cnt] = where[m.argmax(0)]
         masked.append(m)
-    return dict(rows=rows, counts=np.array(COUNTS, np.int32), tbox=tbox, tcls=tcls, timg=timg, tp=exp_tp, best_iou=exp_iou, best_label=exp_lab, masked=masked)
+    return dict(tp=exp_tp, best_iou=exp_iou, best_label=exp_lab, masked=masked)
+
+
+@functools.lru_cache(maxsize=None)
+def full_stage_case():
+    """A stage filled exactly to capacity: 513 labels of one class, all of image 0 and in order (the first step stages 512 entries, the second
+    one), disjoint 8 x 8 squares on a grid; detections = exact copies of labels 0, 511 and 512."""
+    l = np.arange(513)
+    x, y = 4.0 + 12.0 * (l % 23), 4.0 + 12.0 * (l // 23)
+    tbox = np.stack((x, y, x + 8, y + 8), 1).astype(np.float32)
+    rows = np.full((1, 4, 6), 7e5, np.float32)
+    rows[0, :3, :4], rows[0, :3, 4], rows[0, :3, 5] = tbox[[0, 511, 512]], (0.9, 0.8, 0.7), 1.0
+    c = dict(rows=rows, counts=np.array([3], np.int32), tbox=tbox, tcls=np.ones(513, np.float32), timg=np.zeros(513, np.int64))
+    return dict(c, **host_expect(rows, c["counts"], tbox, c["tcls"], c["timg"]))
+
+
+@functools.lru_cache(maxsize=None)
+def bound_case():
+    """The LDS layout at its upper bound: max_det 4096 (32 bytes per detection), all rows kept, 5 labels.  The first five detections are
+    copies of the labels, the rest far-away boxes of a class no label has."""
+    rng = np.random.default_rng(0)
+    x = 10.0 + 40.0 * np.arange(5)
+    tbox = np.stack((x, np.full(5, 10.0), x + 30, np.full(5, 40.0)), 1).astype(np.float32)
+    tcls = np.array([0, 1, 0, 1, 2], np.float32)
+    rows = np.zeros((1, 4096, 6), np.float32)
+    rows[0, :, :4] = np.concatenate((rng.uniform(300, 400, (4096, 2)), rng.uniform(420, 500, (4096, 2))), 1)
+    rows[0, :, 4], rows[0, :, 5] = np.linspace(0.99, 0.01, 4096), 7.0
+    rows[0, :5, :4], rows[0, :5, 5] = tbox, tcls
+    c = dict(rows=rows, counts=np.array([4096], np.int32), tbox=tbox, tcls=tcls, timg=np.zeros(5, np.int64))
+    return dict(c, **host_expect(rows, c["counts"], tbox, tcls, c["timg"]))
 
 
 def test_batch_case_is_as_intended():
@@ -91,6 +126,15 @@ def test_batch_case_is_as_intended():
         if m.shape[0] > 1:
             top2 = np.sort(m, 0)[-2:]
             assert not ((top2[1] >= 0.5) & (top2[0] == top2[1])).any()
+
+
+def test_full_stage_and_bound_cases_are_as_intended():
+    c = full_stage_case()
+    assert len(c["tbox"]) == 513 and not c["timg"].any() and (c["masked"][0] == 1).sum() == 3  # disjoint squares: one label per detection
+    assert c["best_label"][0].tolist() == [0, 511, 512, -1] and c["tp"][0, :3].all() and (c["best_iou"][0, :3] == 1).all()
+    c = bound_case()
+    assert c["rows"].shape == (1, 4096, 6) and not np.isin(c["rows"][0, 5:, 5], c["tcls"]).any()
+    assert c["tp"][0, :5].all() and not c["tp"][0, 5:].any() and c["best_label"][0, :5].tolist() == [0, 1, 2, 3, 4] and not c["best_iou"][0, 5:].any()
 
 
 def nms_buffers(rows, counts, device):
@@ -129,6 +173,24 @@ def test_kernel_with_more_detections_than_threads(device):
         assert np.array_equal(tp[i, :cnt].astype(bool), c["tp"][i, :cnt]), f"image {i}"
         assert not tp[i, cnt:].any() and not bi[i, cnt:].any() and (bl[i, cnt:] == -1).all()
     assert np.array_equal(bi.view(np.uint32), c["best_iou"].view(np.uint32)) and np.array_equal(bl, c["best_label"])
+
+
+@pytest.mark.gpu
+def test_kernel_with_a_stage_filled_to_capacity(device):
+    c = full_stage_case()
+    tp, bi, bl = run(device, c["rows"], c["counts"], c["tbox"], c["tcls"], c["timg"])
+    assert bl[0].tolist() == [0, 511, 512, -1] and np.array_equal(bl, c["best_label"])
+    assert np.array_equal(bi.view(np.uint32), c["best_iou"].view(np.uint32)), "best_iou is not bit-equal to the host's"
+    assert np.array_equal(tp.astype(bool), c["tp"]) and tp[0, :3].all() and not tp[0, 3].any()
+
+
+@pytest.mark.gpu
+def test_kernel_with_the_lds_layout_at_its_bound(device):
+    c = bound_case()
+    tp, bi, bl = run(device, c["rows"], c["counts"], c["tbox"], c["tcls"], c["timg"])
+    assert tp.shape == (1, 4096, 10) and np.array_equal(tp.astype(bool), c["tp"]) and tp[0, :5].all() and not tp[0, 5:].any()
+    assert np.array_equal(bi.view(np.uint32), c["best_iou"].view(np.uint32)) and not bi[0, 5:].any()
+    assert np.array_equal(bl, c["best_label"]) and bl[0, :5].tolist() == [0, 1, 2, 3, 4]
 
 
 def rows_of(tp):

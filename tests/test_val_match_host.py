@@ -63,3 +63,27 @@ def test_device_match_is_a_checked_argument_and_on_by_default():
         get_cfg(dict(device_match=1))
     assert DetectionValidator().device_match is True and DetectionValidator(get_cfg()).device_match is True
     assert DetectionValidator(dict(device_match=False, unknown_key=1)).device_match is False
+
+
+def test_label_preparation_on_cpu_tensors_has_the_bits_of_the_numpy_clip():
+    """``DetectionValidator._labels`` (the one label preparation of the device loop and the host loop) on CPU tensors against the numpy clip
+    the detection host loop used: ``xywh2xyxy * (w, h, w, h)``, then ``.clip``; boxes that stick out of the image included."""
+    import numpy as np
+    import torch
+
+    from drone_yolo_amd.engine.validator import DetectionValidator, SegmentationValidator
+    from drone_yolo_amd.utils import ops
+
+    w, h = 640, 384
+    g = torch.Generator().manual_seed(3)
+    bb = torch.cat((torch.rand((40, 2), generator=g) * 1.2 - 0.1, torch.rand((40, 2), generator=g) * 0.6), 1)  # centres in [-0.1, 1.1]
+    bb[0] = torch.tensor((0.5, 0.5, 2.0, 2.0))  # larger than the image
+    lim = torch.tensor((w, h, w, h), dtype=torch.float32)
+    old = (ops.xywh2xyxy(bb) * torch.tensor((w, h, w, h), dtype=torch.float32)).numpy()
+    assert (old < 0).any() and (old[:, 2] > w).any() and (old[:, 3] > h).any()
+    old[:, [0, 2]] = old[:, [0, 2]].clip(0, w)
+    old[:, [1, 3]] = old[:, [1, 3]].clip(0, h)
+    for v in (DetectionValidator(), SegmentationValidator()):
+        new = v._labels(bb, w, h, lim).numpy()
+        assert new.dtype == np.float32 and np.array_equal(new.view(np.uint32), old.view(np.uint32))
+    assert tuple(DetectionValidator()._labels(bb[:0], w, h, lim).shape) == (0, 4)
