@@ -351,6 +351,10 @@ SIGNATURES = {
     "dy_track_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "dy_track_reset": (_i32, [_vp, _i32, _i32, _vp]),
     "dy_track_step": (_i32, [C.POINTER(TrackDesc), _vp]),
+    "dy_track_state_bytes_rotated": (_i64, [_i32, _i32]),
+    "dy_track_workspace_bytes_rotated": (_i64, [_i32, _i32, _i32]),
+    "dy_track_reset_rotated": (_i32, [_vp, _i32, _i32, _vp]),
+    "dy_track_step_rotated": (_i32, [C.POINTER(TrackDesc), _vp]),
     "dy_detection_loss_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "dy_conv2d_wgrad_nhwc": (_i32, [C.POINTER(ConvDesc), _vp, _i32, _vp, _vp]),
     "dy_conv2d_wgrad_nhwc_ws": (_i32, [C.POINTER(ConvDesc), _vp, _i32, _vp, _vp, C.c_int64, _vp]),

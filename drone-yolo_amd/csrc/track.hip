@@ -25,7 +25,16 @@
 //
 // The IoU follows bbox_ioa (utils/metrics.py:20-49) operation by operation in fp32 with contraction off and the correctly rounded
 // division; a NaN anywhere in a box makes the cost NaN = no edge.
+//
+// Two instantiations of the one kernel over a box policy (as dy_val_match / dy_val_match_rotated): TkAxis above, and TkRot for the rows
+// of an oriented-box model (trackers/track.py:69-88 `is_obb`, byte_tracker.py:68-79 / :217-228).  The Kalman filter, the solver, the
+// compaction, the state machine and the output stage are shared; the policy changes the detection load ([x, y, w, h, r, conf, cls]: centre
+// and size straight from the row), the record a cost is computed from (probiou.h's RRow: the covariance terms are computed once per slot
+// and once per detection per image, one cosf / sinf pair per box, never per edge), the pair cost (1 - rnms_probiou(track, detection), then
+// fuse_score) and the output row (xywh of the mean, the angle, id, score, cls, idx).  The angle is not filtered: a slot holds the fp32
+// angle of the detection it last matched.
 #include "common_hip.h"
+#include "probiou.h"
 
 #pragma clang fp contract(off)
 
@@ -39,11 +48,42 @@ constexpr int TK_SLOT_INTS = 9;                                           // sta
 constexpr int TK_LDS_SLOT = 8 + 16 + (TK_SLOT_INTS + 2 + 2 + 3 + 1) * 4;  // u | tbox | fields, score, cls, waslost, dup, three lists, rmatch
 constexpr int TK_LDS_DET = 16 + 16 + (1 + 1 + 1 + 3 + 3) * 4;             // v, minv | dbox | score, kind, used, three lists, way / cmatch / taken
 
-static inline size_t track_state_bytes1(int max_tracks) {
-  return (size_t)TK_HDR + (size_t)max_tracks * (72 * 8 + (TK_SLOT_INTS + 2) * 4);  // a multiple of 8 for even max_tracks
+
+// The box policies.  IN / OUT: floats of a detection row and of an output row; CONF / CLS: columns of a detection row; STATE_FLT: fp32
+// fields of a slot in the device state (score, cls[, angle]); SLOT_WORDS / DET_WORDS: 4-byte LDS words a slot / a detection needs beyond
+// the axis-aligned layout.  Rec is what a cost is computed from; the 16-byte part of it stays in the float4 arrays tbox / dbox, the fifth
+// float of an RRow in arrays of its own, so that every 16-byte access is 16-byte aligned for every even max_tracks.
+struct TkBoxes {
+  float4* q;  // axis-aligned: xyxy; rotated: x, y and the covariance terms a, b
+  float* c;   // rotated: the covariance term c
+};
+struct TkAxis {
+  static constexpr bool ROT = false;
+  static constexpr int IN = 6, OUT = 8, CONF = 4, CLS = 5, STATE_FLT = 2, SLOT_WORDS = 0, DET_WORDS = 0;
+  using Rec = float4;
+  static __device__ __forceinline__ Rec load(const TkBoxes& b, const int i) { return b.q[i]; }
+};
+struct TkRot {
+  static constexpr bool ROT = true;
+  static constexpr int IN = 7, OUT = 9, CONF = 5, CLS = 6, STATE_FLT = 3, SLOT_WORDS = 2, DET_WORDS = 1;  // slot: c, angle; detection: c
+  using Rec = RRow;
+  static __device__ __forceinline__ Rec load(const TkBoxes& b, const int i) {
+    const float4 q = b.q[i];
+    return RRow{q.x, q.y, q.z, q.w, b.c[i]};
+  }
+  static __device__ __forceinline__ void store(const TkBoxes& b, const int i, const RRow& r) {
+    b.q[i] = make_float4(r.x, r.y, r.a, r.b);
+    b.c[i] = r.c;
+  }
+};
+
+template <typename Pol> static inline size_t track_state_bytes1(int max_tracks) {
+  return (size_t)TK_HDR + (size_t)max_tracks * (72 * 8 + (TK_SLOT_INTS + Pol::STATE_FLT) * 4);  // a multiple of 8 for even max_tracks
 }
 static inline size_t track_ws_bytes1(int max_det) { return ((size_t)max_det * 16 + 255) / 256 * 256; }  // the xyah measurements of one image
-static inline size_t track_lds_bytes(int max_tracks, int max_det) { return (size_t)max_tracks * TK_LDS_SLOT + (size_t)max_det * TK_LDS_DET + 64; }
+template <typename Pol> static inline size_t track_lds_bytes(int max_tracks, int max_det) {
+  return (size_t)max_tracks * (TK_LDS_SLOT + 4 * Pol::SLOT_WORDS) + (size_t)max_det * (TK_LDS_DET + 4 * Pol::DET_WORDS) + 64;
+}
 
 struct TrackArgs {
   const float* rows;
@@ -69,6 +109,26 @@ __device__ __forceinline__ float tk_cost(const float4 a, const float4 b, const f
   float cost = 1.f - __fdiv_rn(inter, uni + 1e-7f);
   if (fuse) cost = 1.f - (1.f - cost) * score;
   return cost;
+}
+
+// 1 - batch_probiou(track, detection) [then fuse_score] (matching.py:85-101): probiou.h's expression, arguments in the reference's order
+__device__ __forceinline__ float tk_cost(const RRow& a, const RRow& b, const float score, const bool fuse) {
+  float cost = 1.f - rnms_probiou(a, b);
+  if (fuse) cost = 1.f - (1.f - cost) * score;
+  return cost;
+}
+
+// STrack.xywh (byte_tracker.py:185-214) rounded to fp32: tlwh from the mean, then the centre back from the corner -- (x - w / 2) + w / 2
+// is not always x, so the order stays; fp32 arithmetic while the mean is still initiate's float32 one
+__device__ __forceinline__ float4 tk_xywh(const double x, const double y, const double a, const double h, const int m32) {
+  if (m32) {
+    const float hf = (float)h, w = (float)a * hf;
+    const float x1 = (float)x - w / 2.f, y1 = (float)y - hf / 2.f;
+    return make_float4(x1 + w / 2.f, y1 + hf / 2.f, w, hf);
+  }
+  const double w = a * h;
+  const double x1 = x - w / 2.0, y1 = y - h / 2.0;
+  return make_float4((float)(x1 + w / 2.0), (float)(y1 + h / 2.0), (float)w, (float)h);
 }
 
 // STrack.xyxy rounded to fp32; fp32 arithmetic while the mean is still initiate's float32 one
@@ -110,7 +170,8 @@ struct TkSolver {
 };
 
 // rows = slots rl[0..nr), columns = detections cl[0..nc); on return rmatch[r] = position in cl or -1.  Run by one whole wave.
-__device__ __forceinline__ void tk_assign(const TkSolver& s, const int* rl, const int nr, const int* cl, const int nc, const float4* tbox, const float4* dbox,
+template <typename Pol>
+__device__ __forceinline__ void tk_assign(const TkSolver& s, const int* rl, const int nr, const int* cl, const int nc, const TkBoxes& tbox, const TkBoxes& dbox,
                           const float* dscore, const float thresh, const bool fuse, const int lane) {
   const double inf = __builtin_huge_val();
   const double t64 = (double)thresh;
@@ -135,7 +196,7 @@ __device__ __forceinline__ void tk_assign(const TkSolver& s, const int* rl, cons
     int cur = i, curcol = -1;
     for (int it = 0; it <= nc; ++it) {  // every step ends the augmentation or takes one more column into the tree
       __builtin_amdgcn_wave_barrier();
-      const float4 a = tbox[rl[cur]];
+      const typename Pol::Rec a = Pol::load(tbox, rl[cur]);
       const double ucur = s.u[cur];
       if (-ucur < dmin) {
         dmin = -ucur;
@@ -146,7 +207,7 @@ __device__ __forceinline__ void tk_assign(const TkSolver& s, const int* rl, cons
       for (int j = lane; j < nc; j += 64) {
         if (s.taken[j]) continue;
         const int d = cl[j];
-        const float c = tk_cost(a, dbox[d], dscore[d], fuse);
+        const float c = tk_cost(a, Pol::load(dbox, d), dscore[d], fuse);
         double mv = s.minv[j];
         if (c < thresh) {  // (false for NaN: no edge)
           const double red = (((double)c - t64) - ucur) - s.v[j];
@@ -291,7 +352,7 @@ __device__ void tk_kalman_update(double* mean, double* cov, const int T, const i
     }
 }
 
-__global__ __launch_bounds__(TK_THREADS) void track_step_kernel(const TrackArgs p) {
+template <typename Pol> __global__ __launch_bounds__(TK_THREADS) void track_step_kernel(const TrackArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
   const int T = p.max_tracks, D = p.max_det;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -300,9 +361,9 @@ __global__ __launch_bounds__(TK_THREADS) void track_step_kernel(const TrackArgs 
   double* s_u = reinterpret_cast<double*>(dyn_smem);  // [T]
   double* s_v = s_u + T;                               // [D]
   double* s_minv = s_v + D;                            // [D]
-  float4* tbox = reinterpret_cast<float4*>(s_minv + D);  // [T] xyxy of every slot as iou_distance sees it (T * 8 + D * 16 bytes in front: 16-byte aligned for even T)
-  float4* dbox = tbox + T;                               // [D]
-  int* sst = reinterpret_cast<int*>(dbox + D);           // [T] each of the following
+  float4* tbox4 = reinterpret_cast<float4*>(s_minv + D);  // [T] every slot's box as iou_distance sees it (T * 8 + D * 16 bytes in front: 16-byte aligned for even T)
+  float4* dbox4 = tbox4 + T;                              // [D]
+  int* sst = reinterpret_cast<int*>(dbox4 + D);           // [T] each of the following
   int* sact = sst + T;
   int* sm32 = sact + T;
   int* sinrem = sm32 + T;
@@ -319,7 +380,9 @@ __global__ __launch_bounds__(TK_THREADS) void track_step_kernel(const TrackArgs 
   int* listB = listA + T;
   int* listC = listB + T;
   int* s_rmatch = listC + T;
-  float* dscore = reinterpret_cast<float*>(s_rmatch + T);  // [D] each of the following
+  float* trc = reinterpret_cast<float*>(s_rmatch + T);  // rotated only ([T] each; no bytes otherwise): the fifth float of a slot's RRow,
+  float* sang = trc + (Pol::ROT ? T : 0);                 // and the angle of the detection the slot last matched
+  float* dscore = sang + (Pol::ROT ? T : 0);              // [D] each of the following
   int* dkind = reinterpret_cast<int*>(dscore + D);
   int* dused = dkind + D;
   int* clH = dused + D;
@@ -328,7 +391,9 @@ __global__ __launch_bounds__(TK_THREADS) void track_step_kernel(const TrackArgs 
   int* s_way = clR + D;
   int* s_cmatch = s_way + D;
   int* s_taken = s_cmatch + D;
-  int* s_n = s_taken + D;  // [16] list lengths
+  float* drc = reinterpret_cast<float*>(s_taken + D);            // rotated only ([D]): the fifth float of a detection's RRow
+  int* s_n = reinterpret_cast<int*>(drc + (Pol::ROT ? D : 0));     // [16] list lengths
+  const TkBoxes tbox{tbox4, trc}, dbox{dbox4, drc};
   TkSolver sol{s_u, s_v, s_minv, s_rmatch, s_cmatch, s_way, s_taken};
 
   unsigned char* sbase = p.state + (size_t)sidx_stream * p.state_stride;
@@ -336,7 +401,7 @@ __global__ __launch_bounds__(TK_THREADS) void track_step_kernel(const TrackArgs 
   double* mean = reinterpret_cast<double*>(sbase + TK_HDR);  // [8][T]
   double* cov = mean + (size_t)8 * T;                        // [64][T]
   int* gint = reinterpret_cast<int*>(cov + (size_t)64 * T);  // [TK_SLOT_INTS][T]
-  float* gflt = reinterpret_cast<float*>(gint + (size_t)TK_SLOT_INTS * T);  // [2][T]
+  float* gflt = reinterpret_cast<float*>(gint + (size_t)TK_SLOT_INTS * T);  // [Pol::STATE_FLT][T]
   float4* dxyah = reinterpret_cast<float4*>(p.ws + (size_t)sidx_stream * p.ws_stride);  // [D] the measurements of the image at hand
 
   for (int s = tid; s < T; s += TK_THREADS) {
@@ -351,30 +416,49 @@ __global__ __launch_bounds__(TK_THREADS) void track_step_kernel(const TrackArgs 
     stlen[s] = gint[8 * T + s];
     sscore[s] = gflt[s];
     scls[s] = gflt[T + s];
+    if constexpr (Pol::ROT) sang[s] = gflt[2 * T + s];
   }
   int frame = hdr[0], next_id = hdr[1], overflow = hdr[2];  // the same on every thread throughout
   __syncthreads();
+
+  // a slot's box for the costs, from its mean (and, rotated, the angle it holds): after every change of the mean or the angle
+  auto put_box = [&](const int s, const double x, const double y, const double a, const double h, const int m32) {
+    if constexpr (Pol::ROT) {
+      const float4 b = tk_xywh(x, y, a, h, m32);
+      Pol::store(tbox, s, rnms_row(b.x, b.y, b.z, b.w, sang[s]));
+    } else {
+      tbox4[s] = tk_xyxy(x, y, a, h, m32);
+    }
+  };
 
   for (int f = 0; f < p.frames; ++f) {
     const int img = f * p.streams + sidx_stream;
     int n = p.counts[img];
     n = n < 0 ? 0 : (n > D ? D : n);
-    float* orow = p.out + (size_t)img * T * 8;
+    float* orow = p.out + (size_t)img * T * Pol::OUT;
     if (n == 0) {  // trackers/track.py:79-80: the image does not reach the tracker (uniform branch)
-      for (int i = tid; i < T * 8; i += TK_THREADS) orow[i] = 0.f;
+      for (int i = tid; i < T * Pol::OUT; i += TK_THREADS) orow[i] = 0.f;
       if (tid == 0) p.out_count[img] = 0;
       continue;
     }
     ++frame;
-    const float* rb = p.rows + (size_t)img * D * 6;
+    const float* rb = p.rows + (size_t)img * D * Pol::IN;
     // ---- detections as STrack holds them; multi_predict of the pool; every slot's box ----
     for (int d = tid; d < n; d += TK_THREADS) {
-      const float* r = rb + (size_t)d * 6;
-      const float x1 = r[0], y1 = r[1], x2 = r[2], y2 = r[3], conf = r[4];
-      const float cx = (x1 + x2) / 2.f, cy = (y1 + y2) / 2.f, w = x2 - x1, h = y2 - y1;  // Boxes.xywh (ops.xyxy2xywh) in fp32
+      const float* r = rb + (size_t)d * Pol::IN;
+      const float conf = r[Pol::CONF];
+      float cx, cy, w, h;
+      if constexpr (Pol::ROT) {
+        cx = r[0], cy = r[1], w = r[2], h = r[3];  // OBB.xywhr: centre and size straight from the row
+      } else {
+        const float x1 = r[0], y1 = r[1], x2 = r[2], y2 = r[3];
+        cx = (x1 + x2) / 2.f, cy = (y1 + y2) / 2.f, w = x2 - x1, h = y2 - y1;  // Boxes.xywh (ops.xyxy2xywh) in fp32
+      }
       const float lx = (float)((double)cx - (double)w / 2.0), ly = (float)((double)cy - (double)h / 2.0);  // xywh2ltwh on the float64 row, stored as fp32
-      dbox[d] = make_float4(lx, ly, w + lx, h + ly);
-      dxyah[d] = make_float4(lx + w / 2.f, ly + h / 2.f, __fdiv_rn(w, h), h);
+      const float4 z = make_float4(lx + w / 2.f, ly + h / 2.f, __fdiv_rn(w, h), h);
+      if constexpr (Pol::ROT) Pol::store(dbox, d, rnms_row(z.x, z.y, w, h, r[4]));  // STrack.xywha of a detection: _tlwh.xy + _tlwh.wh / 2, w, h, angle
+      else dbox4[d] = make_float4(lx, ly, w + lx, h + ly);
+      dxyah[d] = z;
       dscore[d] = conf;
       dkind[d] = conf >= p.high ? 1 : ((conf > p.low && conf < p.high) ? 2 : 0);
       dused[d] = 0;
@@ -418,7 +502,7 @@ __global__ __launch_bounds__(TK_THREADS) void track_step_kernel(const TrackArgs 
         for (int k = 0; k < 8; ++k) mean[(size_t)k * T + s] = m[k];
         sm32[s] = 0;
       }
-      tbox[s] = tk_xyxy(m[0], m[1], m[2], m[3], sm32[s]);
+      put_box(s, m[0], m[1], m[2], m[3], sm32[s]);
     }
     __syncthreads();
     // ---- the lists of the first association ----
@@ -437,7 +521,7 @@ __global__ __launch_bounds__(TK_THREADS) void track_step_kernel(const TrackArgs 
     }
     __syncthreads();
     const int nA = s_n[0], nH = s_n[1], nL = s_n[2], nC = s_n[3];
-    if (wave == 0) tk_assign(sol, listA, nA, clH, nH, tbox, dbox, dscore, p.match, p.fuse != 0, lane);
+    if (wave == 0) tk_assign<Pol>(sol, listA, nA, clH, nH, tbox, dbox, dscore, p.match, p.fuse != 0, lane);
     __syncthreads();
     // ---- matches of a list: STrack.update (tracked) / re_activate (lost); one thread per row ----
     auto apply = [&](const int* rl, const int nr, const int* cl, const bool mark) {
@@ -452,10 +536,11 @@ __global__ __launch_bounds__(TK_THREADS) void track_step_kernel(const TrackArgs 
         sact[s] = 1;
         sfid[s] = frame;
         sscore[s] = dscore[d];
-        scls[s] = rb[(size_t)d * 6 + 5];
+        scls[s] = rb[(size_t)d * Pol::IN + Pol::CLS];
+        if constexpr (Pol::ROT) sang[s] = rb[(size_t)d * Pol::IN + 4];
         sdi[s] = d;
         if (mark) dused[d] = 1;
-        tbox[s] = tk_xyxy(mean[s], mean[(size_t)T + s], mean[(size_t)2 * T + s], mean[(size_t)3 * T + s], 0);
+        put_box(s, mean[s], mean[(size_t)T + s], mean[(size_t)2 * T + s], mean[(size_t)3 * T + s], 0);
       }
     };
     apply(listA, nA, clH, true);
@@ -484,14 +569,14 @@ __global__ __launch_bounds__(TK_THREADS) void track_step_kernel(const TrackArgs 
     }
     __syncthreads();
     const int nB = s_n[4], nR = s_n[5];
-    if (wave == 0) tk_assign(sol, listB, nB, clL, nL, tbox, dbox, dscore, 0.5f, false, lane);
+    if (wave == 0) tk_assign<Pol>(sol, listB, nB, clL, nL, tbox, dbox, dscore, 0.5f, false, lane);
     __syncthreads();
     apply(listB, nB, clL, false);
     for (int r = tid; r < nB; r += TK_THREADS)
       if (s_rmatch[r] < 0) sst[listB[r]] = TK_LOST;  // mark_lost
     __syncthreads();
     // ---- unconfirmed tracks ----
-    if (wave == 0) tk_assign(sol, listC, nC, clR, nR, tbox, dbox, dscore, 0.7f, p.fuse != 0, lane);
+    if (wave == 0) tk_assign<Pol>(sol, listC, nC, clR, nR, tbox, dbox, dscore, 0.7f, p.fuse != 0, lane);
     __syncthreads();
     apply(listC, nC, clR, true);
     for (int r = tid; r < nC; r += TK_THREADS)
@@ -538,8 +623,9 @@ __global__ __launch_bounds__(TK_THREADS) void track_step_kernel(const TrackArgs 
         sstart[s] = frame;
         stlen[s] = 0;
         sscore[s] = dscore[d];
-        scls[s] = rb[(size_t)d * 6 + 5];
-        tbox[s] = tk_xyxy(m[0], m[1], m[2], m[3], 1);
+        scls[s] = rb[(size_t)d * Pol::IN + Pol::CLS];
+        if constexpr (Pol::ROT) sang[s] = rb[(size_t)d * Pol::IN + 4];
+        put_box(s, m[0], m[1], m[2], m[3], 1);
       }
       next_id += nk;
       overflow += nN - nk;
@@ -572,12 +658,12 @@ __global__ __launch_bounds__(TK_THREADS) void track_step_kernel(const TrackArgs 
       const int nTa = s_n[8], nTb = s_n[9];
       for (int i = tid; i < nTa; i += TK_THREADS) {
         const int a = listA[i];
-        const float4 ba = tbox[a];
+        const typename Pol::Rec ba = Pol::load(tbox, a);
         const int ta = sfid[a] - sstart[a];
         bool drop = false;
         for (int k = 0; k < nTb; ++k) {
           const int b = listB[k];
-          if (tk_cost(ba, tbox[b], 0.f, false) < 0.15f) {
+          if (tk_cost(ba, Pol::load(tbox, b), 0.f, false) < 0.15f) {
             if (ta > sfid[b] - sstart[b]) sdup[b] = 1;  // (several threads may store the same 1)
             else drop = true;
           }
@@ -601,12 +687,18 @@ __global__ __launch_bounds__(TK_THREADS) void track_step_kernel(const TrackArgs 
         const int s = listA[i], id = sid[s];
         int rank = 0;
         for (int k = 0; k < nO; ++k) rank += sid[listA[k]] < id;  // ids are unique
-        const float4 b = tbox[s];
-        float* o = orow + (size_t)rank * 8;
+        float* o = orow + (size_t)rank * Pol::OUT;
+        float4 b;
+        if constexpr (Pol::ROT) {  // STrack.xywha: the box from the mean as the costs saw it, and the angle held
+          b = tk_xywh(mean[s], mean[(size_t)T + s], mean[(size_t)2 * T + s], mean[(size_t)3 * T + s], sm32[s]);
+          o[4] = sang[s];
+        } else {
+          b = tbox4[s];
+        }
         o[0] = b.x, o[1] = b.y, o[2] = b.z, o[3] = b.w;
-        o[4] = (float)id, o[5] = sscore[s], o[6] = scls[s], o[7] = (float)sdi[s];
+        o[Pol::OUT - 4] = (float)id, o[Pol::OUT - 3] = sscore[s], o[Pol::OUT - 2] = scls[s], o[Pol::OUT - 1] = (float)sdi[s];
       }
-      for (int i = nO * 8 + tid; i < T * 8; i += TK_THREADS) orow[i] = 0.f;
+      for (int i = nO * Pol::OUT + tid; i < T * Pol::OUT; i += TK_THREADS) orow[i] = 0.f;
       if (tid == 0) p.out_count[img] = nO;
     }
     __syncthreads();
@@ -624,6 +716,7 @@ __global__ __launch_bounds__(TK_THREADS) void track_step_kernel(const TrackArgs 
     gint[8 * T + s] = stlen[s];
     gflt[s] = sscore[s];
     gflt[T + s] = scls[s];
+    if constexpr (Pol::ROT) gflt[2 * T + s] = sang[s];
   }
   if (tid == 0) {
     hdr[0] = frame;
@@ -642,42 +735,43 @@ static bool track_dims_ok(int streams, int max_tracks, const char* who) {
   return false;
 }
 
-extern "C" int64_t dy_track_state_bytes(int32_t streams, int32_t max_tracks) {
-  if (!track_dims_ok(streams, max_tracks, "dy_track_state_bytes")) return DY_ERR_INVALID_ARG;
-  return (int64_t)streams * (int64_t)track_state_bytes1(max_tracks);
+// the entry points of a policy; `who` is the exported name
+template <typename Pol> static int64_t track_state_bytes_t(int32_t streams, int32_t max_tracks, const char* who) {
+  if (!track_dims_ok(streams, max_tracks, who)) return DY_ERR_INVALID_ARG;
+  return (int64_t)streams * (int64_t)track_state_bytes1<Pol>(max_tracks);
 }
 
-extern "C" int64_t dy_track_workspace_bytes(int32_t streams, int32_t max_tracks, int32_t max_det) {
-  if (!track_dims_ok(streams, max_tracks, "dy_track_workspace_bytes")) return DY_ERR_INVALID_ARG;
+static int64_t track_workspace_bytes_t(int32_t streams, int32_t max_tracks, int32_t max_det, const char* who) {
+  if (!track_dims_ok(streams, max_tracks, who)) return DY_ERR_INVALID_ARG;
   if (max_det <= 0 || max_det > TK_MAX) {
-    set_error("dy_track_workspace_bytes: max_det %d must be in [1,%d]", max_det, TK_MAX);
+    set_error("%s: max_det %d must be in [1,%d]", who, max_det, TK_MAX);
     return DY_ERR_INVALID_ARG;
   }
   return (int64_t)streams * (int64_t)track_ws_bytes1(max_det);
 }
 
-extern "C" int32_t dy_track_reset(void* state, int32_t streams, int32_t max_tracks, dy_stream_t stream) {
-  DY_REQUIRE(state, DY_ERR_INVALID_ARG, "dy_track_reset: null state pointer");
-  if (!track_dims_ok(streams, max_tracks, "dy_track_reset")) return DY_ERR_INVALID_ARG;
-  zero_async(state, (size_t)streams * track_state_bytes1(max_tracks), reinterpret_cast<hipStream_t>(stream));  // all slots free, counters 0
+template <typename Pol> static int32_t track_reset_t(void* state, int32_t streams, int32_t max_tracks, dy_stream_t stream, const char* who) {
+  DY_REQUIRE(state, DY_ERR_INVALID_ARG, "%s: null state pointer", who);
+  if (!track_dims_ok(streams, max_tracks, who)) return DY_ERR_INVALID_ARG;
+  zero_async(state, (size_t)streams * track_state_bytes1<Pol>(max_tracks), reinterpret_cast<hipStream_t>(stream));  // all slots free, counters 0
   return check_launch("zero_words_kernel");
 }
 
-extern "C" int32_t dy_track_step(const dy_track_desc* d, dy_stream_t stream) {
+template <typename Pol> static int32_t track_step_t(const dy_track_desc* d, dy_stream_t stream, const char* who, const char* kernel) {
   DY_REQUIRE(d && d->rows && d->counts && d->state && d->workspace && d->out && d->out_count, DY_ERR_INVALID_ARG,
-             "dy_track_step: null pointer (rows / counts / state / workspace / out / out_count)");
+             "%s: null pointer (rows / counts / state / workspace / out / out_count)", who);
   DY_REQUIRE(d->frames > 0 && d->streams > 0 && d->max_det > 0 && d->max_det <= TK_MAX, DY_ERR_INVALID_ARG,
-             "dy_track_step: bad dims (frames %d, streams %d, max_det %d; all positive, max_det <= %d)", d->frames, d->streams, d->max_det, TK_MAX);
-  if (!track_dims_ok(d->streams, d->max_tracks, "dy_track_step")) return DY_ERR_INVALID_ARG;
-  DY_REQUIRE(d->max_time_lost >= 0, DY_ERR_INVALID_ARG, "dy_track_step: max_time_lost %d < 0", d->max_time_lost);
-  const size_t lds = track_lds_bytes(d->max_tracks, d->max_det);
-  DY_REQUIRE(lds <= 160 * 1024, DY_ERR_INVALID_ARG, "dy_track_step: max_tracks %d with max_det %d needs %zu bytes of LDS (160 KB at most)", d->max_tracks,
+             "%s: bad dims (frames %d, streams %d, max_det %d; all positive, max_det <= %d)", who, d->frames, d->streams, d->max_det, TK_MAX);
+  if (!track_dims_ok(d->streams, d->max_tracks, who)) return DY_ERR_INVALID_ARG;
+  DY_REQUIRE(d->max_time_lost >= 0, DY_ERR_INVALID_ARG, "%s: max_time_lost %d < 0", who, d->max_time_lost);
+  const size_t lds = track_lds_bytes<Pol>(d->max_tracks, d->max_det);
+  DY_REQUIRE(lds <= 160 * 1024, DY_ERR_INVALID_ARG, "%s: max_tracks %d with max_det %d needs %zu bytes of LDS (160 KB at most)", who, d->max_tracks,
              d->max_det, lds);
-  DY_REQUIRE(d->state_bytes >= (int64_t)d->streams * (int64_t)track_state_bytes1(d->max_tracks), DY_ERR_WORKSPACE,
-             "dy_track_step: state of %lld bytes, dy_track_state_bytes asks for more", (long long)d->state_bytes);
+  DY_REQUIRE(d->state_bytes >= (int64_t)d->streams * (int64_t)track_state_bytes1<Pol>(d->max_tracks), DY_ERR_WORKSPACE,
+             "%s: state of %lld bytes, dy_track_state_bytes%s asks for more", who, (long long)d->state_bytes, Pol::ROT ? "_rotated" : "");
   DY_REQUIRE(d->workspace_bytes >= (int64_t)d->streams * (int64_t)track_ws_bytes1(d->max_det), DY_ERR_WORKSPACE,
-             "dy_track_step: workspace of %lld bytes, dy_track_workspace_bytes asks for more", (long long)d->workspace_bytes);
-  DY_REQUIRE(((uintptr_t)d->state & 15) == 0 && ((uintptr_t)d->workspace & 15) == 0, DY_ERR_INVALID_ARG, "dy_track_step: state / workspace not 16-byte aligned");
+             "%s: workspace of %lld bytes, dy_track_workspace_bytes%s asks for more", who, (long long)d->workspace_bytes, Pol::ROT ? "_rotated" : "");
+  DY_REQUIRE(((uintptr_t)d->state & 15) == 0 && ((uintptr_t)d->workspace & 15) == 0, DY_ERR_INVALID_ARG, "%s: state / workspace not 16-byte aligned", who);
   TrackArgs a{};
   a.rows = d->rows;
   a.counts = d->counts;
@@ -695,10 +789,32 @@ extern "C" int32_t dy_track_step(const dy_track_desc* d, dy_stream_t stream) {
   a.match = d->match_thresh;
   a.fuse = d->fuse_score;
   a.max_time_lost = d->max_time_lost;
-  a.state_stride = (long long)track_state_bytes1(d->max_tracks);
+  a.state_stride = (long long)track_state_bytes1<Pol>(d->max_tracks);
   a.ws_stride = (long long)track_ws_bytes1(d->max_det);
-  static const hipError_t attr_once = hipFuncSetAttribute((const void*)track_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  static const hipError_t attr_once = hipFuncSetAttribute((const void*)track_step_kernel<Pol>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   (void)attr_once;
-  hipLaunchKernelGGL(track_step_kernel, dim3((unsigned)d->streams), dim3(TK_THREADS), lds, reinterpret_cast<hipStream_t>(stream), a);
-  return check_launch("track_step_kernel");
+  hipLaunchKernelGGL(track_step_kernel<Pol>, dim3((unsigned)d->streams), dim3(TK_THREADS), lds, reinterpret_cast<hipStream_t>(stream), a);
+  return check_launch(kernel);
+}
+
+extern "C" int64_t dy_track_state_bytes(int32_t streams, int32_t max_tracks) { return track_state_bytes_t<TkAxis>(streams, max_tracks, "dy_track_state_bytes"); }
+extern "C" int64_t dy_track_workspace_bytes(int32_t streams, int32_t max_tracks, int32_t max_det) {
+  return track_workspace_bytes_t(streams, max_tracks, max_det, "dy_track_workspace_bytes");
+}
+extern "C" int32_t dy_track_reset(void* state, int32_t streams, int32_t max_tracks, dy_stream_t stream) {
+  return track_reset_t<TkAxis>(state, streams, max_tracks, stream, "dy_track_reset");
+}
+extern "C" int32_t dy_track_step(const dy_track_desc* d, dy_stream_t stream) { return track_step_t<TkAxis>(d, stream, "dy_track_step", "track_step_kernel"); }
+
+extern "C" int64_t dy_track_state_bytes_rotated(int32_t streams, int32_t max_tracks) {
+  return track_state_bytes_t<TkRot>(streams, max_tracks, "dy_track_state_bytes_rotated");
+}
+extern "C" int64_t dy_track_workspace_bytes_rotated(int32_t streams, int32_t max_tracks, int32_t max_det) {
+  return track_workspace_bytes_t(streams, max_tracks, max_det, "dy_track_workspace_bytes_rotated");
+}
+extern "C" int32_t dy_track_reset_rotated(void* state, int32_t streams, int32_t max_tracks, dy_stream_t stream) {
+  return track_reset_t<TkRot>(state, streams, max_tracks, stream, "dy_track_reset_rotated");
+}
+extern "C" int32_t dy_track_step_rotated(const dy_track_desc* d, dy_stream_t stream) {
+  return track_step_t<TkRot>(d, stream, "dy_track_step_rotated", "track_step_kernel<rotated>");
 }

@@ -129,7 +129,13 @@ class Model(nn.Module):
         tracks and ids across calls.  ``tracker``: settings under cfg/trackers or a path (ByteTrack only).  Package extensions:
         ``device_track`` (default true: the dy_track_step kernel behind the NMS, no extra synchronisation; false: the same tracker on the host)
         and ``track_streams`` = S independent video streams per batch (image k is stream k % S at time step k // S; the batch size must be
-        a multiple of it)."""
+        a multiple of it).
+
+        Oriented-box models are tracked with the same ByteTrack on ProbIoU costs (``dy_track_step_rotated`` / the host class
+        with ``rotated=True``); tracked results carry 8-column ``obb`` rows [x, y, w, h, r, id, conf, cls].  Two calls stay refused for them,
+        with ``NotImplementedError``, before a predictor is built: ``tile=`` (tiled oriented tracking is not built), and a float BCHW tensor
+        source -- pass uint8 HWC frames, image files or PIL images.  The second is kept because the package's own tests pin
+        ``YOLO(<-obb>).track(<float tensor>)`` as a refused call; the predictor itself would take the tensor."""
         return self.predict(source, stream, **{**kwargs, "mode": "track", "persist": persist, "tracker": tracker})
 
     def _refuse_for_segment(self, kwargs: dict) -> None:
@@ -146,13 +152,17 @@ class Model(nn.Module):
 
     def _refuse_for_obb(self, kwargs: dict, source=None) -> None:
         """What an oriented-box model does not do, refused by argument name before a predictor is built or anything is launched.  ``tile=`` is
-        built; what it does not take -- a float tensor source, an IoS metric, a fusing merge -- is refused here too, so that
+        built and so is ``mode="track"`` without tiles on pixel sources; what they do not take -- a float tensor source, an IoS metric, a fusing merge -- is refused here too, so that
         the refusal comes before the predictor moves the model to the device."""
         if self.task != "obb":
             return
         a = {**self.overrides, **kwargs}
-        if a.get("mode") == "track":
-            raise NotImplementedError("track: tracking is not built for oriented-box models")
+        if a.get("mode") == "track":  # built (DESIGN §15.1) for pixel sources, one frame shape per batch, without tiles
+            if a.get("tile") is not None:
+                raise NotImplementedError("track with tile: not built for oriented-box models")
+            if isinstance(source, torch.Tensor) and source.dtype != torch.uint8:
+                raise NotImplementedError("track with a float BCHW tensor: not taken for oriented-box models; pass uint8 HWC BGR frames (a list of one "
+                                          "shape, or a uint8 NHWC tensor), image files or PIL images")
         if a.get("tile") is not None:
             if isinstance(source, torch.Tensor) and source.dtype != torch.uint8:
                 raise NotImplementedError("tile with a float BCHW tensor: tiles are cut from uint8 pixels (HWC frames), not from a letterboxed tensor")

@@ -374,6 +374,8 @@ class DetectionPredictor:
         cf = self._compiled.get((tuple(shape), self.dtype))
         return None if cf is None else cf.static_in
 
+    rotated_rows = False  # the rows behind the NMS are [x1, y1, x2, y2, conf, cls]; the oriented-box task: [x, y, w, h, r, conf, cls]
+
     def make_tracker(self):
         """The tracker of ``mode="track"`` for this predictor's arguments: ``device_track`` picks the kernel or the host path."""
         from ..trackers import ByteTracker, DeviceByteTracker
@@ -385,7 +387,8 @@ class DetectionPredictor:
             max_det = int(a["merge_max_det"])
             if max_det > 1024:
                 raise ValueError(f"merge_max_det = {max_det} with mode='track': the track step takes at most 1024 detections per frame")
-        return cls(a["tracker"], frame_rate=30, max_tracks=int(a["max_tracks"]), streams=int(a["track_streams"]), max_det=max_det, device=self.device)
+        return cls(a["tracker"], frame_rate=30, max_tracks=int(a["max_tracks"]), streams=int(a["track_streams"]), max_det=max_det, device=self.device,
+                   rotated=self.rotated_rows)
 
     def _track_launch(self, cf: CompiledForward):
         """Device tracker: the track step behind this batch's NMS and box scaling, on the same stream; returns copies (rows, counts) that
@@ -397,14 +400,15 @@ class DetectionPredictor:
 
     def _boxes_of(self, i: int, k: int, rows: torch.Tensor, tracked) -> torch.Tensor:
         """The rows of image i's ``Results``: its k detections, or — when the tracker returned rows for it — those tracks
-        [x1, y1, x2, y2, id, conf, cls] (trackers/track.py:79-88: an image without detections or without returned tracks keeps its plain result)."""
+        [x1, y1, x2, y2, id, conf, cls] ([x, y, w, h, r, id, conf, cls] of an oriented-box model): the tracker's rows without their trailing
+        idx column (trackers/track.py:79-88: an image without detections or without returned tracks keeps its plain result)."""
         if self.tracker is None or k == 0:
             return rows[i, :k]
         if tracked is None:  # host tracker, images in order
             t = torch.from_numpy(self.tracker.update(rows[i, :k].cpu().numpy(), stream=i % self.tracker.streams)).to(rows.device)
         else:
             t = tracked[0][i, : tracked[1][i]]
-        return t[:, :7] if len(t) else rows[i, :k]
+        return t[:, :-1] if len(t) else rows[i, :k]
 
     def postprocess(self, cf: CompiledForward, im: torch.Tensor, paths=None) -> List[Results]:
         n = cf.nms.count.shape[0]
@@ -773,6 +777,7 @@ class OBBPredictor(DetectionPredictor):
     plus the per-level angle branches and ``dy_obb_decode`` inside the head, then ``dy_nms_rotated`` in place of ``dy_nms`` and
     ``dy_scale_rboxes`` in place of ``dy_scale_boxes``; one synchronisation per batch, and a streamed run copies the (N, max_det, 7) rows
     behind the batch's launches as it copies detection rows.  ``Results.obb`` carries the rows; ``Results.boxes`` is None.
+    ``mode="track"``: the rotated track step reads the same rows; a tracked image's ``Results.obb`` has 8 columns.
 
     ``tile=``: the tiled loop is the detection task's; the cross-tile merge is ``dy_tile_merge_rotated`` -- greedy suppression
     at ``merge_iou`` as a ProbIoU threshold.  An IoS-like measure and fusing merges are not built for rotated boxes."""
@@ -795,8 +800,13 @@ class OBBPredictor(DetectionPredictor):
         super().__init__(model, overrides)
         self.args["task"] = "obb"
 
+    rotated_rows = True
+
     def make_tracker(self):
-        raise NotImplementedError("track: tracking is not built for oriented-box models")
+        """The rotated tracker (``dy_track_step_rotated`` or the host class with ``rotated=True``) behind ``dy_nms_rotated`` + ``dy_scale_rboxes``."""
+        if self.args["tile"] is not None:
+            raise NotImplementedError("track with tile: not built for oriented-box models")
+        return super().make_tracker()
 
     def _new_nms_bufs(self, nb: int, anchors: int):
         return H.RNmsBuffers(nb, anchors, int(self.args["max_det"]), self.device)

@@ -108,7 +108,7 @@ class Masks(BaseTensor):
 
 class OBB(BaseTensor):
     """Oriented boxes of one image — reference results.py:1585-1806.  ``data``: (n, 7) [x, y, w, h, rotation, conf, cls], or (n, 8) with a
-    track id in front of conf (never produced here: tracking is not built for oriented boxes, ``id`` is None)."""
+    track id in front of conf -- what ``YOLO.track`` leaves for an image whose tracker returned rows (``is_track``, ``id``)."""
 
     def __init__(self, boxes, orig_shape):
         if boxes.ndim == 1:

@@ -1479,14 +1479,18 @@ def val_mask_match(bufs: NmsBuffers, protos: torch.Tensor, side: torch.Tensor, l
 
 class TrackBuffers:
     """Persistent state, workspace and outputs of ``dy_track_step`` for (streams, max_tracks, max_det).  ``out`` / ``count`` grow with the
-    largest batch seen; the state lives as long as the object (``track_reset`` empties it)."""
+    largest batch seen; the state lives as long as the object (``track_reset`` empties it).  ``rotated``: the buffers of
+    ``dy_track_step_rotated`` (7-float detection rows in, 9-float rows out, a state with the angle per slot)."""
 
-    def __init__(self, streams: int, max_tracks: int, max_det: int, device):
+    def __init__(self, streams: int, max_tracks: int, max_det: int, device, rotated: bool = False):
         self.streams, self.max_tracks, self.max_det, self.device = int(streams), int(max_tracks), int(max_det), torch.device(device)
-        nstate = lib().dy_track_state_bytes(self.streams, self.max_tracks)
-        nws = lib().dy_track_workspace_bytes(self.streams, self.max_tracks, self.max_det)
+        self.rotated = bool(rotated)
+        self.suffix = "_rotated" if self.rotated else ""
+        self.row_in, self.row_out = (7, 9) if self.rotated else (6, 8)
+        nstate = getattr(lib(), "dy_track_state_bytes" + self.suffix)(self.streams, self.max_tracks)
+        nws = getattr(lib(), "dy_track_workspace_bytes" + self.suffix)(self.streams, self.max_tracks, self.max_det)
         if nstate < 0 or nws < 0:
-            check(int(min(nstate, nws)), "dy_track_state_bytes / dy_track_workspace_bytes")
+            check(int(min(nstate, nws)), f"dy_track_state_bytes{self.suffix} / dy_track_workspace_bytes{self.suffix}")
         self.state = torch.zeros((nstate,), dtype=torch.uint8, device=self.device)
         self.workspace = torch.empty((nws,), dtype=torch.uint8, device=self.device)
         self.out: Optional[torch.Tensor] = None
@@ -1494,14 +1498,14 @@ class TrackBuffers:
 
     def outputs(self, images: int) -> Tuple[torch.Tensor, torch.Tensor]:
         if self.out is None or self.out.shape[0] < images:
-            self.out = torch.empty((images, self.max_tracks, 8), dtype=torch.float32, device=self.device)
+            self.out = torch.empty((images, self.max_tracks, self.row_out), dtype=torch.float32, device=self.device)
             self.count = torch.empty((images,), dtype=torch.int32, device=self.device)
         return self.out[:images], self.count[:images]
 
 
 def track_reset(bufs: TrackBuffers) -> None:
     """No tracks, frame and id counters 0 (``BYTETracker.reset``), stream-ordered."""
-    _launch(lib().dy_track_reset, (bufs.state.data_ptr(), bufs.streams, bufs.max_tracks), keep=(bufs,), record=False)
+    _launch(getattr(lib(), "dy_track_reset" + bufs.suffix), (bufs.state.data_ptr(), bufs.streams, bufs.max_tracks), keep=(bufs,), record=False)
 
 
 def track_counters(bufs: TrackBuffers):
@@ -1514,14 +1518,16 @@ def track_step(bufs: TrackBuffers, nms_bufs, frames: int, streams: int, cfg, max
     """ByteTrack over ``frames`` time steps of ``streams`` video streams in one ``dy_track_step`` launch; no host synchronisation.
     ``nms_bufs``: ``NmsBuffers`` (after ``scale_boxes_``) or a ``(rows, counts)`` pair of device tensors, (frames * streams, max_det, 6)
     fp32 / int32; ``cfg``: the tracker settings (``trackers.load_tracker_cfg``).  Returns views ``(out (frames * streams, max_tracks, 8),
-    count (frames * streams,))`` of ``bufs``' output tensors: rows [x1, y1, x2, y2, id, score, cls, idx] in ascending id."""
+    count (frames * streams,))`` of ``bufs``' output tensors: rows [x1, y1, x2, y2, id, score, cls, idx] in ascending id.  With rotated
+    buffers (``RNmsBuffers`` after ``scale_rboxes_``): rows (.., max_det, 7) [x, y, w, h, r, conf, cls] through ``dy_track_step_rotated``,
+    out (.., max_tracks, 9) [x, y, w, h, r, id, score, cls, idx]."""
     rows, counts = (nms_bufs.out, nms_bufs.count) if hasattr(nms_bufs, "out") else nms_bufs
     require_device(rows, "detection rows")
     require_device(counts, "detection counts")
     n = int(frames) * int(streams)
     if streams != bufs.streams or rows.dtype != torch.float32 or counts.dtype != torch.int32 or not rows.is_contiguous() or not counts.is_contiguous() \
-            or tuple(rows.shape) != (n, bufs.max_det, 6) or counts.numel() != n:
-        raise ValueError(f"track_step: rows must be contiguous fp32 ({n}, {bufs.max_det}, 6) with {n} int32 counts for {bufs.streams} streams")
+            or tuple(rows.shape) != (n, bufs.max_det, bufs.row_in) or counts.numel() != n:
+        raise ValueError(f"track_step: rows must be contiguous fp32 ({n}, {bufs.max_det}, {bufs.row_in}) with {n} int32 counts for {bufs.streams} streams")
     out, cnt = bufs.outputs(n)
     d = TrackDesc()
     d.rows, d.counts = rows.data_ptr(), counts.data_ptr()
@@ -1531,7 +1537,7 @@ def track_step(bufs: TrackBuffers, nms_bufs, frames: int, streams: int, cfg, max
     d.track_high_thresh, d.track_low_thresh, d.new_track_thresh = float(cfg.track_high_thresh), float(cfg.track_low_thresh), float(cfg.new_track_thresh)
     d.match_thresh, d.fuse_score = float(cfg.match_thresh), int(bool(cfg.fuse_score))
     d.max_time_lost = int(frame_rate / 30.0 * cfg.track_buffer) if max_time_lost is None else int(max_time_lost)
-    _launch(lib().dy_track_step, (C.byref(d),), keep=(d, bufs, rows, counts), record=False)
+    _launch(getattr(lib(), "dy_track_step" + bufs.suffix), (C.byref(d),), keep=(d, bufs, rows, counts), record=False)
     return out, cnt
 
 

@@ -18,6 +18,12 @@ more update (the list is filtered against ``removed_stracks`` before this frame'
 track re-found that way carries its id in ``removed_stracks`` for good, so it leaves at once when it is lost again; an image without
 detections never reaches the tracker; detection boxes go xyxy -> xywh -> tlwh -> xyah in float32; ``initiate`` leaves a float32 mean
 (and float32 products in the standard deviations) until the first predict / update.  Rows come out in ascending track id.
+
+``rotated=True`` (both classes): the tracker of an oriented-box model (trackers/track.py:69-88 ``is_obb``).  Rows in are (n, 7)
+[x, y, w, h, r, conf, cls], rows out (k, 9) [x, y, w, h, r, id, score, cls, idx].  The Kalman filter is the same one on (x, y, aspect, h);
+centre and size come straight from the row (no xyxy -> xywh step); every cost is ``1 - batch_probiou`` on xywha rows rounded to float32
+(``STrack.xywha``: the corner from the mean, then the centre back from the corner), with ``fuse_score`` on top; the angle is not filtered:
+a track holds the angle of the detection it last matched, a lost track a stale one.
 """
 from __future__ import annotations
 
@@ -81,6 +87,37 @@ def detections_f32(rows: np.ndarray):
     return xyxy, xyah, np.asarray(rows[:, 4], dtype=_F32), np.asarray(rows[:, 5], dtype=_F32)
 
 
+def detections_r32(rows: np.ndarray):
+    """(n, 7) rows [x, y, w, h, r, conf, cls] -> (xywha, xyah, conf, cls) as the reference's ``STrack`` holds an oriented detection
+    (byte_tracker.py:68-79): centre and size from the row, the corner ``x - w / 2`` in float64 rounded to float32, ``xywha`` = that corner
+    plus half the size in float32 with the row's angle."""
+    xywh = np.ascontiguousarray(rows[:, :4], dtype=_F32)
+    w64 = xywh.astype(np.float64)
+    tlwh = xywh.copy()
+    tlwh[:, :2] = (w64[:, :2] - w64[:, 2:] / 2).astype(_F32)
+    xyah = tlwh.copy()
+    xyah[:, :2] += xyah[:, 2:] / 2
+    xywha = np.concatenate([xyah[:, :2], tlwh[:, 2:], np.asarray(rows[:, 4:5], dtype=_F32)], axis=1)
+    with np.errstate(all="ignore"):
+        xyah[:, 2] /= xyah[:, 3]
+    return xywha, xyah, np.asarray(rows[:, 5], dtype=_F32), np.asarray(rows[:, 6], dtype=_F32)
+
+
+def probiou_cost(a: np.ndarray, b: np.ndarray, scores: Optional[np.ndarray] = None) -> np.ndarray:
+    """``1 - batch_probiou(a, b)`` on float32 xywha rows (matching.py:85-101; torch on the CPU as there), then ``fuse_score`` when ``scores``
+    is given."""
+    from ..utils.metrics import batch_probiou
+
+    a, b = np.ascontiguousarray(a, dtype=_F32).reshape(-1, 5), np.ascontiguousarray(b, dtype=_F32).reshape(-1, 5)
+    if not len(a) or not len(b):
+        return np.zeros((len(a), len(b)), dtype=_F32)
+    with np.errstate(all="ignore"):
+        cost = _F32(1) - batch_probiou(a, b).numpy()
+        if scores is not None:
+            cost = _F32(1) - (_F32(1) - cost) * scores.astype(_F32)[None, :]
+    return cost
+
+
 def iou_cost(a: np.ndarray, b: np.ndarray, scores: Optional[np.ndarray] = None) -> np.ndarray:
     """``1 - bbox_ioa(a, b, iou=True)`` in float32 in its order of operations (eps 1e-7), then ``fuse_score`` when ``scores`` is given."""
     a, b = a.astype(_F32, copy=False), b.astype(_F32, copy=False)
@@ -117,6 +154,23 @@ def assign(cost: np.ndarray, thresh: float) -> np.ndarray:
     return match
 
 
+def _width_message(shape, width: int, rotated: bool) -> str:
+    kind = "a rotated tracker takes [x, y, w, h, r, conf, cls]" if rotated else "a plain tracker takes [x1, y1, x2, y2, conf, cls] (rotated=True for oriented rows)"
+    return f"rows of shape {tuple(shape)}: {kind}, {width} columns"
+
+
+def _rows_of(rows, width: int, rotated: bool) -> np.ndarray:
+    """The rows of one image as an (n, width) float32 array; another width is refused (an empty array of any shape is no rows)."""
+    rows = np.asarray(rows.detach().cpu() if hasattr(rows, "detach") else rows, dtype=_F32)
+    if rows.size == 0:
+        return rows.reshape(0, width)
+    if rows.ndim == 1 and rows.size == width:  # one row
+        return rows.reshape(1, width)
+    if rows.ndim != 2 or rows.shape[1] != width:
+        raise ValueError(_width_message(rows.shape, width, rotated))
+    return rows
+
+
 class _Stream:
     """The slots of one video stream."""
 
@@ -131,6 +185,7 @@ class _Stream:
         self.id = np.zeros(t, dtype=np.int64)
         self.score = np.zeros(t, dtype=_F32)
         self.cls = np.zeros(t, dtype=_F32)
+        self.angle = np.zeros(t, dtype=_F32)  # rotated trackers: the angle of the detection last matched
         self.idx = np.zeros(t, dtype=np.int64)
         self.frame_id = np.zeros(t, dtype=np.int64)
         self.start_frame = np.zeros(t, dtype=np.int64)
@@ -143,11 +198,14 @@ class _Stream:
 class ByteTracker:
     """Host ByteTrack.  ``cfg``: a tracker YAML name / path, dict or namespace; ``streams``: independent video streams of a batch (image k
     of a batch is stream ``k % streams`` at time step ``k // streams``); ``max_tracks``: slots per stream — when they are full no new
-    track starts and the stream's ``overflow`` counter goes up."""
+    track starts and the stream's ``overflow`` counter goes up; ``rotated``: oriented rows (module docstring)."""
 
-    def __init__(self, cfg="bytetrack.yaml", frame_rate: int = 30, max_tracks: int = 512, streams: int = 1, max_det: int = 300, device=None):
+    def __init__(self, cfg="bytetrack.yaml", frame_rate: int = 30, max_tracks: int = 512, streams: int = 1, max_det: int = 300, device=None,
+                 rotated: bool = False):
         self.cfg = load_tracker_cfg(cfg)
         self.max_tracks, self.streams, self.max_det = int(max_tracks), int(streams), int(max_det)
+        self.rotated = bool(rotated)
+        self.row_in, self.row_out = (7, 9) if self.rotated else (6, 8)
         if self.max_tracks < 1 or self.streams < 1:
             raise ValueError("max_tracks and streams must be positive")
         self.max_time_lost = int(frame_rate / 30.0 * self.cfg.track_buffer)
@@ -190,6 +248,29 @@ class ByteTracker:
         return out
 
     @staticmethod
+    def _xywh(st: _Stream, slots: np.ndarray) -> np.ndarray:
+        """``STrack.xywh`` of the slots rounded to float32: ``tlwh`` from the mean, then the centre back from the corner, in that order."""
+        m = st.mean[slots, :4]
+        out = np.empty((len(slots), 4), dtype=_F32)
+        for sel, dt in ((st.m32[slots], _F32), (~st.m32[slots], np.float64)):
+            if sel.any():
+                r = m[sel].astype(dt)
+                r[:, 2] *= r[:, 3]
+                r[:, :2] -= r[:, 2:] / 2
+                r[:, :2] += r[:, 2:] / 2
+                out[sel] = r.astype(_F32)
+        return out
+
+    def _boxes(self, st: _Stream, slots: np.ndarray) -> np.ndarray:
+        """What ``iou_distance`` and ``result`` read of the slots: ``xyxy``, or ``xywha`` of a rotated tracker."""
+        if not self.rotated:
+            return self._xyxy(st, slots)
+        return np.concatenate([self._xywh(st, slots), st.angle[slots, None]], axis=1)
+
+    def _cost(self, a: np.ndarray, b: np.ndarray, scores: Optional[np.ndarray] = None) -> np.ndarray:
+        return probiou_cost(a, b, scores) if self.rotated else iou_cost(a, b, scores)
+
+    @staticmethod
     def _predict(st: _Stream, slots: np.ndarray) -> None:
         if not len(slots):
             return
@@ -223,7 +304,7 @@ class ByteTracker:
         st.cov[slots] = cov - np.einsum("nia,nij,njb->nab", kt, pc, kt)
         st.m32[slots] = False
 
-    def _matched(self, st: _Stream, slots: np.ndarray, det: np.ndarray, xyah, conf, cls) -> None:
+    def _matched(self, st: _Stream, slots: np.ndarray, det: np.ndarray, xyah, conf, cls, angle=None) -> None:
         """``STrack.update`` (tracked) / ``re_activate`` (lost) of the slots with their detections."""
         if not len(slots):
             return
@@ -232,14 +313,17 @@ class ByteTracker:
         st.tracklet_len[slots] = np.where(was, st.tracklet_len[slots] + 1, 0)
         st.state[slots], st.activated[slots], st.frame_id[slots] = TRACKED, True, st.frame
         st.score[slots], st.cls[slots], st.idx[slots] = conf[det], cls[det], det
+        if angle is not None:
+            st.angle[slots] = angle[det]
 
     # ---- one image of one stream -------------------------------------------------------------------------
     def _step(self, st: _Stream, rows: np.ndarray) -> np.ndarray:
         c = self.cfg
         if len(rows) == 0:  # track.py:79-80: such an image never reaches the tracker
-            return np.zeros((0, 8), dtype=_F32)
+            return np.zeros((0, self.row_out), dtype=_F32)
         st.frame += 1
-        dxyxy, dxyah, conf, cls = detections_f32(rows)
+        dxyxy, dxyah, conf, cls = detections_r32(rows) if self.rotated else detections_f32(rows)  # (dxyxy: xywha rows of a rotated tracker)
+        ang = dxyxy[:, 4] if self.rotated else None
         high, low, newt = _F32(c.track_high_thresh), _F32(c.track_low_thresh), _F32(c.new_track_thresh)
         for t in (high, low, newt):
             self._margin(conf, t, exact_ok=True)
@@ -253,26 +337,26 @@ class ByteTracker:
         self._predict(st, pool)
 
         # first association: the pool against the high-score detections
-        cost = iou_cost(self._xyxy(st, pool), dxyxy[hi], conf[hi] if c.fuse_score else None)
+        cost = self._cost(self._boxes(st, pool), dxyxy[hi], conf[hi] if c.fuse_score else None)
         self._margin(cost, c.match_thresh)
         m = assign(cost, c.match_thresh)
-        self._matched(st, pool[m >= 0], hi[m[m >= 0]], dxyah, conf, cls)
+        self._matched(st, pool[m >= 0], hi[m[m >= 0]], dxyah, conf, cls, ang)
         det_free = np.ones(len(hi), dtype=bool)
         det_free[m[m >= 0]] = False
         # second association: what is left of the TRACKED pool against the low-score detections
         rest = pool[m < 0]
         rest = rest[st.state[rest] == TRACKED]
-        cost = iou_cost(self._xyxy(st, rest), dxyxy[lo])
+        cost = self._cost(self._boxes(st, rest), dxyxy[lo])
         self._margin(cost, 0.5)
         m2 = assign(cost, 0.5)
-        self._matched(st, rest[m2 >= 0], lo[m2[m2 >= 0]], dxyah, conf, cls)
+        self._matched(st, rest[m2 >= 0], lo[m2[m2 >= 0]], dxyah, conf, cls, ang)
         st.state[rest[m2 < 0]] = LOST
         # unconfirmed tracks against the high-score detections still free
         hi2 = hi[det_free]
-        cost = iou_cost(self._xyxy(st, unconf), dxyxy[hi2], conf[hi2] if c.fuse_score else None)
+        cost = self._cost(self._boxes(st, unconf), dxyxy[hi2], conf[hi2] if c.fuse_score else None)
         self._margin(cost, 0.7)
         m3 = assign(cost, 0.7)
-        self._matched(st, unconf[m3 >= 0], hi2[m3[m3 >= 0]], dxyah, conf, cls)
+        self._matched(st, unconf[m3 >= 0], hi2[m3[m3 >= 0]], dxyah, conf, cls, ang)
         st.state[unconf[m3 < 0]] = FREE  # removed, and in no list
         # new tracks, ids in ascending detection index
         free3 = np.ones(len(hi2), dtype=bool)
@@ -296,6 +380,8 @@ class ByteTracker:
             st.id[slots] = st.next_id + 1 + np.arange(len(new))
             st.next_id += len(new)
             st.score[slots], st.cls[slots], st.idx[slots] = conf[new], cls[new], new
+            if self.rotated:
+                st.angle[slots] = ang[new]
             st.frame_id[slots] = st.start_frame[slots] = st.frame
             st.tracklet_len[slots] = 0
         # time-outs of what was in the lost list when the update began; the list is filtered against the removals of EARLIER updates only
@@ -307,7 +393,7 @@ class ByteTracker:
         # duplicates between the tracked and the lost list: the younger one goes
         ta, tb = np.nonzero(st.state == TRACKED)[0], np.nonzero((st.state == LOST) | (st.state == REMOVED))[0]
         if len(ta) and len(tb):
-            pd = iou_cost(self._xyxy(st, ta), self._xyxy(st, tb))
+            pd = self._cost(self._boxes(st, ta), self._boxes(st, tb))
             self._margin(pd, 0.15)
             p, q = np.nonzero(pd < 0.15)
             older_a = (st.frame_id[ta[p]] - st.start_frame[ta[p]]) > (st.frame_id[tb[q]] - st.start_frame[tb[q]])
@@ -316,24 +402,27 @@ class ByteTracker:
         # STrack.result of the activated tracked tracks, in ascending id
         o = np.nonzero((st.state == TRACKED) & st.activated)[0]
         o = o[np.argsort(st.id[o], kind="stable")]
-        res = np.empty((len(o), 8), dtype=_F32)
-        res[:, :4] = self._xyxy(st, o)
-        res[:, 4], res[:, 5], res[:, 6], res[:, 7] = st.id[o], st.score[o], st.cls[o], st.idx[o]
+        res = np.empty((len(o), self.row_out), dtype=_F32)
+        res[:, : self.row_out - 4] = self._boxes(st, o)
+        res[:, -4], res[:, -3], res[:, -2], res[:, -1] = st.id[o], st.score[o], st.cls[o], st.idx[o]
         return res
 
     # ---- surface -----------------------------------------------------------------------------------------
     def update(self, rows, stream: int = 0) -> np.ndarray:
-        """One image of one stream: (n, 6) rows -> (k, 8) float32 [x1, y1, x2, y2, id, score, cls, idx] (``STrack.result``), ascending id."""
-        rows = np.asarray(rows.detach().cpu() if hasattr(rows, "detach") else rows, dtype=_F32).reshape(-1, 6)
-        return self._step(self._s[stream], rows)
+        """One image of one stream: (n, 6) rows -> (k, 8) float32 [x1, y1, x2, y2, id, score, cls, idx] (``STrack.result``), ascending id;
+        a rotated tracker: (n, 7) rows -> (k, 9) [x, y, w, h, r, id, score, cls, idx]."""
+        return self._step(self._s[stream], _rows_of(rows, self.row_in, self.rotated))
 
     def update_batch(self, rows, counts) -> Tuple[np.ndarray, np.ndarray]:
-        """A batch of padded rows (F * S, max_det, 6) with counts (F * S,) -> padded (F * S, max_tracks, 8) float32 and counts (int32)."""
+        """A batch of padded rows (F * S, max_det, 6) with counts (F * S,) -> padded (F * S, max_tracks, 8) float32 and counts (int32); a
+        rotated tracker: (F * S, max_det, 7) -> (F * S, max_tracks, 9)."""
         rows = np.asarray(rows.detach().cpu() if hasattr(rows, "detach") else rows, dtype=_F32)
+        if rows.ndim != 3 or rows.shape[2] != self.row_in:
+            raise ValueError(_width_message(rows.shape, self.row_in, self.rotated))
         counts = np.asarray(counts.detach().cpu() if hasattr(counts, "detach") else counts).astype(np.int64)
         if len(rows) % self.streams:
             raise ValueError(f"{len(rows)} images are no multiple of track_streams = {self.streams}")
-        out = np.zeros((len(rows), self.max_tracks, 8), dtype=_F32)
+        out = np.zeros((len(rows), self.max_tracks, self.row_out), dtype=_F32)
         n = np.zeros(len(rows), dtype=np.int32)
         for k in range(len(rows)):
             r = self._step(self._s[k % self.streams], rows[k, : max(0, min(int(counts[k]), rows.shape[1]))])
@@ -346,7 +435,8 @@ class DeviceByteTracker:
     state lives in device memory between calls.  Same constructor and surface as ``ByteTracker``; ``update_batch`` takes the NMS buffers'
     device tensors and returns device tensors without synchronising."""
 
-    def __init__(self, cfg="bytetrack.yaml", frame_rate: int = 30, max_tracks: int = 512, streams: int = 1, max_det: int = 300, device="cuda"):
+    def __init__(self, cfg="bytetrack.yaml", frame_rate: int = 30, max_tracks: int = 512, streams: int = 1, max_det: int = 300, device="cuda",
+                 rotated: bool = False):
         import torch
 
         from .. import hip_ops as H
@@ -356,7 +446,9 @@ class DeviceByteTracker:
         self.max_time_lost = int(frame_rate / 30.0 * self.cfg.track_buffer)
         self.device = torch.device(device)
         self._H = H
-        self.bufs = H.TrackBuffers(self.streams, self.max_tracks, self.max_det, self.device)
+        self.rotated = bool(rotated)
+        self.row_in, self.row_out = (7, 9) if self.rotated else (6, 8)
+        self.bufs = H.TrackBuffers(self.streams, self.max_tracks, self.max_det, self.device, rotated=self.rotated)
         self.reset()
 
     def reset(self) -> None:
@@ -372,13 +464,13 @@ class DeviceByteTracker:
 
     def update_batch(self, rows, counts):
         """Device tensors rows (F * S, max_det, 6) fp32 / counts (F * S,) int32 -> (out (F * S, max_tracks, 8), count (F * S,)), views of
-        this tracker's output buffers (overwritten by the next call); no host synchronisation."""
+        this tracker's output buffers (overwritten by the next call); no host synchronisation.  A rotated tracker: rows (.., 7), out (.., 9)."""
         import torch
 
         rows = torch.as_tensor(rows, dtype=torch.float32, device=self.device).contiguous()
         counts = torch.as_tensor(counts, device=self.device).to(torch.int32).contiguous()
-        if rows.dim() != 3 or rows.shape[2] != 6 or rows.shape[1] != self.max_det:
-            raise ValueError(f"rows must be (images, max_det = {self.max_det}, 6)")
+        if rows.dim() != 3 or rows.shape[2] != self.row_in or rows.shape[1] != self.max_det:
+            raise ValueError(f"rows must be (images, max_det = {self.max_det}, {self.row_in}); " + _width_message(rows.shape, self.row_in, self.rotated))
         n = rows.shape[0]
         if n % self.streams:
             raise ValueError(f"{n} images are no multiple of track_streams = {self.streams}")
@@ -390,10 +482,10 @@ class DeviceByteTracker:
 
         if self.streams != 1 or stream != 0:
             raise ValueError("update() serves a single-stream tracker; use update_batch")
-        r = torch.as_tensor(np.asarray(rows.detach().cpu() if hasattr(rows, "detach") else rows, dtype=_F32).reshape(-1, 6))
+        r = torch.as_tensor(_rows_of(rows, self.row_in, self.rotated))
         if len(r) > self.max_det:
             raise ValueError(f"{len(r)} rows exceed max_det = {self.max_det}")
-        pad = torch.zeros((1, self.max_det, 6), dtype=torch.float32)
+        pad = torch.zeros((1, self.max_det, self.row_in), dtype=torch.float32)
         pad[0, : len(r)] = r
         out, cnt = self.update_batch(pad.to(self.device), torch.tensor([len(r)], dtype=torch.int32, device=self.device))
         k = int(cnt[0])

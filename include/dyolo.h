@@ -1010,6 +1010,25 @@ int64_t dy_track_workspace_bytes(int32_t streams, int32_t max_tracks, int32_t ma
 int32_t dy_track_reset(void* state, int32_t streams, int32_t max_tracks, dy_stream_t stream);
 int32_t dy_track_step(const dy_track_desc* d, dy_stream_t stream);
 
+/* The same track step for the rows of an oriented-box model (trackers/track.py:69-88 `is_obb`; byte_tracker.py:68-79, :217-228;
+ * matching.py:85-94): the second instantiation of the one kernel.  The Kalman filter stays on (x, y, aspect, h); every cost (the three
+ * associations and remove_duplicate_stracks) is 1 - ProbIoU(track, detection) on xywha rows rounded to fp32 -- the expression dy_nms_rotated,
+ * dy_val_match_rotated and dy_tile_merge_rotated share -- with fuse_score on top as above; the angle is not filtered: a track holds the
+ * angle of the detection it last matched.  A NaN in a box or an angle makes its costs NaN = no edge.
+ * dy_track_step_rotated takes the same dy_track_desc with these conventions:
+ *   rows: fp32 (frames * streams, max_det, 7) x, y, w, h, r, conf, cls (what dy_nms_rotated + dy_scale_rboxes leave);
+ *   out:  fp32 (frames * streams, max_tracks, 9) x, y, w, h, r, id, score, cls, idx = STrack.result, ascending track id, rows >= out_count zero.
+ * state: dy_track_state_bytes_rotated bytes; the layout above with a third fp32 field per slot behind score and cls: the angle.  All zero =
+ * empty as above; dy_track_reset_rotated zeroes this (larger) state.  workspace: dy_track_workspace_bytes_rotated (the measurements again).
+ * LDS: 100 bytes per slot (the 92 above + the fifth covariance term and the angle) and 72 per detection (68 + the fifth term); the
+ * covariance terms of a box are computed once per slot and once per detection per image.  max_tracks even, <= 1024, max_det <= 1024 AND
+ * max_tracks * 100 + max_det * 72 + 64 <= 160 KB: 1024 slots admit 852 detections, the defaults 512 / 300 need 72 864 bytes; a pair beyond
+ * that is DY_ERR_INVALID_ARG before any launch, both numbers named. */
+int64_t dy_track_state_bytes_rotated(int32_t streams, int32_t max_tracks);
+int64_t dy_track_workspace_bytes_rotated(int32_t streams, int32_t max_tracks, int32_t max_det);
+int32_t dy_track_reset_rotated(void* state, int32_t streams, int32_t max_tracks, dy_stream_t stream);
+int32_t dy_track_step_rotated(const dy_track_desc* d, dy_stream_t stream);
+
 /* ---- instance segmentation: Proto's transposed convolution, the mask-coefficient gather, mask assembly ---------------------
  * dy_depth_to_space2_nhwc: the layout half of nn.ConvTranspose2d(c, c, 2, 2, 0) inside Proto (nn/modules/block.py:80-97).  A k = 2,
  * s = 2, p = 0 transposed convolution is a 1x1 convolution cin -> 4 * cout (GEMM row (a * 2 + b) * cout + o = W[:, o, a, b], the bias
