@@ -8,12 +8,19 @@
 //                                       key = (~float_bits(score) << 32) | slot,   slot = k * max_det + r
 //                                   so that ascending key order is descending score, ties by ascending slot;
 //                         sort      bitonic, in LDS when the keys fit, in the workspace otherwise (two calls: see nms_core.h on flat accesses);
-//                         scan      nms_greedy_scan on 16 waves (nms_scan.h) with the policy TmScan below.
-//                       A box is the row's xyxy plus its tile's (ox, oy): one fp32 add of an integer-valued float.  Classes are compared as
-//                       integers; nothing is added to the coordinates.  All arithmetic is fp32 with contraction off, the IoU in the expression
-//                       order of nms.hip's iou_gt (the reference's), intersection over the smaller area for metric 1.
-//   tile_merge_kernel<true>   dy_tile_fuse: the same compaction, sort and scan (the same kept rows, scores, classes and slots), then the
-//                       kept row absorbs what it suppressed instead of dropping it (greedy non-maximum merging):
+//                         scan      nms_greedy_scan on 16 waves (nms_scan.h) with the kernel's policy.
+//                       The kernel is a template over that policy; there are three, one per entry point.  TmBase holds what they share: the
+//                       keys, the frame's rows and outputs, the kept list in LDS (a float4, a fifth float and the class per row: 24 bytes),
+//                       the head of a candidate (key -> slot, score, its tile's (ox, oy), its row), kept() and the store of a kept box
+//                       (its LDS row, the output row as the policy writes it, its out_index slot).  A policy adds ROW / SCORE (the floats
+//                       of a row, the score's column), KEEP_BYTES, TAIL (a fusion pass behind the scan), its Cand and the columns it reads,
+//                       box(), suppresses() and the output row.  The host side is shared likewise:
+//                       tm_check tests what the three descriptors have in common, tm_launch<Pol> fills the arguments they have in common.
+//   TmScan              dy_tile_merge.  A box is the row's xyxy plus its tile's (ox, oy): one fp32 add of an integer-valued float.  Classes
+//                       are compared as integers; nothing is added to the coordinates.  All arithmetic is fp32 with contraction off, the IoU
+//                       in the expression order of nms.hip's iou_gt (the reference's), intersection over the smaller area for metric 1.
+//   TmFuseScan          dy_tile_fuse: TmScan (the same kept rows, scores, classes and slots) and the sorted position of every kept row;
+//                       behind the scan the kept row absorbs what it suppressed instead of dropping it (greedy non-maximum merging):
 //                         init      kept row k: members = 1, accumulators = its own box (the scan also left its sorted position, kpos[k]);
 //                         absorb    one thread per candidate j of the sorted list: a binary search of kpos gives the kept rows ahead of j
 //                                   (a prefix of the kept list, j itself when it is kept); the FIRST of them whose own box suppresses j
@@ -26,13 +33,13 @@
 //                       launch: 4,096 keys + 1,000 kept = 60 KB, at merge_max_det 4096 the kept list takes 112 KB and 4,096 keys the rest.
 //                       The accumulators (40 bytes per kept row) do not fit beside that, so they lie in the workspace behind the keys; only
 //                       this workgroup touches its frame's, with an agent-scope fence and a barrier between the phases.
-//   tile_merge_kernel<false, true>   dy_tile_merge_rotated: the merge for oriented boxes.  Rows are the 7 columns of dy_nms_rotated (x, y, w, h,
-//                       theta, conf, cls); compaction, keys and sort are the same.  The scan's policy is TmrScan: a box is the covariance row of
-//                       probiou.h (rnms_row of the centre plus (ox, oy), w, h, theta: sinf / cosf once per candidate of a chunk, never per
-//                       pair) and the predicate rnms_probiou(kept, candidate) >= thr -- the one expression the per-tile NMS and the validator
-//                       use.  ScanBox's five floats hold x, y, a, b, c, so the kept list stays 24 bytes a row and the LDS budget above holds.
-//                       The expression's second half runs only when a ballot finds a lane that can still be suppressed: of the kept
-//                       row's class and not ruled out by its distance terms (tmr_far_bound; no verdict can change).
+//   TmrScan             dy_tile_merge_rotated: the merge for oriented boxes.  Rows are the 7 columns of dy_nms_rotated (x, y, w, h, theta,
+//                       conf, cls).  A box is the covariance row of probiou.h (rnms_row of the centre plus (ox, oy), w, h, theta: sinf / cosf
+//                       once per candidate of a chunk, never per pair) and the predicate rnms_probiou(kept, candidate) >= thr -- the one
+//                       expression the per-tile NMS and the validator use.  ScanBox's five floats hold x, y, a, b, c, so the kept list stays
+//                       24 bytes a row and TmScan's LDS budget holds.  The expression's second half runs only when a ballot finds a lane that
+//                       can still be suppressed: of the kept row's class and not ruled out by its distance terms (tmr_far_bound; no verdict
+//                       can change).
 #include "nms_scan.h"
 #include "probiou.h"
 
@@ -123,13 +130,54 @@ struct TmArgs {
   u64* keys;  // [frames][P]
   int K, max_det, N, P, SL;
   float fw, fh, thr;
-  int metric, agnostic, keep;
+  int metric, agnostic, keep;  // metric: dy_tile_merge and dy_tile_fuse
   // dy_tile_fuse only
   int mode;
   int* out_members;
   u64* acc;  // [frames][keep][TM_ACC_WORDS]
-  // dy_tile_merge_rotated only (behind everything else: the other kernels' argument offsets stay what they were)
+  // dy_tile_merge_rotated only
   float far;  // tmr_far_bound(thr)
+};
+
+// What every merge policy holds and does alike.  RW: the floats of an input and of an output row.
+template <int RW>
+struct TmBase {
+  const TmArgs& p;
+  const u64* skeys;
+  const u64* gkeys;
+  const float* frows;
+  float* outb;
+  int* outi;
+  float4* kbox;  // [keep]: the first four floats of a kept ScanBox
+  float* k5;     // its fifth
+  int* kcls;
+  bool in_lds;
+  // the head of candidate i < n of the sorted list: slot and score from its key, its tile's place (ox, oy) in the frame, its row
+  struct Head {
+    int slot;
+    float score, ox, oy;
+    const float* q;
+  };
+  __device__ __forceinline__ Head head(int i) const {
+    const u64 key = in_lds ? skeys[i] : gkeys[i];
+    const int slot = (int)(unsigned)(key & 0xffffffffull);
+    const int tile = slot / p.max_det;
+    const float oy = (float)p.offs[2 * tile], ox = (float)p.offs[2 * tile + 1];
+    return Head{slot, __uint_as_float(~(unsigned)(key >> 32)), ox, oy, frows + (size_t)slot * RW};
+  }
+  __device__ __forceinline__ ScanBox kept(int k) const {
+    const float4 kb = kbox[k];
+    return ScanBox{kb.x, kb.y, kb.z, kb.w, k5[k], kcls[k]};
+  }
+  // kept box `at` of the LDS list, output row `at` as the policy's write_row(float*) fills it, and its out_index slot
+  template <typename WriteRow>
+  __device__ __forceinline__ void keep_box(int at, const ScanBox& bx, int slot, WriteRow write_row) const {
+    kbox[at] = make_float4(bx.x1, bx.y1, bx.x2, bx.y2);
+    k5[at] = bx.area;
+    kcls[at] = bx.cls;
+    write_row(outb + (size_t)at * RW);
+    if (outi) outi[at] = slot;
+  }
 };
 
 struct TmCand {
@@ -150,32 +198,22 @@ __device__ __forceinline__ bool tm_suppresses(int metric, int agnostic, float th
   return (agnostic || icls == jcls) && ovr > thr;
 }
 
-struct TmScan {  // nms_greedy_scan's policy: frame-coordinate boxes, classes compared as integers, IoU or IoS, clamped rows
-  const TmArgs& p;
-  const u64* skeys;
-  const u64* gkeys;
-  const float* frows;
-  float* outb;
-  int* outi;
-  float4* kbox;  // [keep]
-  float* kar;
-  int* kcls;
-  bool in_lds;
+struct TmScan : TmBase<6> {  // nms_greedy_scan's policy: frame-coordinate boxes, classes compared as integers, IoU or IoS, clamped rows
+  static constexpr int ROW = 6, SCORE = 4, KEEP_BYTES = TM_KEEP_BYTES;
+  static constexpr bool TAIL = false;
   typedef TmCand Cand;
+  __device__ __forceinline__ TmScan(const TmBase<6>& b) : TmBase<6>(b) {}
   __device__ __forceinline__ Cand fetch(int i, int n) const {
     Cand c{0.f, 0.f, 0.f, 0.f, 0.f, 0, -1};
     if (i < n) {
-      const u64 key = in_lds ? skeys[i] : gkeys[i];
-      c.slot = (int)(unsigned)(key & 0xffffffffull);
-      c.score = __uint_as_float(~(unsigned)(key >> 32));
-      const int tile = c.slot / p.max_det;
-      const float oy = (float)p.offs[2 * tile], ox = (float)p.offs[2 * tile + 1];
-      const float* q = frows + (size_t)c.slot * 6;
-      c.x1 = q[0] + ox;
-      c.y1 = q[1] + oy;
-      c.x2 = q[2] + ox;
-      c.y2 = q[3] + oy;
-      c.cls = (int)q[5];
+      const Head h = head(i);
+      c.slot = h.slot;
+      c.score = h.score;
+      c.x1 = h.q[0] + h.ox;
+      c.y1 = h.q[1] + h.oy;
+      c.x2 = h.q[2] + h.ox;
+      c.y2 = h.q[3] + h.oy;
+      c.cls = (int)h.q[5];
     }
     return c;
   }
@@ -183,22 +221,15 @@ struct TmScan {  // nms_greedy_scan's policy: frame-coordinate boxes, classes co
   __device__ __forceinline__ bool suppresses(const ScanBox& i, const ScanBox& j) const {
     return tm_suppresses(p.metric, p.agnostic, p.thr, i.x1, i.y1, i.x2, i.y2, i.area, i.cls, j.x1, j.y1, j.x2, j.y2, j.area, j.cls);
   }
-  __device__ __forceinline__ ScanBox kept(int k) const {
-    const float4 kb = kbox[k];
-    return ScanBox{kb.x, kb.y, kb.z, kb.w, kar[k], kcls[k]};
-  }
   __device__ __forceinline__ void keep(int at, const Cand& c, const ScanBox& bx) const {
-    kbox[at] = make_float4(c.x1, c.y1, c.x2, c.y2);
-    kar[at] = bx.area;
-    kcls[at] = c.cls;
-    float* o = outb + (size_t)at * 6;
-    o[0] = fminf(fmaxf(c.x1, 0.f), p.fw);
-    o[1] = fminf(fmaxf(c.y1, 0.f), p.fh);
-    o[2] = fminf(fmaxf(c.x2, 0.f), p.fw);
-    o[3] = fminf(fmaxf(c.y2, 0.f), p.fh);
-    o[4] = c.score;
-    o[5] = (float)c.cls;
-    if (outi) outi[at] = c.slot;
+    keep_box(at, bx, c.slot, [&](float* o) {
+      o[0] = fminf(fmaxf(c.x1, 0.f), p.fw);
+      o[1] = fminf(fmaxf(c.y1, 0.f), p.fh);
+      o[2] = fminf(fmaxf(c.x2, 0.f), p.fw);
+      o[3] = fminf(fmaxf(c.y2, 0.f), p.fh);
+      o[4] = c.score;
+      o[5] = (float)c.cls;
+    });
   }
 };
 
@@ -233,33 +264,23 @@ static inline float tmr_far_bound(float thr) {
   return (float)(-log(1.0 - keep + 1e-7) + 9.0);
 }
 
-struct TmrScan {  // nms_greedy_scan's policy: ScanBox = {x, y, a, b, c, cls}, the covariance row of a frame-coordinate box and its class
-  const TmArgs& p;
-  const u64* skeys;
-  const u64* gkeys;
-  const float* frows;
-  float* outb;
-  int* outi;
-  float4* kbox;  // [keep]: x, y, a, b
-  float* kc;
-  int* kcls;
-  bool in_lds;
+struct TmrScan : TmBase<7> {  // nms_greedy_scan's policy: ScanBox = {x, y, a, b, c, cls}, the covariance row of a frame-coordinate box and its class
+  static constexpr int ROW = 7, SCORE = 5, KEEP_BYTES = TM_KEEP_BYTES;
+  static constexpr bool TAIL = false;
   typedef TmrCand Cand;
+  __device__ __forceinline__ TmrScan(const TmBase<7>& b) : TmBase<7>(b) {}
   __device__ __forceinline__ Cand fetch(int i, int n) const {
     Cand c{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0, -1};
     if (i < n) {
-      const u64 key = in_lds ? skeys[i] : gkeys[i];
-      c.slot = (int)(unsigned)(key & 0xffffffffull);
-      c.score = __uint_as_float(~(unsigned)(key >> 32));
-      const int tile = c.slot / p.max_det;
-      const float oy = (float)p.offs[2 * tile], ox = (float)p.offs[2 * tile + 1];
-      const float* q = frows + (size_t)c.slot * 7;
-      c.x = q[0] + ox;
-      c.y = q[1] + oy;
-      c.w = q[2];
-      c.h = q[3];
-      c.th = q[4];
-      c.cls = (int)q[6];
+      const Head h = head(i);
+      c.slot = h.slot;
+      c.score = h.score;
+      c.x = h.q[0] + h.ox;
+      c.y = h.q[1] + h.oy;
+      c.w = h.q[2];
+      c.h = h.q[3];
+      c.th = h.q[4];
+      c.cls = (int)h.q[6];
     }
     return c;
   }
@@ -279,23 +300,16 @@ struct TmrScan {  // nms_greedy_scan's policy: ScanBox = {x, y, a, b, c, cls}, t
     if (__ballot(open) == 0ull) return false;
     return open && rnms_probiou(ri, rj) >= p.thr;
   }
-  __device__ __forceinline__ ScanBox kept(int k) const {
-    const float4 kb = kbox[k];
-    return ScanBox{kb.x, kb.y, kb.z, kb.w, kc[k], kcls[k]};
-  }
   __device__ __forceinline__ void keep(int at, const Cand& c, const ScanBox& bx) const {
-    kbox[at] = make_float4(bx.x1, bx.y1, bx.x2, bx.y2);
-    kc[at] = bx.area;
-    kcls[at] = c.cls;
-    float* o = outb + (size_t)at * 7;  // clip_boxes on an xywh row, as dy_scale_rboxes: x and w to [0, frame_w], y and h to [0, frame_h]
-    o[0] = fminf(fmaxf(c.x, 0.f), p.fw);
-    o[1] = fminf(fmaxf(c.y, 0.f), p.fh);
-    o[2] = fminf(fmaxf(c.w, 0.f), p.fw);
-    o[3] = fminf(fmaxf(c.h, 0.f), p.fh);
-    o[4] = c.th;
-    o[5] = c.score;
-    o[6] = (float)c.cls;
-    if (outi) outi[at] = c.slot;
+    keep_box(at, bx, c.slot, [&](float* o) {  // clip_boxes on an xywh row, as dy_scale_rboxes: x and w to [0, frame_w], y and h to [0, frame_h]
+      o[0] = fminf(fmaxf(c.x, 0.f), p.fw);
+      o[1] = fminf(fmaxf(c.y, 0.f), p.fh);
+      o[2] = fminf(fmaxf(c.w, 0.f), p.fw);
+      o[3] = fminf(fmaxf(c.h, 0.f), p.fh);
+      o[4] = c.th;
+      o[5] = c.score;
+      o[6] = (float)c.cls;
+    });
   }
 };
 
@@ -305,8 +319,11 @@ struct TmFuseCand : TmCand {
 };
 
 struct TmFuseScan : TmScan {  // TmScan, and the sorted position of every kept row
-  int* kpos;                  // [keep]
+  static constexpr int KEEP_BYTES = TM_FUSE_KEEP_BYTES;
+  static constexpr bool TAIL = true;
+  int* kpos;  // [keep], behind kcls
   typedef TmFuseCand Cand;
+  __device__ __forceinline__ TmFuseScan(const TmBase<6>& b) : TmScan(b), kpos(b.kcls + b.p.keep) {}
   __device__ __forceinline__ Cand fetch(int i, int n) const {
     Cand c;
     static_cast<TmCand&>(c) = TmScan::fetch(i, n);
@@ -439,20 +456,19 @@ __device__ __forceinline__ void tm_fuse_tail(const TmArgs& p, const TmFuseScan& 
   }
 }
 
-// FUSE = false is dy_tile_merge's kernel; FUSE = true goes on behind the scan (dy_tile_fuse): a kernel of its own, the suppress path is at
-// 115 of its 128 VGPRs.  ROT = true is dy_tile_merge_rotated's: rows of 7 floats with the score in column 5, and the policy TmrScan.
-template <bool FUSE, bool ROT = false>
+// One instantiation per policy: TmScan (dy_tile_merge), TmFuseScan (dy_tile_fuse), TmrScan (dy_tile_merge_rotated).  The fusing merge is
+// a kernel of its own and not a run-time mode of TmScan's: the suppress path is at 115 of its 128 VGPRs.
+template <typename Pol>
 __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(const TmArgs p) {
-  static_assert(!(FUSE && ROT), "fusing merges are not built for oriented boxes");
-  constexpr int ROW = ROT ? 7 : 6, SCORE = ROT ? 5 : 4;
+  constexpr int ROW = Pol::ROW, SCORE = Pol::SCORE;
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
   u64* skeys = reinterpret_cast<u64*>(dyn_smem);  // [SL]
   u64* mrows = skeys + p.SL;                      // [64]
   u64* verdict = mrows + 64;                      // [TM_WAVES]
   int* ctr = reinterpret_cast<int*>(verdict + TM_WAVES);  // candidates of the frame, append cursor
   float4* kbox = reinterpret_cast<float4*>(dyn_smem + (size_t)p.SL * 8 + TM_FIXED_LDS);  // [keep]
-  float* kar = reinterpret_cast<float*>(kbox + p.keep);
-  int* kcls = reinterpret_cast<int*>(kar + p.keep);
+  float* k5 = reinterpret_cast<float*>(kbox + p.keep);
+  int* kcls = reinterpret_cast<int*>(k5 + p.keep);
   const int f = blockIdx.x;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -508,17 +524,9 @@ __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(const TmArgs p) 
 
   float* outb = p.out + (size_t)f * p.keep * ROW;
   int* outi = p.out_index ? p.out_index + (size_t)f * p.keep : nullptr;
-  if constexpr (ROT) {
-    const TmrScan pol{p, skeys, gkeys, frows, outb, outi, kbox, kar, kcls, in_lds};
-    nms_greedy_scan<TM_WAVES, 7>(pol, n, p.keep, mrows, verdict, outb, outi, p.out_count + f);
-  } else if constexpr (!FUSE) {
-    const TmScan pol{p, skeys, gkeys, frows, outb, outi, kbox, kar, kcls, in_lds};
-    nms_greedy_scan<TM_WAVES>(pol, n, p.keep, mrows, verdict, outb, outi, p.out_count + f);
-  } else {
-    const TmFuseScan pol{{p, skeys, gkeys, frows, outb, outi, kbox, kar, kcls, in_lds}, kcls + p.keep};
-    const int nk = nms_greedy_scan<TM_WAVES>(pol, n, p.keep, mrows, verdict, outb, outi, p.out_count + f);
-    tm_fuse_tail(p, pol, f, n, nk);
-  }
+  const Pol pol(TmBase<ROW>{p, skeys, gkeys, frows, outb, outi, kbox, k5, kcls, in_lds});
+  const int nk = nms_greedy_scan<TM_WAVES, ROW>(pol, n, p.keep, mrows, verdict, outb, outi, p.out_count + f);
+  if constexpr (Pol::TAIL) tm_fuse_tail(p, pol, f, n, nk);
 }
 
 }  // namespace dy
@@ -546,9 +554,26 @@ extern "C" int64_t dy_tile_merge_workspace_bytes(int32_t frames, int32_t tiles, 
   return (int64_t)frames * nms_next_pow2(tiles * max_det) * 8;
 }
 
-// The kernel arguments a checked descriptor describes (dy_tile_merge_desc / dy_tile_fuse_desc: the fields they share; `a` holds what only
-// the fusion has) and the launch.
-template <bool FUSE, bool ROT = false, typename Desc>
+// What the three descriptors share, by the fields they name alike.  `need`: the entry point's workspace size; `own`: its further required
+// pointers are set (`own_names`, as the message lists them).  What one entry point alone has (metric, mode, the wbf side limit) it checks itself.
+template <typename Desc>
+static int tm_check(const Desc* d, const char* who, int64_t need, bool own = true, const char* own_names = "") {
+  DY_REQUIRE(d && d->rows && d->counts && d->offsets_yx && d->out && d->out_count && own && d->workspace, DY_ERR_INVALID_ARG,
+             "%s: null pointer (rows / counts / offsets_yx / out / out_count / %sworkspace)", who, own_names);
+  DY_REQUIRE(d->frames > 0 && d->tiles > 0 && d->max_det > 0 && d->nc > 0 && d->frame_h > 0 && d->frame_w > 0 && d->merge_max_det > 0, DY_ERR_INVALID_ARG,
+             "%s: bad dims (frames %d, tiles %d, max_det %d, nc %d, frame %d x %d, merge_max_det %d)", who, d->frames, d->tiles, d->max_det, d->nc, d->frame_h,
+             d->frame_w, d->merge_max_det);
+  DY_REQUIRE(d->thr >= 0.f && d->thr <= 1.f, DY_ERR_INVALID_ARG, "%s: thr must be in [0,1]", who);
+  DY_REQUIRE((long long)d->tiles * d->max_det <= TM_MAX_SLOTS, DY_ERR_UNSUPPORTED, "%s: tiles * max_det = %lld > %d", who, (long long)d->tiles * d->max_det,
+             TM_MAX_SLOTS);
+  DY_REQUIRE(d->merge_max_det <= TM_MAX_KEEP, DY_ERR_UNSUPPORTED, "%s: merge_max_det %d > %d", who, d->merge_max_det, TM_MAX_KEEP);
+  DY_REQUIRE(d->workspace_bytes >= need, DY_ERR_WORKSPACE, "%s: workspace %lld < %lld bytes", who, (long long)d->workspace_bytes, (long long)need);
+  DY_REQUIRE(aligned16(d->workspace), DY_ERR_INVALID_ARG, "%s: workspace not 16-byte aligned", who);
+  return DY_OK;
+}
+
+// The kernel arguments a checked descriptor describes (the fields the three share; `a` holds what only the entry point's own has) and the launch.
+template <typename Pol, typename Desc>
 static int tm_launch(const Desc* d, TmArgs a, const char* who, dy_stream_t stream) {
   a.rows = d->rows;
   a.counts = d->counts;
@@ -564,36 +589,25 @@ static int tm_launch(const Desc* d, TmArgs a, const char* who, dy_stream_t strea
   a.fw = (float)d->frame_w;
   a.fh = (float)d->frame_h;
   a.thr = d->thr;
-  if constexpr (!ROT) a.metric = d->metric;
-  if constexpr (ROT) a.far = tmr_far_bound(d->thr);
   a.agnostic = d->agnostic ? 1 : 0;
   a.keep = d->merge_max_det;
   // LDS by need: the keys of every slot when they fit beside the kept list, the largest power of two that does otherwise
-  const size_t rest = (size_t)TM_FIXED_LDS + nms_align_up((size_t)a.keep * (FUSE ? TM_FUSE_KEEP_BYTES : TM_KEEP_BYTES), 16);
+  const size_t rest = (size_t)TM_FIXED_LDS + nms_align_up((size_t)a.keep * Pol::KEEP_BYTES, 16);
   a.SL = a.P < TM_MAX_LDS_KEYS ? a.P : TM_MAX_LDS_KEYS;
   while ((size_t)a.SL * 8 + rest > 160 * 1024) a.SL >>= 1;
   const size_t smem = (size_t)a.SL * 8 + rest;
-  static const hipError_t attr_once = hipFuncSetAttribute((const void*)tile_merge_kernel<FUSE, ROT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  static const hipError_t attr_once = hipFuncSetAttribute((const void*)tile_merge_kernel<Pol>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   (void)attr_once;
-  hipLaunchKernelGGL((tile_merge_kernel<FUSE, ROT>), dim3((unsigned)d->frames), dim3(TM_THREADS), smem, reinterpret_cast<hipStream_t>(stream), a);
+  hipLaunchKernelGGL(tile_merge_kernel<Pol>, dim3((unsigned)d->frames), dim3(TM_THREADS), smem, reinterpret_cast<hipStream_t>(stream), a);
   return check_launch(who);
 }
 
 extern "C" int32_t dy_tile_merge(const dy_tile_merge_desc* d, dy_stream_t stream) {
-  DY_REQUIRE(d && d->rows && d->counts && d->offsets_yx && d->out && d->out_count && d->workspace, DY_ERR_INVALID_ARG,
-             "dy_tile_merge: null pointer (rows / counts / offsets_yx / out / out_count / workspace)");
-  DY_REQUIRE(d->frames > 0 && d->tiles > 0 && d->max_det > 0 && d->nc > 0 && d->frame_h > 0 && d->frame_w > 0 && d->merge_max_det > 0, DY_ERR_INVALID_ARG,
-             "dy_tile_merge: bad dims (frames %d, tiles %d, max_det %d, nc %d, frame %d x %d, merge_max_det %d)", d->frames, d->tiles, d->max_det, d->nc,
-             d->frame_h, d->frame_w, d->merge_max_det);
+  if (const int s = tm_check(d, "dy_tile_merge", d ? dy_tile_merge_workspace_bytes(d->frames, d->tiles, d->max_det) : 0)) return s;
   DY_REQUIRE(d->metric == 0 || d->metric == 1, DY_ERR_INVALID_ARG, "dy_tile_merge: metric %d (0 = IoU, 1 = IoS)", d->metric);
-  DY_REQUIRE(d->thr >= 0.f && d->thr <= 1.f, DY_ERR_INVALID_ARG, "dy_tile_merge: thr must be in [0,1]");
-  DY_REQUIRE((long long)d->tiles * d->max_det <= TM_MAX_SLOTS, DY_ERR_UNSUPPORTED, "dy_tile_merge: tiles * max_det = %lld > %d", (long long)d->tiles * d->max_det,
-             TM_MAX_SLOTS);
-  DY_REQUIRE(d->merge_max_det <= TM_MAX_KEEP, DY_ERR_UNSUPPORTED, "dy_tile_merge: merge_max_det %d > %d", d->merge_max_det, TM_MAX_KEEP);
-  const int64_t need = dy_tile_merge_workspace_bytes(d->frames, d->tiles, d->max_det);
-  DY_REQUIRE(d->workspace_bytes >= need, DY_ERR_WORKSPACE, "dy_tile_merge: workspace %lld < %lld bytes", (long long)d->workspace_bytes, (long long)need);
-  DY_REQUIRE(aligned16(d->workspace), DY_ERR_INVALID_ARG, "dy_tile_merge: workspace not 16-byte aligned");
-  return tm_launch<false>(d, TmArgs{}, "dy_tile_merge", stream);
+  TmArgs a{};
+  a.metric = d->metric;
+  return tm_launch<TmScan>(d, a, "dy_tile_merge", stream);
 }
 
 extern "C" int64_t dy_tile_fuse_workspace_bytes(int32_t frames, int32_t tiles, int32_t max_det, int32_t merge_max_det) {
@@ -603,27 +617,18 @@ extern "C" int64_t dy_tile_fuse_workspace_bytes(int32_t frames, int32_t tiles, i
 }
 
 extern "C" int32_t dy_tile_fuse(const dy_tile_fuse_desc* d, dy_stream_t stream) {
-  DY_REQUIRE(d && d->rows && d->counts && d->offsets_yx && d->out && d->out_count && d->out_members && d->workspace, DY_ERR_INVALID_ARG,
-             "dy_tile_fuse: null pointer (rows / counts / offsets_yx / out / out_count / out_members / workspace)");
-  DY_REQUIRE(d->frames > 0 && d->tiles > 0 && d->max_det > 0 && d->nc > 0 && d->frame_h > 0 && d->frame_w > 0 && d->merge_max_det > 0, DY_ERR_INVALID_ARG,
-             "dy_tile_fuse: bad dims (frames %d, tiles %d, max_det %d, nc %d, frame %d x %d, merge_max_det %d)", d->frames, d->tiles, d->max_det, d->nc,
-             d->frame_h, d->frame_w, d->merge_max_det);
+  const int64_t need = d ? dy_tile_fuse_workspace_bytes(d->frames, d->tiles, d->max_det, d->merge_max_det) : 0;
+  if (const int s = tm_check(d, "dy_tile_fuse", need, d && d->out_members, "out_members / ")) return s;
   DY_REQUIRE(d->metric == 0 || d->metric == 1, DY_ERR_INVALID_ARG, "dy_tile_fuse: metric %d (0 = IoU, 1 = IoS)", d->metric);
   DY_REQUIRE(d->mode == TM_UNION || d->mode == TM_WBF, DY_ERR_INVALID_ARG, "dy_tile_fuse: mode %d (1 = union, 2 = wbf; suppression is dy_tile_merge)", d->mode);
-  DY_REQUIRE(d->thr >= 0.f && d->thr <= 1.f, DY_ERR_INVALID_ARG, "dy_tile_fuse: thr must be in [0,1]");
-  DY_REQUIRE((long long)d->tiles * d->max_det <= TM_MAX_SLOTS, DY_ERR_UNSUPPORTED, "dy_tile_fuse: tiles * max_det = %lld > %d", (long long)d->tiles * d->max_det,
-             TM_MAX_SLOTS);
-  DY_REQUIRE(d->merge_max_det <= TM_MAX_KEEP, DY_ERR_UNSUPPORTED, "dy_tile_fuse: merge_max_det %d > %d", d->merge_max_det, TM_MAX_KEEP);
   DY_REQUIRE(d->mode != TM_WBF || (d->frame_h <= TM_WBF_MAX_SIDE && d->frame_w <= TM_WBF_MAX_SIDE), DY_ERR_UNSUPPORTED,
              "dy_tile_fuse: wbf on a frame of %d x %d, sides above %d are beyond its integer sums", d->frame_h, d->frame_w, TM_WBF_MAX_SIDE);
-  const int64_t need = dy_tile_fuse_workspace_bytes(d->frames, d->tiles, d->max_det, d->merge_max_det);
-  DY_REQUIRE(d->workspace_bytes >= need, DY_ERR_WORKSPACE, "dy_tile_fuse: workspace %lld < %lld bytes", (long long)d->workspace_bytes, (long long)need);
-  DY_REQUIRE(aligned16(d->workspace), DY_ERR_INVALID_ARG, "dy_tile_fuse: workspace not 16-byte aligned");
   TmArgs a{};
+  a.metric = d->metric;
   a.mode = d->mode;
   a.out_members = d->out_members;
   a.acc = reinterpret_cast<u64*>(reinterpret_cast<unsigned char*>(d->workspace) + dy_tile_merge_workspace_bytes(d->frames, d->tiles, d->max_det));
-  return tm_launch<true>(d, a, "dy_tile_fuse", stream);
+  return tm_launch<TmFuseScan>(d, a, "dy_tile_fuse", stream);
 }
 
 extern "C" int64_t dy_tile_merge_rotated_workspace_bytes(int32_t frames, int32_t tiles, int32_t max_det) {
@@ -631,17 +636,8 @@ extern "C" int64_t dy_tile_merge_rotated_workspace_bytes(int32_t frames, int32_t
 }
 
 extern "C" int32_t dy_tile_merge_rotated(const dy_tile_merge_rotated_desc* d, dy_stream_t stream) {
-  DY_REQUIRE(d && d->rows && d->counts && d->offsets_yx && d->out && d->out_count && d->workspace, DY_ERR_INVALID_ARG,
-             "dy_tile_merge_rotated: null pointer (rows / counts / offsets_yx / out / out_count / workspace)");
-  DY_REQUIRE(d->frames > 0 && d->tiles > 0 && d->max_det > 0 && d->nc > 0 && d->frame_h > 0 && d->frame_w > 0 && d->merge_max_det > 0, DY_ERR_INVALID_ARG,
-             "dy_tile_merge_rotated: bad dims (frames %d, tiles %d, max_det %d, nc %d, frame %d x %d, merge_max_det %d)", d->frames, d->tiles, d->max_det,
-             d->nc, d->frame_h, d->frame_w, d->merge_max_det);
-  DY_REQUIRE(d->thr >= 0.f && d->thr <= 1.f, DY_ERR_INVALID_ARG, "dy_tile_merge_rotated: thr must be in [0,1]");
-  DY_REQUIRE((long long)d->tiles * d->max_det <= TM_MAX_SLOTS, DY_ERR_UNSUPPORTED, "dy_tile_merge_rotated: tiles * max_det = %lld > %d",
-             (long long)d->tiles * d->max_det, TM_MAX_SLOTS);
-  DY_REQUIRE(d->merge_max_det <= TM_MAX_KEEP, DY_ERR_UNSUPPORTED, "dy_tile_merge_rotated: merge_max_det %d > %d", d->merge_max_det, TM_MAX_KEEP);
-  const int64_t need = dy_tile_merge_rotated_workspace_bytes(d->frames, d->tiles, d->max_det);
-  DY_REQUIRE(d->workspace_bytes >= need, DY_ERR_WORKSPACE, "dy_tile_merge_rotated: workspace %lld < %lld bytes", (long long)d->workspace_bytes, (long long)need);
-  DY_REQUIRE(aligned16(d->workspace), DY_ERR_INVALID_ARG, "dy_tile_merge_rotated: workspace not 16-byte aligned");
-  return tm_launch<false, true>(d, TmArgs{}, "dy_tile_merge_rotated", stream);
+  if (const int s = tm_check(d, "dy_tile_merge_rotated", d ? dy_tile_merge_rotated_workspace_bytes(d->frames, d->tiles, d->max_det) : 0)) return s;
+  TmArgs a{};
+  a.far = tmr_far_bound(d->thr);
+  return tm_launch<TmrScan>(d, a, "dy_tile_merge_rotated", stream);
 }

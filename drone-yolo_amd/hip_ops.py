@@ -2008,9 +2008,67 @@ class TileMergeBuffers:
         self.members = torch.empty((self.batch, self.max_det), dtype=torch.int32, device=self.out.device)
 
 
-_TILE_MERGE_BUFS: dict = {}
+class RTileMergeBuffers(TileMergeBuffers):
+    """``TileMergeBuffers`` of ``dy_tile_merge_rotated``: ``out`` (frames, merge_max_det, 7) = x, y, w, h, theta, conf, cls; ``out`` / ``count`` /
+    ``index`` / ``batch`` / ``max_det`` mean what they mean on ``RNmsBuffers``.  The workspace is ``dy_tile_merge``'s (the sort keys)."""
+
+    ROW = 7
+
+    def enable_fuse(self) -> None:
+        raise NotImplementedError("tile_merge_rotated: fusing merges (union / wbf) are not built for oriented boxes")
+
+
+_TILE_MERGE_BUFS: dict = {}  # (buffer class, device, frames, tiles, max_det, merge_max_det) -> buffers
 TILE_MERGE_METRICS = {"iou": 0, "ios": 1}
 TILE_MERGE_MODES = {"suppress": 0, "union": 1, "wbf": 2}
+
+
+def _tile_merge_inputs(who: str, row: int, nms_bufs, offsets: torch.Tensor, K: int):
+    """The per-tile rows (``row`` floats wide) and counts of ``nms_bufs``, checked with ``offsets`` against ``K`` tiles a frame: rows, counts,
+    frames, per-tile max_det."""
+    rows, counts = (nms_bufs.out, nms_bufs.count) if hasattr(nms_bufs, "out") else nms_bufs
+    require_device(rows, "per-tile rows")
+    require_device(counts, "per-tile counts")
+    require_device(offsets, "tile offsets")
+    K = int(K)
+    if rows.dtype != torch.float32 or rows.dim() != 3 or rows.shape[2] != row or not rows.is_contiguous() or rows.shape[0] % K or counts.dtype != torch.int32 \
+            or counts.numel() != rows.shape[0] or not counts.is_contiguous():
+        raise ValueError(f"{who}: rows must be contiguous fp32 (F * {K}, max_det, {row}) with as many int32 counts")
+    if offsets.dtype != torch.int32 or tuple(offsets.shape) != (K, 2) or not offsets.is_contiguous():
+        raise ValueError(f"{who}: offsets must be a contiguous int32 ({K}, 2) device tensor")
+    return rows, counts, rows.shape[0] // K, int(rows.shape[1])
+
+
+def _tile_merge_bufs(cls, bufs, device, sizes: Tuple[int, int, int, int]):
+    """``bufs`` when it has ``cls``'s rows on ``device`` at ``sizes`` = (frames, tiles, max_det, merge_max_det), else the persistent ``cls``
+    buffers of that device and those sizes."""
+    if bufs is None or bufs.ROW != cls.ROW or (bufs.batch, bufs.tiles, bufs.tile_max_det, bufs.max_det) != sizes or bufs.out.device != device:
+        key = (cls, device) + sizes
+        bufs = _TILE_MERGE_BUFS.get(key)
+        if bufs is None:
+            bufs = _TILE_MERGE_BUFS[key] = cls(*sizes, device)
+    return bufs
+
+
+def _tile_merge_code(what: str, value, names: dict) -> int:
+    """The code of a metric / mode given by name (any case) or by code."""
+    if isinstance(value, str):
+        if value.lower() not in names:
+            raise ValueError(f"tile_merge: {what} '{value}', expected one of {sorted(names)}")
+        return names[value.lower()]
+    return int(value)
+
+
+def _tile_merge_launch(fn, d, rows, counts, offsets, frame_hw, nc, thr, agnostic, bufs: TileMergeBuffers, workspace: torch.Tensor) -> TileMergeBuffers:
+    """Fill what the three merge descriptors share and launch ``fn`` on ``d``."""
+    d.rows, d.counts, d.offsets_yx = rows.data_ptr(), counts.data_ptr(), offsets.data_ptr()
+    d.frames, d.tiles, d.max_det, d.nc = bufs.batch, bufs.tiles, bufs.tile_max_det, int(nc)
+    d.frame_h, d.frame_w = int(frame_hw[0]), int(frame_hw[1])
+    d.thr, d.agnostic, d.merge_max_det = float(thr), int(bool(agnostic)), bufs.max_det
+    d.out, d.out_count, d.out_index = bufs.out.data_ptr(), bufs.count.data_ptr(), bufs.index.data_ptr()
+    d.workspace, d.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    _launch(fn, (C.byref(d),), keep=(d, rows, counts, offsets, bufs))
+    return bufs
 
 
 def tile_merge(nms_bufs, offsets: torch.Tensor, K: int, frame_hw: Tuple[int, int], nc: int, thr: float, metric=0, agnostic: bool = False,
@@ -2021,65 +2079,20 @@ def tile_merge(nms_bufs, offsets: torch.Tensor, K: int, frame_hw: Tuple[int, int
     and 2 / "wbf" go through one ``dy_tile_fuse`` launch instead: the same rows are kept, each with the bounding box / the score-weighted mean
     of itself and the rows it absorbed, and ``bufs.members`` counts them.  Returns rows in frame pixels, clamped to the frame, in buffers
     that persist per (F, K, max_det, merge_max_det): the next call with the same sizes overwrites them."""
-    rows, counts = (nms_bufs.out, nms_bufs.count) if hasattr(nms_bufs, "out") else nms_bufs
-    require_device(rows, "per-tile rows")
-    require_device(counts, "per-tile counts")
-    require_device(offsets, "tile offsets")
-    K = int(K)
-    if rows.dtype != torch.float32 or rows.dim() != 3 or rows.shape[2] != 6 or not rows.is_contiguous() or rows.shape[0] % K or counts.dtype != torch.int32 \
-            or counts.numel() != rows.shape[0] or not counts.is_contiguous():
-        raise ValueError(f"tile_merge: rows must be contiguous fp32 (F * {K}, max_det, 6) with as many int32 counts")
-    if offsets.dtype != torch.int32 or tuple(offsets.shape) != (K, 2) or not offsets.is_contiguous():
-        raise ValueError(f"tile_merge: offsets must be a contiguous int32 ({K}, 2) device tensor")
-    if isinstance(metric, str):
-        if metric.lower() not in TILE_MERGE_METRICS:
-            raise ValueError(f"tile_merge: metric '{metric}', expected one of {sorted(TILE_MERGE_METRICS)}")
-        metric = TILE_MERGE_METRICS[metric.lower()]
-    if isinstance(mode, str):
-        if mode.lower() not in TILE_MERGE_MODES:
-            raise ValueError(f"tile_merge: mode '{mode}', expected one of {sorted(TILE_MERGE_MODES)}")
-        mode = TILE_MERGE_MODES[mode.lower()]
-    if int(mode) not in TILE_MERGE_MODES.values():
+    rows, counts, f, md = _tile_merge_inputs("tile_merge", 6, nms_bufs, offsets, K)
+    metric = _tile_merge_code("metric", metric, TILE_MERGE_METRICS)
+    mode = _tile_merge_code("mode", mode, TILE_MERGE_MODES)
+    if mode not in TILE_MERGE_MODES.values():
         raise ValueError(f"tile_merge: mode {mode}, expected 0 (suppress), 1 (union) or 2 (wbf)")
-    f, md = rows.shape[0] // K, int(rows.shape[1])
-    if bufs is None or (bufs.batch, bufs.tiles, bufs.tile_max_det, bufs.max_det) != (f, K, md, int(merge_max_det)) or bufs.out.device != rows.device:
-        key = (rows.device, f, K, md, int(merge_max_det))
-        bufs = _TILE_MERGE_BUFS.get(key)
-        if bufs is None:
-            bufs = _TILE_MERGE_BUFS[key] = TileMergeBuffers(f, K, md, int(merge_max_det), rows.device)
-    fuse = int(mode) != 0
-    if fuse:
+    bufs = _tile_merge_bufs(TileMergeBuffers, bufs, rows.device, (f, int(K), md, int(merge_max_det)))
+    if mode == 0:
+        d, fn, workspace = TileMergeDesc(), lib().dy_tile_merge, bufs.workspace
+    else:
         bufs.enable_fuse()
-    d = TileFuseDesc() if fuse else TileMergeDesc()
-    d.rows, d.counts, d.offsets_yx = rows.data_ptr(), counts.data_ptr(), offsets.data_ptr()
-    d.frames, d.tiles, d.max_det, d.nc = f, K, md, int(nc)
-    d.frame_h, d.frame_w = int(frame_hw[0]), int(frame_hw[1])
-    d.thr, d.metric, d.agnostic, d.merge_max_det = float(thr), int(metric), int(bool(agnostic)), int(merge_max_det)
-    d.out, d.out_count, d.out_index = bufs.out.data_ptr(), bufs.count.data_ptr(), bufs.index.data_ptr()
-    if fuse:
-        d.mode, d.out_members = int(mode), bufs.members.data_ptr()
-        d.workspace, d.workspace_bytes = bufs.fuse_workspace.data_ptr(), bufs.fuse_workspace.numel()
-        _launch(lib().dy_tile_fuse, (C.byref(d),), keep=(d, rows, counts, offsets, bufs))
-        return bufs
-    d.workspace, d.workspace_bytes = bufs.workspace.data_ptr(), bufs.workspace.numel()
-    _launch(lib().dy_tile_merge, (C.byref(d),), keep=(d, rows, counts, offsets, bufs))
-    return bufs
-
-
-class RTileMergeBuffers(TileMergeBuffers):
-    """``TileMergeBuffers`` of ``dy_tile_merge_rotated``: ``out`` (frames, merge_max_det, 7) = x, y, w, h, theta, conf, cls; ``out`` / ``count`` /
-    ``index`` / ``batch`` / ``max_det`` mean what they mean on ``RNmsBuffers``.  The workspace is ``dy_tile_merge``'s (the sort keys)."""
-
-    ROW = 7
-
-    def __init__(self, frames: int, tiles: int, tile_max_det: int, merge_max_det: int, device):
-        super().__init__(frames, tiles, tile_max_det, merge_max_det, device)
-
-    def enable_fuse(self) -> None:
-        raise NotImplementedError("tile_merge_rotated: fusing merges (union / wbf) are not built for oriented boxes")
-
-
-_RTILE_MERGE_BUFS: dict = {}
+        d, fn, workspace = TileFuseDesc(), lib().dy_tile_fuse, bufs.fuse_workspace
+        d.mode, d.out_members = mode, bufs.members.data_ptr()
+    d.metric = metric
+    return _tile_merge_launch(fn, d, rows, counts, offsets, frame_hw, nc, thr, agnostic, bufs, workspace)
 
 
 def tile_merge_rotated(nms_bufs, offsets: torch.Tensor, K: int, frame_hw: Tuple[int, int], nc: int, thr: float, agnostic: bool = False,
@@ -2089,31 +2102,9 @@ def tile_merge_rotated(nms_bufs, offsets: torch.Tensor, K: int, frame_hw: Tuple[
     ``offsets``: device int32 (K, 2) = (y, x); ``thr``: the ProbIoU at or above which a kept row of the same class (any class with
     ``agnostic``) suppresses a candidate -- greedily, as ``tile_merge`` does.  Returns rows in frame pixels, centre and size clamped to the
     frame, in buffers that persist per (F, K, max_det, merge_max_det): the next call with the same sizes overwrites them."""
-    rows, counts = (nms_bufs.out, nms_bufs.count) if hasattr(nms_bufs, "out") else nms_bufs
-    require_device(rows, "per-tile rows")
-    require_device(counts, "per-tile counts")
-    require_device(offsets, "tile offsets")
-    K = int(K)
-    if rows.dtype != torch.float32 or rows.dim() != 3 or rows.shape[2] != 7 or not rows.is_contiguous() or rows.shape[0] % K or counts.dtype != torch.int32 \
-            or counts.numel() != rows.shape[0] or not counts.is_contiguous():
-        raise ValueError(f"tile_merge_rotated: rows must be contiguous fp32 (F * {K}, max_det, 7) with as many int32 counts")
-    if offsets.dtype != torch.int32 or tuple(offsets.shape) != (K, 2) or not offsets.is_contiguous():
-        raise ValueError(f"tile_merge_rotated: offsets must be a contiguous int32 ({K}, 2) device tensor")
-    f, md = rows.shape[0] // K, int(rows.shape[1])
-    if bufs is None or bufs.ROW != 7 or (bufs.batch, bufs.tiles, bufs.tile_max_det, bufs.max_det) != (f, K, md, int(merge_max_det)) or bufs.out.device != rows.device:
-        key = (rows.device, f, K, md, int(merge_max_det))
-        bufs = _RTILE_MERGE_BUFS.get(key)
-        if bufs is None:
-            bufs = _RTILE_MERGE_BUFS[key] = RTileMergeBuffers(f, K, md, int(merge_max_det), rows.device)
-    d = _lib.TileMergeRotatedDesc()
-    d.rows, d.counts, d.offsets_yx = rows.data_ptr(), counts.data_ptr(), offsets.data_ptr()
-    d.frames, d.tiles, d.max_det, d.nc = f, K, md, int(nc)
-    d.frame_h, d.frame_w = int(frame_hw[0]), int(frame_hw[1])
-    d.thr, d.agnostic, d.merge_max_det = float(thr), int(bool(agnostic)), int(merge_max_det)
-    d.out, d.out_count, d.out_index = bufs.out.data_ptr(), bufs.count.data_ptr(), bufs.index.data_ptr()
-    d.workspace, d.workspace_bytes = bufs.workspace.data_ptr(), bufs.workspace.numel()
-    _launch(lib().dy_tile_merge_rotated, (C.byref(d),), keep=(d, rows, counts, offsets, bufs))
-    return bufs
+    rows, counts, f, md = _tile_merge_inputs("tile_merge_rotated", 7, nms_bufs, offsets, K)
+    bufs = _tile_merge_bufs(RTileMergeBuffers, bufs, rows.device, (f, int(K), md, int(merge_max_det)))
+    return _tile_merge_launch(lib().dy_tile_merge_rotated, _lib.TileMergeRotatedDesc(), rows, counts, offsets, frame_hw, nc, thr, agnostic, bufs, bufs.workspace)
 
 
 def augment_batch(src: torch.Tensor, table: torch.Tensor, s: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:

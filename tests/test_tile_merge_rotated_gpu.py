@@ -17,7 +17,8 @@ import torch
 from drone_yolo_amd import _lib
 from drone_yolo_amd import hip_ops as H
 from tests import _tile_rot_util as T
-from tests._tile_util import block_frame
+from tests._fuse_util import fuse_ref
+from tests._tile_util import IOU_THR, block_frame, merge_ref
 from tests._util import golden
 from tests.test_obb_gpu import _yolo
 
@@ -117,6 +118,39 @@ def test_tile_merge_rotated_is_deterministic_and_leaves_no_stale_rows(device):
     H.tile_merge_rotated((rows, fewer), offs, K, hw, nc, T.THR, False, 1000, bufs=a)
     _assert_equal(a, T.merge_ref_rotated(host_rows, fewer.cpu().numpy(), host_offs, hw, T.THR, False, 1000), 1000, "reused buffers")
     assert int(a.count[0]) == 0 and not bool(a.out[0].any()) and bool((a.index[0] == -1).all()) and 0 < int(a.count[2]) <= 5 * K
+
+
+def test_one_buffer_cache_keeps_the_three_merges_apart(device):
+    """``tile_merge``, ``tile_merge_rotated`` and ``tile_merge(mode="union")`` at one (F, K, max_det, merge_max_det) = (1, 1, 8, 16), forwards and
+    backwards: the cache they share hands each its own class of buffers (6 / 7 / 6 floats a row), the same object to a repeated call, and every
+    result is its restatement's -- the suppressing call's also once ``members`` exists.  Three rows per kind: two of one class that overlap above
+    the threshold (IoU 380 / 420 against 0.6; views of one oriented box half a pixel apart) and one far from both."""
+    hw, K, md, keep, nc = (64, 64), 1, 8, 16, 3
+    axis, rot = np.zeros((1, md, 6), np.float32), np.zeros((1, md, 7), np.float32)
+    axis[0, :3] = [[10, 10, 30, 30, 0.9, 1], [11, 10, 31, 30, 0.8, 1], [40, 40, 60, 60, 0.7, 1]]
+    rot[0, :3] = [[20, 20, 20, 10, 0.3, 0.9, 1], [20.5, 20.25, 20, 10, 0.3, 0.8, 1], [48, 48, 20, 10, 0.3, 0.7, 1]]
+    counts, offs = np.array([3], np.int32), np.zeros((1, 2), np.int32)
+    kept, p64, p32 = T.greedy64(rot, counts, offs, T.THR, False, keep)
+    m, dist = T.margin(p64, p32, T.THR)
+    assert len(p64) == 2 and kept[0].tolist() == [0, 2] and dist >= m, (p64, m, dist)  # both decided pairs keep the margin from the threshold
+    exp = {"suppress": merge_ref(axis, counts, offs, hw, IOU_THR, 0, False, keep), "union": fuse_ref(axis, counts, offs, hw, IOU_THR, 0, False, keep, "union"),
+           "rotated": T.merge_ref_rotated(rot, counts, offs, hw, T.THR, False, keep)}
+    assert all(e[1][0] == 2 and e[2][0, :2].tolist() == [0, 2] for e in exp.values()) and exp["union"][3][0, :3].tolist() == [2, 1, 0]
+    da, dr, dc, do = _dev((axis, rot, counts, offs), device)
+    calls = {"suppress": lambda: H.tile_merge((da, dc), do, K, hw, nc, IOU_THR, 0, False, keep),
+             "rotated": lambda: H.tile_merge_rotated((dr, dc), do, K, hw, nc, T.THR, False, keep),
+             "union": lambda: H.tile_merge((da, dc), do, K, hw, nc, IOU_THR, 0, False, keep, mode="union")}
+    seen = {}
+    for kind in ("suppress", "rotated", "union", "union", "rotated", "suppress"):
+        got = calls[kind]()
+        cls, row = (H.RTileMergeBuffers, 7) if kind == "rotated" else (H.TileMergeBuffers, 6)
+        assert type(got) is cls and got.out.shape == (1, keep, row), kind
+        assert seen.setdefault(kind, got) is got, f"{kind}: a repeated call returned other buffers"
+        _assert_equal(got, exp[kind][:3], keep, kind)
+        if kind == "union":
+            assert np.array_equal(got.members.cpu().numpy(), exp[kind][3])
+    assert seen["rotated"] is not seen["suppress"] and seen["rotated"] is not seen["union"]
+    assert seen["suppress"].members is not None and seen["rotated"].members is None
 
 
 # ---- tile= through YOLO.predict on an -obb model -----------------------------------------------------------------------------------------
