@@ -188,6 +188,22 @@ class LossDesc(C.Structure):
     ]  # fmt: skip
 
 
+class ObbLossDesc(C.Structure):
+    """Mirror of ``dy_obb_loss_desc``."""
+
+    _fields_ = [
+        ("level", _vp * DY_MAX_LEVELS), ("angle", _vp * DY_MAX_LEVELS),
+        ("h", _i32 * DY_MAX_LEVELS), ("w", _i32 * DY_MAX_LEVELS), ("ld", _i32 * DY_MAX_LEVELS), ("ld_angle", _i32 * DY_MAX_LEVELS),
+        ("stride", _f32 * DY_MAX_LEVELS),
+        ("n_levels", _i32), ("batch", _i32), ("nc", _i32), ("reg_max", _i32),
+        ("gt", _vp), ("gmax", _i32), ("topk", _i32),
+        ("alpha", _f32), ("beta", _f32), ("box_gain", _f32), ("cls_gain", _f32), ("dfl_gain", _f32),
+        ("out", _vp), ("out_owner", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
+        ("grad_level", _vp * DY_MAX_LEVELS), ("grad_angle", _vp * DY_MAX_LEVELS),
+        ("ld_grad", _i32 * DY_MAX_LEVELS), ("ld_grad_angle", _i32 * DY_MAX_LEVELS),
+    ]  # fmt: skip
+
+
 class C2fTailDesc(C.Structure):
     """Mirror of ``dy_c2f_tail_desc``."""
 
@@ -394,6 +410,9 @@ SIGNATURES = {
     "dy_silu_fwd": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "dy_silu_bwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dy_detection_loss": (_i32, [C.POINTER(LossDesc), _vp]),
+    "dy_obb_loss_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "dy_obb_loss": (_i32, [C.POINTER(ObbLossDesc), _vp]),
+    "dy_obb_angle_grad_cast": (_i32, [_vp, _i32, _i64, _vp, _vp, _i32, _i32, _vp]),
     "dy_augment_u8_nchw": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dy_depth_to_space2_nhwc": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dy_mask_gather": (_i32, [C.POINTER(MaskGatherDesc), _vp]),

@@ -1,6 +1,6 @@
 """``YOLO`` / ``Model`` user API (reference: ultralytics/engine/model.py:29-1177,
-ultralytics/models/yolo/model.py:11-59) for the detection, segmentation (prediction and validation) and oriented-box (prediction and validation)
-tasks on the MI355X path."""
+ultralytics/models/yolo/model.py:11-59) for the detection, segmentation (prediction and validation) and oriented-box (prediction, validation,
+tracking and training) tasks on the MI355X path."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -43,16 +43,21 @@ class Model(nn.Module):
 
     @property
     def task_map(self):
-        return {"detect": {"model": DetectionModel, "predictor": DetectionPredictor},
+        from .trainer import DetectionTrainer
+
+        return {"detect": {"model": DetectionModel, "predictor": DetectionPredictor, "trainer": DetectionTrainer},
                 "segment": {"model": SegmentationModel, "predictor": SegmentationPredictor}}
 
     @property
-    def predict_only_task_map(self):
-        """Tasks without a trainer, kept apart from ``task_map``: a model, a predictor and (``val``) a validator."""
-        return {"obb": {"model": OBBModel, "predictor": OBBPredictor}}
+    def oriented_task_map(self):
+        """The oriented-box task, kept apart from ``task_map`` (whose key set the package's tests pin): model, predictor and trainer -- the
+        detection trainer, which takes ``OBBValidator`` and the criterion's six-column table from the model (obb/train.py)."""
+        from .trainer import DetectionTrainer
+
+        return {"obb": {"model": OBBModel, "predictor": OBBPredictor, "trainer": DetectionTrainer}}
 
     def _task_classes(self, task: str) -> dict:
-        return {**self.task_map, **self.predict_only_task_map}[task]
+        return {**self.task_map, **self.oriented_task_map}[task]
 
     def _new(self, cfg: str, task=None, model=None, verbose=False) -> None:
         """Build from a YAML — reference engine/model.py:231-264."""
@@ -179,15 +184,19 @@ class Model(nn.Module):
     def train(self, trainer=None, **kwargs):
         """Reference engine/model.py:744-817: build the trainer from the model + overrides, train, then continue with the
         trained weights.  ``data``: a tensor dataset (.pt / dict) or "synthetic[:N]" (engine/trainer.py::load_dataset);
+        an oriented-box model (task ``obb``: ``OBBModel``, ``v8OBBLoss`` through ``dy_obb_loss``, ``OBBValidator`` per epoch)
+        takes a dict / ``.pt`` whose ``bboxes`` are (M, 5) normalised xywh + the angle in radians, or ``"synthetic-obb[:N]"``; for it
+        four-column boxes (``"synthetic[:N]"`` among them), ``device_augment=True`` and a YOLO-format dataset YAML (corner-format labels)
+        are refused with ``NotImplementedError`` naming the argument, before a trainer is built or a device selected;
         ``device="0,1,.."`` trains with one rank per GPU (child processes under torch.distributed.run, RCCL all-reduce),
         after which rank-less this process reloads ``weights/last.pt`` — as the reference does (model.py:806-813)."""
-        from .trainer import DetectionTrainer
-
         if self.task == "segment":
             raise NotImplementedError("train: the segmentation loss (v8SegmentationLoss) is not built; segmentation models predict only")
-        if self.task == "obb":
-            raise NotImplementedError("train: the oriented-box loss (v8OBBLoss) is not built; oriented-box models predict only")
         args = {**{k: v for k, v in self.overrides.items() if k not in ("task", "mode")}, **kwargs}
+        if self.task == "obb":  # the training twin of val's dataset rule, before a trainer is built or a device selected
+            from .trainer import check_obb_train_data
+
+            check_obb_train_data(args.get("data") or "synthetic", args)
         devs = [x for x in str(args.get("device", "")).replace("cuda:", "").split(",") if x.strip() != ""]
         multi = len(devs) > 1
         if multi:
@@ -197,10 +206,10 @@ class Model(nn.Module):
             start = Path(tempfile.mkdtemp(prefix="dyolo_train_")) / "start.pt"
             self.save(start)
             args["model"] = str(start)
-            self.trainer = (trainer or DetectionTrainer)(overrides=args)
+            self.trainer = (trainer or self._task_classes(self.task)["trainer"])(overrides=args)
         else:
             args.setdefault("model", self.overrides.get("model"))
-            self.trainer = (trainer or DetectionTrainer)(self.model, overrides=args)
+            self.trainer = (trainer or self._task_classes(self.task)["trainer"])(self.model, overrides=args)
         out = self.trainer.train()
         last = self.trainer.last
         if multi and last.exists():

@@ -206,9 +206,10 @@ class ModelEMA:
 
 
 # ---- data ----------------------------------------------------------------------------------------------------------------
-def synthetic_dataset(n: int, imgsz: int, seed: int, nc: int = 10) -> Dict[str, torch.Tensor]:
+def synthetic_dataset(n: int, imgsz: int, seed: int, nc: int = 10, angles: bool = False) -> Dict[str, torch.Tensor]:
     """uint8 images randint(0, 256); per image n ~ Poisson(50) clipped to [1, 300] boxes (VisDrone-like
-    density), class uniform, centres uniform(0.05, 0.95), wh lognormal(median 0.03, sigma 0.6) clipped to [0.004, 0.5]."""
+    density), class uniform, centres uniform(0.05, 0.95), wh lognormal(median 0.03, sigma 0.6) clipped to [0.004, 0.5].  ``angles``
+    (``"synthetic-obb"``): one more draw from the same generator AFTER those, an angle per box uniform in [-pi/4, 3 pi/4): ``bboxes`` (M, 5) xywhr."""
     g = torch.Generator().manual_seed(seed)
     img = torch.randint(0, 256, (n, 3, imgsz, imgsz), generator=g, dtype=torch.uint8)
     counts = torch.poisson(torch.full((n,), 50.0), generator=g).clamp(1, 300).long()
@@ -217,16 +218,44 @@ def synthetic_dataset(n: int, imgsz: int, seed: int, nc: int = 10) -> Dict[str, 
     cls = torch.randint(0, nc, (m, 1), generator=g).float()
     cxy = torch.rand(m, 2, generator=g) * 0.9 + 0.05
     wh = (torch.randn(m, 2, generator=g) * 0.6 + math.log(0.03)).exp().clamp(0.004, 0.5)
-    return dict(img=img, batch_idx=bi, cls=cls, bboxes=torch.cat((cxy, wh), 1))
+    cols = (cxy, wh, (torch.rand(m, 1, generator=g) - 0.25) * math.pi) if angles else (cxy, wh)
+    return dict(img=img, batch_idx=bi, cls=cls, bboxes=torch.cat(cols, 1))
+
+
+def check_obb_train_data(data, args: dict) -> None:
+    """What training an oriented-box model does not take, refused with ``NotImplementedError`` naming the argument before any device use
+    (``YOLO.train`` and the trainer's own set-up both call it): ``device_augment=True`` (the reference augments rotated labels as polygons
+    and refits rectangles with OpenCV), a YOLO-format dataset YAML (its oriented labels are corner rows ``cls x1 y1 .. x4 y4``; labels
+    enter as tensors) and a dataset whose ``bboxes`` are not (M, 5) xywhr -- a ``.pt`` file is read here, on the host, to see them."""
+    if args.get("device_augment"):
+        raise NotImplementedError("train: device_augment=True is not built for oriented-box models (rotated labels are not carried through mosaic / affine / flips)")
+    if isinstance(data, (str, Path)) and str(data).endswith((".yaml", ".yml")):
+        raise NotImplementedError(f"train: data={str(data)!r}: a YOLO-format dataset YAML carries oriented labels as corner rows (cls x1 y1 x2 y2 x3 y3 x4 y4), which "
+                                  "are not read; an oriented-box model needs a dataset whose 'bboxes' are (M, 5) xywhr tensors (dict / .pt) or 'synthetic-obb[:N]'")
+    boxes = None
+    if isinstance(data, (str, Path)) and str(data).endswith(".pt") and os.path.isfile(str(data)):
+        boxes = torch.load(str(data), map_location="cpu", weights_only=True).get("bboxes")
+    elif isinstance(data, dict):
+        boxes = data.get("bboxes")
+    elif isinstance(data, str) and data.startswith("synthetic") and not data.startswith("synthetic-obb"):
+        boxes = torch.zeros(0, 4)
+    if boxes is not None and (not isinstance(boxes, torch.Tensor) or boxes.dim() != 2 or boxes.shape[1] != 5):
+        shape = tuple(boxes.shape) if isinstance(boxes, torch.Tensor) else type(boxes).__name__
+        name = str(data) if isinstance(data, (str, Path)) else type(data).__name__
+        raise NotImplementedError(f"train: an oriented-box model needs a dataset whose 'bboxes' are (M, 5) xywhr (normalised xywh and the angle in radians); "
+                                  f"data={name!r} has {shape} (no angles)")
 
 
 def load_dataset(data, imgsz: int, nc: int, seed: int) -> Dict[str, torch.Tensor]:
     """``data``: a dict / a ``.pt`` file of tensors ``img`` (N,3,H,W) uint8, ``batch_idx`` (M,), ``cls`` (M,1), ``bboxes`` (M,4
     normalised xywh; (M,5) with the angle in radians for an oriented-box set, passed through as it is) — the reference's collate layout
-    (data/dataset.py:232-248) over the whole set — or ``"synthetic[:N]"``, or a
+    (data/dataset.py:232-248) over the whole set — or ``"synthetic[:N]"``, ``"synthetic-obb[:N]"`` (the same draws plus an angle per box), or a
     YOLO-format dataset YAML (``load_yaml_dataset``: decoded once into the same tensor layout)."""
     if isinstance(data, dict):
         d = data
+    elif isinstance(data, str) and data.startswith("synthetic-obb"):  # before "synthetic": the longer name first
+        n = int(data.split(":")[1]) if ":" in data else 128
+        d = synthetic_dataset(n, imgsz, seed=1000 + seed, nc=nc, angles=True)
     elif isinstance(data, str) and data.startswith("synthetic"):
         n = int(data.split(":")[1]) if ":" in data else 128
         d = synthetic_dataset(n, imgsz, seed=1000 + seed, nc=nc)
@@ -682,7 +711,7 @@ class DetectionTrainer:
         self.device = torch.device("cuda", index)
         torch.manual_seed(int(a.get("seed", 0)))  # trainer.py:121 init_seeds, BEFORE the model is built: two runs of one process start from the same weights
         if self.model is None:
-            from ..nn.tasks import DetectionModel
+            from ..nn.tasks import TASK_MODELS, guess_model_task, yaml_model_load
 
             src = str(a.get("model") or "yolov8s-p2-repvgg.yaml")
             if src.endswith(".pt"):
@@ -690,7 +719,7 @@ class DetectionTrainer:
 
                 self.model, _ = load_reference_checkpoint(src)
             else:
-                self.model = DetectionModel(src, nc=a.get("nc") or None, verbose=False)
+                self.model = TASK_MODELS[guess_model_task(yaml_model_load(src))](src, nc=a.get("nc") or None, verbose=False)  # the head decides: DetectionModel, OBBModel
         self.model = self.model.to(self.device).train()
         for k, v in self.model.named_parameters():  # _setup_train's freeze block (trainer.py:238-254): '.dfl' stays frozen, the rest trains
             v.requires_grad_(".dfl" not in k and v.dtype.is_floating_point)  # (a predictor may have frozen the graph before)
@@ -841,7 +870,7 @@ class DetectionTrainer:
         if gs is None:
             for k in [k for k in graphs if k[:3] == shape_key]:  # a smaller capacity of this shape is never used again
                 del graphs[k]
-            gs = dict(key=key, img=torch.empty_like(img), gt=torch.zeros((b, cap, 5), dtype=torch.float32, device=img.device))
+            gs = dict(key=key, img=torch.empty_like(img), gt=torch.zeros((b, cap, model.criterion.width), dtype=torch.float32, device=img.device))
             gs["img"].copy_(img)
             armed = bk.armed if bk is not None else False
             if bk is not None:
@@ -882,7 +911,7 @@ class DetectionTrainer:
         # then started on an idle GPU: the launch cost was serial to every step instead of hidden behind the one before.
         ring = gs.get("gt_ring")
         if ring is None:
-            ring = gs["gt_ring"] = dict(tables=[torch.zeros((b, cap, 5), dtype=torch.float32).pin_memory() for _ in range(3)], events=[None] * 3, at=0)
+            ring = gs["gt_ring"] = dict(tables=[torch.zeros((b, cap, model.criterion.width), dtype=torch.float32).pin_memory() for _ in range(3)], events=[None] * 3, at=0)
         k = ring["at"]
         ring["at"] = (k + 1) % 3
         if ring["events"][k] is not None:
@@ -1066,6 +1095,10 @@ class DetectionTrainer:
         a = self.args
         nc_hint = int(a.get("nc") or (self.model.yaml["nc"] if self.model is not None else 10))
         data = load_dataset(a.get("data") or "synthetic", int(a["imgsz"]), nc_hint, int(a.get("seed", 0)))
+        from ..nn.tasks import OBBModel
+
+        if isinstance(self.model, OBBModel):
+            check_obb_train_data(data, a)
         if self.flat is None:
             # build_optimizer's 'auto' rule looks at the planned number of iterations (trainer.py:309-310)
             self.iterations_hint = math.ceil(data["img"].shape[0] / max(int(a["batch"]), a["nbs"])) * self.epochs
@@ -1085,7 +1118,7 @@ class DetectionTrainer:
             if a.get("val", True):
                 # _setup_train (trainer.py:288-296): the validation loader lives on rank 0 at twice the per-rank batch.  A tensor dataset
                 # carries its split as data["val"] (same layout); without one the training tensors are evaluated
-                from .validator import DetectionValidator
+                from .validator import DetectionValidator, OBBValidator
 
                 # the reference needs a real val split (check_det_dataset).  Without one there is nothing to validate ON: the
                 # metrics/* and val/* columns and best.pt stay out rather than being computed on the training tensors under a validation
@@ -1095,7 +1128,7 @@ class DetectionTrainer:
                     LOGGER.info("val: the dataset has no 'val' split -- validation skipped (fitness = -loss decides best.pt)")
                 else:
                     self.val_loader = TensorLoader({k: vd[k] for k in ("img", "batch_idx", "cls", "bboxes")}, per_rank * 2, 0, 1, shuffle=False)
-                    self.validator = DetectionValidator(a)
+                    self.validator = (OBBValidator if isinstance(self.model, OBBModel) else DetectionValidator)(a)  # obb/train.py:39-43
         self.resume_training(self._resume_ckpt)  # trainer.py:315 (after the optimizer exists)
         self._resume_ckpt = None
 

@@ -302,8 +302,9 @@ class OBBValidator(DetectionValidator):
     (``dy_nms_rotated_ml``: ProbIoU fast NMS over every (anchor, class) pair above conf) and whose matching is ``match_predictions`` on
     ``batch_probiou(gt, det)``.  With ``device_match`` a batch is matched by ``dy_val_match_rotated`` behind the NMS and nothing in the batch
     loop waits for the device; without it the matching is the reference's data flow on the host, image by image.  The dataset's ``bboxes``
-    are (M, 5) normalised xywh + the angle in radians.  No validation loss (``v8OBBLoss`` is not built, and the reference's stand-alone
-    ``val`` computes none): the dict holds the four metrics and ``fitness``."""
+    are (M, 5) normalised xywh + the angle in radians.  No validation loss (in eval mode the head hands on the angle, ``v8OBBLoss`` takes its
+    logit; the reference's stand-alone ``val`` computes none): the dict holds the four metrics and ``fitness``.  The trainer calls this
+    validator per epoch for an ``OBBModel`` (engine/trainer.py)."""
 
     metrics_cls = OBBMetrics
     val_loss = False

@@ -21,7 +21,7 @@ import warnings
 import torch
 
 from . import _lib
-from ._lib import DY_ACT_NONE, DY_ACT_SILU, DY_ACT_SILU_L2E, BnDesc, BranchDesc, C2fDesc, C2fFrontDesc, C2fTailDesc, ConvDesc, DecodeDesc, HeadDecodeDesc, LossDesc, NmsDesc, Stem2Desc, TileFuseDesc, TileMergeDesc, TrackDesc, ValMaskMatchDesc, ValMatchDesc, check, lib
+from ._lib import DY_ACT_NONE, DY_ACT_SILU, DY_ACT_SILU_L2E, BnDesc, BranchDesc, C2fDesc, C2fFrontDesc, C2fTailDesc, ConvDesc, DecodeDesc, HeadDecodeDesc, LossDesc, NmsDesc, ObbLossDesc, Stem2Desc, TileFuseDesc, TileMergeDesc, TrackDesc, ValMaskMatchDesc, ValMatchDesc, check, lib
 
 FP8 = torch.float8_e4m3fn  # OCP e4m3fn: gfx950's fp8 (MI300's fnuz is another encoding)
 # DY_F16X2 (include/dyolo.h): split float16 pairs, x ~= hi + lo * 2^-11 — the bar-exact precision on the 16-bit MFMA.  torch has no such
@@ -1586,6 +1586,60 @@ def detection_loss(levels: Sequence[torch.Tensor], gt: torch.Tensor, strides: Se
     return (out, owner, grads) if want_grad else (out, owner)
 
 
+def obb_loss(levels: Sequence[torch.Tensor], angles: Sequence[torch.Tensor], gt: torch.Tensor, strides: Sequence[float], nc: int, reg_max: int = 16,
+             topk: int = 10, alpha: float = 0.5, beta: float = 6.0, box: float = 7.5, cls: float = 0.5, dfl: float = 1.5,
+             want_owner: bool = False, want_grad: bool = False, buffers: Optional[dict] = None):
+    """v8OBBLoss forward (and gradient) through ``dy_obb_loss``.
+
+    levels[i]: fp32 NHWC view (N, 4*reg_max+nc, H_i, W_i); angles[i]: fp32 NHWC view (N, >=1, H_i, W_i) whose channel 0 is the raw angle
+    logit; gt: fp32 (N, gmax, 6) [cls, x, y, w, h, r], pixels and radians, zero rows = padding, on the host or the device.  Returns
+    (out[4] = box, cls, dfl, total, owner or None) and, with ``want_grad``, two more items: d total / d levels[i] and d total / d angles[i]
+    (NHWC views shaped and pitched like the inputs; the angle gradient's channel 0 carries the value, the others zeros).  ``buffers``: a
+    dict the call fills on first use and reuses afterwards (out, owner, workspace, gradient maps) -- static buffers, as under graph replay."""
+    n = levels[0].shape[0]
+    if len(angles) != len(levels):
+        raise ValueError("obb_loss: one angle map per level")
+    d = ObbLossDesc()
+    A = 0
+    for i, (t, an) in enumerate(zip(levels, angles)):
+        require_device(t)
+        require_device(an)
+        if t.dtype != torch.float32 or t.shape[1] != 4 * reg_max + nc:
+            raise ValueError("obb_loss: levels must be fp32 with 4*reg_max+nc channels")
+        if an.dtype != torch.float32 or an.shape[0] != n or an.shape[1] < 1 or an.shape[2:] != t.shape[2:]:
+            raise ValueError("obb_loss: angles must be fp32 maps of the levels' sizes")
+        p_, ld = view_params(t)
+        d.level[i], d.h[i], d.w[i], d.ld[i], d.stride[i] = p_, t.shape[2], t.shape[3], ld, float(strides[i])
+        d.angle[i], d.ld_angle[i] = view_params(an)
+        A += t.shape[2] * t.shape[3]
+    dev = levels[0].device
+    gt = gt.to(dev, torch.float32).contiguous()
+    if gt.dim() != 3 or gt.shape[0] != n or gt.shape[2] != 6:
+        raise ValueError("obb_loss: gt must be (N, gmax, 6)")
+    gmax = gt.shape[1]
+    d.n_levels, d.batch, d.nc, d.reg_max = len(levels), n, nc, reg_max
+    d.gt, d.gmax, d.topk = (gt.data_ptr() if gmax else None), gmax, topk
+    d.alpha, d.beta, d.box_gain, d.cls_gain, d.dfl_gain = alpha, beta, box, cls, dfl
+    bufs = buffers if buffers is not None else {}
+    if "out" not in bufs:
+        bufs["out"] = torch.empty(4, dtype=torch.float32, device=dev)
+        bufs["owner"] = torch.empty((n, A), dtype=torch.int32, device=dev) if want_owner else None
+        bufs["ws"] = torch.empty(lib().dy_obb_loss_workspace_bytes(n, A, gmax, topk), dtype=torch.uint8, device=dev)
+        bufs["grads"] = bufs["agrads"] = None
+        if want_grad:
+            bufs["grads"] = [alloc_nhwc(n, t.shape[1], t.shape[2], t.shape[3], torch.float32, dev, ld=d.ld[i]) for i, t in enumerate(levels)]
+            bufs["agrads"] = [alloc_nhwc(n, an.shape[1], an.shape[2], an.shape[3], torch.float32, dev, ld=d.ld_angle[i]) for i, an in enumerate(angles)]
+    out, owner, ws, grads, agrads = bufs["out"], bufs["owner"], bufs["ws"], bufs["grads"], bufs["agrads"]
+    d.out, d.out_owner = out.data_ptr(), (owner.data_ptr() if owner is not None else None)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    if want_grad:
+        for i in range(len(levels)):
+            d.grad_level[i], d.ld_grad[i] = view_params(grads[i])
+            d.grad_angle[i], d.ld_grad_angle[i] = view_params(agrads[i])
+    _launch(lib().dy_obb_loss, (C.byref(d),), keep=(d, out, owner, ws, gt, *levels, *angles, *(grads or ()), *(agrads or ())))
+    return (out, owner, grads, agrads) if want_grad else (out, owner)
+
+
 # ---- train-mode BatchNorm (+ SiLU) -------------------------------------------------------------------------------
 
 
@@ -1859,6 +1913,24 @@ def head_grad_split(g: torch.Tensor, nb: int, nc: int, ncp: int, dtype: torch.dt
     _launch(lib().dy_head_grad_split, (gp, ldg, _rows(g), nb, nc, ncp, scale.data_ptr() if scale is not None else None, bp, ldb, cp, ldc, dy_dtype(dtype)),
             keep=(g, dzb, dzc, scale))
     return dzb, dzc
+
+
+ANGLE_PAD = 8  # channels of the OBB angle tail's padded maps (OBB.ANGLE_COUT; kObbAngleCout in csrc/obb_loss.hip)
+
+
+def obb_angle_grad_cast(g: torch.Tensor, dtype: torch.dtype, scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``dy_obb_angle_grad_cast``: ``g`` an fp32 NHWC view (n, >= 1, h, w) whose channel 0 is d loss / d angle logit -> (n, 8, h, w) of
+    ``dtype``: g[:, 0] * scale in channel 0, zeros behind.  ``scale``: a device fp32 scalar or None."""
+    n, _, h, w = g.shape
+    if g.dtype != torch.float32:
+        raise ValueError("obb_angle_grad_cast: g must be fp32")
+    if scale is not None and (scale.dtype != torch.float32 or not scale.is_cuda or scale.numel() != 1):
+        raise ValueError("obb_angle_grad_cast: scale must be one fp32 value on the device")
+    gp, ldg = view_params(g[:, :1])
+    dz = alloc_nhwc(n, ANGLE_PAD, h, w, dtype, g.device)
+    dp, ldd = view_params(dz)
+    _launch(lib().dy_obb_angle_grad_cast, (gp, ldg, n * h * w, scale.data_ptr() if scale is not None else None, dp, ldd, dy_dtype(dtype)), keep=(g, dz, scale))
+    return dz
 
 
 def add_nhwc(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -528,3 +528,62 @@ class DetectionLossFn(torch.autograd.Function):
                 LAZY_SEED[g.data_ptr()] = g_total
             return (None, None, None, None, None, *gs)
         return (None, None, None, None, None, *[g * g_total for g in gs])
+
+
+class AngleTail(torch.autograd.Function):
+    """conv1x1(x, w) + b with ONE output channel (OBB's cv4[i][2], head.py:213) as an fp32 NHWC map whose channel 0 is the raw angle logit.
+    One channel is narrower than the 1x1 kernels serve: weights, bias and maps are padded with zeros to ``H.ANGLE_PAD`` channels, as
+    ``OBB.ANGLE_COUT`` pads the prediction pack and ``HeadTail`` pads its class slot; the returned view is channel 0 at pitch 8."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        dtype, dev = x.dtype, x.device
+        n, _, h, wd = x.shape
+        pad = H.ANGLE_PAD
+        wp = torch.zeros((pad, w.shape[1], 1, 1), device=dev, dtype=w.dtype)
+        wp[: w.shape[0]] = w.detach()
+        bp = torch.zeros(pad, device=dev, dtype=b.dtype)
+        bp[: b.shape[0]] = b.detach()
+        buf = H.alloc_nhwc(n, pad, h, wd, torch.float32, dev)
+        H.conv2d(x, H.PackedConv(wp, bp, 1, 0, 1, False, dtype, dev, for_out_f32=True), out=buf, out_f32=True)
+        ctx.save_for_backward(x, w, wp)
+        ctx.bias = b
+        return buf[:, :1]
+
+    @_commits_sink
+    def backward(ctx, dy):
+        x, w, wp = ctx.saved_tensors
+        b = ctx.bias
+        dtype, dev = x.dtype, x.device
+        seed = LAZY_SEED.pop(dy.data_ptr(), None)  # by the address OBBLossFn.backward handed over (HeadTail.backward does the same)
+        dz = H.obb_angle_grad_cast(dy, dtype, scale=seed)  # (n, 8, h, w): the value, scaled, in channel 0; zeros behind
+        sw, sb = grad_sink(w), grad_sink(b)
+        dw = H.conv_wgrad(x, dz[:, :1], 1, 1, 0, out=None if sw is None else sw.view(1, 1, 1, w.shape[1]))
+        db = H.colsum(dz[:, :1], out=sb)
+        dx = H.conv_dgrad(dz, H.pack_dgrad(wp, 1, dtype, dev), 1)
+        return dx, (None if sw is not None else dw), (None if sb is not None else db)
+
+
+class OBBLossFn(torch.autograd.Function):
+    """v8OBBLoss on the per-level fp32 head maps and angle-logit maps through dy_obb_loss (value + both gradients in one call)."""
+
+    @staticmethod
+    def forward(ctx, gt, strides, nc, reg_max, hyp, nl, *maps):
+        levels, angles = maps[:nl], maps[nl:]
+        out, _, grads, agrads = H.obb_loss(levels, angles, gt, strides, nc, reg_max, box=hyp[0], cls=hyp[1], dfl=hyp[2], want_grad=True)
+        ctx.grads = [g[:, : levels[0].shape[1]] for g in grads] + list(agrads)
+        total, items = out[3].clone(), out[:3].clone()
+        ctx.mark_non_differentiable(items)
+        return total, items
+
+    @staticmethod
+    def backward(ctx, g_total, g_items):
+        if g_total is None:
+            return (None, None, None, None, None, None, *([None] * len(ctx.grads)))
+        if _LAZY[0] and g_total.is_cuda and g_total.dtype == torch.float32 and g_total.numel() == 1:
+            # the trainer's own backward: both kinds of map go on UNSCALED; HeadTail.backward and AngleTail.backward multiply by the seed
+            # inside their cast kernels (a device read) -- no full-map torch multiply
+            for g in ctx.grads:
+                LAZY_SEED[g.data_ptr()] = g_total
+            return (None, None, None, None, None, None, *ctx.grads)
+        return (None, None, None, None, None, None, *[g * g_total for g in ctx.grads])

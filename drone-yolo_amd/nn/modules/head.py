@@ -301,7 +301,8 @@ class OBB(Detect):
 
     The box and class branches go through every fusion of ``Detect`` unchanged and give the axis-aligned (N, 4 + nc, A) decode; ``dy_obb_decode``
     then turns each centre about its anchor point by the anchor's angle, which IS the reference's dist2rbox, and writes
-    theta = (sigmoid(logit) - 0.25) * pi.  Eval forward returns the reference's ``(cat([y, angle], 1), (feats, angle))``.  On the
+    theta = (sigmoid(logit) - 0.25) * pi.  Training: ``OBBModel.forward_train`` -> ``train_forward.obb_train`` (the box and class maps of
+    ``detect_train`` plus, per level, ``cv4`` through ``AngleTail``); this module's own ``forward`` raises in training mode.  Eval forward returns the reference's ``(cat([y, angle], 1), (feats, angle))``.  On the
     predictor's fast path (``fuse_tail``) nothing is concatenated: the return is ``(y, (None, theta, levels))`` with theta (N, A) and
     ``levels`` the per-level fp32 NHWC angle-logit maps.
     """
@@ -339,7 +340,8 @@ class OBB(Detect):
 
     def forward(self, x):
         if self.training:
-            raise NotImplementedError("OBB: training an oriented-box model (v8OBBLoss) is not built; prediction only")
+            raise NotImplementedError("OBB.forward in training mode is not built: training goes through OBBModel.forward_train (nn/train_forward.py::obb_train), "
+                                      "which returns (feats, angle_levels) with the angle as its raw logit")
         if any(t.dtype == H.FP8 for t in x):
             raise NotImplementedError("OBB is built for the 16-bit, split-float16 and fp32 storage types")
         if self.ne != 1:

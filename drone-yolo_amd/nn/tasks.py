@@ -523,19 +523,23 @@ class SegmentationModel(DetectionModel):
 
 
 class OBBModel(DetectionModel):
-    """YOLO oriented-box model — reference tasks.py:392-400.  Prediction only: the rotated loss (v8OBBLoss) is not built."""
+    """YOLO oriented-box model -- reference tasks.py:392-400.  Predicts, validates, tracks and trains: ``forward_train`` returns
+    ``(feats, angle_levels)`` (nn/train_forward.py::obb_train: the per-level raw head maps and, per level, the fp32 map of the raw angle
+    logit), ``init_criterion`` the device loss ``v8OBBLoss`` (utils/loss.py, ``dy_obb_loss``).  The criterion exists on the device only:
+    ``init_criterion`` on a model whose parameters are still on the CPU raises ``NotImplementedError`` (the trainer moves the model first)."""
 
     def __init__(self, cfg="yolov8s-p2-repvgg-obb.yaml", ch=3, nc=None, verbose=True):
         super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
 
     def init_criterion(self):
-        raise NotImplementedError("train: the oriented-box loss (v8OBBLoss) is not built; oriented-box models predict only")
+        if not next(self.parameters()).is_cuda:
+            raise NotImplementedError("train: the oriented-box loss (v8OBBLoss) runs on the device only (dy_obb_loss); move the model to the MI355X first")
+        from ..utils.loss import v8OBBLoss
+
+        return v8OBBLoss(self)
 
     def _predict_augment(self, x, image_dtype=None):
         raise NotImplementedError("augment=True is not built for oriented-box models")
-
-    def forward_train(self, img, dtype=None):
-        raise NotImplementedError("train: oriented-box models predict only")
 
 
 TASK_MODELS = {"detect": DetectionModel, "segment": SegmentationModel, "obb": OBBModel}

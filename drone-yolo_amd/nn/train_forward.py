@@ -82,8 +82,18 @@ def detect_train(m, xs: List[torch.Tensor]) -> List[torch.Tensor]:
     return out
 
 
+def obb_train(m, xs: List[torch.Tensor]):
+    """OBB.forward's training return (head.py:200-227) with the angle left as its raw logit: ``(feats, angle_levels)`` = ``detect_train``'s
+    maps and, per level, the fp32 map of cv4 whose channel 0 is the logit (v8OBBLoss / dy_obb_loss apply (sigmoid - 0.25) pi)."""
+    if m.ne != 1:
+        raise NotImplementedError("OBB training: one extra parameter per box (the angle) is what the loss is built for")
+    feats = detect_train(m, xs)
+    angles = [A.AngleTail.apply(conv_pair_train(c[0], c[1], x), c[2].weight, c[2].bias) for c, x in zip(m.cv4, xs)]
+    return feats, angles
+
+
 def module_train(m, x, first: bool = False, img_u8=None):
-    from .modules import C2f, Concat, Conv, Detect, RepVGGBlock, SPPF, Upsample
+    from .modules import C2f, Concat, Conv, Detect, OBB, RepVGGBlock, SPPF, Upsample
 
     if isinstance(m, nn.Sequential):
         for mm in m:
@@ -101,6 +111,8 @@ def module_train(m, x, first: bool = False, img_u8=None):
         return A.Upsample2x.apply(x)
     if isinstance(m, Concat):
         return A.ConcatC.apply(*x)
+    if isinstance(m, OBB):  # before Detect: OBB is a Detect
+        return obb_train(m, x)
     if isinstance(m, Detect):
         return detect_train(m, x)
     raise NotImplementedError(f"no training forward for {type(m).__name__}")

@@ -14,6 +14,8 @@ from .. import hip_ops as H
 class v8DetectionLoss:
     """Same constructor idea and call contract as the reference: ``loss, loss_items = criterion(preds, batch)``."""
 
+    width = 5  # columns of the label table ``targets_to_gt`` builds and ``from_gt`` takes (the trainer sizes its static table by it)
+
     def __init__(self, model, tal_topk: int = 10, box: float = 7.5, cls: float = 0.5, dfl: float = 1.5):
         m = model.model[-1]  # Detect()
         h = getattr(model, "args", None)
@@ -85,4 +87,69 @@ class v8DetectionLoss:
             total, items = DetectionLossFn.apply(gt, strides, self.nc, self.reg_max, (self.box, self.cls, self.dfl), *feats)
             return total, items
         out, _ = H.detection_loss(feats, gt, strides, self.nc, self.reg_max, topk=self.topk, box=self.box, cls=self.cls, dfl=self.dfl)
+        return out[3], out[:3]
+
+
+class v8OBBLoss(v8DetectionLoss):
+    """Oriented-box training loss on the device (reference: ultralytics/utils/loss.py:612-725 ``v8OBBLoss``): rotated TaskAlignedAssigner +
+    BCE / ProbIoU / DFL, value and gradient w.r.t. the head maps AND the angle logits, through ``dy_obb_loss``.
+
+    ``preds`` is ``(feats, angle_levels)``: the per-level fp32 head maps and, per level, the fp32 map whose channel 0 is the RAW angle logit
+    (the kernel applies ``(sigmoid - 0.25) * pi`` itself; the reference's training head hands the loss the angle).  The label table has six
+    columns ``[cls, x, y, w, h, r]``: xywh in pixels, r in radians."""
+
+    width = 6  # columns of the label table (v8DetectionLoss: 5)
+
+    @staticmethod
+    def preprocess(targets: torch.Tensor, batch_size: int, scale_tensor: torch.Tensor) -> torch.Tensor:
+        """(N, 7) [image, cls, x, y, w, h normalised, r] -> (B, n_max, 6) [cls, x, y, w, h pixels, r] -- loss.py:621-636, vectorised in numpy on
+        the host like the parent's (and for its reason)."""
+        t = targets.detach().cpu().float().numpy()
+        nl = t.shape[0]
+        if nl == 0:
+            return torch.zeros(batch_size, 0, 6)
+        img = t[:, 0].astype(np.int64)
+        counts = np.bincount(img, minlength=batch_size)
+        order = np.argsort(img, kind="stable")
+        start = np.cumsum(counts) - counts
+        pos = np.arange(nl) - start[img[order]]
+        out = np.zeros((batch_size, int(counts.max()), 6), dtype=np.float32)
+        out[img[order], pos] = t[order, 1:]
+        out[..., 1:5] *= scale_tensor.detach().cpu().float().numpy()
+        return torch.from_numpy(out)
+
+    def targets_to_gt(self, batch, batch_size: int, img_hw) -> torch.Tensor:
+        """The batch's labels as the (B, n_max, 6) table on the host; img_hw = (h, w).  Two rules of the reference's ``__call__`` live here:
+        the tiny-box filter (loss.py:660-661) multiplies the normalised WIDTH by the image HEIGHT and the height by the width (``imgsz`` is
+        (h, w)) -- kept as it is; and ``mask_gt`` (loss.py:664) is the sign of x + y + w + h + r, so a real label whose five numbers sum to
+        zero or less is treated like padding: such rows are dropped here and never reach the table."""
+        bboxes = batch["bboxes"].float().cpu()
+        if bboxes.dim() != 2 or bboxes.shape[1] != 5:
+            raise TypeError(f"the oriented-box loss needs labels whose 'bboxes' are (M, 5) xywhr, got {tuple(bboxes.shape)}")
+        t = torch.cat((batch["batch_idx"].view(-1, 1).float().cpu(), batch["cls"].view(-1, 1).float().cpu(), bboxes), 1).numpy()
+        h, w = np.float32(img_hw[0]), np.float32(img_hw[1])
+        t = t[(t[:, 4] * h >= 2) & (t[:, 5] * w >= 2)]
+        scaled = t[:, 2:6] * np.array([w, h, w, h], np.float32)
+        t = t[(scaled.sum(1, dtype=np.float32) + t[:, 6]) > 0] if t.shape[0] else t
+        gt = self.preprocess(torch.from_numpy(t), batch_size, torch.tensor([float(w), float(h), float(w), float(h)]))
+        self.check_classes(gt, self.nc)
+        return gt
+
+    def __call__(self, preds, batch):
+        feats = preds[0]
+        hw = (feats[0].shape[2] * float(self.stride[0]), feats[0].shape[3] * float(self.stride[0]))
+        return self.from_gt(preds, self.targets_to_gt(batch, feats[0].shape[0], hw))
+
+    def from_gt(self, preds, gt: torch.Tensor):
+        """loss, loss_items from the six-column table itself (host or device, rows with x + y + w + h + r <= 0 = padding)."""
+        feats, angles = preds
+        self.check_classes(gt, self.nc)
+        strides = [float(s) for s in self.stride]
+        if any(t.requires_grad for t in (*feats, *angles)):
+            if self.topk != 10:
+                raise NotImplementedError("the differentiable path uses the default tal_topk of 10")
+            from ..nn.autograd_ops import OBBLossFn
+
+            return OBBLossFn.apply(gt, strides, self.nc, self.reg_max, (self.box, self.cls, self.dfl), len(feats), *feats, *angles)
+        out, _ = H.obb_loss(feats, angles, gt, strides, self.nc, self.reg_max, topk=self.topk, box=self.box, cls=self.cls, dfl=self.dfl)
         return out[3], out[:3]

@@ -803,6 +803,42 @@ typedef struct dy_loss_desc {
 int64_t dy_detection_loss_workspace_bytes(int32_t batch, int32_t anchors, int32_t gmax, int32_t topk);
 int32_t dy_detection_loss(const dy_loss_desc* d, dy_stream_t stream);
 
+/* ---- oriented-box training loss (forward + gradient w.r.t. the head outputs and the angle logits) ---------------------
+ * Replaces: v8OBBLoss.__call__ (utils/loss.py:638-708) = RotatedTaskAlignedAssigner (utils/tal.py:298-330 on :14-295: the anchor
+ * centre inside the rotated rectangle, edges included; overlap = probiou(gt, pred).clamp(0) on pixel-unit xywhr) + BCE class loss +
+ * RotatedBboxLoss (loss.py:116-137: 1 - probiou(pred, target / stride) in grid units, DFL against the UNROTATED box of the target's
+ * xywh) on the (feats, angle) pair OBB returns in training mode (head.py:200-227), and its autograd.
+ * level[l], grad_level[l], out, out_owner, workspace, the gains, topk / alpha / beta: as in dy_loss_desc.
+ * angle[l]: fp32 NHWC view (batch, h_l, w_l, >= 1), pitch ld_angle[l]; channel 0 is the raw angle logit z, theta = (sigmoid(z) - 0.25) pi.
+ * gt: DEVICE fp32 (batch, gmax, 6) = class, x, y, w, h in input pixels, r in radians; a row with x + y + w + h + r <= 0 is padding
+ * (mask_gt, loss.py:664: a real label with such a sum is masked all the same).
+ * grad_angle[l] (with grad_level, all or none): fp32 (batch, h_l, w_l) rows of pitch ld_grad_angle[l] <= 64 floats; every row is written
+ * WHOLE on every call: d total / d z in channel 0 (0 for a background anchor), zeros behind it.  Nothing synchronises the host; the launch
+ * sequence can be captured into a hipGraph. */
+typedef struct dy_obb_loss_desc {
+  const float* level[DY_MAX_LEVELS];
+  const float* angle[DY_MAX_LEVELS];
+  int32_t h[DY_MAX_LEVELS], w[DY_MAX_LEVELS], ld[DY_MAX_LEVELS], ld_angle[DY_MAX_LEVELS];
+  float stride[DY_MAX_LEVELS];
+  int32_t n_levels, batch, nc, reg_max;
+  const float* gt;
+  int32_t gmax, topk;
+  float alpha, beta, box_gain, cls_gain, dfl_gain;
+  float* out;
+  int32_t* out_owner;
+  void* workspace;
+  int64_t workspace_bytes;
+  float* grad_level[DY_MAX_LEVELS];
+  float* grad_angle[DY_MAX_LEVELS];
+  int32_t ld_grad[DY_MAX_LEVELS], ld_grad_angle[DY_MAX_LEVELS];
+} dy_obb_loss_desc;
+int64_t dy_obb_loss_workspace_bytes(int32_t batch, int32_t anchors, int32_t gmax, int32_t topk);
+int32_t dy_obb_loss(const dy_obb_loss_desc* d, dy_stream_t stream);
+/* The angle tail's dz from dy_obb_loss's grad_angle map: g fp32, channel 0 of `rows` rows of pitch ld_g; dz: rows of 8 channels of `dtype`
+ * (DY_BF16 / DY_F16 / DY_F32; pitch ld_dz >= 8, whole 16-byte chunks) = g * (*scale, a DEVICE fp32 value, or 1 when scale is null) in
+ * channel 0, zeros in channels 1..7: the one-channel 1x1 convolution of the OBB head padded to a width the convolution gradients serve. */
+int32_t dy_obb_angle_grad_cast(const float* g, int32_t ld_g, int64_t rows, const float* scale, void* dz, int32_t ld_dz, int32_t dtype, dy_stream_t stream);
+
 /* ---- convolution gradients ------------------------------------------------------------------
  * Replaces: autograd of F.conv2d inside Conv / RepVGGBlock / Detect (nn/modules/conv.py:37-55) during
  * loss.backward() (engine/trainer.py:381-389).
