@@ -204,6 +204,22 @@ class ObbLossDesc(C.Structure):
     ]  # fmt: skip
 
 
+class SegLossDesc(C.Structure):
+    """Mirror of ``dy_seg_loss_desc``."""
+
+    _fields_ = [
+        ("owner", _vp), ("gt", _vp), ("coef", _vp * DY_MAX_LEVELS),
+        ("h", _i32 * DY_MAX_LEVELS), ("w", _i32 * DY_MAX_LEVELS), ("ld_coef", _i32 * DY_MAX_LEVELS),
+        ("n_levels", _i32), ("batch", _i32), ("nm", _i32), ("gmax", _i32), ("topk", _i32),
+        ("proto", _vp), ("proto_dtype", _i32), ("ld_proto", _i32), ("mh", _i32), ("mw", _i32),
+        ("masks", _vp), ("mask_dtype", _i32), ("gh", _i32), ("gw", _i32),
+        ("img_h", _f32), ("img_w", _f32), ("box_gain", _f32),
+        ("out", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
+        ("grad_coef", _vp * DY_MAX_LEVELS), ("ld_grad_coef", _i32 * DY_MAX_LEVELS),
+        ("grad_proto", _vp), ("ld_grad_proto", _i32),
+    ]  # fmt: skip
+
+
 class C2fTailDesc(C.Structure):
     """Mirror of ``dy_c2f_tail_desc``."""
 
@@ -413,6 +429,10 @@ SIGNATURES = {
     "dy_obb_loss_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "dy_obb_loss": (_i32, [C.POINTER(ObbLossDesc), _vp]),
     "dy_obb_angle_grad_cast": (_i32, [_vp, _i32, _i64, _vp, _vp, _i32, _i32, _vp]),
+    "dy_seg_loss_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "dy_seg_loss": (_i32, [C.POINTER(SegLossDesc), _vp]),
+    "dy_space_to_depth2_nhwc": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "dy_grad_cast_scaled": (_i32, [_vp, _i32, _i64, _i32, _vp, _vp, _i32, _i32, _vp]),
     "dy_augment_u8_nchw": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dy_depth_to_space2_nhwc": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dy_mask_gather": (_i32, [C.POINTER(MaskGatherDesc), _vp]),

@@ -1,5 +1,5 @@
 """``YOLO`` / ``Model`` user API (reference: ultralytics/engine/model.py:29-1177,
-ultralytics/models/yolo/model.py:11-59) for the detection, segmentation (prediction and validation) and oriented-box (prediction, validation,
+ultralytics/models/yolo/model.py:11-59) for the detection, segmentation (prediction, validation and training) and oriented-box (prediction, validation,
 tracking and training) tasks on the MI355X path."""
 from __future__ import annotations
 
@@ -46,7 +46,7 @@ class Model(nn.Module):
         from .trainer import DetectionTrainer
 
         return {"detect": {"model": DetectionModel, "predictor": DetectionPredictor, "trainer": DetectionTrainer},
-                "segment": {"model": SegmentationModel, "predictor": SegmentationPredictor}}
+                "segment": {"model": SegmentationModel, "predictor": SegmentationPredictor, "trainer": DetectionTrainer}}
 
     @property
     def oriented_task_map(self):
@@ -188,11 +188,18 @@ class Model(nn.Module):
         takes a dict / ``.pt`` whose ``bboxes`` are (M, 5) normalised xywh + the angle in radians, or ``"synthetic-obb[:N]"``; for it
         four-column boxes (``"synthetic[:N]"`` among them), ``device_augment=True`` and a YOLO-format dataset YAML (corner-format labels)
         are refused with ``NotImplementedError`` naming the argument, before a trainer is built or a device selected;
+        a segmentation model (task ``segment``: ``SegmentationModel``, ``v8SegmentationLoss`` through ``dy_detection_loss`` + ``dy_seg_loss``,
+        ``SegmentationValidator`` per epoch) takes a dict / ``.pt`` with ``masks`` (uint8 / int32 (N, gh, gw) overlap index maps, value
+        k + 1 = the image's k-th label; the prototype grid equals the map or is exactly twice it) or ``"synthetic-seg[:N]"``; for it a dataset
+        without ``masks`` (``"synthetic[:N]"`` among them), float per-label masks, another grid ratio, ``device_augment=True`` and a dataset
+        YAML are refused the same way;
         ``device="0,1,.."`` trains with one rank per GPU (child processes under torch.distributed.run, RCCL all-reduce),
         after which rank-less this process reloads ``weights/last.pt`` — as the reference does (model.py:806-813)."""
-        if self.task == "segment":
-            raise NotImplementedError("train: the segmentation loss (v8SegmentationLoss) is not built; segmentation models predict only")
         args = {**{k: v for k, v in self.overrides.items() if k not in ("task", "mode")}, **kwargs}
+        if self.task == "segment":  # the training twin of val's dataset rule, before a trainer is built or a device selected
+            from .trainer import check_seg_train_data
+
+            check_seg_train_data(args.get("data") or "synthetic", args, float(self.model.stride[0]))
         if self.task == "obb":  # the training twin of val's dataset rule, before a trainer is built or a device selected
             from .trainer import check_obb_train_data
 

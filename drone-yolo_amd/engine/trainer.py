@@ -206,10 +206,11 @@ class ModelEMA:
 
 
 # ---- data ----------------------------------------------------------------------------------------------------------------
-def synthetic_dataset(n: int, imgsz: int, seed: int, nc: int = 10, angles: bool = False) -> Dict[str, torch.Tensor]:
+def synthetic_dataset(n: int, imgsz: int, seed: int, nc: int = 10, angles: bool = False, masks: bool = False) -> Dict[str, torch.Tensor]:
     """uint8 images randint(0, 256); per image n ~ Poisson(50) clipped to [1, 300] boxes (VisDrone-like
     density), class uniform, centres uniform(0.05, 0.95), wh lognormal(median 0.03, sigma 0.6) clipped to [0.004, 0.5].  ``angles``
-    (``"synthetic-obb"``): one more draw from the same generator AFTER those, an angle per box uniform in [-pi/4, 3 pi/4): ``bboxes`` (M, 5) xywhr."""
+    (``"synthetic-obb"``): one more draw from the same generator AFTER those, an angle per box uniform in [-pi/4, 3 pi/4): ``bboxes`` (M, 5) xywhr.
+    ``masks`` (``"synthetic-seg"``): the same draws, then ``synthetic_overlap_masks`` at imgsz / 4."""
     g = torch.Generator().manual_seed(seed)
     img = torch.randint(0, 256, (n, 3, imgsz, imgsz), generator=g, dtype=torch.uint8)
     counts = torch.poisson(torch.full((n,), 50.0), generator=g).clamp(1, 300).long()
@@ -219,7 +220,72 @@ def synthetic_dataset(n: int, imgsz: int, seed: int, nc: int = 10, angles: bool 
     cxy = torch.rand(m, 2, generator=g) * 0.9 + 0.05
     wh = (torch.randn(m, 2, generator=g) * 0.6 + math.log(0.03)).exp().clamp(0.004, 0.5)
     cols = (cxy, wh, (torch.rand(m, 1, generator=g) - 0.25) * math.pi) if angles else (cxy, wh)
-    return dict(img=img, batch_idx=bi, cls=cls, bboxes=torch.cat(cols, 1))
+    d = dict(img=img, batch_idx=bi, cls=cls, bboxes=torch.cat(cols, 1))
+    return synthetic_overlap_masks(d, imgsz // 4, imgsz // 4) if masks else d
+
+
+def synthetic_overlap_masks(d: Dict[str, torch.Tensor], gh: int, gw: int) -> Dict[str, torch.Tensor]:
+    """``"synthetic-seg"``: the dataset with an overlap index map (N, gh, gw) and its labels in the maps' order.  Per image the labels are
+    sorted by box area, largest first (a stable sort), and each label's box-inscribed ellipse is painted in that order with the label's new
+    position + 1 (pixel centres inside the ellipse), so the smaller label wins where two overlap and value k + 1 is the image's k-th label:
+    the rule of data/utils.py::polygons2masks_overlap.  uint8 maps while every image has at most 255 labels, int32 otherwise."""
+    bi, box = d["batch_idx"].long().numpy(), d["bboxes"].float().numpy()
+    n = d["img"].shape[0]
+    area = box[:, 2] * box[:, 3]
+    order = np.lexsort((np.arange(len(bi)), -area, bi))  # by image, then area descending, then the order the labels came in
+    counts = np.bincount(bi, minlength=n)
+    start = np.cumsum(counts) - counts
+    maps = np.zeros((n, gh, gw), np.int32)
+    ys, xs = np.arange(gh, dtype=np.float32) + 0.5, np.arange(gw, dtype=np.float32) + 0.5
+    for i in range(n):
+        for k, j in enumerate(order[start[i] : start[i] + counts[i]]):
+            cx, cy, rx, ry = box[j, 0] * gw, box[j, 1] * gh, box[j, 2] * gw / 2, box[j, 3] * gh / 2
+            y0, y1 = max(int(np.floor(cy - ry)), 0), min(int(np.ceil(cy + ry)) + 1, gh)
+            x0, x1 = max(int(np.floor(cx - rx)), 0), min(int(np.ceil(cx + rx)) + 1, gw)
+            if y1 <= y0 or x1 <= x0:
+                continue
+            inside = ((xs[None, x0:x1] - cx) / rx) ** 2 + ((ys[y0:y1, None] - cy) / ry) ** 2 <= 1.0
+            maps[i, y0:y1, x0:x1][inside] = k + 1
+    order = torch.from_numpy(order)
+    out = dict(d, batch_idx=d["batch_idx"][order], cls=d["cls"][order], bboxes=d["bboxes"][order])
+    out["masks"] = torch.from_numpy(maps.astype(np.uint8) if counts.max(initial=0) <= 255 else maps)
+    return out
+
+
+def check_seg_train_data(data, args: dict, stride0: float) -> None:
+    """What training a segmentation model does not take, refused with ``NotImplementedError`` naming the argument before any device use
+    (``YOLO.train`` and the trainer's own set-up both call it): ``device_augment=True`` (the index maps are not warped), a YOLO-format dataset
+    YAML (polygons are not rasterised), a dataset without ``masks`` (``"synthetic[:N]"`` among them), one float mask per label
+    (``overlap_mask=False``) and an index map whose size is neither the prototype grid's (2 x the first level's) nor half of it -- a
+    ``.pt`` file is read here, on the host, to see them."""
+    if args.get("device_augment"):
+        raise NotImplementedError("train: device_augment=True is not built for segmentation models (the index maps are not carried through mosaic / affine / flips)")
+    if isinstance(data, (str, Path)) and str(data).endswith((".yaml", ".yml")):
+        raise NotImplementedError(f"train: data={str(data)!r}: a YOLO-format dataset YAML carries segments as polygons, which are not rasterised; a segmentation "
+                                  "model needs a dataset with 'masks' (overlap index maps; dict / .pt) or 'synthetic-seg[:N]'")
+    d = None
+    if isinstance(data, (str, Path)) and str(data).endswith(".pt") and os.path.isfile(str(data)):
+        d = torch.load(str(data), map_location="cpu", weights_only=True)
+    elif isinstance(data, dict):
+        d = data
+    elif isinstance(data, str) and data.startswith("synthetic") and not data.startswith("synthetic-seg"):
+        d = {}
+    if d is None:
+        return
+    name = str(data) if isinstance(data, (str, Path)) else type(data).__name__
+    masks = d.get("masks")
+    if masks is None:
+        raise NotImplementedError(f"train: a segmentation model needs a dataset with 'masks' (the overlap index map (N, gh, gw) of every image) or "
+                                  f"'synthetic-seg[:N]'; data={name!r} has none")
+    img = d.get("img")
+    if not isinstance(masks, torch.Tensor) or masks.dim() != 3 or masks.dtype not in (torch.uint8, torch.int32) or (isinstance(img, torch.Tensor) and masks.shape[0] != img.shape[0]):
+        raise NotImplementedError("train: 'masks' must be the overlap index map, uint8 / int32 (N, gh, gw) with one map per image; one float mask per label "
+                                  "(overlap_mask=False) is not built")
+    if isinstance(img, torch.Tensor) and img.dim() == 4:
+        mh, mw = int(img.shape[2] / stride0) * 2, int(img.shape[3] / stride0) * 2
+        gh, gw = int(masks.shape[1]), int(masks.shape[2])
+        if (mh, mw) != (gh, gw) and (mh, mw) != (2 * gh, 2 * gw):
+            raise NotImplementedError(f"train: the prototype grid {mh} x {mw} must equal the index map's {gh} x {gw} or be exactly twice it on both axes")
 
 
 def check_obb_train_data(data, args: dict) -> None:
@@ -249,13 +315,17 @@ def check_obb_train_data(data, args: dict) -> None:
 def load_dataset(data, imgsz: int, nc: int, seed: int) -> Dict[str, torch.Tensor]:
     """``data``: a dict / a ``.pt`` file of tensors ``img`` (N,3,H,W) uint8, ``batch_idx`` (M,), ``cls`` (M,1), ``bboxes`` (M,4
     normalised xywh; (M,5) with the angle in radians for an oriented-box set, passed through as it is) — the reference's collate layout
-    (data/dataset.py:232-248) over the whole set — or ``"synthetic[:N]"``, ``"synthetic-obb[:N]"`` (the same draws plus an angle per box), or a
+    (data/dataset.py:232-248) over the whole set — or ``"synthetic[:N]"``, ``"synthetic-obb[:N]"`` (the same draws plus an angle per box), ``"synthetic-seg[:N]"`` (the same draws plus an
+    overlap index map at imgsz / 4, labels in the maps' order), or a
     YOLO-format dataset YAML (``load_yaml_dataset``: decoded once into the same tensor layout)."""
     if isinstance(data, dict):
         d = data
     elif isinstance(data, str) and data.startswith("synthetic-obb"):  # before "synthetic": the longer name first
         n = int(data.split(":")[1]) if ":" in data else 128
         d = synthetic_dataset(n, imgsz, seed=1000 + seed, nc=nc, angles=True)
+    elif isinstance(data, str) and data.startswith("synthetic-seg"):
+        n = int(data.split(":")[1]) if ":" in data else 128
+        d = synthetic_dataset(n, imgsz, seed=1000 + seed, nc=nc, masks=True)
     elif isinstance(data, str) and data.startswith("synthetic"):
         n = int(data.split(":")[1]) if ":" in data else 128
         d = synthetic_dataset(n, imgsz, seed=1000 + seed, nc=nc)
@@ -719,7 +789,7 @@ class DetectionTrainer:
 
                 self.model, _ = load_reference_checkpoint(src)
             else:
-                self.model = TASK_MODELS[guess_model_task(yaml_model_load(src))](src, nc=a.get("nc") or None, verbose=False)  # the head decides: DetectionModel, OBBModel
+                self.model = TASK_MODELS[guess_model_task(yaml_model_load(src))](src, nc=a.get("nc") or None, verbose=False)  # the head decides: DetectionModel, SegmentationModel, OBBModel
         self.model = self.model.to(self.device).train()
         for k, v in self.model.named_parameters():  # _setup_train's freeze block (trainer.py:238-254): '.dfl' stays frozen, the rest trains
             v.requires_grad_(".dfl" not in k and v.dtype.is_floating_point)  # (a predictor may have frozen the graph before)
@@ -872,6 +942,8 @@ class DetectionTrainer:
                 del graphs[k]
             gs = dict(key=key, img=torch.empty_like(img), gt=torch.zeros((b, cap, model.criterion.width), dtype=torch.float32, device=img.device))
             gs["img"].copy_(img)
+            if "masks" in batch:  # segmentation: the index maps in a static buffer next to the label table
+                gs["masks"] = torch.zeros(batch["masks"].shape, dtype=batch["masks"].dtype, device=img.device)
             armed = bk.armed if bk is not None else False
             if bk is not None:
                 bk.arm(armed, capturing=True)
@@ -880,7 +952,8 @@ class DetectionTrainer:
                 if packs is not None:
                     packs.pack_all()
                 with sink_armed():
-                    loss, items = model.criterion.from_gt(model.forward_train(gs["img"]), gs["gt"])
+                    extra = (gs["masks"],) if "masks" in gs else ()
+                    loss, items = model.criterion.from_gt(model.forward_train(gs["img"]), gs["gt"], *extra)
                 backward(loss)
                 gs.update(loss=loss, items=items)
 
@@ -925,6 +998,14 @@ class DetectionTrainer:
             gs["gt"].copy_(host.clone().to(img.device, non_blocking=True))
         else:
             gs["gt"].copy_(host, non_blocking=True)
+        if "masks" in gs:  # the same ring slot and event: a pinned copy of the batch's index maps, one asynchronous copy, no host stall
+            if batch["masks"].is_cuda:
+                gs["masks"].copy_(batch["masks"], non_blocking=True)
+            else:
+                if "masks" not in ring:
+                    ring["masks"] = [torch.zeros(gs["masks"].shape, dtype=gs["masks"].dtype).pin_memory() for _ in range(3)]
+                ring["masks"][k].numpy()[...] = batch["masks"].numpy()
+                gs["masks"].copy_(ring["masks"][k], non_blocking=True)
         ev = ring["events"][k] = ring["events"][k] or torch.cuda.Event()
         ev.record()
         tick("label_copy")
@@ -1095,14 +1176,20 @@ class DetectionTrainer:
         a = self.args
         nc_hint = int(a.get("nc") or (self.model.yaml["nc"] if self.model is not None else 10))
         data = load_dataset(a.get("data") or "synthetic", int(a["imgsz"]), nc_hint, int(a.get("seed", 0)))
-        from ..nn.tasks import OBBModel
+        from ..nn.tasks import OBBModel, SegmentationModel
 
         if isinstance(self.model, OBBModel):
             check_obb_train_data(data, a)
+        if isinstance(self.model, SegmentationModel):  # (a trainer given the model; one given a YAML path builds it below)
+            check_seg_train_data(data, a, float(self.model.stride[0]))
         if self.flat is None:
             # build_optimizer's 'auto' rule looks at the planned number of iterations (trainer.py:309-310)
             self.iterations_hint = math.ceil(data["img"].shape[0] / max(int(a["batch"]), a["nbs"])) * self.epochs
             self._setup_model_state()
+        seg = isinstance(self.model, SegmentationModel)  # after the model exists: a trainer built from a YAML path or a checkpoint has none before
+        if seg:
+            check_seg_train_data(data, a, float(self.model.stride[0]))
+            self.loss_names = ("box_loss", "seg_loss", "cls_loss", "dfl_loss")  # segment/train.py:41
         per_rank = max(self.batch_size // max(world, 1), 1)  # trainer.py:286
         if a.get("device_augment"):
             self.train_loader = AugmentLoader(data, per_rank, a, int(a["imgsz"]), self.device, self.epochs, self.rank if world > 1 else 0, max(world, 1),
@@ -1118,7 +1205,7 @@ class DetectionTrainer:
             if a.get("val", True):
                 # _setup_train (trainer.py:288-296): the validation loader lives on rank 0 at twice the per-rank batch.  A tensor dataset
                 # carries its split as data["val"] (same layout); without one the training tensors are evaluated
-                from .validator import DetectionValidator, OBBValidator
+                from .validator import DetectionValidator, OBBValidator, SegmentationValidator
 
                 # the reference needs a real val split (check_det_dataset).  Without one there is nothing to validate ON: the
                 # metrics/* and val/* columns and best.pt stay out rather than being computed on the training tensors under a validation
@@ -1126,9 +1213,13 @@ class DetectionTrainer:
                 vd = data.get("val") if isinstance(data.get("val"), dict) else (data if a.get("val") == "train" else None)
                 if vd is None:
                     LOGGER.info("val: the dataset has no 'val' split -- validation skipped (fitness = -loss decides best.pt)")
+                elif seg and vd.get("masks") is None:
+                    LOGGER.info("val: the dataset's 'val' split has no 'masks' -- validation skipped (fitness = -loss decides best.pt)")
                 else:
-                    self.val_loader = TensorLoader({k: vd[k] for k in ("img", "batch_idx", "cls", "bboxes")}, per_rank * 2, 0, 1, shuffle=False)
-                    self.validator = (OBBValidator if isinstance(self.model, OBBModel) else DetectionValidator)(a)  # obb/train.py:39-43
+                    keys = ("img", "batch_idx", "cls", "bboxes") + (("masks",) if seg else ())
+                    self.val_loader = TensorLoader({k: vd[k] for k in keys}, per_rank * 2, 0, 1, shuffle=False)
+                    cls_v = OBBValidator if isinstance(self.model, OBBModel) else (SegmentationValidator if seg else DetectionValidator)
+                    self.validator = cls_v(a)  # obb/train.py:39-43, segment/train.py:39-44
         self.resume_training(self._resume_ckpt)  # trainer.py:315 (after the optimizer exists)
         self._resume_ckpt = None
 

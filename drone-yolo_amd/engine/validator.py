@@ -244,8 +244,9 @@ class SegmentationValidator(DetectionValidator):
     box matching run as in the detection validator; with ``device_match`` the masks are scored by ``dy_val_mask_match`` on the prototypes
     (no mask is stored, nothing in the batch loop waits for the device), without it by the reference's data flow on the host, image by
     image (``host_pred_masks`` / ``host_gt_masks`` / ``host_mask_iou`` / ``match_predictions``).  The dataset carries ``masks``: the
-    reference's ``overlap_mask=True`` index map (N, gh, gw).  No validation loss (the segmentation criterion is not built, and the
-    reference's stand-alone ``val`` computes none): the dict holds the eight metrics and ``fitness``."""
+    reference's ``overlap_mask=True`` index map (N, gh, gw).  No validation loss (in eval mode the head hands on concatenated coefficients, ``v8SegmentationLoss``
+    takes the per-level maps; the reference's stand-alone ``val`` computes none): the dict holds the eight metrics and ``fitness``.  The trainer
+    calls this validator per epoch for a ``SegmentationModel`` whose validation split carries ``masks`` (engine/trainer.py)."""
 
     stat_keys = ("tp", "tp_m")
     metrics_cls = SegmentMetrics

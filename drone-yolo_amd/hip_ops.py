@@ -21,7 +21,7 @@ import warnings
 import torch
 
 from . import _lib
-from ._lib import DY_ACT_NONE, DY_ACT_SILU, DY_ACT_SILU_L2E, BnDesc, BranchDesc, C2fDesc, C2fFrontDesc, C2fTailDesc, ConvDesc, DecodeDesc, HeadDecodeDesc, LossDesc, NmsDesc, ObbLossDesc, Stem2Desc, TileFuseDesc, TileMergeDesc, TrackDesc, ValMaskMatchDesc, ValMatchDesc, check, lib
+from ._lib import DY_ACT_NONE, DY_ACT_SILU, DY_ACT_SILU_L2E, BnDesc, BranchDesc, C2fDesc, C2fFrontDesc, C2fTailDesc, ConvDesc, DecodeDesc, HeadDecodeDesc, LossDesc, NmsDesc, ObbLossDesc, SegLossDesc, Stem2Desc, TileFuseDesc, TileMergeDesc, TrackDesc, ValMaskMatchDesc, ValMatchDesc, check, lib
 
 FP8 = torch.float8_e4m3fn  # OCP e4m3fn: gfx950's fp8 (MI300's fnuz is another encoding)
 # DY_F16X2 (include/dyolo.h): split float16 pairs, x ~= hi + lo * 2^-11 — the bar-exact precision on the 16-bit MFMA.  torch has no such
@@ -1640,6 +1640,72 @@ def obb_loss(levels: Sequence[torch.Tensor], angles: Sequence[torch.Tensor], gt:
     return (out, owner, grads, agrads) if want_grad else (out, owner)
 
 
+def seg_loss(owner: torch.Tensor, gt: torch.Tensor, coefs: Sequence[torch.Tensor], proto: torch.Tensor, masks: torch.Tensor, img_hw, box: float = 7.5,
+             topk: int = 10, want_grad: bool = False, buffers: Optional[dict] = None):
+    """The mask term of v8SegmentationLoss (and its gradient) through ``dy_seg_loss``, behind ``detection_loss(..., want_owner=True)``.
+
+    owner: int32 (N, A) from ``detection_loss``; gt: its fp32 (N, gmax, 5) table; coefs[i]: fp32 NHWC views (N, 32, h_i, w_i) of Segment.cv4;
+    proto: an NHWC view (N, 32, mh, mw) in bf16, f16 or fp32; masks: uint8 or int32 (N, gh, gw) overlap index maps (value k + 1 = row k of the
+    image in ``gt``) with (mh, mw) = (gh, gw) or exactly twice it; img_hw = (h, w) of the input in pixels.  Every argument is checked here, on the
+    host, before any launch.  Returns ``out`` (fp32[2] = seg, seg * N) and, with ``want_grad``, the fp32 gradient maps of d (seg * N): one per
+    coefficient level (shape and pitch of ``coefs[i]``) and the prototypes' (N, 32, mh, mw).  ``buffers``: a dict the call fills on first use
+    and reuses afterwards (out, workspace, gradient maps)."""
+    require_device(owner, "seg_loss owner")
+    require_device(proto, "seg_loss proto")
+    if not isinstance(masks, torch.Tensor) or masks.dtype not in (torch.uint8, torch.int32):
+        raise TypeError(f"seg_loss: masks must be uint8 or int32 overlap index maps (overlap_mask=True), got {getattr(masks, 'dtype', type(masks).__name__)}")
+    n, nm, mh, mw = proto.shape
+    if nm != NM or any(t.shape[1] != NM for t in coefs):
+        raise NotImplementedError(f"seg_loss: built for nm = {NM} mask coefficients, got {nm}")
+    if masks.dim() != 3 or masks.shape[0] != n:
+        raise ValueError(f"seg_loss: masks must be (N, gh, gw) index maps, got {tuple(masks.shape)}")
+    gh, gw = int(masks.shape[1]), int(masks.shape[2])
+    if (mh, mw) != (gh, gw) and (mh, mw) != (2 * gh, 2 * gw):
+        raise ValueError(f"seg_loss: the prototype grid {mh} x {mw} must equal the index map's {gh} x {gw} or be exactly twice it on both axes")
+    if proto.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+        raise TypeError(f"seg_loss: prototypes must be bfloat16, float16 or float32, got {proto.dtype}")
+    dev = proto.device
+    A = sum(t.shape[2] * t.shape[3] for t in coefs)
+    if owner.dtype != torch.int32 or tuple(owner.shape) != (n, A) or not owner.is_contiguous():
+        raise ValueError(f"seg_loss: owner must be a contiguous int32 ({n}, {A}) map")
+    gt = gt.to(dev, torch.float32).contiguous()
+    if gt.dim() != 3 or gt.shape[0] != n or gt.shape[2] != 5:
+        raise ValueError("seg_loss: gt must be (N, gmax, 5)")
+    gmax = gt.shape[1]
+    if masks.dtype == torch.uint8 and gmax > 255:
+        raise ValueError(f"seg_loss: {gmax} label rows do not fit a uint8 index map; pass int32 maps")
+    masks = masks.to(dev).contiguous()
+    d = SegLossDesc()
+    for i, t in enumerate(coefs):
+        require_device(t)
+        if t.dtype != torch.float32 or t.shape[0] != n:
+            raise ValueError("seg_loss: coefficient maps must be fp32 (N, 32, h, w)")
+        d.coef[i], d.ld_coef[i] = view_params(t)
+        d.h[i], d.w[i] = t.shape[2], t.shape[3]
+    d.owner, d.gt = owner.data_ptr(), (gt.data_ptr() if gmax else None)
+    d.n_levels, d.batch, d.nm, d.gmax, d.topk = len(coefs), n, nm, gmax, topk
+    d.proto, d.ld_proto = view_params(proto)
+    d.proto_dtype, d.mh, d.mw = dy_dtype(proto.dtype), mh, mw
+    d.masks, d.mask_dtype, d.gh, d.gw = masks.data_ptr(), (1 if masks.dtype == torch.int32 else 0), gh, gw
+    d.img_h, d.img_w, d.box_gain = float(img_hw[0]), float(img_hw[1]), box
+    bufs = buffers if buffers is not None else {}
+    if "out" not in bufs:
+        bufs["out"] = torch.empty(2, dtype=torch.float32, device=dev)
+        bufs["ws"] = torch.empty(lib().dy_seg_loss_workspace_bytes(n, A, gmax, topk), dtype=torch.uint8, device=dev)
+        bufs["gcoef"] = bufs["gproto"] = None
+        if want_grad:
+            bufs["gcoef"] = [alloc_nhwc(n, NM, t.shape[2], t.shape[3], torch.float32, dev, ld=d.ld_coef[i]) for i, t in enumerate(coefs)]
+            bufs["gproto"] = alloc_nhwc(n, NM, mh, mw, torch.float32, dev)
+    out, ws, gcoef, gproto = bufs["out"], bufs["ws"], bufs["gcoef"], bufs["gproto"]
+    d.out, d.workspace, d.workspace_bytes = out.data_ptr(), ws.data_ptr(), ws.numel()
+    if want_grad:
+        for i in range(len(coefs)):
+            d.grad_coef[i], d.ld_grad_coef[i] = view_params(gcoef[i])
+        d.grad_proto, d.ld_grad_proto = view_params(gproto)
+    _launch(lib().dy_seg_loss, (C.byref(d),), keep=(d, out, ws, owner, gt, masks, proto, *coefs, *(gcoef or ()), gproto))
+    return (out, gcoef, gproto) if want_grad else out
+
+
 # ---- train-mode BatchNorm (+ SiLU) -------------------------------------------------------------------------------
 
 
@@ -1930,6 +1996,34 @@ def obb_angle_grad_cast(g: torch.Tensor, dtype: torch.dtype, scale: Optional[tor
     dz = alloc_nhwc(n, ANGLE_PAD, h, w, dtype, g.device)
     dp, ldd = view_params(dz)
     _launch(lib().dy_obb_angle_grad_cast, (gp, ldg, n * h * w, scale.data_ptr() if scale is not None else None, dp, ldd, dy_dtype(dtype)), keep=(g, dz, scale))
+    return dz
+
+
+def space_to_depth2(x: torch.Tensor) -> torch.Tensor:
+    """(n, c, 2h, 2w) -> (n, 4c, h, w), out[:, (a * 2 + b) * c + o, y, x] = x[:, o, 2y + a, 2x + b] (``dy_space_to_depth2_nhwc``): the inverse of
+    ``depth_to_space2``, for the backward of Proto's transposed convolution."""
+    require_device(x, "space_to_depth2 input")
+    n, c, h2, w2 = x.shape
+    if h2 % 2 or w2 % 2:
+        raise ValueError("space_to_depth2: even height and width are expected")
+    out = alloc_nhwc(n, 4 * c, h2 // 2, w2 // 2, x.dtype, x.device)
+    (xp, lds), (op, ldd) = view_params(x), view_params(out)
+    _launch(lib().dy_space_to_depth2_nhwc, (xp, op, n, h2 // 2, w2 // 2, c, lds, ldd, dy_dtype(x.dtype)), keep=(x, out))
+    return out
+
+
+def grad_cast_scaled(g: torch.Tensor, dtype: torch.dtype, scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``dy_grad_cast_scaled``: ``g`` an fp32 NHWC view (n, c, h, w), c a multiple of 8 -> the same map in ``dtype``, times ``scale`` (a device
+    fp32 scalar or None): the dz of the convolution gradients from a loss kernel's fp32 gradient map."""
+    n, c, h, w = g.shape
+    if g.dtype != torch.float32:
+        raise ValueError("grad_cast_scaled: g must be fp32")
+    if scale is not None and (scale.dtype != torch.float32 or not scale.is_cuda or scale.numel() != 1):
+        raise ValueError("grad_cast_scaled: scale must be one fp32 value on the device")
+    gp, ldg = view_params(g)
+    dz = alloc_nhwc(n, c, h, w, dtype, g.device)
+    dp, ldd = view_params(dz)
+    _launch(lib().dy_grad_cast_scaled, (gp, ldg, n * h * w, c, scale.data_ptr() if scale is not None else None, dp, ldd, dy_dtype(dtype)), keep=(g, dz, scale))
     return dz
 
 

@@ -587,3 +587,106 @@ class OBBLossFn(torch.autograd.Function):
                 LAZY_SEED[g.data_ptr()] = g_total
             return (None, None, None, None, None, None, *ctx.grads)
         return (None, None, None, None, None, None, *[g * g_total for g in ctx.grads])
+
+
+class CoefTail(torch.autograd.Function):
+    """conv1x1(x, w) + b to the 32 mask coefficients (Segment's cv4[i][2], head.py:184) as an fp32 NHWC map: ``AngleTail`` without the
+    padding (32 channels are whole chunks in every storage type)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        dtype, dev = x.dtype, x.device
+        n, _, h, wd = x.shape
+        buf = H.alloc_nhwc(n, w.shape[0], h, wd, torch.float32, dev)
+        H.conv2d(x, H.PackedConv(w, b, 1, 0, 1, False, dtype, dev, for_out_f32=True), out=buf, out_f32=True)
+        ctx.save_for_backward(x, w)
+        ctx.bias = b
+        return buf
+
+    @_commits_sink
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        b = ctx.bias
+        dtype, dev = x.dtype, x.device
+        seed = LAZY_SEED.pop(dy.data_ptr(), None)  # by the address SegLossFn.backward handed over, before any re-layout
+        dz = H.grad_cast_scaled(dy if dy.stride(1) == 1 else as_nhwc(dy), dtype, scale=seed)
+        sw, sb = grad_sink(w), grad_sink(b)
+        dw = H.conv_wgrad(x, dz, 1, 1, 0, out=None if sw is None else sw.view(w.shape[0], 1, 1, w.shape[1]))
+        db = H.colsum(dz, out=sb)
+        dx = H.conv_dgrad(dz, H.pack_dgrad(w, 1, dtype, dev), 1)
+        return dx, (None if sw is not None else dw), (None if sb is not None else db)
+
+
+class DeconvUp2x(torch.autograd.Function):
+    """nn.ConvTranspose2d(c, c, 2, 2, 0, bias=True) in training (Proto.upsample, block.py:91): the 1x1 convolution c -> 4c on the live weights
+    repacked by ``H.deconv2x2_as_conv1x1`` plus the depth-to-space, as in prediction.  Backward: the space-to-depth of dy is the 1x1
+    convolution's dz; its weight gradient (4c, c) goes back to the parameter's (in, out, 2, 2) element order, the bias gradient is the column
+    sum folded over the four sub-positions."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        dtype, dev = x.dtype, x.device
+        w1, b1 = H.deconv2x2_as_conv1x1(weight, bias)
+        y = H.depth_to_space2(H.conv2d(x, H.PackedConv(w1, b1, 1, 0, 1, False, dtype, dev)))
+        ctx.save_for_backward(x, weight, w1)
+        ctx.bias = bias
+        return y
+
+    @_commits_sink
+    def backward(ctx, dy):
+        x, weight, w1 = ctx.saved_tensors
+        bias = ctx.bias
+        dtype, dev = x.dtype, x.device
+        cin, cout = weight.shape[0], weight.shape[1]
+        dz = H.space_to_depth2(as_nhwc(dy))  # (n, 4 cout, h, w): channel (a * 2 + b) * cout + o
+        sw, sb = grad_sink(weight), grad_sink(bias)
+        dw1 = H.conv_wgrad(x, dz, 1, 1, 0).permute(0, 2, 3, 1).reshape(2, 2, cout, cin)  # the kernel's (4 cout, 1, 1, cin) buffer
+        if sw is not None:  # the sink's order for a 4-D parameter is (dim 0, k, k, dim 1) (FlatState.enable_sink): here (in, 2, 2, out)
+            sw.view(cin, 2, 2, cout).add_(dw1.permute(3, 0, 1, 2))
+            dw = None
+        else:
+            dw = dw1.permute(3, 2, 0, 1)
+        db = None
+        if bias is not None:
+            db4 = H.colsum(dz).view(4, cout).sum(0)
+            if sb is not None:
+                sb.add_(db4)
+            else:
+                db = db4
+        dx = H.conv_dgrad(dz, H.pack_dgrad(w1, 1, dtype, dev), 1)
+        return dx, dw, db
+
+
+class SegLossFn(torch.autograd.Function):
+    """v8SegmentationLoss as ONE node: dy_detection_loss (box / class / DFL value, gradients and the owner map) on the head maps, then
+    dy_seg_loss (the mask term and its gradients w.r.t. the coefficient maps and the prototypes) behind that owner map.
+    ``maps``: nl head maps, nl coefficient maps, the prototypes (storage type).  Returns total and items = (box, seg, cls, dfl)."""
+
+    @staticmethod
+    def forward(ctx, gt, masks, strides, nc, reg_max, hyp, nl, *maps):
+        levels, coefs, proto = maps[:nl], maps[nl : 2 * nl], maps[2 * nl]
+        out, owner, grads = H.detection_loss(levels, gt, strides, nc, reg_max, box=hyp[0], cls=hyp[1], dfl=hyp[2], want_owner=True, want_grad=True)
+        hw = (levels[0].shape[2] * float(strides[0]), levels[0].shape[3] * float(strides[0]))
+        sout, gcoef, gproto = H.seg_loss(owner, gt, coefs, proto, masks, hw, box=hyp[0], want_grad=True)
+        ctx.grads = [g[:, : levels[0].shape[1]] for g in grads] + list(gcoef)
+        ctx.gproto, ctx.proto_dtype = gproto, proto.dtype
+        total = out[3] + sout[1]
+        items = torch.stack((out[0], sout[0], out[1], out[2]))
+        ctx.mark_non_differentiable(items)
+        return total, items
+
+    @staticmethod
+    def backward(ctx, g_total, g_items):
+        none = (None,) * 7
+        if g_total is None:
+            return (*none, *([None] * (len(ctx.grads) + 1)))
+        lazy = g_total.is_cuda and g_total.dtype == torch.float32 and g_total.numel() == 1
+        # the prototypes' gradient leaves in the storage type: the cast is this node's, and the seed rides in it (a device read)
+        gp = H.grad_cast_scaled(ctx.gproto, ctx.proto_dtype, scale=g_total.reshape(1)) if lazy else (ctx.gproto * g_total).to(ctx.proto_dtype)
+        if _LAZY[0] and lazy:
+            # the trainer's own backward: head and coefficient maps go on UNSCALED; HeadTail.backward and CoefTail.backward multiply by the
+            # seed inside their cast kernels
+            for g in ctx.grads:
+                LAZY_SEED[g.data_ptr()] = g_total
+            return (*none, *ctx.grads, gp)
+        return (*none, *[g * g_total for g in ctx.grads], gp)

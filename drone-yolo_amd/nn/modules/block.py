@@ -68,7 +68,7 @@ class Proto(_PackedMixin, nn.Module):
 
     def forward(self, x):
         if self.training:
-            raise NotImplementedError("Proto: training a segmentation model (v8SegmentationLoss) is not built; prediction only")
+            raise NotImplementedError("Proto.forward in training mode is not built: training goes through nn/train_forward.py::proto_train (SegmentationModel.forward_train)")
         t = self.cv1(x)
         t = H.conv_transpose2x2(t, self._packed_for(t))
         t = self.cv2(t)

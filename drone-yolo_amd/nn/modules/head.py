@@ -259,7 +259,8 @@ class Segment(Detect):
     (N, nm, mh, mw) fp32 in true units (an NHWC view).  On the predictor's fast path (``fuse_tail``) nothing is concatenated: the
     Detect kernels produce y and the candidate list as for a detection model and the return is ``(y, (None, levels, p))`` with ``levels``
     the per-level fp32 NHWC coefficient maps (N, nm, h_i, w_i) that ``dy_mask_gather`` reads.  The box and class branches go through
-    every fusion of ``Detect`` unchanged.
+    every fusion of ``Detect`` unchanged.  Training: ``SegmentationModel.forward_train`` -> ``train_forward.segment_train`` (the maps of
+    ``detect_train``, ``cv4`` through ``CoefTail``, ``proto`` through ``proto_train``); this module's own ``forward`` raises in training mode.
     """
 
     def __init__(self, nc=80, nm=32, npr=256, ch=()):
@@ -281,7 +282,8 @@ class Segment(Detect):
 
     def forward(self, x):
         if self.training:
-            raise NotImplementedError("Segment: training a segmentation model (v8SegmentationLoss) is not built; prediction only")
+            raise NotImplementedError("Segment.forward in training mode is not built: training goes through SegmentationModel.forward_train "
+                                      "(nn/train_forward.py::segment_train), which returns (feats, coef_levels, proto)")
         if any(t.dtype == H.FP8 for t in x):
             raise NotImplementedError("Segment is built for the 16-bit, split-float16 and fp32 storage types")
         x = list(x)

@@ -507,19 +507,23 @@ class DetectionModel(BaseModel):
 
 
 class SegmentationModel(DetectionModel):
-    """YOLO segmentation model — reference tasks.py:403-412.  Prediction only: the mask loss (v8SegmentationLoss) is not built."""
+    """YOLO segmentation model -- reference tasks.py:403-412.  Predicts, validates and trains: ``forward_train`` returns
+    ``(feats, coef_levels, proto)`` (nn/train_forward.py::segment_train), ``init_criterion`` the device loss ``v8SegmentationLoss``
+    (utils/loss.py: ``dy_detection_loss`` + ``dy_seg_loss``).  The criterion exists on the device only: ``init_criterion`` on a model whose
+    parameters are still on the CPU raises ``NotImplementedError`` (the trainer moves the model first)."""
 
     def __init__(self, cfg="yolov8s-p2-repvgg-seg.yaml", ch=3, nc=None, verbose=True):
         super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
 
     def init_criterion(self):
-        raise NotImplementedError("train: the segmentation loss (v8SegmentationLoss) is not built; segmentation models predict only")
+        if not next(self.parameters()).is_cuda:
+            raise NotImplementedError("train: the segmentation loss (v8SegmentationLoss) runs on the device only (dy_seg_loss); move the model to the MI355X first")
+        from ..utils.loss import v8SegmentationLoss
+
+        return v8SegmentationLoss(self)
 
     def _predict_augment(self, x, image_dtype=None):
         raise NotImplementedError("augment=True is not built for segmentation models")
-
-    def forward_train(self, img, dtype=None):
-        raise NotImplementedError("train: segmentation models predict only")
 
 
 class OBBModel(DetectionModel):

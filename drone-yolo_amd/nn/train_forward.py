@@ -92,8 +92,27 @@ def obb_train(m, xs: List[torch.Tensor]):
     return feats, angles
 
 
+def proto_train(m, x):
+    """Proto.forward in training (block.py:80-97): cv1 -> the transposed convolution (``A.DeconvUp2x``) -> cv2 -> cv3.  The prototypes stay
+    in the training storage type; ``dy_seg_loss`` reads them as stored."""
+    t = conv_train(m.cv1, x)
+    t = A.DeconvUp2x.apply(t, m.upsample.weight, m.upsample.bias)
+    return conv_train(m.cv3, conv_train(m.cv2, t))
+
+
+def segment_train(m, xs: List[torch.Tensor]):
+    """Segment.forward's training return (head.py:186-197): ``(feats, coef_levels, proto)`` = ``detect_train``'s maps, per level the fp32
+    map of the 32 mask coefficients (cv4 through ``A.CoefTail``) and the prototypes of the first level."""
+    if m.nm != H.NM:
+        raise NotImplementedError(f"Segment training is built for nm = {H.NM} mask coefficients")
+    p = proto_train(m.proto, xs[0])
+    feats = detect_train(m, xs)
+    coefs = [A.CoefTail.apply(conv_pair_train(c[0], c[1], x), c[2].weight, c[2].bias) for c, x in zip(m.cv4, xs)]
+    return feats, coefs, p
+
+
 def module_train(m, x, first: bool = False, img_u8=None):
-    from .modules import C2f, Concat, Conv, Detect, OBB, RepVGGBlock, SPPF, Upsample
+    from .modules import C2f, Concat, Conv, Detect, OBB, RepVGGBlock, Segment, SPPF, Upsample
 
     if isinstance(m, nn.Sequential):
         for mm in m:
@@ -113,6 +132,8 @@ def module_train(m, x, first: bool = False, img_u8=None):
         return A.ConcatC.apply(*x)
     if isinstance(m, OBB):  # before Detect: OBB is a Detect
         return obb_train(m, x)
+    if isinstance(m, Segment):  # before Detect: Segment is a Detect
+        return segment_train(m, x)
     if isinstance(m, Detect):
         return detect_train(m, x)
     raise NotImplementedError(f"no training forward for {type(m).__name__}")

@@ -153,3 +153,41 @@ class v8OBBLoss(v8DetectionLoss):
             return OBBLossFn.apply(gt, strides, self.nc, self.reg_max, (self.box, self.cls, self.dfl), len(feats), *feats, *angles)
         out, _ = H.obb_loss(feats, angles, gt, strides, self.nc, self.reg_max, topk=self.topk, box=self.box, cls=self.cls, dfl=self.dfl)
         return out[3], out[:3]
+
+
+class v8SegmentationLoss(v8DetectionLoss):
+    """Segmentation training loss on the device (reference: ultralytics/utils/loss.py:263-443 ``v8SegmentationLoss``, ``overlap_mask=True``):
+    the detection loss through ``dy_detection_loss`` as the parent runs it, then the mask term through ``dy_seg_loss`` behind its owner map.
+
+    ``preds`` is ``(feats, coef_levels, proto)``: the per-level fp32 head maps, per level the fp32 map of the 32 mask coefficients, and the
+    prototypes (N, 32, mh, mw) in the storage type.  ``batch["masks"]``: uint8 / int32 (N, gh, gw) overlap index maps, value k + 1 = the
+    image's k-th label in the batch's order (= row k of the label table), with (mh, mw) = (gh, gw) or exactly twice it.  Items come back in
+    the reference's order: box, seg, cls, dfl.  The foreground set of the mask term is the owner map's (anchors with a positive alignment
+    metric); the reference's zero-metric picks, which follow ``torch.topk``'s tie order, are left out (DESIGN)."""
+
+    width = 5  # the parent's table: [cls, x1, y1, x2, y2]
+
+    def __call__(self, preds, batch):
+        feats = preds[0]
+        if "masks" not in batch:
+            raise TypeError("the segmentation loss needs batch['masks'] (overlap index maps); is this a detection dataset?")
+        hw = (feats[0].shape[2] * float(self.stride[0]), feats[0].shape[3] * float(self.stride[0]))
+        return self.from_gt(preds, self.targets_to_gt(batch, feats[0].shape[0], hw), batch["masks"])
+
+    def from_gt(self, preds, gt: torch.Tensor, masks: torch.Tensor):
+        """loss, loss_items from the label table and the index maps themselves (host or device): the graphed step keeps both in static
+        device buffers."""
+        feats, coefs, proto = preds
+        self.check_classes(gt, self.nc)
+        strides = [float(s) for s in self.stride]
+        hyp = (self.box, self.cls, self.dfl)
+        if any(t.requires_grad for t in (*feats, *coefs, proto)):
+            if self.topk != 10:
+                raise NotImplementedError("the differentiable path uses the default tal_topk of 10")
+            from ..nn.autograd_ops import SegLossFn
+
+            return SegLossFn.apply(gt, masks, strides, self.nc, self.reg_max, hyp, len(feats), *feats, *coefs, proto)
+        out, owner = H.detection_loss(feats, gt, strides, self.nc, self.reg_max, topk=self.topk, box=self.box, cls=self.cls, dfl=self.dfl, want_owner=True)
+        hw = (feats[0].shape[2] * strides[0], feats[0].shape[3] * strides[0])
+        sout = H.seg_loss(owner, gt, coefs, proto, masks, hw, box=self.box, topk=self.topk)
+        return out[3] + sout[1], torch.stack((out[0], sout[0], out[1], out[2]))

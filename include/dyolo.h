@@ -839,6 +839,61 @@ int32_t dy_obb_loss(const dy_obb_loss_desc* d, dy_stream_t stream);
  * channel 0, zeros in channels 1..7: the one-channel 1x1 convolution of the OBB head padded to a width the convolution gradients serve. */
 int32_t dy_obb_angle_grad_cast(const float* g, int32_t ld_g, int64_t rows, const float* scale, void* dz, int32_t ld_dz, int32_t dtype, dy_stream_t stream);
 
+/* ---- segmentation training loss: the mask term (forward + gradient w.r.t. the mask coefficients and the prototypes) ------------
+ * Replaces: the mask part of v8SegmentationLoss.__call__ (utils/loss.py:334-350), calculate_segmentation_loss and single_mask_loss
+ * (loss.py:354-443) and crop_mask (utils/ops.py:660-676), overlap_mask = True, and their autograd.  The box, class and DFL terms and the
+ * assignment stay with dy_detection_loss, called in front of it: `owner` is its out_owner, `gt` its label table.
+ * owner: DEVICE int32 (batch, A): the label row of every anchor, < 0 = background.  The foreground set is owner >= 0, i.e. the anchors whose
+ * alignment metric is positive (the reference's fg_mask may also hold picks at metric 0, whose choice follows torch.topk's tie order).
+ * gt: DEVICE fp32 (batch, gmax, 5) = class, x1, y1, x2, y2 in input pixels.  img_h, img_w: the input size in pixels.
+ * coef[l]: fp32 NHWC view (batch, h_l, w_l, nm) of pitch ld_coef[l] (a multiple of 4, 16-byte aligned): the outputs of Segment.cv4[l]; anchors
+ * are numbered level by level, row-major, as in dy_loss_desc.  proto: NHWC (batch, mh, mw, nm) of proto_dtype (DY_BF16 / DY_F16 / DY_F32),
+ * pitch ld_proto.  nm must be 32 (DY_ERR_UNSUPPORTED otherwise).
+ * masks: (batch, gh, gw) overlap index maps, mask_dtype DY_MASK_U8 or DY_MASK_I32: value k + 1 = row k of that image in gt (padding rows in
+ * the middle count as rows), 0 = nothing.  (mh, mw) = (gh, gw), or exactly twice it: then prototype pixel (y, x) reads map pixel (y >> 1, x >> 1),
+ * F.interpolate(mode="nearest") at scale 2; any other ratio: DY_ERR_UNSUPPORTED.
+ * Per foreground anchor a of image b with label row g: logit(p) = coef[a] . proto[b, p, :], target(p) = (masks[b, p] == g + 1), l(p) the BCE
+ * with logits in its stable form; the crop is the LABEL's box on the prototype grid: column r is in iff r >= x1m && r < x2m with
+ * x1m = (x1 / img_w) * mw in fp32 in that order, rows alike; term = sum_crop l / (mh * mw) / area, area = (x2/img_w - x1/img_w) *
+ * (y2/img_h - y1/img_h); seg = box_gain * sum(term) / n_fg (0 with n_fg = 0, and every gradient 0).
+ * out: DEVICE fp32[2] = seg, seg * batch (its contribution to the total).  grad_proto null: value only.  Otherwise grad_coef[l] (fp32, pitch
+ * ld_grad_coef[l], a multiple of 4; channels 0..31 of EVERY row written on every call, zeros for a background anchor) and grad_proto (fp32
+ * NHWC (batch, mh, mw, 32), pitch ld_grad_proto; every pixel written) hold d (seg * batch) / d input.  No atomics: two calls on the same inputs
+ * give the same bits.  topk: dy_detection_loss's (an image has at most gmax * topk foreground anchors).  Nothing synchronises the host; the
+ * launch sequence can be captured into a hipGraph. */
+#define DY_MASK_U8 0
+#define DY_MASK_I32 1
+typedef struct dy_seg_loss_desc {
+  const int32_t* owner;
+  const float* gt;
+  const float* coef[DY_MAX_LEVELS];
+  int32_t h[DY_MAX_LEVELS], w[DY_MAX_LEVELS], ld_coef[DY_MAX_LEVELS];
+  int32_t n_levels, batch, nm, gmax, topk;
+  const void* proto;
+  int32_t proto_dtype, ld_proto, mh, mw;
+  const void* masks;
+  int32_t mask_dtype, gh, gw;
+  float img_h, img_w, box_gain;
+  float* out;
+  void* workspace;
+  int64_t workspace_bytes;
+  float* grad_coef[DY_MAX_LEVELS];
+  int32_t ld_grad_coef[DY_MAX_LEVELS];
+  float* grad_proto;
+  int32_t ld_grad_proto;
+} dy_seg_loss_desc;
+int64_t dy_seg_loss_workspace_bytes(int32_t batch, int32_t anchors, int32_t gmax, int32_t topk);
+int32_t dy_seg_loss(const dy_seg_loss_desc* d, dy_stream_t stream);
+/* dy_space_to_depth2_nhwc: the inverse of dy_depth_to_space2_nhwc (below), for the backward of Proto's transposed convolution:
+ * src (n, 2h, 2w, c) -> dst (n, h, w, 4c), dst[n, y, x, (a * 2 + b) * c + o] = src[n, 2y + a, 2x + b, o].  Same dtypes, alignment and c % 8 rule.
+ * dy_grad_cast_scaled: fp32 rows (rows, c) of pitch ld_g (a multiple of 4, 16-byte aligned) -> rows of `dtype` (DY_BF16 / DY_F16 / DY_F32; pitch
+ * ld_dz, whole 16-byte chunks) = g * (*scale, a DEVICE fp32 value, or 1 when scale is null); c % 8 != 0: DY_ERR_UNSUPPORTED.  It turns
+ * dy_seg_loss's gradient maps into the dz of the convolution gradients and applies the deferred seed of the backward pass. */
+int32_t dy_space_to_depth2_nhwc(const void* src, void* dst, int32_t n, int32_t h, int32_t w, int32_t c, int32_t ld_src, int32_t ld_dst,
+                                int32_t dtype, dy_stream_t stream);
+int32_t dy_grad_cast_scaled(const float* g, int32_t ld_g, int64_t rows, int32_t c, const float* scale, void* dz, int32_t ld_dz, int32_t dtype,
+                            dy_stream_t stream);
+
 /* ---- convolution gradients ------------------------------------------------------------------
  * Replaces: autograd of F.conv2d inside Conv / RepVGGBlock / Detect (nn/modules/conv.py:37-55) during
  * loss.backward() (engine/trainer.py:381-389).
