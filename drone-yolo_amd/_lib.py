@@ -161,6 +161,28 @@ class TileMergeRotatedDesc(C.Structure):
     ]  # fmt: skip
 
 
+class TileMaskOwnerDesc(C.Structure):
+    """Mirror of ``dy_tile_mask_owner_desc``."""
+
+    _fields_ = [
+        ("rows", _vp), ("counts", _vp), ("offsets_yx", _vp), ("kept_index", _vp), ("kept_count", _vp),
+        ("frames", _i32), ("tiles", _i32), ("max_det", _i32), ("merge_max_det", _i32),
+        ("thr", _f32), ("metric", _i32), ("agnostic", _i32), ("stitch", _i32),
+        ("owner", _vp),
+    ]  # fmt: skip
+
+
+class TileProcessMaskDesc(C.Structure):
+    """Mirror of ``dy_tile_process_mask_desc``."""
+
+    _fields_ = [
+        ("protos", _vp), ("side", _vp), ("counts", _vp), ("offsets_yx", _vp), ("owner", _vp), ("dest", _vp),
+        ("frames", _i32), ("tiles", _i32), ("max_det", _i32), ("merge_max_det", _i32), ("nm", _i32), ("mh", _i32), ("mw", _i32), ("ld_p", _i32),
+        ("tile_h", _i32), ("tile_w", _i32), ("frame_h", _i32), ("frame_w", _i32), ("stride", _i32), ("total", _i32),
+        ("out", _vp),
+    ]  # fmt: skip
+
+
 class TrackDesc(C.Structure):
     """Mirror of ``dy_track_desc``."""
 
@@ -409,6 +431,8 @@ SIGNATURES = {
     "dy_tile_fuse": (_i32, [C.POINTER(TileFuseDesc), _vp]),
     "dy_tile_merge_rotated_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "dy_tile_merge_rotated": (_i32, [C.POINTER(TileMergeRotatedDesc), _vp]),
+    "dy_tile_mask_owner": (_i32, [C.POINTER(TileMaskOwnerDesc), _vp]),
+    "dy_tile_process_mask": (_i32, [C.POINTER(TileProcessMaskDesc), _vp]),
     "dy_upsample2x_bwd_nhwc": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dy_maxpool_bwd_nhwc": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dy_add_nhwc": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),

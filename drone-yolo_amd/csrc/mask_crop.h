@@ -37,4 +37,17 @@ __device__ __forceinline__ float proto_dot32(const float (&cf)[32], const float*
   return v;
 }
 
+// What dy_process_mask and dy_tile_process_mask (mask_ops.hip) share, so that a frame mask at stride 1 is the tile's mask bit for bit.
+// Source coordinate of PyTorch's bilinear resize (align_corners = False) for the output pixel whose CENTRE is at `centre` (dst + 0.5
+// in output pixels): scale * centre - 0.5, clamped at 0.
+__device__ __forceinline__ float pm_src_at(float scale, float centre) {
+  const float s = scale * centre - 0.5f;
+  return s < 0.f ? 0.f : s;
+}
+
+// The blend of the four corner values (top / bottom row, left / right column) with the weights of the two rows and the two columns.
+__device__ __forceinline__ float pm_blend(float ly0, float ly1, float lx0, float lx1, float tl, float tr, float bl, float br) {
+  return ly0 * (lx0 * tl + lx1 * tr) + ly1 * (lx0 * bl + lx1 * br);
+}
+
 }  // namespace dy

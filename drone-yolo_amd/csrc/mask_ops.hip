@@ -3,6 +3,7 @@
 // of the reference, utils/ops.py:660-753) in one launch.
 #include "common_hip.h"
 #include "mask_crop.h"
+#include "tile_limits.h"
 
 namespace dy {
 
@@ -121,10 +122,7 @@ __device__ __forceinline__ PmCol pm_column(const PmDet& D, int xx, int y0, int y
   return c;
 }
 
-__device__ __forceinline__ float pm_src(float scale, int dst) {
-  const float s = scale * ((float)dst + 0.5f) - 0.5f;
-  return s < 0.f ? 0.f : s;
-}
+__device__ __forceinline__ float pm_src(float scale, int dst) { return pm_src_at(scale, (float)dst + 0.5f); }
 
 // 0 / 1 of output pixel (y, x); (A, B, cy) carry the columns of the thread's previous pixel (cy: the row they belong to, -1: none)
 __device__ __forceinline__ unsigned pm_pixel(const PmDet& D, int y, int x, PmCol& A, PmCol& B, int& cy) {
@@ -145,7 +143,7 @@ __device__ __forceinline__ unsigned pm_pixel(const PmDet& D, int y, int x, PmCol
   }
   if (A.x != x0) A = (B.x == x0) ? B : pm_column(D, x0, y0, y1);
   if (B.x != x1) B = (A.x == x1) ? A : pm_column(D, x1, y0, y1);
-  const float v = ly0 * (lx0 * A.top + lx1 * B.top) + ly1 * (lx0 * A.bot + lx1 * B.bot);
+  const float v = pm_blend(ly0, ly1, lx0, lx1, A.top, B.top, A.bot, B.bot);
   return v > 0.f ? 1u : 0u;
 }
 
@@ -259,6 +257,121 @@ __global__ __launch_bounds__(kPmThreads) void process_mask_kernel(PmArgs a) {
   }
 }
 
+// ---- dy_tile_process_mask ----------------------------------------------------------------------------------------------------
+// Frame masks of tiled inference, driven by candidate: blockIdx.x = slot j = k * max_det + r of frame blockIdx.z.  A slot below its tile's
+// count whose owner t is a kept row with dest[t] = m >= 0 ORs its tile's mask into mask m of the output; every other workgroup leaves at
+// once and reads nothing more.  The workgroups of a live slot (gridDim.y of them, striding) cover the bounding region of its crop window in
+// output pixels, one aligned 32-bit word of the output (four bytes of one mask row) per thread: the four pixels share corner columns as in
+// dy_process_mask, and a word that holds a set pixel is OR-ed in with one integer atomic, so members of one row in overlapping tiles meet
+// in any order with the same result.  The entry point zeroes the output in front (tile_mask_zero_kernel on the same stream).  The pixel itself is
+// dy_process_mask's: pm_src_at / pm_column / pm_blend on the tile's proto grid at scale 0.25, the output pixel's centre taken in tile pixels.
+constexpr int kTpmThreads = 256;
+
+struct TpmArgs {
+  const float* protos;
+  const float* side;
+  const int* counts;
+  const int* offs;
+  const int* owner;
+  const int* dest;
+  unsigned char* out;
+  int K, max_det, N, keep, mh, mw, ld_p, th, tw, oh, ow, s, total;
+};
+
+// Zeroes `bytes` bytes at the 4-byte aligned p: 16-byte stores where p allows them, then the words and the at most three bytes that are left.
+// (A kernel, not a memset: see zero_async in common_hip.h.)
+__global__ __launch_bounds__(256) void tile_mask_zero_kernel(unsigned char* p, long long bytes, int vec) {
+  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x, step = (long long)gridDim.x * 256;
+  const long long n16 = vec ? bytes / 16 : 0;
+  for (long long i = gid; i < n16; i += step) reinterpret_cast<u32x4*>(p)[i] = u32x4{0u, 0u, 0u, 0u};
+  const long long n4 = bytes / 4;
+  for (long long i = n16 * 4 + gid; i < n4; i += step) reinterpret_cast<unsigned*>(p)[i] = 0u;
+  for (long long i = n4 * 4 + gid; i < bytes; i += step) p[i] = 0;
+}
+
+__global__ __launch_bounds__(kTpmThreads) void tile_process_mask_kernel(TpmArgs a) {
+  const int f = blockIdx.z, j = blockIdx.x;
+  const int tile = j / a.max_det, r = j - tile * a.max_det;
+  const long long b = (long long)f * a.K + tile;
+  if (r >= a.counts[b]) return;
+  const int t = a.owner[(long long)f * a.N + j];
+  if (t < 0 || t >= a.keep) return;
+  const int m = a.dest[(long long)f * a.keep + t];
+  if (m < 0 || m >= a.total) return;
+
+  const float* srow = a.side + (b * a.max_det + r) * 36;
+  const CropWin cw = crop_window(srow[0] * 0.25f, srow[1] * 0.25f, srow[2] * 0.25f, srow[3] * 0.25f, a.mw, a.mh);
+  if (cw.x_lo > cw.x_hi || cw.y_lo > cw.y_hi) return;
+  PmDet D;
+  D.ld_p = a.ld_p;
+  D.mw_ld = a.mw * a.ld_p;
+  D.sh = a.mh, D.sw = a.mw;
+  D.proto = a.protos + b * a.mh * D.mw_ld;
+  D.cx_lo = cw.x_lo, D.cx_hi = cw.x_hi, D.cy_lo = cw.y_lo, D.cy_hi = cw.y_hi;
+#pragma unroll
+  for (int k = 0; k < 32; ++k) D.cf[k] = srow[4 + k];
+
+  // Tile pixels whose corners can touch the crop: source coordinate in [c_lo - 1, c_hi + 1), i.e. t in [4 c_lo - 2, 4 c_hi + 6); then the
+  // output pixels whose centres (X + 0.5) * s - o can lie there, one pixel of slack each side (the pixel test below is the exact one).
+  const int oy = a.offs[2 * tile], ox = a.offs[2 * tile + 1];
+  const float fs = (float)a.s, inv = 1.f / fs;
+  const int tx_lo = max(4 * cw.x_lo - 2, 0), tx_hi = min(4 * cw.x_hi + 6, a.tw - 1);
+  const int ty_lo = max(4 * cw.y_lo - 2, 0), ty_hi = min(4 * cw.y_hi + 6, a.th - 1);
+  const int X_lo = max((int)floorf((float)(tx_lo + ox) * inv) - 1, 0), X_hi = min((int)floorf((float)(tx_hi + ox) * inv) + 1, a.ow - 1);
+  const int Y_lo = max((int)floorf((float)(ty_lo + oy) * inv) - 1, 0), Y_hi = min((int)floorf((float)(ty_hi + oy) * inv) + 1, a.oh - 1);
+  if (X_lo > X_hi || Y_lo > Y_hi) return;
+  const int W = X_hi - X_lo + 1, H = Y_hi - Y_lo + 1;
+  const int wpr = (W + 3) / 4 + 1;  // aligned words that can hold a row's W bytes
+  const long long items = (long long)H * wpr;
+  const long long base = (long long)m * a.oh * a.ow, bytes = (long long)a.total * a.oh * a.ow;
+  const float foy = (float)oy, fox = (float)ox, fth = (float)a.th, ftw = (float)a.tw;
+
+  for (long long i = (long long)blockIdx.y * kTpmThreads + threadIdx.x; i < items; i += (long long)gridDim.y * kTpmThreads) {
+    const int row = (int)(i / wpr), wi = (int)(i - (long long)row * wpr);
+    const int Y = Y_lo + row;
+    const long long rowbase = base + (long long)Y * a.ow;
+    const long long g_lo = rowbase + X_lo, g_hi = rowbase + X_hi;
+    const long long w0 = ((g_lo >> 2) + wi) << 2;  // first byte of this thread's word
+    if (w0 > g_hi) continue;
+    const float ty = ((float)Y + 0.5f) * fs - foy;
+    if (!(ty >= 0.f && ty < fth)) continue;
+    const float sy = pm_src_at(0.25f, ty);
+    int y0 = (int)sy;
+    y0 = y0 > a.mh - 1 ? a.mh - 1 : y0;
+    const int y1 = y0 + (y0 < a.mh - 1 ? 1 : 0);
+    const float ly1 = sy - (float)y0, ly0 = 1.f - ly1;
+    PmCol A, B;
+    A.x = B.x = -1;
+    A.top = A.bot = B.top = B.bot = 0.f;
+    unsigned word = 0u;
+#pragma unroll 1
+    for (int e = 0; e < 4; ++e) {
+      const long long g = w0 + e;
+      if (g < g_lo || g > g_hi) continue;
+      const int X = (int)(g - rowbase);
+      const float tx = ((float)X + 0.5f) * fs - fox;
+      if (!(tx >= 0.f && tx < ftw)) continue;
+      const float sx = pm_src_at(0.25f, tx);
+      int x0 = (int)sx;
+      x0 = x0 > a.mw - 1 ? a.mw - 1 : x0;
+      const int x1 = x0 + (x0 < a.mw - 1 ? 1 : 0);
+      const float lx1 = sx - (float)x0, lx0 = 1.f - lx1;
+      if (A.x != x0) A = (B.x == x0) ? B : pm_column(D, x0, y0, y1);
+      if (B.x != x1) B = (A.x == x1) ? A : pm_column(D, x1, y0, y1);
+      const float v = pm_blend(ly0, ly1, lx0, lx1, A.top, B.top, A.bot, B.bot);
+      if (v > 0.f) word |= 1u << (8 * e);
+    }
+    if (word == 0u) continue;
+    if (w0 + 4 <= bytes) {
+      atomicOr(reinterpret_cast<unsigned*>(a.out + w0), word);
+    } else {  // the buffer's last, partial word: every writer of it stores bytes
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if ((word >> (8 * e)) & 1u) a.out[w0 + e] = 1;
+    }
+  }
+}
+
 }  // namespace dy
 
 using namespace dy;
@@ -326,4 +439,42 @@ extern "C" int32_t dy_process_mask(const dy_process_mask_desc* d, dy_stream_t st
   a.div_ow = make_fastdiv((unsigned)d->ow);
   hipLaunchKernelGGL(process_mask_kernel, dim3((unsigned)d->total, (unsigned)gy), dim3(kPmThreads), 0, reinterpret_cast<hipStream_t>(stream), a);
   return check_launch("process_mask_kernel");
+}
+
+extern "C" int32_t dy_tile_process_mask(const dy_tile_process_mask_desc* d, dy_stream_t stream) {
+  DY_REQUIRE(d && d->protos && d->side && d->counts && d->offsets_yx && d->owner && d->dest, DY_ERR_INVALID_ARG,
+             "dy_tile_process_mask: null pointer (protos / side / counts / offsets_yx / owner / dest)");
+  DY_REQUIRE(d->nm == 32, DY_ERR_UNSUPPORTED, "dy_tile_process_mask: built for nm = 32 mask coefficients");
+  DY_REQUIRE(d->stride == 1 || d->stride == 2 || d->stride == 4, DY_ERR_UNSUPPORTED, "dy_tile_process_mask: stride %d (1, 2 or 4)", d->stride);
+  DY_REQUIRE(d->frames > 0 && d->tiles > 0 && d->max_det > 0 && d->merge_max_det > 0 && d->mh > 0 && d->mw > 0 && d->tile_h > 0 && d->tile_w > 0 &&
+                 d->frame_h > 0 && d->frame_w > 0 && d->total >= 0,
+             DY_ERR_INVALID_ARG, "dy_tile_process_mask: bad dims");
+  DY_REQUIRE((long long)d->mh * 4 == d->tile_h && (long long)d->mw * 4 == d->tile_w, DY_ERR_UNSUPPORTED,
+             "dy_tile_process_mask: a proto grid of %d x %d is not a quarter of the %d x %d tile", d->mh, d->mw, d->tile_h, d->tile_w);
+  DY_REQUIRE((long long)d->tiles * d->max_det <= TM_MAX_SLOTS, DY_ERR_UNSUPPORTED, "dy_tile_process_mask: tiles * max_det = %lld > %d",
+             (long long)d->tiles * d->max_det, TM_MAX_SLOTS);
+  DY_REQUIRE(d->merge_max_det <= TM_MAX_KEEP, DY_ERR_UNSUPPORTED, "dy_tile_process_mask: merge_max_det %d > %d", d->merge_max_det, TM_MAX_KEEP);
+  DY_REQUIRE(d->frames <= 65535, DY_ERR_UNSUPPORTED, "dy_tile_process_mask: %d frames are beyond the launch grid", d->frames);
+  DY_REQUIRE(d->tile_h < (1 << 20) && d->tile_w < (1 << 20) && d->frame_h < (1 << 20) && d->frame_w < (1 << 20), DY_ERR_INVALID_ARG,
+             "dy_tile_process_mask: sides of 2^20 pixels and more are beyond the exact fp32 coordinates");
+  DY_REQUIRE(d->ld_p >= 32 && d->ld_p % 4 == 0 && aligned16(d->protos), DY_ERR_INVALID_ARG,
+             "dy_tile_process_mask: protos must be 16-byte aligned 128-byte rows");
+  const int oh = (d->frame_h + d->stride - 1) / d->stride, ow = (d->frame_w + d->stride - 1) / d->stride;
+  DY_REQUIRE((long long)oh * ow < (1ll << 31), DY_ERR_INVALID_ARG, "dy_tile_process_mask: masks of %d x %d pixels", oh, ow);
+  DY_REQUIRE((long long)d->total <= (long long)d->frames * d->merge_max_det, DY_ERR_INVALID_ARG, "dy_tile_process_mask: total exceeds frames * merge_max_det");
+  if (d->total == 0) return DY_OK;
+  DY_REQUIRE(d->out && (reinterpret_cast<uintptr_t>(d->out) & 3u) == 0, DY_ERR_INVALID_ARG, "dy_tile_process_mask: out must be 4-byte aligned");
+  TpmArgs a;
+  a.protos = d->protos, a.side = d->side, a.counts = d->counts, a.offs = d->offsets_yx, a.owner = d->owner, a.dest = d->dest, a.out = d->out;
+  a.K = d->tiles, a.max_det = d->max_det, a.N = d->tiles * d->max_det, a.keep = d->merge_max_det, a.mh = d->mh, a.mw = d->mw, a.ld_p = d->ld_p;
+  a.th = d->tile_h, a.tw = d->tile_w, a.oh = oh, a.ow = ow, a.s = d->stride, a.total = d->total;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const long long bytes = (long long)d->total * oh * ow;
+  hipLaunchKernelGGL(tile_mask_zero_kernel, dim3(mask_grid_for(bytes / 16 + 1)), dim3(256), 0, st, d->out, bytes, aligned16(d->out) ? 1 : 0);
+  // workgroups per live slot: a tile-sized region in steps of eight words a thread, at most 16
+  const long long words = ((long long)d->tile_h / d->stride + 3) * (((long long)d->tile_w / d->stride + 3) / 4 + 2);
+  long long gy = (words + kTpmThreads * 8 - 1) / (kTpmThreads * 8);
+  gy = gy < 1 ? 1 : (gy > 16 ? 16 : gy);
+  hipLaunchKernelGGL(tile_process_mask_kernel, dim3((unsigned)a.N, (unsigned)gy, (unsigned)d->frames), dim3(kTpmThreads), 0, st, a);
+  return check_launch("tile_process_mask_kernel");
 }

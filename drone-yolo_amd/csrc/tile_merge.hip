@@ -42,6 +42,7 @@
 //                       can change).
 #include "nms_scan.h"
 #include "probiou.h"
+#include "tile_limits.h"
 
 #pragma clang fp contract(off)
 
@@ -109,8 +110,6 @@ __global__ __launch_bounds__(256) void tiles_batch_kernel(const uint8_t* __restr
 // ---- merge --------------------------------------------------------------------------------------------------------------------------------
 constexpr int TM_THREADS = 1024;
 constexpr int TM_WAVES = TM_THREADS / 64;
-constexpr int TM_MAX_SLOTS = 32768;                     // K * max_det
-constexpr int TM_MAX_KEEP = 4096;                       // merge_max_det
 constexpr int TM_MAX_LDS_KEYS = 16384;                  // 128 KiB of the CU's 160 KiB
 constexpr int TM_FIXED_LDS = 64 * 8 + TM_WAVES * 8 + 16;  // bit matrix, verdict words, two counters
 constexpr int TM_KEEP_BYTES = 24;                       // float4 box, area, class per kept row
@@ -179,6 +178,9 @@ struct TmBase {
     if (outi) outi[at] = slot;
   }
 };
+
+// the sort key of a candidate: ascending key order is descending score, ties by ascending slot (the compact pass, dy_tile_mask_owner)
+__device__ __forceinline__ u64 tm_key(float score, int slot) { return ((u64)(~__float_as_uint(score)) << 32) | (u64)(unsigned)slot; }
 
 struct TmCand {
   float x1, y1, x2, y2, score;
@@ -508,7 +510,7 @@ __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(const TmArgs p) 
     base = __shfl(base, 0);
     if (valid) {
       const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-      const u64 key = ((u64)(~__float_as_uint(score)) << 32) | (u64)(unsigned)j;
+      const u64 key = tm_key(score, j);
       if (in_lds) skeys[pos] = key;
       else gkeys[pos] = key;
     }
@@ -527,6 +529,99 @@ __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(const TmArgs p) 
   const Pol pol(TmBase<ROW>{p, skeys, gkeys, frows, outb, outi, kbox, k5, kcls, in_lds});
   const int nk = nms_greedy_scan<TM_WAVES, ROW>(pol, n, p.keep, mrows, verdict, outb, outi, p.out_count + f);
   if constexpr (Pol::TAIL) tm_fuse_tail(p, pol, f, n, nk);
+}
+
+// ---- dy_tile_mask_owner ------------------------------------------------------------------------------------------------------
+// One thread per slot j of a frame, brute force over the frame's kept rows in chunks of a workgroup's width staged in LDS (box, area, class
+// and sort key of the kept row's own candidate -- what the scan kept in its list).  Kept row t owns j when it IS j (equal keys) or, with
+// stitch, when it stands before j (smaller key) and tm_suppresses(t, j): tm_fuse_tail's absorb rule, the first such t.  A kept j meets no
+// earlier kept row that suppresses it (the scan would have dropped it), so it reaches itself.
+constexpr int TMO_THREADS = 256;
+
+struct TmoArgs {
+  const float* rows;
+  const int* counts;
+  const int* offs;
+  const int* kidx;
+  const int* kcnt;
+  int* owner;
+  int K, max_det, N, keep, metric, agnostic, stitch;
+  float thr;
+};
+
+struct TmoBox {
+  float x1, y1, x2, y2, area;
+  int cls;
+  u64 key;
+};
+
+// candidate `slot` of the frame whose rows are frows: TmScan's fetch() and box(), and the key of the compact pass
+__device__ __forceinline__ TmoBox tmo_box(const TmoArgs& p, const float* frows, int slot) {
+  const int tile = slot / p.max_det;
+  const float oy = (float)p.offs[2 * tile], ox = (float)p.offs[2 * tile + 1];
+  const float* q = frows + (size_t)slot * 6;
+  TmoBox b;
+  b.x1 = q[0] + ox;
+  b.y1 = q[1] + oy;
+  b.x2 = q[2] + ox;
+  b.y2 = q[3] + oy;
+  b.area = (b.x2 - b.x1) * (b.y2 - b.y1);
+  b.cls = (int)q[5];
+  b.key = tm_key(q[4], slot);
+  return b;
+}
+
+__global__ __launch_bounds__(TMO_THREADS) void tile_mask_owner_kernel(const TmoArgs p) {
+  __shared__ float4 sbox[TMO_THREADS];
+  __shared__ float sarea[TMO_THREADS];
+  __shared__ int scls[TMO_THREADS];
+  __shared__ u64 skey[TMO_THREADS];
+  const int f = blockIdx.y, tid = threadIdx.x;
+  const int j = blockIdx.x * TMO_THREADS + tid;
+  const float* frows = p.rows + (size_t)f * p.N * 6;
+  const int* fcounts = p.counts + (size_t)f * p.K;
+  const int* fkidx = p.kidx + (size_t)f * p.keep;
+  const int nk = min(max(p.kcnt[f], 0), p.keep);
+  bool valid = false;
+  if (j < p.N) {
+    const int tile = j / p.max_det;
+    valid = j - tile * p.max_det < fcounts[tile];
+  }
+  TmoBox me{0.f, 0.f, 0.f, 0.f, 0.f, -1, 0ull};
+  if (valid) me = tmo_box(p, frows, j);
+  int own = -1;
+  bool done = !valid;
+  for (int t0 = 0; t0 < nk; t0 += TMO_THREADS) {
+    const int t = t0 + tid;
+    TmoBox kb{0.f, 0.f, 0.f, 0.f, 0.f, -2, ~0ull};  // a kept_index outside the frame's slots: before nothing, equal to nothing
+    if (t < nk) {
+      const int slot = fkidx[t];
+      if (slot >= 0 && slot < p.N) kb = tmo_box(p, frows, slot);
+    }
+    sbox[tid] = make_float4(kb.x1, kb.y1, kb.x2, kb.y2);
+    sarea[tid] = kb.area;
+    scls[tid] = kb.cls;
+    skey[tid] = kb.key;
+    __syncthreads();
+    const int lim = min(TMO_THREADS, nk - t0);
+    if (!done) {
+      for (int u = 0; u < lim; ++u) {
+        const u64 ku = skey[u];
+        if (ku == me.key) {
+          own = t0 + u, done = true;
+          break;
+        }
+        if (!p.stitch || ku > me.key) continue;
+        const float4 b = sbox[u];
+        if (tm_suppresses(p.metric, p.agnostic, p.thr, b.x, b.y, b.z, b.w, sarea[u], scls[u], me.x1, me.y1, me.x2, me.y2, me.area, me.cls)) {
+          own = t0 + u, done = true;
+          break;
+        }
+      }
+    }
+    if (__syncthreads_and(done)) break;  // (a barrier as well: the next chunk overwrites the LDS rows)
+  }
+  if (j < p.N) p.owner[(size_t)f * p.N + j] = own;
 }
 
 }  // namespace dy
@@ -640,4 +735,24 @@ extern "C" int32_t dy_tile_merge_rotated(const dy_tile_merge_rotated_desc* d, dy
   TmArgs a{};
   a.far = tmr_far_bound(d->thr);
   return tm_launch<TmrScan>(d, a, "dy_tile_merge_rotated", stream);
+}
+
+extern "C" int32_t dy_tile_mask_owner(const dy_tile_mask_owner_desc* d, dy_stream_t stream) {
+  DY_REQUIRE(d && d->rows && d->counts && d->offsets_yx && d->kept_index && d->kept_count && d->owner, DY_ERR_INVALID_ARG,
+             "dy_tile_mask_owner: null pointer (rows / counts / offsets_yx / kept_index / kept_count / owner)");
+  DY_REQUIRE(d->frames > 0 && d->tiles > 0 && d->max_det > 0 && d->merge_max_det > 0, DY_ERR_INVALID_ARG,
+             "dy_tile_mask_owner: bad dims (frames %d, tiles %d, max_det %d, merge_max_det %d)", d->frames, d->tiles, d->max_det, d->merge_max_det);
+  DY_REQUIRE(d->thr >= 0.f && d->thr <= 1.f, DY_ERR_INVALID_ARG, "dy_tile_mask_owner: thr must be in [0,1]");
+  DY_REQUIRE(d->metric == 0 || d->metric == 1, DY_ERR_INVALID_ARG, "dy_tile_mask_owner: metric %d (0 = IoU, 1 = IoS)", d->metric);
+  DY_REQUIRE((long long)d->tiles * d->max_det <= TM_MAX_SLOTS, DY_ERR_UNSUPPORTED, "dy_tile_mask_owner: tiles * max_det = %lld > %d",
+             (long long)d->tiles * d->max_det, TM_MAX_SLOTS);
+  DY_REQUIRE(d->merge_max_det <= TM_MAX_KEEP, DY_ERR_UNSUPPORTED, "dy_tile_mask_owner: merge_max_det %d > %d", d->merge_max_det, TM_MAX_KEEP);
+  DY_REQUIRE(d->frames <= 65535, DY_ERR_UNSUPPORTED, "dy_tile_mask_owner: %d frames are beyond the launch grid", d->frames);
+  TmoArgs a;
+  a.rows = d->rows, a.counts = d->counts, a.offs = d->offsets_yx, a.kidx = d->kept_index, a.kcnt = d->kept_count, a.owner = d->owner;
+  a.K = d->tiles, a.max_det = d->max_det, a.N = d->tiles * d->max_det, a.keep = d->merge_max_det;
+  a.metric = d->metric, a.agnostic = d->agnostic ? 1 : 0, a.stitch = d->stitch ? 1 : 0, a.thr = d->thr;
+  hipLaunchKernelGGL(tile_mask_owner_kernel, dim3((unsigned)((a.N + TMO_THREADS - 1) / TMO_THREADS), (unsigned)d->frames), dim3(TMO_THREADS), 0,
+                     reinterpret_cast<hipStream_t>(stream), a);
+  return check_launch("tile_mask_owner_kernel");
 }

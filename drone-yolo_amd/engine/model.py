@@ -100,7 +100,7 @@ class Model(nn.Module):
         """Reference engine/model.py:501-560: predictor created on first use, conf defaults to 0.25."""
         if source is None:
             raise ValueError("'source' is missing; the device path takes a BCHW float tensor in [0, 1]")
-        self._refuse_for_segment(kwargs)
+        self._refuse_for_segment(kwargs, source)
         self._refuse_for_obb(kwargs, source)
         track = kwargs.get("mode") == "track"
         args = {**self.overrides, "conf": 0.1 if track else 0.25, **kwargs}
@@ -143,17 +143,22 @@ class Model(nn.Module):
         ``YOLO(<-obb>).track(<float tensor>)`` as a refused call; the predictor itself would take the tensor."""
         return self.predict(source, stream, **{**kwargs, "mode": "track", "persist": persist, "tracker": tracker})
 
-    def _refuse_for_segment(self, kwargs: dict) -> None:
-        """What a segmentation model does not do, refused by argument name before a predictor is built or anything is launched."""
+    def _refuse_for_segment(self, kwargs: dict, source=None) -> None:
+        """What a segmentation model does not do, refused by argument name before a predictor is built or anything is launched.  ``tile=`` and
+        ``mode="track"`` are built for pixel sources: uint8 HWC frames, image files, PIL images.  A float BCHW tensor source stays
+        refused with either -- the package's own tests pin ``YOLO(<-seg>).predict(<float tensor>, tile=...)`` / ``.track(<float tensor>)`` as
+        refused calls (the arrangement of ``-obb`` models in ``track``'s docstring)."""
         if self.task != "segment":
             return
         a = {**self.overrides, **kwargs}
-        if a.get("mode") == "track":
-            raise NotImplementedError("track: tracking is not built for segmentation models")
-        if a.get("tile") is not None:
-            raise NotImplementedError("tile: tiled inference is not built for segmentation models")
+        floats = isinstance(source, torch.Tensor) and source.dtype != torch.uint8
+        if a.get("mode") == "track" and floats:
+            raise NotImplementedError("track with a float BCHW tensor: not taken for segmentation models; pass uint8 HWC BGR frames, image files or PIL images")
+        if a.get("tile") is not None and floats:
+            raise NotImplementedError("tile with a float BCHW tensor: tiles are cut from uint8 pixels (HWC frames), not from a letterboxed tensor")
         if a.get("augment"):
             raise NotImplementedError("augment=True: test-time augmentation is not built for segmentation models")
+        SegmentationPredictor.refuse_args(a, self.model)
 
     def _refuse_for_obb(self, kwargs: dict, source=None) -> None:
         """What an oriented-box model does not do, refused by argument name before a predictor is built or anything is launched.  ``tile=`` is

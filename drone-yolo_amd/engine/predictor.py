@@ -87,13 +87,15 @@ class CompiledForward:
 class DetectionPredictor:
     """Device-resident predictor (reference predictor.py:64-323, detect/predict.py:8-73)."""
 
+    keeps_track_index = False  # the segmentation task: ``last_track_index``, the detection every result row came from (its mask follows it)
     max_compiled = 8  # recorded (batch, H, W) passes kept alive (each holds activations, NMS buffers and a graph: a video's ragged last batch must not pile up)
 
     def __init__(self, model, overrides: Optional[dict] = None):
         a = dict(conf=0.25, iou=0.7, max_det=300, classes=None, agnostic_nms=False, half=False, dtype=None, device="",
                  verbose=False, graph=True, max_nms=30000, max_wh=7680, imgsz=640, fp8_layers=None, batch=None, augment=False,
                  tracker="bytetrack.yaml", device_track=True, track_streams=1, max_tracks=512,
-                 tile=None, tile_overlap=0.2, merge_iou=0.7, merge_metric="iou", merge_mode="suppress", merge_max_det=1000, retina_masks=False)
+                 tile=None, tile_overlap=0.2, merge_iou=0.7, merge_metric="iou", merge_mode="suppress", merge_max_det=1000, retina_masks=False,
+                 tile_mask_stride=4)
         a.update(overrides or {})
         self.args = a
         if a["tile"] is not None:  # tiled inference (DESIGN §16): checked before anything touches the device
@@ -408,7 +410,16 @@ class DetectionPredictor:
             t = torch.from_numpy(self.tracker.update(rows[i, :k].cpu().numpy(), stream=i % self.tracker.streams)).to(rows.device)
         else:
             t = tracked[0][i, : tracked[1][i]]
+        if len(t) and self.keeps_track_index:
+            self.last_track_index[i] = t[:, -1].long()
         return t[:, :-1] if len(t) else rows[i, :k]
+
+    def _all_boxes(self, counts, rows, tracked) -> list:
+        """``_boxes_of`` for every image of a batch, in order; ``last_track_index[i]`` then holds, per row of image i's result, the index of
+        its detection among the image's plain rows (the tracker's idx column; 0 .. k - 1 where the plain result stands)."""
+        if self.keeps_track_index:  # (a detection model needs no index: nothing is launched for it here)
+            self.last_track_index = [torch.arange(k, device=rows.device) for k in counts]
+        return [self._boxes_of(i, k, rows, tracked) for i, k in enumerate(counts)]
 
     def postprocess(self, cf: CompiledForward, im: torch.Tensor, paths=None) -> List[Results]:
         n = cf.nms.count.shape[0]
@@ -424,10 +435,11 @@ class DetectionPredictor:
         out = []
         info = getattr(self, "letterbox_info", None)
         rows = cf.nms.out.clone()  # ONE copy of the padded (N, max_det, 6) rows: the next pass overwrites the buffer, the Results keep views of this one
+        boxes = self._all_boxes(counts, rows, tracked)
         masks = self._masks_for(self._mask_stash(cf, streamed=False), counts, rows, im, info)
         for i, k in enumerate(counts):
             one = (info[i] if isinstance(info, list) else info) if info else None
-            out.append(self._result(im[i], paths[i] if paths else f"image{i}.jpg", names, self._boxes_of(i, k, rows, tracked),
+            out.append(self._result(im[i], paths[i] if paths else f"image{i}.jpg", names, boxes[i],
                                     (one[0], one[1]) if one else im.shape[2:], masks[i]))
         return out
 
@@ -510,10 +522,11 @@ class DetectionPredictor:
             counts = both[: rows.shape[0]]
             tracked = (trows, both[rows.shape[0] :]) if trows is not None else None
             out = []
+            boxes = self._all_boxes(counts, rows, tracked)
             masks = self._masks_for(stash, counts, rows, im, info)
             for i, k in enumerate(counts):
                 one = (info[i] if isinstance(info, list) else info) if info else None
-                r = self._result(frames[i] if frames is not None else im[i], paths[i] if paths else f"image{lo + i}.jpg", names, self._boxes_of(i, k, rows, tracked),
+                r = self._result(frames[i] if frames is not None else im[i], paths[i] if paths else f"image{lo + i}.jpg", names, boxes[i],
                                  (one[0], one[1]) if one else im.shape[2:], masks[i])
                 out.append(r)
             dt = (time.perf_counter() - t0) * 1e3 / max(len(out), 1)
@@ -583,6 +596,14 @@ class DetectionPredictor:
         return H.tile_merge(cf.nms, offs_d, k, frame_hw, self.model.yaml["nc"], float(a["merge_iou"]), str(a["merge_metric"]),
                             bool(a["agnostic_nms"]), int(a["merge_max_det"]), bufs=mbufs, mode=str(a["merge_mode"]))
 
+    def _tile_mask_stash(self, cf: CompiledForward, offs_d: torch.Tensor, k: int, merged):
+        """Hook behind the cross-tile merge: what the frame masks of this group are assembled from (None: a detection model)."""
+        return None
+
+    def _tile_masks_for(self, stash, counts, frame_hw) -> list:
+        """Per frame of a group the (k, oh, ow) masks of the rows of its result, or None."""
+        return [None] * len(counts)
+
     def _tiled_enqueue(self, lo: int, frames, paths):
         """Everything one batch of frames launches — per group of frames of one shape: the slicer, the recorded pass over the (F * K)-tile batch,
         the cross-tile merge and, in track mode, the track step — then ONE asynchronous copy of the merged (and the tracker's) counts."""
@@ -631,7 +652,7 @@ class DetectionPredictor:
                 tracked = tout.clone()
                 tcounts.append(tcnt)
             # copies that outlive the next batch (and the next group: groups of one size share the buffers)
-            parts.append((idxs, (hf, wf), merged.out.clone(), tracked))
+            parts.append((idxs, (hf, wf), merged.out.clone(), tracked, self._tile_mask_stash(cf, offs_d, k, merged)))
             mcounts.append(merged.count.clone() if len(groups) > 1 else merged.count)
         counts_dev = mcounts + tcounts  # (track mode has one group: the tracker's counts follow the merged counts)
         counts_dev = torch.cat(counts_dev) if len(counts_dev) > 1 else counts_dev[0]
@@ -647,15 +668,22 @@ class DetectionPredictor:
         ev.synchronize()  # the batch's only device->host synchronisation
         both = counts_host.tolist()
         names, out, o = self.model.names, [None] * len(frames), 0
-        for idxs, hw, rows, trows in parts:
+        index = [None] * len(frames)
+        for idxs, hw, rows, trows, stash in parts:
             counts = both[o : o + len(idxs)]
             o += len(idxs)
             tracked = (trows, both[o : o + len(idxs)]) if trows is not None else None
+            boxes = self._all_boxes(counts, rows, tracked)
+            masks = self._tile_masks_for(stash, counts, hw)
             for j, i in enumerate(idxs):
                 img = frames[i]
                 if isinstance(img, torch.Tensor):
                     img = img.cpu().numpy()
-                out[i] = self._result(img, paths[i] if paths else f"image{lo + i}.jpg", names, self._boxes_of(j, counts[j], rows, tracked), hw, None)
+                out[i] = self._result(img, paths[i] if paths else f"image{lo + i}.jpg", names, boxes[j], hw, masks[j])
+                if self.keeps_track_index:
+                    index[i] = self.last_track_index[j]
+        if self.keeps_track_index:
+            self.last_track_index = index
         dt = (time.perf_counter() - t0) * 1e3 / max(len(out), 1)
         for r in out:
             r.speed = {"preprocess": 0.0, "inference": t_inf, "postprocess": dt}
@@ -718,15 +746,36 @@ class SegmentationPredictor(DetectionPredictor):
     output holds sum(counts) masks), so ``dy_process_mask`` is launched where the counts are read back anyway: one launch per batch, still
     one synchronisation.  The prototypes and the side buffer live in the recorded plan and are overwritten by its next replay; a streamed
     run, whose device works a batch ahead, therefore takes stream-ordered copies of both (and of the counts the kernel bounds its reads by)
-    behind the batch's launches, where the detection rows are copied too; a single call assembles from the plan's own buffers."""
+    behind the batch's launches, where the detection rows are copied too; a single call assembles from the plan's own buffers.
+
+    ``tile=`` and ``mode="track"`` run on pixel sources.  Tiled: the owner map behind the merge, copies of the tiles' prototypes,
+    side rows and counts per batch in flight, one ``dy_tile_process_mask`` launch per frame-shape group in ``_tiled_finish``; masks at
+    1 / ``tile_mask_stride`` of the frame.  Tracked: ``last_track_index`` holds per image of the last batch the detection every result row came
+    from; the side rows are gathered by it (``dest`` scattered from it with ``tile=``), so a track carries the mask of its detection."""
 
     def __init__(self, model, overrides: Optional[dict] = None):
         a = overrides or {}
-        for k in ("tile", "augment"):  # before anything touches the device
-            if a.get(k) not in (None, False):
-                raise NotImplementedError(f"{k}: not built for segmentation models")
+        self.refuse_args(a, model)  # before anything touches the device
         super().__init__(model, overrides)
         self.args["task"] = "segment"
+        self.last_track_index: list = []
+
+    keeps_track_index = True
+
+    @staticmethod
+    def refuse_args(a: dict, model=None) -> None:
+        """What a segmentation predictor does not take, by argument (YOLO.predict asks before it builds one)."""
+        if a.get("augment") not in (None, False):
+            raise NotImplementedError("augment: not built for segmentation models")
+        if a.get("tile") is not None:
+            if a.get("retina_masks"):
+                raise NotImplementedError("retina_masks with tile: frame masks at full resolution are tile_mask_stride=1")
+            strides = getattr(model, "stride", None)
+            if strides is not None and float(min(strides)) != 8.0:  # Proto runs at half the finest level: stride 8 -> a quarter of the tile
+                raise NotImplementedError(f"tile with a segmentation model whose finest level has stride {float(min(strides)):g} (the P2 -seg models): its "
+                                          "prototypes are not a quarter of the tile, which is what the frame masks are built for")
+            if a.get("tile_mask_stride", 4) not in H.TILE_MASK_STRIDES or isinstance(a.get("tile_mask_stride", 4), bool):
+                raise ValueError(f"tile_mask_stride = {a.get('tile_mask_stride')}, expected one of {H.TILE_MASK_STRIDES}")
 
     def preprocess(self, im) -> torch.Tensor:
         out = super().preprocess(im)
@@ -734,8 +783,34 @@ class SegmentationPredictor(DetectionPredictor):
             raise NotImplementedError("retina_masks with sources of different shapes in one batch: the masks of a batch share one size")
         return out
 
-    def make_tracker(self):
-        raise NotImplementedError("track: tracking is not built for segmentation models")
+    def _tile_mask_stash(self, cf: CompiledForward, offs_d: torch.Tensor, k: int, merged):
+        # the owner map behind the merge, and stream-ordered copies of what the next batch's pass overwrites: F * K * mh * mw * 128 bytes of
+        # prototypes (13 MB per 1280-pixel tile) per batch in flight, the side rows and the per-tile counts
+        a = self.args
+        if tuple(cf.protos.shape[2:]) != (int(a["tile"]) // 4,) * 2:  # (a P2 head's Proto runs at half the input: not built)
+            raise NotImplementedError(f"tile with a segmentation model whose prototypes are {tuple(cf.protos.shape[2:])} on a {a['tile']}-pixel tile: "
+                                      "frame masks are built for prototypes at a quarter of the tile")
+        owner = H.tile_mask_owner(cf.nms, offs_d, k, merged, float(a["merge_iou"]), str(a["merge_metric"]), bool(a["agnostic_nms"]),
+                                  stitch=str(a["merge_mode"]).lower() != "suppress")
+        return cf.protos.clone(), cf.side.clone(), cf.nms.count.clone(), owner, offs_d
+
+    def _tile_masks_for(self, stash, counts, frame_hw) -> list:
+        protos, side, tcount, owner, offs_d = stash
+        f, m, tile = len(counts), int(self.args["merge_max_det"]), int(self.args["tile"])
+        # dest: the output mask of every kept row -- the rows of the frame's result in their order (the tracker's idx where it returned rows)
+        dest = torch.full((f, m), -1, dtype=torch.int32, device=self.device)
+        total, spans = 0, []
+        for j in range(f):
+            idx = self.last_track_index[j]
+            n = int(idx.numel())
+            if n:
+                dest[j, idx.to(self.device)] = torch.arange(total, total + n, dtype=torch.int32, device=self.device)
+            spans.append((total, n))
+            total += n
+        if total == 0:
+            return [None] * f
+        allm = H.tile_process_mask(protos, side, tcount, offs_d, owner, dest, total, (tile, tile), frame_hw, int(self.args["tile_mask_stride"]))
+        return [allm[o : o + n] if n else None for o, n in spans]
 
     def _record_masks(self, cf: CompiledForward, aux) -> None:
         if not (isinstance(aux, tuple) and len(aux) == 3):
@@ -752,6 +827,15 @@ class SegmentationPredictor(DetectionPredictor):
     def _masks_for(self, stash, counts, rows, im, info) -> list:
         protos, side, count = stash
         n, _, mh, mw = protos.shape
+        if self.tracker is not None:
+            # a track carries the mask of the detection it matched (trackers/track.py: results[i][idx]): the side rows (and the retina form's
+            # crop rows) are gathered by the tracker's idx in front of the assembly -- 36 floats a row, not a mask copy
+            # (one padded index per batch, one gather per buffer)
+            counts = [int(idx.numel()) for idx in self.last_track_index]
+            pad = torch.nn.utils.rnn.pad_sequence(list(self.last_track_index) + [torch.zeros(side.shape[1], dtype=torch.long, device=side.device)], batch_first=True)[:n]
+            side = torch.gather(side, 1, pad[:, :, None].expand(-1, -1, side.shape[2]))
+            rows = torch.gather(rows, 1, pad[:, :, None].expand(-1, -1, rows.shape[2]))
+            count = torch.tensor(counts, dtype=torch.int32, pin_memory=True).to(self.device, non_blocking=True)
         ih, iw = int(im.shape[2]), int(im.shape[3])
         if self.args["retina_masks"]:
             h0, w0 = (info[0], info[1]) if info else (ih, iw)

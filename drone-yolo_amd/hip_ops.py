@@ -2273,6 +2273,86 @@ def tile_merge_rotated(nms_bufs, offsets: torch.Tensor, K: int, frame_hw: Tuple[
     return _tile_merge_launch(lib().dy_tile_merge_rotated, _lib.TileMergeRotatedDesc(), rows, counts, offsets, frame_hw, nc, thr, agnostic, bufs, bufs.workspace)
 
 
+# ---- frame masks of tiled segmentation (csrc/tile_merge.hip: the owner map; csrc/mask_ops.hip: the assembly) --------------------
+
+
+TILE_MASK_STRIDES = (1, 2, 4)
+
+
+def tile_mask_owner(nms_bufs, offsets: torch.Tensor, K: int, merged, thr: float, metric=0, agnostic: bool = False, stitch: bool = False,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Which kept frame row every per-tile candidate belongs to: int32 (F, K * max_det), one ``dy_tile_mask_owner`` launch behind the merge, no
+    host synchronisation.  ``nms_bufs`` / ``offsets`` / ``K`` / ``thr`` / ``metric`` / ``agnostic``: what ``tile_merge`` was given;
+    ``merged``: what it returned (or an ``(index, count)`` pair).  The slot of kept row t gets t; with ``stitch`` a candidate that is not
+    kept gets the kept row that absorbs it under ``dy_tile_fuse``'s rule; every other slot -1."""
+    rows, counts, f, md = _tile_merge_inputs("tile_mask_owner", 6, nms_bufs, offsets, K)
+    index, count = merged if isinstance(merged, (tuple, list)) else (merged.index, merged.count)
+    require_device(index, "kept index")
+    require_device(count, "kept count")
+    if index.dtype != torch.int32 or index.dim() != 2 or index.shape[0] != f or not index.is_contiguous() or count.dtype != torch.int32 \
+            or count.numel() != f or not count.is_contiguous():
+        raise ValueError(f"tile_mask_owner: the merge's index must be contiguous int32 ({f}, merge_max_det) with {f} int32 counts")
+    n = int(K) * md
+    if out is None:
+        out = torch.empty((f, n), dtype=torch.int32, device=rows.device)
+    elif tuple(out.shape) != (f, n) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != rows.device:
+        raise ValueError(f"tile_mask_owner: out must be a contiguous int32 ({f}, {n}) tensor on the rows' device")
+    d = _lib.TileMaskOwnerDesc()
+    d.rows, d.counts, d.offsets_yx, d.kept_index, d.kept_count = rows.data_ptr(), counts.data_ptr(), offsets.data_ptr(), index.data_ptr(), count.data_ptr()
+    d.frames, d.tiles, d.max_det, d.merge_max_det = f, int(K), md, int(index.shape[1])
+    d.thr, d.metric, d.agnostic, d.stitch = float(thr), _tile_merge_code("metric", metric, TILE_MERGE_METRICS), int(bool(agnostic)), int(bool(stitch))
+    d.owner = out.data_ptr()
+    _launch(lib().dy_tile_mask_owner, (C.byref(d),), keep=(d, rows, counts, offsets, index, count, out))
+    return out
+
+
+def tile_process_mask(protos: torch.Tensor, side: torch.Tensor, counts: torch.Tensor, offsets: torch.Tensor, owner: torch.Tensor,
+                      dest: torch.Tensor, total: int, tile_hw: Tuple[int, int], frame_hw: Tuple[int, int], stride: int = 4,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The frame masks of tiled inference in one ``dy_tile_process_mask`` launch: uint8 (total, ceil(frame_h / stride), ceil(frame_w / stride)).
+    ``protos``: fp32 NHWC view (F * K, 32, mh, mw) with (mh, mw) a quarter of the tile; ``side``: ``mask_gather``'s output of the tiles;
+    ``counts``: the per-tile counts; ``offsets``: device int32 (K, 2) = (y, x); ``owner``: ``tile_mask_owner``'s map (F, K * max_det);
+    ``dest``: int32 (F, merge_max_det), the output mask of every kept row or -1.  Mask ``dest[f, t]`` is the OR of the tile masks of the
+    slots that kept row t owns, each pasted at its tile's offset; at stride 1 a tile's part is ``process_mask``'s output bit for bit."""
+    for t, what in ((protos, "protos"), (side, "side"), (counts, "counts"), (offsets, "tile offsets"), (owner, "owner"), (dest, "dest")):
+        require_device(t, what)
+    fk, nm, mh, mw = protos.shape
+    k = int(offsets.shape[0])
+    if protos.dtype != torch.float32 or side.dtype != torch.float32 or not side.is_contiguous() or side.dim() != 3 or side.shape[0] != fk or side.shape[2] != 4 + nm:
+        raise ValueError("tile_process_mask: protos must be fp32 (F * K, nm, mh, mw), side a contiguous fp32 (F * K, max_det, 4 + nm) tensor")
+    if nm != NM:
+        raise NotImplementedError(f"tile_process_mask: {nm} mask coefficients; dy_tile_process_mask is built for {NM}")
+    if int(stride) not in TILE_MASK_STRIDES:
+        raise ValueError(f"tile_process_mask: stride {stride}, expected one of {TILE_MASK_STRIDES}")
+    md = int(side.shape[1])
+    if offsets.dtype != torch.int32 or offsets.dim() != 2 or offsets.shape[1] != 2 or not offsets.is_contiguous() or k == 0 or fk % k:
+        raise ValueError("tile_process_mask: offsets must be a contiguous int32 (K, 2) tensor with F * K tiles in protos")
+    f = fk // k
+    if counts.dtype != torch.int32 or counts.numel() != fk or not counts.is_contiguous():
+        raise ValueError(f"tile_process_mask: counts must be {fk} contiguous int32")
+    if owner.dtype != torch.int32 or tuple(owner.shape) != (f, k * md) or not owner.is_contiguous():
+        raise ValueError(f"tile_process_mask: owner must be a contiguous int32 ({f}, {k * md}) tensor")
+    if dest.dtype != torch.int32 or dest.dim() != 2 or dest.shape[0] != f or not dest.is_contiguous():
+        raise ValueError(f"tile_process_mask: dest must be a contiguous int32 ({f}, merge_max_det) tensor")
+    stride, total = int(stride), int(total)
+    oh, ow = -(-int(frame_hw[0]) // stride), -(-int(frame_hw[1]) // stride)
+    if out is None:
+        out = torch.empty((total, oh, ow), dtype=torch.uint8, device=protos.device)
+    elif out.dtype != torch.uint8 or out.numel() != total * oh * ow or not out.is_contiguous() or out.data_ptr() % 4 or out.device != protos.device:
+        raise ValueError("tile_process_mask: out must be a contiguous, 4-byte aligned uint8 tensor of total * oh * ow elements on the prototypes' device")
+    else:
+        out = out.view(total, oh, ow)
+    d = _lib.TileProcessMaskDesc()
+    d.protos, d.ld_p = view_params(protos)
+    d.side, d.counts, d.offsets_yx, d.owner, d.dest, d.out = side.data_ptr(), counts.data_ptr(), offsets.data_ptr(), owner.data_ptr(), dest.data_ptr(), out.data_ptr()
+    d.frames, d.tiles, d.max_det, d.merge_max_det, d.nm, d.mh, d.mw = f, k, md, int(dest.shape[1]), nm, mh, mw
+    d.tile_h, d.tile_w, d.frame_h, d.frame_w, d.stride, d.total = int(tile_hw[0]), int(tile_hw[1]), int(frame_hw[0]), int(frame_hw[1]), stride, total
+    if total == 0:
+        return out
+    _launch(lib().dy_tile_process_mask, (C.byref(d),), keep=(d, protos, side, counts, offsets, owner, dest, out))
+    return out
+
+
 def augment_batch(src: torch.Tensor, table: torch.Tensor, s: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Mosaic + affine / perspective warp + HSV + flips of a training batch in one ``dy_augment_u8_nchw`` launch.  src: device uint8
     (N, 3, Hs, Ws) source images (channel 0 = R); table: device uint8 (B, sizeof(dy_aug_row)) rows built by ``data.augment.DeviceAugment``;

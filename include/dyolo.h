@@ -528,6 +528,54 @@ typedef struct dy_tile_merge_rotated_desc {
 int64_t dy_tile_merge_rotated_workspace_bytes(int32_t frames, int32_t tiles, int32_t max_det);
 int32_t dy_tile_merge_rotated(const dy_tile_merge_rotated_desc* d, dy_stream_t stream);
 
+/* ---- frame masks of tiled segmentation (csrc/tile_merge.hip, csrc/mask_ops.hip) --------------------------
+ * dy_tile_mask_owner: which kept frame row every per-tile candidate belongs to; one launch, no host synchronisation.
+ *   rows / counts / offsets_yx / frames / tiles / max_det / thr / metric / agnostic / merge_max_det: what dy_tile_merge (or dy_tile_fuse)
+ *   was given; kept_index int32 (f, merge_max_det) and kept_count int32 (f): its out_index and out_count.
+ *   owner: int32 (f, tiles * max_det).  Slot j = k' * max_det + r:  r >= counts[tile] -> -1;  the slot of kept row t -> t;  otherwise, with
+ *   stitch == 0, -1, and with stitch != 0 the smallest t such that kept row t stands before j in the merge's order (key = ~bits(conf) << 32 |
+ *   slot ascending) and the OWN box of t (row xyxy plus tile offset, before the clamp) suppresses j under dy_tile_merge's predicate (the one
+ *   expression of tile_merge.hip, fp32 without contraction) -- dy_tile_fuse's absorb rule: the histogram of owner is its out_members --
+ *   or -1 when there is none.  Limits and codes as dy_tile_merge; every argument is checked before the launch.
+ * dy_tile_process_mask: one uint8 0 / 1 mask per emitted kept row, assembled from per-tile prototypes and coefficient rows.
+ *   protos: fp32 NHWC (f * tiles, mh, mw, 32), pitch ld_p, 16-byte aligned, mh * 4 == tile_h and mw * 4 == tile_w; side: the dy_mask_gather
+ *   output (f * tiles, max_det, 36), boxes in tile pixels; counts, offsets_yx as above; owner from dy_tile_mask_owner (or hand-made);
+ *   dest: int32 (f, merge_max_det): the index in [0, total) of the output mask of kept row t, -1: not emitted.
+ *   out: uint8 (total, oh, ow), oh = ceil(frame_h / stride), ow = ceil(frame_w / stride), 4-byte aligned; every byte is defined on return
+ *   (the call zeroes it on the stream, then ORs with 32-bit integer atomics: bit-reproducible).  Pixel (Y, X) of mask dest[f, t] is the OR
+ *   over the slots j of frame f with owner[f, j] == t of member j's value: with (oy, ox) its tile's offset, in fp32,
+ *     ty = ((float)Y + 0.5f) * stride - oy, tx likewise; 0 unless 0 <= ty < tile_h and 0 <= tx < tile_w;
+ *     sy = max(0.25f * ty - 0.5f, 0), y0 = min((int)sy, mh - 1), y1 = min(y0 + 1, mh - 1), ly1 = sy - y0 (x likewise);
+ *     the blend of the four corners > 0, a corner = the 32-term dot product of the row's coefficients and the proto pixel, counted as 0
+ *     outside the crop window of the row's box * 0.25f on the (mh, mw) grid (a NaN corner: empty) -- dy_process_mask's expressions: at
+ *     stride 1 a single-member row is dy_process_mask's (tile_h, tile_w) mask of its tile row pasted at (oy, ox), bit for bit.
+ *   A slot with owner -1, dest -1 or r >= counts is neither read nor written.  total == 0: DY_OK without a launch.  nm != 32, a stride
+ *   other than 1 / 2 / 4, a proto grid that is not a quarter of the tile: DY_ERR_UNSUPPORTED; oh * ow >= 2^31: DY_ERR_INVALID_ARG. */
+typedef struct dy_tile_mask_owner_desc {
+  const float* rows;
+  const int32_t* counts;
+  const int32_t* offsets_yx;
+  const int32_t* kept_index;
+  const int32_t* kept_count;
+  int32_t frames, tiles, max_det, merge_max_det;
+  float thr;
+  int32_t metric, agnostic, stitch;
+  int32_t* owner;
+} dy_tile_mask_owner_desc;
+int32_t dy_tile_mask_owner(const dy_tile_mask_owner_desc* d, dy_stream_t stream);
+
+typedef struct dy_tile_process_mask_desc {
+  const float* protos;
+  const float* side;
+  const int32_t* counts;
+  const int32_t* offsets_yx;
+  const int32_t* owner;
+  const int32_t* dest;
+  int32_t frames, tiles, max_det, merge_max_det, nm, mh, mw, ld_p, tile_h, tile_w, frame_h, frame_w, stride, total;
+  uint8_t* out;
+} dy_tile_process_mask_desc;
+int32_t dy_tile_process_mask(const dy_tile_process_mask_desc* d, dy_stream_t stream);
+
 /* ---- layout / copy ops ------------------------------------------------------ */
 
 /* Replaces: predictor preprocess `.half()/.float()` + the NCHW->device layout step

@@ -1,5 +1,5 @@
 """Times tiled inference on 4K frames (GPU box): the parent's per-frame stages against the batched slicer and the one-launch merge.
-usage: python tools/bench_tiled.py [--rounds 10] [--frames 24] [--scale s] [--dtype float16] [--tile 1280] [--overlap 0.2] [--obb]
+usage: python tools/bench_tiled.py [--rounds 10] [--frames 24] [--scale s] [--dtype float16] [--tile 1280] [--overlap 0.2] [--obb | --seg]
 
 A synthetic 3840 x 2160 uint8 video, tile 1280, overlap 0.2 (eight tiles per frame).  Every comparison alternates A and B in one process
 after warm-up and is timed with device events; each figure is the median over `--rounds` rounds, with the smallest and largest beside it.
@@ -12,6 +12,10 @@ after warm-up and is timed with device events; each figure is the median over `-
 --obb: oriented boxes.  (a) gains R = dy_tile_merge_rotated (one frame) and R8 (eight frames, per frame) on the same objects as xywh rows with
 an angle each -- the same counts, so the difference to B / B8 is the price of the ProbIoU predicate; (c) runs the `-obb` model of the scale
 through predict(frames, tile=..., batch=F, stream=True) only (TiledPredictor is the detection task's).
+--seg: segmentation, this row alone.  The frame masks of one frame on synthetic prototypes (K, 320, 320, 32) and about 30 rows per
+tile: dy_tile_mask_owner + dy_tile_process_mask at stride 4 and 1, merge_mode suppress and union; beside them dy_process_mask to (tile, tile) for
+the same kept rows, tile by tile -- what the package could do with them before.  Then frames/s of predict(frames, tile=..., batch=F, stream=True)
+of the `-seg` model of the scale (yolov8<scale>-seg.yaml) at tile_mask_stride 4, F = 1, 2, 4.
 Prints one JSON line."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -27,6 +31,7 @@ ap.add_argument("--tile", type=int, default=1280)
 ap.add_argument("--overlap", type=float, default=0.2)
 ap.add_argument("--no-e2e", action="store_true")
 ap.add_argument("--obb", action="store_true")
+ap.add_argument("--seg", action="store_true")
 a = ap.parse_args()
 assert torch.cuda.is_available(), "tools/bench_tiled.py needs an MI355X"
 dev = torch.device("cuda", 0)
@@ -91,6 +96,73 @@ def scene_rows(seed, per_tile, frames):
 
 
 out = {"frame": [HF, WF], "tile": a.tile, "overlap": a.overlap, "tiles": K, "rounds": a.rounds, "merge": [], "slicer": None, "end_to_end": None}
+
+# ---- --seg: the frame masks of a tiled segmentation model, and frames per second end to end --------------------------------------------------
+if a.seg:
+    mh = a.tile // 4
+    rows, counts = scene_rows(30, 30, 1)
+    rows_d, counts_d = torch.from_numpy(rows).to(dev), torch.from_numpy(counts).to(dev)
+    g = torch.Generator(device="cpu").manual_seed(3)
+    protos = torch.randn(K, mh, mh, 32, generator=g).to(dev).permute(0, 3, 1, 2)  # the NHWC view
+    side = torch.cat([rows_d[:, :, :4], torch.randn(K, MAX_DET, 32, generator=g).to(dev)], 2).contiguous()
+    seg = {"rows_per_tile": round(float(counts.mean()), 1), "masks": {}}
+    fns = {}
+    for mode in ("suppress", "union"):
+        merged = H.tile_merge((rows_d, counts_d), offs_d, K, (HF, WF), NC, THR, 0, False, KEEP, mode=mode)
+        index, count = merged.index.clone(), merged.count.clone()
+        n = int(count[0])
+        dest = torch.full((1, KEEP), -1, dtype=torch.int32, device=dev)
+        dest[0, :n] = torch.arange(n, dtype=torch.int32, device=dev)
+        seg["kept"] = n
+        for s_ in (4, 1):
+            buf = torch.empty((n, -(-HF // s_), -(-WF // s_)), dtype=torch.uint8, device=dev)
+
+            def run(mode=mode, index=index, count=count, dest=dest, s_=s_, buf=buf, n=n):
+                owner = H.tile_mask_owner((rows_d, counts_d), offs_d, K, (index, count), THR, 0, False, stitch=mode != "suppress")
+                H.tile_process_mask(protos, side, counts_d, offs_d, owner, dest, n, (a.tile, a.tile), (HF, WF), s_, out=buf)
+
+            fns[f"{mode}_stride{s_}"] = run
+    # the same kept rows through dy_process_mask, tile by tile, to (tile, tile)
+    merged = H.tile_merge((rows_d, counts_d), offs_d, K, (HF, WF), NC, THR, 0, False, KEEP)
+    kept = merged.index[0, : int(merged.count[0])].long().cpu().numpy()
+    side_k, counts_k = torch.zeros_like(side), np.zeros((K,), np.int32)
+    for slot in np.sort(kept):
+        k, r = divmod(int(slot), MAX_DET)
+        side_k[k, counts_k[k]] = side[k, r]
+        counts_k[k] += 1
+    counts_kd = torch.from_numpy(counts_k).to(dev)
+    pm_out = torch.empty((int(counts_k.sum()), a.tile, a.tile), dtype=torch.uint8, device=dev)
+    fns["process_mask_per_tile"] = lambda: H.process_mask(protos, side_k, counts_kd, counts_k.tolist(), (a.tile, a.tile), ratio=(0.25, 0.25), out=pm_out)
+    ts = ab(fns, a.rounds)
+    seg["masks"] = {k: stat(v) for k, v in ts.items()}
+    print(json.dumps(seg), file=sys.stderr, flush=True)
+    del pm_out, fns
+    if not a.no_e2e:
+        from drone_yolo_amd.utils.parity import seeded_state_dict
+
+        yolo = D.YOLO(f"yolov8{a.scale}-seg.yaml")
+        yolo.model.load_state_dict(seeded_state_dict(yolo.model.state_dict(), 5, cls_bias=-1.2))
+        video = [np.ascontiguousarray(f) for f in np.random.default_rng(2).integers(0, 256, (a.frames, HF, WF, 3), dtype=np.uint8)]
+
+        def batched(F):
+            return [len(r) for r in yolo.predict(video, tile=a.tile, tile_overlap=a.overlap, merge_iou=THR, merge_max_det=KEEP, batch=F, stream=True,
+                                                 tile_mask_stride=4, conf=0.25, iou=0.7, dtype=a.dtype, device=0)]
+
+        fps, boxes = {F: [] for F in (1, 2, 4)}, {}
+        for F in fps:
+            boxes[F] = int(sum(batched(F)))
+        rounds = max(3, a.rounds // 2)
+        for _ in range(rounds):
+            for F in fps:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                batched(F)
+                torch.cuda.synchronize()
+                fps[F].append(a.frames / (time.perf_counter() - t0))
+        seg["end_to_end"] = {"frames": a.frames, "scale": a.scale, "dtype": a.dtype, "rounds": rounds, "boxes": boxes,
+                             "frames_per_s": {f"predict_batch{F}": stat(v) for F, v in fps.items()}}
+    print(json.dumps({"frame": [HF, WF], "tile": a.tile, "overlap": a.overlap, "tiles": K, "rounds": a.rounds, "seg": seg}))
+    sys.exit(0)
 
 # ---- (a) the merge stage alone --------------------------------------------------------------------------------------------------------------
 for per_tile in (30, 300):
