@@ -321,6 +321,21 @@ class ProcessMaskDesc(C.Structure):
     ]  # fmt: skip
 
 
+class KptDecodeDesc(C.Structure):
+    """Mirror of ``dy_kpt_decode_desc``."""
+
+    _fields_ = [
+        ("level", _vp * DY_MAX_LEVELS),
+        ("h", _i32 * DY_MAX_LEVELS), ("w", _i32 * DY_MAX_LEVELS), ("ld", _i32 * DY_MAX_LEVELS),
+        ("stride", _f32 * DY_MAX_LEVELS),
+        ("n_levels", _i32),
+        ("batch", _i32), ("anchors", _i32), ("nkpt", _i32), ("ndim", _i32),
+        ("pred_kpt", _vp), ("counts", _vp), ("index", _vp),
+        ("max_det", _i32),
+        ("out", _vp),
+    ]  # fmt: skip
+
+
 DY_MAP_U8, DY_MAP_I32 = 0, 1
 VAL_MASK_MAX_LABELS = 1024  # labels per image dy_val_mask_match takes (csrc/val_mask.hip: one LDS bin each)
 
@@ -462,6 +477,9 @@ SIGNATURES = {
     "dy_mask_gather": (_i32, [C.POINTER(MaskGatherDesc), _vp]),
     "dy_process_mask": (_i32, [C.POINTER(ProcessMaskDesc), _vp]),
     "dy_val_mask_match": (_i32, [C.POINTER(ValMaskMatchDesc), _vp]),
+    "dy_kpt_decode": (_i32, [C.POINTER(KptDecodeDesc), _vp]),
+    "dy_scale_coords": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "dy_crops_letterbox_u8_to_nchw_f32": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
 }
 
 _lib = None

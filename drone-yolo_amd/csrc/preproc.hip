@@ -5,8 +5,9 @@
 // fused stem kernel consumes.  The resize follows OpenCV's 8-bit INTER_LINEAR arithmetic exactly as restated in
 // oracle/letterbox_oracle.py (11-bit fixed-point coefficients, source coordinate (d + 0.5) * scale - 0.5 clamped at the
 // borders, vertical pass (((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16) + 2) >> 2), so the uint8 image equals the oracle's bit
-// for bit.  One thread per output pixel: three planes written with lane-contiguous stores.
-#include "common_hip.h"
+// for bit; the arithmetic lives in letterbox_px.h, which the crop slicer (pose.hip) shares.  One thread per output pixel: three planes
+// written with lane-contiguous stores.
+#include "letterbox_px.h"
 
 namespace dy {
 
@@ -17,20 +18,6 @@ struct LbArgs {
   float scale, pad;
   double sx, sy;  // h0/new_h, w0/new_w
 };
-
-__device__ __forceinline__ void axis_coeff(int d, double scale, int src, int* s0, int* s1, int* a0, int* a1) {
-  // unfused double arithmetic so that the result equals numpy's (oracle): (d + 0.5) * scale - 0.5
-  double f = __dsub_rn(__dmul_rn((double)d + 0.5, scale), 0.5);
-  int s = (int)floor(f);
-  f = f - (double)s;
-  if (s < 0) f = 0.0, s = 0;
-  if (s >= src - 1) f = 0.0, s = src - 1;
-  const float ff = (float)f;
-  *a0 = (int)rintf(__fmul_rn(__fsub_rn(1.0f, ff), 2048.0f));
-  *a1 = (int)rintf(__fmul_rn(ff, 2048.0f));
-  *s0 = s;
-  *s1 = s + 1 < src ? s + 1 : src - 1;
-}
 
 __global__ __launch_bounds__(256) void letterbox_kernel(const LbArgs p) {
   const long long total = (long long)p.n * p.hn * p.wn;
@@ -43,25 +30,10 @@ __global__ __launch_bounds__(256) void letterbox_kernel(const LbArgs p) {
     float v[3] = {p.pad, p.pad, p.pad};
     const int ry = y - p.top, rx = x - p.left;
     if ((unsigned)ry < (unsigned)p.new_h && (unsigned)rx < (unsigned)p.new_w) {
-      const uint8_t* s = p.src + (size_t)img * p.h0 * p.w0 * 3;
-      if (p.new_h == p.h0 && p.new_w == p.w0) {
-        const uint8_t* q = s + ((size_t)ry * p.w0 + rx) * 3;
-        v[0] = (float)q[0], v[1] = (float)q[1], v[2] = (float)q[2];
-      } else {
-        int x0, x1, ax0, ax1, y0, y1, by0, by1;
-        axis_coeff(rx, p.sx, p.w0, &x0, &x1, &ax0, &ax1);
-        axis_coeff(ry, p.sy, p.h0, &y0, &y1, &by0, &by1);
-        const uint8_t* r0 = s + (size_t)y0 * p.w0 * 3;
-        const uint8_t* r1 = s + (size_t)y1 * p.w0 * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const int h0v = (int)r0[x0 * 3 + c] * ax0 + (int)r0[x1 * 3 + c] * ax1;
-          const int h1v = (int)r1[x0 * 3 + c] * ax0 + (int)r1[x1 * 3 + c] * ax1;
-          int o = (((by0 * (h0v >> 4)) >> 16) + ((by1 * (h1v >> 4)) >> 16) + 2) >> 2;
-          o = o < 0 ? 0 : (o > 255 ? 255 : o);
-          v[c] = (float)o;
-        }
-      }
+      const bool copy = p.new_h == p.h0 && p.new_w == p.w0;
+      LbRow row{};
+      if (!copy) row = letterbox_row(ry, p.sy, p.h0);
+      letterbox_px(p.src + (size_t)img * p.h0 * p.w0 * 3, (size_t)p.w0 * 3, p.h0, p.w0, p.new_h, p.new_w, p.sx, row, ry, rx, v);
     }
     float* d = p.dst + (size_t)img * 3 * plane + (size_t)y * p.wn + x;
     // dst channel c takes source channel (swap_rb ? 2 - c : c); x / 255 as the reference's `im /= 255`

@@ -1,6 +1,7 @@
 """``YOLO`` / ``Model`` user API (reference: ultralytics/engine/model.py:29-1177,
-ultralytics/models/yolo/model.py:11-59) for the detection, segmentation (prediction, validation and training) and oriented-box (prediction, validation,
-tracking and training) tasks on the MI355X path."""
+ultralytics/models/yolo/model.py:11-59) for the detection, segmentation (prediction, validation and training), oriented-box (prediction, validation,
+tracking and training) and pose (prediction: whole images, and batched person crops of frames through ``predict(frames, crops=boxes)``) tasks on the
+MI355X path."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -9,10 +10,15 @@ from typing import List, Union
 import torch
 import torch.nn as nn
 
-from ..nn.tasks import DetectionModel, OBBModel, SegmentationModel, guess_model_task, yaml_model_load
+from ..nn.tasks import DetectionModel, OBBModel, PoseModel, SegmentationModel, guess_model_task, yaml_model_load
 from ..utils import LOGGER
-from .predictor import DetectionPredictor, OBBPredictor, SegmentationPredictor
+from .predictor import DetectionPredictor, OBBPredictor, PosePredictor, SegmentationPredictor
 from .results import Results
+
+
+class TaskMismatch(ValueError, NotImplementedError):
+    """``task="pose"`` asked of a YAML whose head is another task's.  A ``ValueError`` like every other task / head mismatch; also a
+    ``NotImplementedError``, which is what the same call raised while the pose task did not exist, so callers that catch either keep working."""
 
 
 class Model(nn.Module):
@@ -28,8 +34,8 @@ class Model(nn.Module):
         self.ckpt_path = None
         self.overrides = {}
         self.task = task
-        if task not in (None, "detect", "segment", "obb"):
-            raise NotImplementedError(f"task '{task}': only 'detect', 'segment' and 'obb' are on the accelerated path")
+        if task not in (None, "detect", "segment", "obb", "pose"):
+            raise NotImplementedError(f"task '{task}': only 'detect', 'segment', 'obb' and 'pose' are on the accelerated path")
         model = str(model).strip()
         if Path(model).suffix in {".yaml", ".yml"}:
             self._new(model, verbose=verbose)
@@ -56,8 +62,14 @@ class Model(nn.Module):
 
         return {"obb": {"model": OBBModel, "predictor": OBBPredictor, "trainer": DetectionTrainer}}
 
+    @property
+    def pose_task_map(self):
+        """The pose task, kept apart from ``task_map`` like the oriented-box one: model and predictor.  There is no trainer: ``train`` refuses
+        a pose model before it looks for one."""
+        return {"pose": {"model": PoseModel, "predictor": PosePredictor}}
+
     def _task_classes(self, task: str) -> dict:
-        return {**self.task_map, **self.oriented_task_map}[task]
+        return {**self.task_map, **self.oriented_task_map, **self.pose_task_map}[task]
 
     def _new(self, cfg: str, task=None, model=None, verbose=False) -> None:
         """Build from a YAML — reference engine/model.py:231-264."""
@@ -65,7 +77,7 @@ class Model(nn.Module):
         self.cfg = cfg
         found = guess_model_task(cfg_dict)
         if self.task is not None and self.task != found:
-            raise ValueError(f"task '{self.task}' was asked for, but the head of '{cfg}' makes it a '{found}' model")
+            raise (TaskMismatch if self.task == "pose" else ValueError)(f"task '{self.task}' was asked for, but the head of '{cfg}' makes it a '{found}' model")
         self.task = found
         self.model = (model or self._task_classes(self.task)["model"])(cfg_dict, verbose=verbose)
         self.overrides["model"] = self.cfg
@@ -97,15 +109,22 @@ class Model(nn.Module):
         return self.predict(source, stream, **kwargs)
 
     def predict(self, source=None, stream: bool = False, predictor=None, **kwargs) -> List[Results]:
-        """Reference engine/model.py:501-560: predictor created on first use, conf defaults to 0.25."""
+        """Reference engine/model.py:501-560: predictor created on first use, conf defaults to 0.25.
+
+        Pose models only: ``crops=boxes`` with ``source`` = uint8 HWC frames of one shape ((F, H, W, 3) array or list) and ``boxes`` = a
+        list of F host arrays (n_i, 4) of xyxy frame pixels runs the model on the window of every box grown by ``crop_expand`` (default 0.2) of its
+        width / height per side; one ``Results`` per box, frame by frame in box order, in frame pixels, with ``Results.crop``.  An empty crop,
+        frames of different shapes, a tensor source or a model of another task: ``ValueError`` before any device use."""
         if source is None:
             raise ValueError("'source' is missing; the device path takes a BCHW float tensor in [0, 1]")
         self._refuse_for_segment(kwargs, source)
         self._refuse_for_obb(kwargs, source)
+        self._refuse_for_pose(kwargs, source)
         track = kwargs.get("mode") == "track"
         args = {**self.overrides, "conf": 0.1 if track else 0.25, **kwargs}
         args.pop("model", None), args.pop("task", None), args.pop("mode", None)
         persist = bool(args.pop("persist", False))
+        crops = args.pop("crops", None)  # (host arrays: not part of what a predictor is keyed on)
         if not track:
             args.pop("tracker", None)
         elif args.get("tile") is not None and int(args.get("merge_max_det", 1000)) > 1024:  # (before a predictor is built or anything is launched)
@@ -125,6 +144,9 @@ class Model(nn.Module):
             p.tracker = self._tracker
         else:
             self.predictor.tracker = None
+        if crops is not None:
+            gen = self.predictor.predict_crops(source, crops)
+            return gen if stream else list(gen)
         return self.predictor(source, stream=stream)
 
     def track(self, source=None, stream: bool = False, persist: bool = False, tracker="bytetrack.yaml", **kwargs) -> List[Results]:
@@ -180,6 +202,24 @@ class Model(nn.Module):
         if a.get("augment"):
             raise NotImplementedError("augment=True: test-time augmentation is not built for oriented-box models")
 
+    def _refuse_for_pose(self, kwargs: dict, source=None) -> None:
+        """What a pose model does not do -- ``track``, ``tile=``, ``augment=True`` -- refused by argument name before a predictor is built or
+        anything is launched; and ``crops=``, which only a pose model takes, checked on the host: the frames, the boxes and every
+        crop rectangle."""
+        a = {**self.overrides, **kwargs}
+        if self.task != "pose":
+            if a.get("crops") is not None:
+                raise ValueError(f"crops: person crops are taken by pose models only; this is a '{self.task}' model")
+            return
+        if a.get("mode") == "track":
+            raise NotImplementedError("track: not built for pose models")
+        if a.get("tile") is not None:
+            raise NotImplementedError("tile: not built for pose models (crops= runs a pose model on windows of a large frame)")
+        if a.get("augment"):
+            raise NotImplementedError("augment=True: test-time augmentation is not built for pose models")
+        if a.get("crops") is not None:
+            PosePredictor.check_crops(source, a["crops"], float(a.get("crop_expand", 0.2)))
+
     def profile(self, source, **kwargs) -> list:
         """Per-layer device time of one pass over ``source`` (reference ``predict(profile=True)`` -> ``_profile_one_layer``, nn/tasks.py:171-191):
         [{layer, type, launches, ms, kernels}], see ``DetectionPredictor.profile_layers``."""
@@ -200,6 +240,8 @@ class Model(nn.Module):
         YAML are refused the same way;
         ``device="0,1,.."`` trains with one rank per GPU (child processes under torch.distributed.run, RCCL all-reduce),
         after which rank-less this process reloads ``weights/last.pt`` — as the reference does (model.py:806-813)."""
+        if self.task == "pose":  # before a trainer is built or a device selected
+            raise NotImplementedError("train: pose training (v8PoseLoss) is not built")
         args = {**{k: v for k, v in self.overrides.items() if k not in ("task", "mode")}, **kwargs}
         if self.task == "segment":  # the training twin of val's dataset rule, before a trainer is built or a device selected
             from .trainer import check_seg_train_data
@@ -257,6 +299,8 @@ class Model(nn.Module):
         from .. import hip_ops as H
         from ..utils.torch_utils import select_device
 
+        if self.task == "pose":  # before a dataset is read or a device selected
+            raise NotImplementedError("val: pose validation (OKS matching) is not built")
         args = {**{k: v for k, v in self.overrides.items() if k not in ("task", "mode")}, **kwargs}
         if args.get("data") is None:
             raise ValueError("val(): 'data' is missing (a tensor dataset: dict / .pt, or 'synthetic[:N]')")

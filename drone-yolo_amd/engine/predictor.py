@@ -43,8 +43,14 @@ def split_supported(model) -> bool:
     layer's input and the class logits excepted)."""
     import torch.nn as nn
 
+    from ..nn.modules.head import Pose
+
     convs = [m for k, m in model.named_modules() if isinstance(m, nn.Conv2d) and ".dfl" not in k]  # (DFL's fixed 16 -> 1 conv lives inside the decode kernel)
+    # a Pose head's keypoint branch (51 channels for the n, s and m scales) runs on packs padded to a served width (Pose.served_width): its channel counts are not the kernels'
+    padded = {id(c) for m in model.modules() if isinstance(m, Pose) for c in m.cv4.modules() if isinstance(c, nn.Conv2d)}
     for c in convs:
+        if id(c) in padded and c.groups == 1 and c.kernel_size in ((1, 1), (3, 3)) and c.stride[0] == 1:
+            continue
         if c.groups != 1:  # DWConv of the -sf YAML: the small-group kernel (one output channel per group, 1 / 2 / 4 inputs each)
             if c.out_channels != c.groups or c.in_channels // c.groups not in (1, 2, 4) or c.out_channels % 8 or c.kernel_size[0] ** 2 * (c.in_channels // c.groups) * c.out_channels * 4 > 48 * 1024:
                 return False
@@ -95,7 +101,7 @@ class DetectionPredictor:
                  verbose=False, graph=True, max_nms=30000, max_wh=7680, imgsz=640, fp8_layers=None, batch=None, augment=False,
                  tracker="bytetrack.yaml", device_track=True, track_streams=1, max_tracks=512,
                  tile=None, tile_overlap=0.2, merge_iou=0.7, merge_metric="iou", merge_mode="suppress", merge_max_det=1000, retina_masks=False,
-                 tile_mask_stride=4)
+                 tile_mask_stride=4, crop_expand=0.2)
         a.update(overrides or {})
         self.args = a
         if a["tile"] is not None:  # tiled inference: checked before anything touches the device
@@ -916,3 +922,153 @@ class OBBPredictor(DetectionPredictor):
         a = self.args
         return H.tile_merge_rotated(cf.nms, offs_d, k, frame_hw, self.model.yaml["nc"], float(a["merge_iou"]), bool(a["agnostic_nms"]),
                                     int(a["merge_max_det"]), bufs=mbufs)
+
+
+class PosePredictor(DetectionPredictor):
+    """Predictor of the pose models -- reference models/yolo/pose/predict.py:8-53.
+
+    The recorded pass is the detection pass (every Detect fusion and the fused candidate filter unchanged) plus the per-level keypoint
+    branches, then ``dy_nms``, ``dy_kpt_decode`` in its gather form (the keypoints of the kept anchors only), ``dy_scale_boxes`` and
+    ``dy_scale_coords``; one synchronisation per batch, and a streamed run copies the (N, max_det, nk) keypoint rows behind the batch's
+    launches where it copies the detection rows.  ``Results.boxes`` as for detection, ``Results.keypoints.data`` (n, *kpt_shape) fp32 on the
+    device.  ``track``, ``tile=`` and ``augment=True`` are refused.
+
+    ``predict_crops`` (``YOLO.predict(frames, crops=boxes)``): every box of every frame becomes an expanded integer window of
+    its frame, letterboxed to ``imgsz x imgsz`` by ONE ``dy_crops_letterbox_u8_to_nchw_f32`` launch per batch of crops and run through the
+    recorded pass; boxes and keypoints are clamped to the crop and moved to frame pixels by ``dy_scale_coords``' offset."""
+
+    def __init__(self, model, overrides: Optional[dict] = None):
+        a = overrides or {}
+        self.refuse_args(a)  # before anything touches the device
+        super().__init__(model, overrides)
+        self.args["task"] = "pose"
+        head = self.model.model[-1]
+        if not hasattr(head, "kpt_shape"):
+            raise RuntimeError("PosePredictor needs a model whose head is Pose")
+        self.kpt_shape = (int(head.kpt_shape[0]), int(head.kpt_shape[1]))
+        self._crop_off = None  # predict_crops: per image of the batch the (x0, y0) of its window
+        self._crop_bufs: Dict[int, torch.Tensor] = {}
+
+    @staticmethod
+    def refuse_args(a: dict) -> None:
+        """What a pose predictor does not take, by argument (YOLO.predict asks before it builds one)."""
+        if a.get("augment") not in (None, False):
+            raise NotImplementedError("augment: not built for pose models")
+        if a.get("tile") is not None:
+            raise NotImplementedError("tile: not built for pose models")
+
+    @staticmethod
+    def check_crops(source, boxes, expand: float):
+        """The host checks of ``crops=``: (frames, rects) or ``ValueError`` -- nothing here touches a device."""
+        from .crops import as_frames, crop_rects
+
+        frames = as_frames(source)
+        return frames, crop_rects(frames, boxes, expand)
+
+    def make_tracker(self):
+        raise NotImplementedError("track: not built for pose models")
+
+    def preprocess(self, im) -> torch.Tensor:
+        self._crop_off = None
+        return super().preprocess(im)
+
+    def _kpt_params(self, h: int, w: int, n: int):
+        """Per image (gain, pad_x, pad_y, clip_w, clip_h, off_x, off_y) of ops.scale_coords (utils/ops.py:756-788; the pads unrounded, in
+        Python floats) for the current source: n rows."""
+        info = getattr(self, "letterbox_info", None)
+        if info is None:
+            return [[1.0, 0.0, 0.0, float(w), float(h), 0.0, 0.0]] * n
+        off = self._crop_off or [(0, 0)] * n
+        rows = []
+        for (h0, w0, hn, wn), (ox, oy) in zip((info if isinstance(info, list) else [info] * n), off):
+            gain = min(hn / h0, wn / w0)
+            rows.append([gain, (wn - w0 * gain) / 2, (hn - h0 * gain) / 2, float(w0), float(h0), float(ox), float(oy)])
+        return rows
+
+    def _record_masks(self, cf: CompiledForward, aux) -> None:
+        if not (isinstance(aux, tuple) and len(aux) == 2 and isinstance(aux[1], (list, tuple))):
+            raise RuntimeError("PosePredictor needs a model whose head is Pose")
+        head = self.model.model[-1]
+        cf.kpts = H.kpt_gather(cf.nms, aux[1], [float(s) for s in head.stride], self.kpt_shape)
+
+    def _record_scale(self, cf: CompiledForward, params: torch.Tensor) -> None:
+        H.scale_boxes_(cf.nms, params)
+        n = cf.nms.batch
+        cf.kpt_key = self._kpt_params(self._recording_hw[0], self._recording_hw[1], n)
+        cf.kpt_params = torch.tensor(cf.kpt_key, dtype=torch.float32, device=self.device)
+        H.scale_coords_(cf.kpts, cf.nms.count, cf.kpt_params, self.kpt_shape, boxes=cf.nms.out)
+
+    def _record(self, im: torch.Tensor) -> CompiledForward:
+        self._recording_hw = (int(im.shape[2]), int(im.shape[3]))
+        return super()._record(im)
+
+    def forward_device(self, im: torch.Tensor) -> CompiledForward:
+        cf = self._compiled.get((tuple(im.shape), self.dtype))
+        if cf is not None and hasattr(cf, "kpt_params"):  # the recorded dy_scale_coords launch reads this device tensor: refresh it when the source geometry changed
+            kp = self._kpt_params(im.shape[2], im.shape[3], im.shape[0])
+            if kp != cf.kpt_key:
+                cf.kpt_params.copy_(torch.tensor(kp, dtype=torch.float32))
+                cf.kpt_key = kp
+        return super().forward_device(im)
+
+    def _mask_stash(self, cf: CompiledForward, streamed: bool):
+        return cf.kpts.clone()  # (the next pass overwrites the plan's buffer: the Results keep views of this copy, as of the rows')
+
+    def _masks_for(self, stash, counts, rows, im, info) -> list:
+        return [stash[i, :k].view(k, *self.kpt_shape) for i, k in enumerate(counts)]
+
+    def _result(self, img, path, names, rows, orig_shape, masks) -> Results:
+        from .results import Keypoints
+
+        shape = tuple(orig_shape)
+        return Results(img, path, names, boxes=rows, orig_shape=shape, keypoints=Keypoints(masks, shape, masked=True))
+
+    # ---- person crops of frames (DESIGN §25.3) ----
+    def predict_crops(self, source, boxes):
+        """Generator: one ``Results`` per crop, frame by frame in box order; ``Results.crop = (frame, x0, y0, x1e, y1e)``, boxes and keypoints
+        in frame pixels, ``orig_shape`` the frame's.  All crops of the call run ``batch`` at a time: one slicer launch, one recorded pass and
+        one synchronisation per batch, the device one batch ahead of the host."""
+        import numpy as np
+
+        from .crops import crop_table
+
+        frames, rects = self.check_crops(source, boxes, float(self.args.get("crop_expand", 0.2)))  # (ValueError before any device use)
+        size = int(self.args.get("imgsz", 640))
+        table = torch.from_numpy(crop_table(rects, size, int(self.model.stride.max())))
+        stacked = torch.from_numpy(np.ascontiguousarray(np.stack(frames))).to(self.device, non_blocking=True)
+        hw = tuple(frames[0].shape[:2])
+        b = int(self.args.get("batch") or len(rects))
+        names = self.model.names
+
+        def finish(item):
+            lo, rows, kpts, counts_host, ev = item
+            ev.synchronize()  # the batch's only device->host synchronisation
+            out = []
+            for i, k in enumerate(counts_host.tolist()):
+                rect = rects[lo + i]
+                r = self._result(frames[rect[0]], f"image{rect[0]}.jpg", names, rows[i, :k], hw, kpts[i, :k].view(k, *self.kpt_shape))
+                r.crop = rect
+                out.append(r)
+            return out
+
+        pending = None
+        for lo in range(0, len(rects), b):
+            t = table[lo : lo + b].contiguous()
+            n = int(t.shape[0])
+            buf = self._crop_bufs.get(n)
+            if buf is None or tuple(buf.shape[2:]) != (size, size):
+                buf = self._crop_bufs[n] = torch.empty((n, 3, size, size), dtype=torch.float32, device=self.device)
+            self.letterbox_info = [(int(r[4]), int(r[3]), size, size) for r in t.tolist()]
+            self._crop_off = [(int(r[1]), int(r[2])) for r in t.tolist()]
+            H.crops_letterbox(stacked, t, size, size, out=buf)
+            cf = self.forward_device(buf)
+            rows, kpts = cf.nms.out.clone(), cf.kpts.clone()  # stream-ordered behind this batch's launches, in front of the next batch's
+            counts_host = torch.empty(cf.nms.count.shape, dtype=cf.nms.count.dtype, pin_memory=True)
+            counts_host.copy_(cf.nms.count, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            if pending is not None:
+                yield from finish(pending)
+            pending = (lo, rows, kpts, counts_host, ev)
+        if pending is not None:
+            yield from finish(pending)

@@ -1,9 +1,10 @@
-"""Result containers (reference: ultralytics/engine/results.py: ``Results``, ``Boxes`` :1004, ``OBB`` :1585).
+"""Result containers (reference: ultralytics/engine/results.py: ``Results``, ``Boxes`` :1004, ``Keypoints`` :1320, ``OBB`` :1585).
 
-Only the tensor-view surface the detection, segmentation and oriented-box paths fill is kept (boxes, masks, obb); plotting /
-saving / keypoints are out of scope.  ``Boxes`` wraps the (n, 6) rows [x1, y1, x2, y2, conf, cls]
+Only the tensor-view surface the detection, segmentation, oriented-box and pose paths fill is kept (boxes, masks, obb, keypoints);
+plotting / saving are out of scope.  ``Boxes`` wraps the (n, 6) rows [x1, y1, x2, y2, conf, cls]
 that ``dy_nms`` + ``dy_scale_boxes`` produced on the device, ``Masks`` the (n, H, W) bytes of ``dy_process_mask``, ``OBB`` the (n, 7) rows
-[x, y, w, h, rotation, conf, cls] of ``dy_nms_rotated`` + ``dy_scale_rboxes``.
+[x, y, w, h, rotation, conf, cls] of ``dy_nms_rotated`` + ``dy_scale_rboxes``, ``Keypoints`` the (n, nkpt, 2 | 3) rows of ``dy_kpt_decode`` +
+``dy_scale_coords``.
 """
 from __future__ import annotations
 
@@ -106,6 +107,41 @@ class Masks(BaseTensor):
         raise NotImplementedError("Masks.xyn: polygon outlines need cv2.findContours, which this package does not depend on; use .data")
 
 
+class Keypoints(BaseTensor):
+    """Keypoints of one image — reference results.py:1320-1440.  ``data``: (n, nkpt, 2) x, y or (n, nkpt, 3) x, y, visibility.  As in the
+    reference, the x and y of a point whose visibility is below 0.5 are set to 0 (results.py:1373-1375); rows that come from the predictor
+    have that done already by ``dy_scale_coords`` (``masked=True``)."""
+
+    def __init__(self, keypoints, orig_shape, masked: bool = False):
+        """``masked``: the rows already have the x and y of their invisible points at 0 (the predictor's, from ``dy_scale_coords``)."""
+        if keypoints.ndim == 2:
+            keypoints = keypoints[None, :]
+        if keypoints.shape[2] == 3 and not masked:  # x, y, conf
+            mask = keypoints[..., 2] < 0.5  # points with conf < 0.5 (not visible)
+            if isinstance(keypoints, torch.Tensor) and keypoints.is_cuda:  # (no host round trip to ask whether any point is invisible)
+                keypoints = torch.cat((torch.where(mask[..., None], torch.zeros_like(keypoints[..., :2]), keypoints[..., :2]), keypoints[..., 2:]), -1)
+            elif bool(mask.any()):
+                keypoints = keypoints.clone() if isinstance(keypoints, torch.Tensor) else np.copy(keypoints)
+                keypoints[..., :2][mask] = 0
+        super().__init__(keypoints, orig_shape)
+        self.has_visible = self.data.shape[-1] == 3
+
+    @property
+    def xy(self):
+        return self.data[..., :2]
+
+    @property
+    def xyn(self):
+        xy = self.xy.clone() if isinstance(self.xy, torch.Tensor) else np.copy(self.xy)
+        xy[..., 0] /= self.orig_shape[1]
+        xy[..., 1] /= self.orig_shape[0]
+        return xy
+
+    @property
+    def conf(self):
+        return self.data[..., 2] if self.has_visible else None
+
+
 class OBB(BaseTensor):
     """Oriented boxes of one image — reference results.py:1585-1806.  ``data``: (n, 7) [x, y, w, h, rotation, conf, cls], or (n, 8) with a
     track id in front of conf -- what ``YOLO.track`` leaves for an image whose tracker returned rows (``is_track``, ``id``)."""
@@ -157,16 +193,19 @@ class OBB(BaseTensor):
 
 
 class Results:
-    """Per-image result — reference results.py (`Results`): orig_img, orig_shape, boxes, masks, obb, names, path, speed.  An oriented-box
-    result carries ``obb`` and no ``boxes``."""
+    """Per-image result — reference results.py (`Results`): orig_img, orig_shape, boxes, masks, obb, keypoints, names, path, speed.  An
+    oriented-box result carries ``obb`` and no ``boxes``.  ``crop``: None, or — a result of ``predict(frames, crops=...)`` — the window of the
+    frame the result was computed on, ``(frame, x0, y0, x1, y1)``; its boxes and keypoints are in frame pixels."""
 
-    def __init__(self, orig_img, path, names, boxes=None, speed=None, orig_shape=None, masks=None, obb=None):
+    def __init__(self, orig_img, path, names, boxes=None, speed=None, orig_shape=None, masks=None, obb=None, keypoints=None):
         self._orig_img = orig_img
         self.orig_shape = tuple(orig_shape) if orig_shape is not None else tuple(orig_img.shape[:2])
         self.boxes = Boxes(boxes, self.orig_shape) if boxes is not None else None
         self.masks = Masks(masks, self.orig_shape) if masks is not None else None
         self.obb = OBB(obb, self.orig_shape) if obb is not None else None
-        self.probs = self.keypoints = None
+        self.keypoints = (keypoints if isinstance(keypoints, Keypoints) else Keypoints(keypoints, self.orig_shape)) if keypoints is not None else None
+        self.probs = None
+        self.crop = None
         self.speed = speed if speed is not None else {"preprocess": None, "inference": None, "postprocess": None}
         self.names = names
         self.path = path
@@ -181,7 +220,7 @@ class Results:
         return im
 
     def __len__(self):
-        for v in (self.boxes, self.masks, self.obb):  # (the first that is there, as the reference's __len__)
+        for v in (self.boxes, self.masks, self.keypoints, self.obb):  # (the first that is there, as the reference's __len__)
             if v is not None:
                 return len(v)
         return 0
@@ -191,6 +230,8 @@ class Results:
         r.boxes = self.boxes.cpu() if self.boxes is not None else None
         r.masks = self.masks.cpu() if self.masks is not None else None
         r.obb = self.obb.cpu() if self.obb is not None else None
+        r.keypoints = self.keypoints.cpu() if self.keypoints is not None else None
+        r.crop = self.crop
         return r
 
     def numpy(self):
@@ -198,6 +239,8 @@ class Results:
         r.boxes = self.boxes.numpy() if self.boxes is not None else None
         r.masks = self.masks.numpy() if self.masks is not None else None
         r.obb = self.obb.numpy() if self.obb is not None else None
+        r.keypoints = self.keypoints.numpy() if self.keypoints is not None else None
+        r.crop = self.crop
         return r
 
     def to(self, *args, **kwargs):
@@ -205,6 +248,8 @@ class Results:
         r.boxes = self.boxes.to(*args, **kwargs) if self.boxes is not None else None
         r.masks = self.masks.to(*args, **kwargs) if self.masks is not None else None
         r.obb = self.obb.to(*args, **kwargs) if self.obb is not None else None
+        r.keypoints = self.keypoints.to(*args, **kwargs) if self.keypoints is not None else None
+        r.crop = self.crop
         return r
 
     def __getitem__(self, idx):
@@ -212,6 +257,8 @@ class Results:
         r.boxes = self.boxes[idx] if self.boxes is not None else None
         r.masks = self.masks[idx] if self.masks is not None else None
         r.obb = self.obb[idx] if self.obb is not None else None
+        r.keypoints = self.keypoints[idx] if self.keypoints is not None else None
+        r.crop = self.crop
         return r
 
     # ---- text forms of a detection result (reference results.py:633-666 verbose, :668-757 save_txt, :759-823 summary, :906-940 to_json) ----

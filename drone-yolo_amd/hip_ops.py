@@ -2117,6 +2117,99 @@ def scale_img(img: torch.Tensor, ratio: float, gs: int = 32, flip_lr: bool = Fal
     return out
 
 
+# ---- pose: keypoint decode, keypoint rescale, batched person crops (csrc/pose.hip) ----------------------------------
+CROP_COLS = 9  # columns of a crop table row: frame, x0, y0, cw, ch, new_w, new_h, top, left
+
+
+def _kpt_desc(levels: Sequence[torch.Tensor], strides: Sequence[float], kpt_shape, n: int) -> "_lib.KptDecodeDesc":
+    nkpt, ndim = int(kpt_shape[0]), int(kpt_shape[1])
+    if len(levels) > _lib.DY_MAX_LEVELS or len(levels) != len(strides):
+        raise ValueError("kpt_decode: one stride per level, at most DY_MAX_LEVELS levels")
+    d = _lib.KptDecodeDesc()
+    for i, t in enumerate(levels):
+        require_device(t, "keypoint map")
+        if t.dtype != torch.float32 or t.shape[0] != n or t.shape[1] != nkpt * ndim:
+            raise ValueError(f"kpt_decode: keypoint maps must be fp32 (N, {nkpt * ndim}, h, w) NHWC views")
+        d.level[i], d.ld[i] = view_params(t)
+        d.h[i], d.w[i], d.stride[i] = t.shape[2], t.shape[3], float(strides[i])
+    d.n_levels, d.batch, d.nkpt, d.ndim = len(levels), n, nkpt, ndim
+    d.anchors = sum(t.shape[2] * t.shape[3] for t in levels)
+    return d
+
+
+def kpt_decode(levels: Sequence[torch.Tensor], strides: Sequence[float], kpt_shape, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``Pose.kpts_decode`` of every anchor (``dy_kpt_decode``, dense form): the per-level fp32 NHWC keypoint logits (N, nk, h_i, w_i) ->
+    ``pred_kpt`` (N, nk, A) fp32."""
+    n = levels[0].shape[0]
+    d = _kpt_desc(levels, strides, kpt_shape, n)
+    shape = (n, d.nkpt * d.ndim, d.anchors)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=levels[0].device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"kpt_decode: out must be a contiguous fp32 {shape} tensor")
+    d.pred_kpt = out.data_ptr()
+    _launch(lib().dy_kpt_decode, (C.byref(d),), keep=(d, out, *levels))
+    return out
+
+
+def kpt_gather(bufs: "NmsBuffers", levels: Sequence[torch.Tensor], strides: Sequence[float], kpt_shape, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The kept rows' decoded keypoints -> (N, max_det, nk) fp32 (``dy_kpt_decode``, gather form; call it behind ``nms``).  Rows beyond the
+    counts are left as they are."""
+    n, md = bufs.batch, bufs.max_det
+    d = _kpt_desc(levels, strides, kpt_shape, n)
+    if d.anchors != bufs.anchors:
+        raise ValueError(f"kpt_gather: the levels hold {d.anchors} anchors, the NMS buffers {bufs.anchors}")
+    shape = (n, md, d.nkpt * d.ndim)
+    if out is None:
+        out = torch.zeros(shape, dtype=torch.float32, device=bufs.out.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"kpt_gather: out must be a contiguous fp32 {shape} tensor")
+    d.counts, d.index, d.max_det, d.out = bufs.count.data_ptr(), bufs.index.data_ptr(), md, out.data_ptr()
+    _launch(lib().dy_kpt_decode, (C.byref(d),), keep=(d, bufs, out, *levels))
+    return out
+
+
+def scale_coords_(kpts: torch.Tensor, count: torch.Tensor, params: torch.Tensor, kpt_shape, boxes: Optional[torch.Tensor] = None) -> None:
+    """In-place ``ops.scale_coords`` + the ``Keypoints`` masking of the kept rows (``dy_scale_coords``).  kpts: fp32 (N, max_det, nk);
+    count: int32 (N); params: device fp32 (N, 7) gain, pad_x, pad_y, clip_w, clip_h, off_x, off_y (unrounded pads); ``boxes``: the
+    (N, max_det, 6) rows behind ``scale_boxes_``, whose xyxy take a non-zero offset too."""
+    nkpt, ndim = int(kpt_shape[0]), int(kpt_shape[1])
+    if kpts.dtype != torch.float32 or kpts.dim() != 3 or kpts.shape[2] != nkpt * ndim or not kpts.is_contiguous():
+        raise ValueError(f"scale_coords_: kpts must be a contiguous fp32 (N, max_det, {nkpt * ndim}) tensor")
+    n, md = kpts.shape[0], kpts.shape[1]
+    if tuple(params.shape) != (n, 7) or params.dtype != torch.float32 or not params.is_contiguous() or count.dtype != torch.int32 or count.numel() != n:
+        raise ValueError("scale_coords_: params must be fp32 (N, 7) and count int32 (N)")
+    require_device(kpts, "keypoint rows")
+    if boxes is not None and (tuple(boxes.shape) != (n, md, 6) or boxes.dtype != torch.float32 or not boxes.is_contiguous()):
+        raise ValueError("scale_coords_: boxes must be the contiguous fp32 (N, max_det, 6) rows of nms")
+    _launch(lib().dy_scale_coords, (kpts.data_ptr(), boxes.data_ptr() if boxes is not None else None, count.data_ptr(), params.data_ptr(), n, md, nkpt, ndim),
+            keep=(kpts, boxes, count, params))
+
+
+def crops_letterbox(frames: torch.Tensor, table: torch.Tensor, hn: int, wn: int, out: Optional[torch.Tensor] = None, swap_rb: bool = True,
+                    pad_value: float = 114.0, table_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 (F, H, W, 3) device frames + a HOST int32 (K, 9) crop table (frame, x0, y0, cw, ch, new_w, new_h, top, left) -> fp32
+    (K, 3, hn, wn) / 255, crop j letterboxed as ``letterbox`` does a contiguous copy of its window: one
+    ``dy_crops_letterbox_u8_to_nchw_f32`` launch.  The table is checked on the host (a bad row raises, nothing is launched) and uploaded
+    (``table_dev``: a device copy the caller already made)."""
+    require_device(frames, "frames")
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise ValueError("crops_letterbox expects a contiguous uint8 (F, H, W, 3) device tensor")
+    if table.is_cuda or table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != CROP_COLS or not table.is_contiguous() or table.shape[0] < 1:
+        raise ValueError("crops_letterbox expects the crop table as a contiguous int32 (K, 9) host tensor")
+    f, hf, wf, _ = frames.shape
+    k = int(table.shape[0])
+    if out is None:
+        out = torch.empty((k, 3, hn, wn), dtype=torch.float32, device=frames.device)
+    elif tuple(out.shape) != (k, 3, hn, wn) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"crops_letterbox: out must be a contiguous fp32 ({k}, 3, {hn}, {wn}) tensor")
+    if table_dev is None:
+        table_dev = table.to(frames.device, non_blocking=True)
+    _launch(lib().dy_crops_letterbox_u8_to_nchw_f32, (frames.data_ptr(), table_dev.data_ptr(), table.data_ptr(), out.data_ptr(), f, hf, wf, k, int(hn), int(wn),
+                                                      int(swap_rb), float(pad_value)), keep=(frames, table, table_dev, out))
+    return out
+
+
 # ---- tiled inference on batches of frames (csrc/tile_merge.hip, DESIGN §16) -------------------------------------------------
 
 

@@ -64,6 +64,7 @@ def _own_classes() -> Dict[str, type]:
     out["DetectionModel"] = T.DetectionModel
     out["SegmentationModel"] = T.SegmentationModel
     out["OBBModel"] = T.OBBModel
+    out["PoseModel"] = T.PoseModel
     out["BaseModel"] = T.BaseModel
     return out
 
@@ -150,7 +151,8 @@ _REF_PATHS = {"Conv": "ultralytics.nn.modules.conv", "DWConv": "ultralytics.nn.m
               "Bottleneck": "ultralytics.nn.modules.block", "RepVGGBlock": "ultralytics.nn.modules.block", "SEBlock": "ultralytics.nn.modules.block",
               "Detect": "ultralytics.nn.modules.head", "DetectionModel": "ultralytics.nn.tasks", "BaseModel": "ultralytics.nn.tasks",
               "Proto": "ultralytics.nn.modules.block", "Segment": "ultralytics.nn.modules.head", "SegmentationModel": "ultralytics.nn.tasks",
-              "OBB": "ultralytics.nn.modules.head", "OBBModel": "ultralytics.nn.tasks"}
+              "OBB": "ultralytics.nn.modules.head", "OBBModel": "ultralytics.nn.tasks",
+              "Pose": "ultralytics.nn.modules.head", "PoseModel": "ultralytics.nn.tasks"}
 _DROP_ATTRS = (PACKED, "_sig_tensors", "_weights_epoch", "_place", "_srcs", "_virtual", "_skip", "_front",
                "_consumers0", "_out_ch", "_cum_stride", "criterion", "train_dtype", "args", "fused_nms", "fuse_tail")
 

@@ -1,4 +1,4 @@
-"""Detect, Segment and OBB heads of the Drone-YOLO path (reference: ultralytics/nn/modules/head.py:21-227)."""
+"""Detect, Segment, OBB and Pose heads of the Drone-YOLO path (reference: ultralytics/nn/modules/head.py:21-279)."""
 from __future__ import annotations
 
 import math
@@ -11,7 +11,7 @@ from .block import DFL, Proto
 from .conv import Conv, DWConv, PlainConv2d
 from .packs import PackOwner, packed
 
-__all__ = ("Detect", "Segment", "OBB")
+__all__ = ("Detect", "Segment", "OBB", "Pose")
 
 
 class Detect(PackOwner, nn.Module):
@@ -356,3 +356,81 @@ class OBB(Detect):
             return y, (None, theta, levels)
         angle = theta[:, None]
         return torch.cat([y, angle], 1), (feats, angle)
+
+
+class Pose(Detect):
+    """YOLO Pose head — reference head.py:230-279: Detect plus, per level, the keypoint branch ``cv4`` = Conv(x, c4, 3), Conv(c4, c4, 3),
+    Conv2d(c4, nk, 1) with ``c4 = max(ch[0] // 4, nk)``; same constructor ``(nc, kpt_shape, ch)`` and state-dict keys.
+
+    The box and class branches go through every fusion of ``Detect`` unchanged.  For the n, s and m scales c4 = nk = 51, which is no whole
+    number of the channel groups the convolution kernels address (``H.chan_gran``: 16-byte chunks of a pixel row); the parameters keep the
+    reference's shapes and the branch's PACKS are padded with zero rows, zero columns and zero bias entries to ``served_width`` -- a padded
+    channel is SiLU(0) = 0 in either activation domain and meets zero weights in the next layer, so the logits are those of the unpadded
+    branch.  ``keypoint_maps`` returns the per-level fp32 NHWC logit maps (N, nk, h_i, w_i) in true units, views into buffers of the
+    padded width.  Eval forward returns the reference's ``(cat([y, pred_kpt], 1), (feats, kpt))`` with ``pred_kpt`` from ``dy_kpt_decode``;
+    on the predictor's fast path (``fuse_tail``) nothing is concatenated: the return is ``(y, (None, levels))`` and the predictor decodes
+    the kept anchors only.  Training mode raises: pose training is not built.
+    """
+
+    CH_GRAN = 16  # served_width rounds up to this: whole chunks of every storage type (fp32 4, 16-bit and split float16 8) and whole 16-row MFMA tiles
+
+    def __init__(self, nc=80, kpt_shape=(17, 3), ch=()):
+        super().__init__(nc, ch)
+        self.kpt_shape = kpt_shape
+        self.nk = kpt_shape[0] * kpt_shape[1]
+        c4 = max(ch[0] // 4, self.nk)
+        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), PlainConv2d(c4, self.nk, 1)) for x in ch)
+
+    @classmethod
+    def served_width(cls, c: int, dtype) -> int:
+        """The channel count a ``c``-channel activation of the keypoint branch is stored with: ``c`` where the convolution kernels take it
+        as input and output (whole channel groups of ``dtype``, ``H.chan_gran``, and whole groups of 8, as ``split_supported`` asks of every
+        layer), the next multiple of ``CH_GRAN`` otherwise."""
+        g = max(H.chan_gran(dtype), 8)
+        return c if c % g == 0 else -(-c // cls.CH_GRAN) * cls.CH_GRAN
+
+    def _packed_kpt(self, i, dtype, device):
+        """The three packs of ``cv4[i]`` at the served widths (c4 -> c4p between the convolutions, nk -> nkp on the logits)."""
+        a, b, t = self.cv4[i]
+        c4p, nkp = self.served_width(a.conv.out_channels, dtype), self.served_width(self.nk, dtype)
+
+        def pad(w, bias, cout, cin):
+            w = torch.nn.functional.pad(w.detach().float(), (0, 0, 0, 0, 0, cin - w.shape[1], 0, cout - w.shape[0]))
+            return w, torch.nn.functional.pad(bias.detach().float(), (0, cout - bias.shape[0]))
+
+        def build():
+            (wa, ba, act_a), (wb, bb, act_b) = a._folded(), b._folded()
+            wt, bt, act_t = H.domain_fold(t.weight, t.bias, False, raw_output=True)  # (the plain last conv leaves the scaled domain: true units)
+            wa, ba = pad(wa, ba, c4p, wa.shape[1])
+            wb, bb = pad(wb, bb, c4p, c4p)
+            wt, bt = pad(wt, bt, nkp, c4p)
+            return (H.PackedConv(wa, ba, 1, 1, 1, act_a, dtype, device), H.PackedConv(wb, bb, 1, 1, 1, act_b, dtype, device),
+                    H.PackedConv(wt, bt, 1, 0, 1, act_t, dtype, device, for_out_f32=True))
+
+        return packed(self, ("kpt", i), (a, b, t), dtype, device, build)
+
+    def keypoint_maps(self, x):
+        """cv4 of every level: fp32 NHWC views (N, nk, h_i, w_i) of the raw keypoint logits, true units."""
+        out = []
+        for i in range(self.nl):
+            n, _, h, w = x[i].shape
+            pa, pb, pt = self._packed_kpt(i, x[i].dtype, x[i].device)
+            buf = H.alloc_nhwc(n, pt.cout, h, w, torch.float32, x[i].device)
+            H.conv2d(H.conv2d(H.conv2d(x[i], pa), pb), pt, out=buf, out_f32=True)
+            out.append(buf[:, : self.nk])
+        return out
+
+    def forward(self, x):
+        if self.training:
+            raise NotImplementedError("Pose.forward in training mode is not built: pose training (v8PoseLoss) is out of scope")
+        if any(t.dtype == H.FP8 for t in x):
+            raise NotImplementedError("Pose is built for the 16-bit, split-float16 and fp32 storage types")
+        x = list(x)
+        levels = self.keypoint_maps(x)
+        y, feats = Detect.forward(self, x)
+        if self.fuse_tail:
+            return y, (None, levels)
+        bs = y.shape[0]
+        kpt = torch.cat([t.reshape(bs, self.nk, -1) for t in levels], 2)  # (layout glue of the module-level return only)
+        pred_kpt = H.kpt_decode(levels, [float(s) for s in self.stride], self.kpt_shape)
+        return torch.cat([y, pred_kpt], 1), (feats, kpt)

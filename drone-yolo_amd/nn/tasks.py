@@ -33,7 +33,7 @@ from .. import hip_ops as H
 from ..utils import LOGGER
 from ..utils.ops import make_divisible
 from ..utils.torch_utils import initialize_weights
-from .modules import OBB, SPPF, Bottleneck, C2f, Concat, Conv, Detect, DWConv, Proto, RepVGGBlock, Segment, Upsample
+from .modules import OBB, SPPF, Bottleneck, C2f, Concat, Conv, Detect, DWConv, Pose, Proto, RepVGGBlock, Segment, Upsample
 from .modules.block import DFL
 from .modules.conv import PlainConv2d
 from .modules.packs import PACKED, PackOwner, packed
@@ -42,7 +42,7 @@ CFG_DIR = Path(__file__).resolve().parents[1] / "cfg"
 
 _MODULES = {
     "Conv": Conv, "DWConv": DWConv, "RepVGGBlock": RepVGGBlock, "C2f": C2f, "SPPF": SPPF, "Bottleneck": Bottleneck,
-    "Concat": Concat, "Detect": Detect, "Segment": Segment, "OBB": OBB, "nn.Upsample": Upsample,
+    "Concat": Concat, "Detect": Detect, "Segment": Segment, "OBB": OBB, "Pose": Pose, "nn.Upsample": Upsample,
 }  # fmt: skip
 _BASE_MODULES = frozenset({Conv, DWConv, RepVGGBlock, C2f, SPPF, Bottleneck})
 _REPEAT_MODULES = frozenset({C2f})
@@ -95,7 +95,7 @@ def parse_model(d: dict, ch: int, verbose: bool = True):
         for j, a in enumerate(args):
             if isinstance(a, str):
                 with contextlib.suppress(ValueError, SyntaxError):
-                    args[j] = nc if a == "nc" else ast.literal_eval(a)
+                    args[j] = nc if a == "nc" else (tuple(d["kpt_shape"]) if a == "kpt_shape" and d.get("kpt_shape") else ast.literal_eval(a))
         n = n_ = max(round(n * depth), 1) if n > 1 else n
         if m in _BASE_MODULES:
             c1, c2 = ch[f], args[0]
@@ -107,7 +107,7 @@ def parse_model(d: dict, ch: int, verbose: bool = True):
                 n = 1
         elif m is Concat:
             c2 = sum(ch[x] for x in f)
-        elif m in (Detect, Segment, OBB):
+        elif m in (Detect, Segment, OBB, Pose):
             args.append([ch[x] for x in f])
             if m is Segment:  # the proto channels follow the width multiple (tasks.py:1058-1064)
                 args[2] = make_divisible(min(args[2], max_channels) * width, 8)
@@ -546,26 +546,52 @@ class OBBModel(DetectionModel):
         raise NotImplementedError("augment=True is not built for oriented-box models")
 
 
-TASK_MODELS = {"detect": DetectionModel, "segment": SegmentationModel, "obb": OBBModel}
+class PoseModel(DetectionModel):
+    """YOLO pose model -- reference tasks.py:415-431: ``kpt_shape`` comes from the YAML (``data_kpt_shape`` overrides it, as a dataset's would).
+    Predicts (``PosePredictor``); pose training, validation (OKS), tracking, tiling and test-time augmentation are not built and refused by name."""
+
+    def __init__(self, cfg="yolov8s-p2-repvgg-pose.yaml", ch=3, nc=None, data_kpt_shape=(None, None), verbose=True):
+        if not isinstance(cfg, dict):
+            cfg = yaml_model_load(cfg)
+        if any(data_kpt_shape) and list(data_kpt_shape) != list(cfg["kpt_shape"]):
+            if verbose:
+                LOGGER.info(f"Overriding model.yaml kpt_shape={cfg['kpt_shape']} with kpt_shape={data_kpt_shape}")
+            cfg["kpt_shape"] = data_kpt_shape
+        super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
+        self.kpt_shape = tuple(self.model[-1].kpt_shape)
+
+    def init_criterion(self):
+        raise NotImplementedError("train: pose training (v8PoseLoss) is not built")
+
+    def forward_train(self, img, dtype=None):
+        raise NotImplementedError("train: pose training (v8PoseLoss) is not built")
+
+    def _predict_augment(self, x, image_dtype=None):
+        raise NotImplementedError("augment=True is not built for pose models")
+
+
+TASK_MODELS = {"detect": DetectionModel, "segment": SegmentationModel, "obb": OBBModel, "pose": PoseModel}
 
 
 def guess_model_task(model) -> str:
-    """'segment', 'obb' or 'detect' from a YAML dict (its head's last module), a module graph (its head class) or a file name ('-seg',
-    '-obb') — reference tasks.py:1127-1190, for the three tasks built here."""
+    """'segment', 'obb', 'pose' or 'detect' from a YAML dict (its head's last module), a module graph (its head class) or a file name ('-seg',
+    '-obb', '-pose') — reference tasks.py:1127-1190, for the four tasks built here."""
     if isinstance(model, dict):
         with contextlib.suppress(Exception):
-            return {"segment": "segment", "obb": "obb"}.get(str(model["head"][-1][-2]).lower(), "detect")
+            return {"segment": "segment", "obb": "obb", "pose": "pose"}.get(str(model["head"][-1][-2]).lower(), "detect")
     if isinstance(model, nn.Module):
         for m in model.modules():
             if isinstance(m, Segment):
                 return "segment"
             if isinstance(m, OBB):
                 return "obb"
+            if isinstance(m, Pose):
+                return "pose"
         y = getattr(model, "yaml", None)
         return guess_model_task(y) if isinstance(y, dict) else "detect"
     if isinstance(model, (str, Path)):
         stem = Path(model).stem
-        return "segment" if "-seg" in stem else ("obb" if "-obb" in stem else "detect")
+        return "segment" if "-seg" in stem else ("obb" if "-obb" in stem else ("pose" if "-pose" in stem else "detect"))
     return "detect"
 
 

@@ -114,6 +114,38 @@ def scale_boxes(img1_shape, boxes, img0_shape, ratio_pad=None, padding=True, xyw
     return clip_boxes(boxes, img0_shape)
 
 
+def clip_coords(coords, shape):
+    """Clip point coordinates (..., 2+) to the image (h, w) — reference ops.py:357-374."""
+    if isinstance(coords, torch.Tensor):
+        coords[..., 0] = coords[..., 0].clamp(0, shape[1])
+        coords[..., 1] = coords[..., 1].clamp(0, shape[0])
+    else:
+        coords[..., 0] = coords[..., 0].clip(0, shape[1])
+        coords[..., 1] = coords[..., 1].clip(0, shape[0])
+    return coords
+
+
+def scale_coords(img1_shape, coords, img0_shape, ratio_pad=None, normalize=False, padding=True):
+    """Rescale point coordinates (..., 2+) from img1_shape to img0_shape, in place — reference ops.py:756-788.  Unlike ``scale_boxes`` the
+    pad is NOT rounded: (img1 - img0 * gain) / 2 as it comes.  The device form is ``dy_scale_coords``."""
+    if ratio_pad is None:
+        gain = min(img1_shape[0] / img0_shape[0], img1_shape[1] / img0_shape[1])
+        pad = (img1_shape[1] - img0_shape[1] * gain) / 2, (img1_shape[0] - img0_shape[0] * gain) / 2
+    else:
+        gain = ratio_pad[0][0]
+        pad = ratio_pad[1]
+    if padding:
+        coords[..., 0] -= pad[0]
+        coords[..., 1] -= pad[1]
+    coords[..., 0] /= gain
+    coords[..., 1] /= gain
+    coords = clip_coords(coords, img0_shape)
+    if normalize:
+        coords[..., 0] /= img0_shape[1]
+        coords[..., 1] /= img0_shape[0]
+    return coords
+
+
 def regularize_rboxes(rboxes):
     """xywhr boxes with the angle brought into [0, pi/2): w and h swap where ``t % pi >= pi/2`` — reference ops.py:791-807."""
     x, y, w, h, t = rboxes.unbind(dim=-1)

@@ -1271,6 +1271,51 @@ typedef struct dy_val_mask_match_desc {
 } dy_val_mask_match_desc;
 int32_t dy_val_mask_match(const dy_val_mask_match_desc* d, dy_stream_t stream);
 
+/* ---- pose estimation: keypoint decode, keypoint rescale, batched person crops (csrc/pose.hip) ------------------------------
+ * dy_kpt_decode: Pose.kpts_decode (nn/modules/head.py:274-279, the non-export branch).  level[i]: fp32 NHWC (batch, h[i], w[i], nk) with
+ * pitch ld[i] >= nk = nkpt * ndim, the outputs of Pose.cv4[i]; anchors are numbered level by level, row-major.  Per keypoint k of the
+ * anchor in cell (col, row) of a level with stride s, every step rounded to fp32:
+ *   x = (logit[k * ndim] * 2 + ((col + 0.5) - 0.5)) * s,  y the same with row,  v = sigmoid(logit[k * ndim + 2]) when ndim == 3.
+ * Two forms, exactly one of pred_kpt / out set:
+ *   dense   pred_kpt: fp32 (batch, nk, anchors), the module-level return;
+ *   gather  behind dy_nms: out (batch, max_det, nk); for every kept row r < counts[b]: out[b, r, :] = the keypoints of anchor index[b, r].
+ *           Rows >= counts[b] are neither read nor written; an index outside [0, anchors) writes zeros.
+ * ndim outside {2, 3} or nk > 256: DY_ERR_UNSUPPORTED. */
+typedef struct dy_kpt_decode_desc {
+  const float* level[DY_MAX_LEVELS];
+  int32_t h[DY_MAX_LEVELS], w[DY_MAX_LEVELS], ld[DY_MAX_LEVELS];
+  float stride[DY_MAX_LEVELS];
+  int32_t n_levels;
+  int32_t batch, anchors, nkpt, ndim;
+  float* pred_kpt;        /* dense form, or NULL */
+  const int32_t* counts;  /* gather form: (batch) dy_nms out_count */
+  const int32_t* index;   /* (batch, max_det) dy_nms out_index */
+  int32_t max_det;
+  float* out;             /* (batch, max_det, nk), or NULL */
+} dy_kpt_decode_desc;
+int32_t dy_kpt_decode(const dy_kpt_decode_desc* d, dy_stream_t stream);
+
+/* dy_scale_coords: PosePredictor.construct_result's ops.scale_coords (models/yolo/pose/predict.py:46-48; utils/ops.py:756-788 with
+ * clip_coords :357-374) and the Keypoints constructor's masking (engine/results.py:1373-1375), in place on the gathered rows
+ * kpts (batch, max_det, nkpt, ndim) for rows < counts[b].  params: fp32 (batch, 7) gain, pad_x, pad_y, clip_w, clip_h, off_x, off_y; the
+ * pads are the UNROUNDED (img1 - img0 * gain) / 2 (scale_boxes rounds them, scale_coords does not).  Per keypoint:
+ *   x = min(max((x - pad_x) / gain, 0), clip_w), y the same; then ndim == 3 and v < 0.5: x = y = 0; otherwise x += off_x, y += off_y
+ * (the offsets are zero except for crops of a frame).  boxes: NULL, or the dy_nms rows (batch, max_det, 6) AFTER dy_scale_boxes: a
+ * non-zero offset is added to x1, y1, x2, y2 of every row < counts[b] as well (a crop's boxes, clamped to the crop, move to frame pixels).
+ * ndim outside {2, 3}: DY_ERR_UNSUPPORTED. */
+int32_t dy_scale_coords(float* kpts, float* boxes, const int32_t* counts, const float* params, int32_t batch, int32_t max_det, int32_t nkpt,
+                        int32_t ndim, dy_stream_t stream);
+
+/* dy_crops_letterbox_u8_to_nchw_f32: the batched person-crop slicer.  frames: DEVICE uint8 (f, hf, wf, 3), all frames one shape.
+ * table: DEVICE int32 (k, 9), per crop  frame, x0, y0, cw, ch, new_w, new_h, top, left;  table_host: the same table in HOST memory, read
+ * during the call for the argument check.  dst: fp32 (k, 3, hn, wn).  Crop j is the ch x cw window of its frame at (y0, x0), resized to
+ * new_h x new_w by the 8-bit bilinear rule of dy_letterbox_u8_to_nchw_f32 (a size equal to the window copies), placed at (top, left),
+ * pad_value elsewhere, / 255, swap_rb: bit for bit what dy_letterbox_u8_to_nchw_f32 writes for a contiguous copy of the window.
+ * A row whose window leaves the frame, whose cw or ch is < 1 or whose resized image leaves the output: DY_ERR_INVALID_ARG, nothing launched.
+ * k <= 65535. */
+int32_t dy_crops_letterbox_u8_to_nchw_f32(const uint8_t* frames, const int32_t* table, const int32_t* table_host, float* dst, int32_t f, int32_t hf,
+                                          int32_t wf, int32_t k, int32_t hn, int32_t wn, int32_t swap_rb, float pad_value, dy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
