@@ -352,6 +352,22 @@ class ValMaskMatchDesc(C.Structure):
     ]  # fmt: skip
 
 
+OKS_MAX_KPT = 32  # DY_OKS_MAX_KPT: keypoints per label dy_val_oks_match takes (csrc/val_oks.hip: the LDS stage is sized for it)
+
+
+class ValOksMatchDesc(C.Structure):
+    """Mirror of ``dy_val_oks_match_desc``."""
+
+    _fields_ = [
+        ("rows", _vp), ("counts", _vp), ("kpts", _vp), ("index", _vp),
+        ("stride_b", _i64), ("stride_ch", _i64), ("stride_d", _i64), ("anchors", _i32),
+        ("tbox", _vp), ("tkpt", _vp), ("tcls", _vp), ("timg", _vp), ("sigma", C.POINTER(_f32)), ("iouv", C.POINTER(_f32)),
+        ("batch", _i32), ("max_det", _i32), ("n_labels", _i32), ("n_iouv", _i32), ("nkpt", _i32), ("ndim", _i32),
+        ("clip_w", _f32), ("clip_h", _f32), ("single_cls", _i32),
+        ("tp", _vp), ("best_iou", _vp), ("best_label", _vp),
+    ]  # fmt: skip
+
+
 DY_AUG_FLIPLR, DY_AUG_FLIPUD, DY_AUG_HSV_OFF = 1, 2, 4
 
 
@@ -478,6 +494,7 @@ SIGNATURES = {
     "dy_process_mask": (_i32, [C.POINTER(ProcessMaskDesc), _vp]),
     "dy_val_mask_match": (_i32, [C.POINTER(ValMaskMatchDesc), _vp]),
     "dy_kpt_decode": (_i32, [C.POINTER(KptDecodeDesc), _vp]),
+    "dy_val_oks_match": (_i32, [C.POINTER(ValOksMatchDesc), _vp]),
     "dy_scale_coords": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "dy_crops_letterbox_u8_to_nchw_f32": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
 }

@@ -64,8 +64,8 @@ class Model(nn.Module):
 
     @property
     def pose_task_map(self):
-        """The pose task, kept apart from ``task_map`` like the oriented-box one: model and predictor.  There is no trainer: ``train`` refuses
-        a pose model before it looks for one."""
+        """The pose task, kept apart from ``task_map`` like the oriented-box one: model and predictor; ``val`` scores a pose model with
+        ``PoseValidator`` (its task table).  There is no trainer: ``train`` refuses a pose model before it looks for one."""
         return {"pose": {"model": PoseModel, "predictor": PosePredictor}}
 
     def _task_classes(self, task: str) -> dict:
@@ -291,16 +291,19 @@ class Model(nn.Module):
         the map's or is exactly twice it.  ``SegmentMetrics``' dict (the four (B) and four (M) entries, ``fitness``), no validation loss.
         obb (models/yolo/obb/val.py; ``OBBValidator``): the rotated ``multi_label`` NMS (``dy_nms_rotated_ml``) and the ProbIoU matching
         (``dy_val_match_rotated``).  The dataset's ``bboxes`` must be (M, 5): normalised xywh and the angle in radians.  ``OBBMetrics``' dict
-        (the four (B) entries, ``fitness``), no validation loss.  ``save_json``, plots, the DOTA merge (``eval_json``) and ``save_txt`` are
-        not built."""
+        (the four (B) entries, ``fitness``), no validation loss.
+        pose (models/yolo/pose/val.py; ``PoseValidator``): box metrics and keypoint metrics, the keypoints scored by object keypoint
+        similarity through ``dy_val_oks_match``.  The dataset must carry ``keypoints`` (M, nkpt, 3), normalised x, y and the visibility of
+        every label, with the model's nkpt ((M, nkpt, 2), all visible, for a ``kpt_shape`` of two values per keypoint), or be
+        ``"synthetic-pose[:N]"``; anything else is refused with ``NotImplementedError`` before a device is selected.  ``PoseMetrics``' dict
+        (the four (B) and four (P) entries, ``fitness``), no validation loss.
+        ``save_json``, plots, the DOTA merge (``eval_json``) and ``save_txt`` are not built."""
         from .predictor import resolve_dtype
         from .trainer import TensorLoader, load_dataset
         from . import validator as V
         from .. import hip_ops as H
         from ..utils.torch_utils import select_device
 
-        if self.task == "pose":  # before a dataset is read or a device selected
-            raise NotImplementedError("val: pose validation (OKS matching) is not built")
         args = {**{k: v for k, v in self.overrides.items() if k not in ("task", "mode")}, **kwargs}
         if args.get("data") is None:
             raise ValueError("val(): 'data' is missing (a tensor dataset: dict / .pt, or 'synthetic[:N]')")
@@ -309,12 +312,15 @@ class Model(nn.Module):
         keys = ("img", "batch_idx", "cls", "bboxes")
         check, fp8_refused, keys, default = {"detect": (None, None, keys, V.DetectionValidator),
                                              "segment": (self._check_val_masks, "Segment", keys + ("masks",), V.SegmentationValidator),
-                                             "obb": (self._check_val_xywhr, "OBB", keys, V.OBBValidator)}[self.task]
+                                             "obb": (self._check_val_xywhr, "OBB", keys, V.OBBValidator),
+                                             "pose": (self._check_val_keypoints, "Pose", keys + ("keypoints",), V.PoseValidator)}[self.task]
         # the dataset first: whatever it lacks is refused before a device is selected, the model moved or a validator built
-        data = load_dataset(args["data"], int(args.get("imgsz", 640)), self.model.yaml["nc"], int(args.get("seed", 0)))
+        kpt_shape = tuple(int(v) for v in self.model.model[-1].kpt_shape) if self.task == "pose" else None
+        data = load_dataset(args["data"], int(args.get("imgsz", 640)), self.model.yaml["nc"], int(args.get("seed", 0)), kpt_shape=kpt_shape)
         data = data.get("val") or data
         if check is not None:
-            check(data, repr(args["data"] if isinstance(args["data"], str) else type(args["data"]).__name__))
+            name = repr(args["data"] if isinstance(args["data"], str) else type(args["data"]).__name__)
+            check(data, name, kpt_shape) if kpt_shape is not None else check(data, name)
         device = select_device(args.get("device", ""))
         dtype = resolve_dtype(args.get("dtype"), bool(args.get("half", False)), self.model)
         if fp8_refused is None and dtype not in (torch.float32, torch.float16, torch.bfloat16):
@@ -348,6 +354,21 @@ class Model(nn.Module):
             shape = tuple(boxes.shape) if isinstance(boxes, torch.Tensor) else type(boxes).__name__
             raise NotImplementedError(f"val: an oriented-box model needs a dataset whose 'bboxes' are (M, 5) xywhr (normalised xywh and the angle in radians); "
                                       f"data={name} has {shape} (no angles)")
+
+    @staticmethod
+    def _check_val_keypoints(data: dict, name: str, kpt_shape) -> None:
+        kpts = data.get("keypoints")
+        nkpt, ndim = int(kpt_shape[0]), int(kpt_shape[1])
+        takes = f"(M, {nkpt}, 3)" + (f" or (M, {nkpt}, 2)" if ndim == 2 else "")
+        if kpts is None:
+            raise NotImplementedError(f"val: a pose model needs a dataset with 'keypoints' {takes} (normalised x, y and the visibility of every label; dict / "
+                                      f".pt) or 'synthetic-pose[:N]'; data={name} has none")
+        ok = isinstance(kpts, torch.Tensor) and kpts.dim() == 3 and kpts.shape[0] == data["bboxes"].shape[0] and kpts.shape[1] == nkpt \
+            and (kpts.shape[2] == 3 or (kpts.shape[2] == 2 and ndim == 2))
+        if not ok:
+            shape = tuple(kpts.shape) if isinstance(kpts, torch.Tensor) else type(kpts).__name__
+            raise NotImplementedError(f"val: a pose model needs a dataset with 'keypoints' {takes}, one row per label, as the model's kpt_shape "
+                                      f"{[nkpt, ndim]} asks; data={name} has {shape}")
 
     def fuse(self):
         self.model.fuse()

@@ -206,11 +206,14 @@ class ModelEMA:
 
 
 # ---- data ----------------------------------------------------------------------------------------------------------------
-def synthetic_dataset(n: int, imgsz: int, seed: int, nc: int = 10, angles: bool = False, masks: bool = False) -> Dict[str, torch.Tensor]:
+def synthetic_dataset(n: int, imgsz: int, seed: int, nc: int = 10, angles: bool = False, masks: bool = False, kpt_shape=None) -> Dict[str, torch.Tensor]:
     """uint8 images randint(0, 256); per image n ~ Poisson(50) clipped to [1, 300] boxes (VisDrone-like
     density), class uniform, centres uniform(0.05, 0.95), wh lognormal(median 0.03, sigma 0.6) clipped to [0.004, 0.5].  ``angles``
     (``"synthetic-obb"``): one more draw from the same generator AFTER those, an angle per box uniform in [-pi/4, 3 pi/4): ``bboxes`` (M, 5) xywhr.
-    ``masks`` (``"synthetic-seg"``): the same draws, then ``synthetic_overlap_masks`` at imgsz / 4."""
+    ``masks`` (``"synthetic-seg"``): the same draws, then ``synthetic_overlap_masks`` at imgsz / 4.
+    ``kpt_shape`` (``"synthetic-pose"``): the same draws, then from the same generator AFTER them nkpt points per box uniform inside the box and
+    a visibility per point in {0, 1, 2}, the first point of a label without a visible one set to 2: ``keypoints`` (M, nkpt, 3), normalised x, y
+    and the visibility."""
     g = torch.Generator().manual_seed(seed)
     img = torch.randint(0, 256, (n, 3, imgsz, imgsz), generator=g, dtype=torch.uint8)
     counts = torch.poisson(torch.full((n,), 50.0), generator=g).clamp(1, 300).long()
@@ -221,6 +224,12 @@ def synthetic_dataset(n: int, imgsz: int, seed: int, nc: int = 10, angles: bool 
     wh = (torch.randn(m, 2, generator=g) * 0.6 + math.log(0.03)).exp().clamp(0.004, 0.5)
     cols = (cxy, wh, (torch.rand(m, 1, generator=g) - 0.25) * math.pi) if angles else (cxy, wh)
     d = dict(img=img, batch_idx=bi, cls=cls, bboxes=torch.cat(cols, 1))
+    if kpt_shape is not None:
+        nkpt = int(kpt_shape[0])
+        xy = cxy[:, None] + (torch.rand(m, nkpt, 2, generator=g) - 0.5) * wh[:, None]
+        vis = torch.randint(0, 3, (m, nkpt), generator=g).float()
+        vis[vis.sum(1) == 0, 0] = 2.0
+        d["keypoints"] = torch.cat((xy, vis[..., None]), 2)
     return synthetic_overlap_masks(d, imgsz // 4, imgsz // 4) if masks else d
 
 
@@ -312,11 +321,12 @@ def check_obb_train_data(data, args: dict) -> None:
                                   f"data={name!r} has {shape} (no angles)")
 
 
-def load_dataset(data, imgsz: int, nc: int, seed: int) -> Dict[str, torch.Tensor]:
+def load_dataset(data, imgsz: int, nc: int, seed: int, kpt_shape=None) -> Dict[str, torch.Tensor]:
     """``data``: a dict / a ``.pt`` file of tensors ``img`` (N,3,H,W) uint8, ``batch_idx`` (M,), ``cls`` (M,1), ``bboxes`` (M,4
     normalised xywh; (M,5) with the angle in radians for an oriented-box set, passed through as it is) — the reference's collate layout
     (data/dataset.py:232-248) over the whole set — or ``"synthetic[:N]"``, ``"synthetic-obb[:N]"`` (the same draws plus an angle per box), ``"synthetic-seg[:N]"`` (the same draws plus an
-    overlap index map at imgsz / 4, labels in the maps' order), or a
+    overlap index map at imgsz / 4, labels in the maps' order), ``"synthetic-pose[:N]"`` (the same draws plus ``keypoints`` (M, nkpt, 3) inside the
+    boxes, nkpt from ``kpt_shape``, the model's; a dict / ``.pt`` pose set carries ``keypoints`` (M, nkpt, 3): normalised x, y and the visibility), or a
     YOLO-format dataset YAML (``load_yaml_dataset``: decoded once into the same tensor layout)."""
     if isinstance(data, dict):
         d = data
@@ -326,6 +336,11 @@ def load_dataset(data, imgsz: int, nc: int, seed: int) -> Dict[str, torch.Tensor
     elif isinstance(data, str) and data.startswith("synthetic-seg"):
         n = int(data.split(":")[1]) if ":" in data else 128
         d = synthetic_dataset(n, imgsz, seed=1000 + seed, nc=nc, masks=True)
+    elif isinstance(data, str) and data.startswith("synthetic-pose"):
+        if kpt_shape is None:
+            raise NotImplementedError("data='synthetic-pose' needs a pose model: the number of keypoints comes from its kpt_shape")
+        n = int(data.split(":")[1]) if ":" in data else 128
+        d = synthetic_dataset(n, imgsz, seed=1000 + seed, nc=nc, kpt_shape=kpt_shape)
     elif isinstance(data, str) and data.startswith("synthetic"):
         n = int(data.split(":")[1]) if ":" in data else 128
         d = synthetic_dataset(n, imgsz, seed=1000 + seed, nc=nc)
@@ -448,7 +463,8 @@ class TensorLoader:
     multiple of world size by wrapping around, rank r takes indices r::world); labels re-indexed per batch as the reference's
     collate_fn does (``batch_idx`` = position in the batch).  An image's labels are yielded contiguously and in dataset order; a dataset
     with ``masks`` (integer (N, gh, gw), the reference's ``overlap_mask=True`` index maps of data/utils.py::polygons2masks_overlap) also
-    yields ``masks`` of the batch's images."""
+    yields ``masks`` of the batch's images; a dataset with ``keypoints`` (M, nkpt, 2 | 3), one row per label, also yields the ``keypoints`` of the
+    batch's label rows, sliced as ``bboxes`` is."""
 
     def __init__(self, data: Dict[str, torch.Tensor], batch: int, rank: int = 0, world: int = 1, seed: int = 0, shuffle: bool = True):
         self.d, self.batch, self.rank, self.world, self.seed, self.shuffle, self.epoch = data, max(int(batch), 1), rank, world, seed, shuffle, 0
@@ -489,6 +505,8 @@ class TensorLoader:
                        bboxes=self.d["bboxes"][rows].float())
             if self.d.get("masks") is not None:  # segmentation: the overlap label map of every image (value k = the image's k-th label, in the order above)
                 out["masks"] = self.d["masks"][take]
+            if self.d.get("keypoints") is not None:  # pose: per label, in the label rows' order
+                out["keypoints"] = self.d["keypoints"][rows].float()
             yield out
 
 

@@ -17,7 +17,9 @@ layout — or, when the dataset has no split, the training tensors themselves.
 ``SegmentationValidator`` (models/yolo/segment/val.py) adds the mask statistics of a segmentation model: ``dy_val_mask_match`` behind the box
 matching, or the reference's mask branch on the host ("Segmentation validation").
 ``OBBValidator`` (models/yolo/obb/val.py) scores an oriented-box model: ``dy_nms_rotated_ml`` and ``dy_val_match_rotated`` (ProbIoU), or the
-reference's data flow on the host ("Oriented-box validation")."""
+reference's data flow on the host ("Oriented-box validation").
+``PoseValidator`` (models/yolo/pose/val.py) adds the keypoint statistics of a pose model: ``dy_val_oks_match`` (object keypoint similarity) behind
+the box matching, or the reference's keypoint branch on the host ("Pose validation")."""
 from __future__ import annotations
 
 from typing import Dict, Optional
@@ -28,7 +30,7 @@ import torch.nn.functional as F
 
 from .. import hip_ops as H
 from ..utils import ops
-from ..utils.metrics import DetMetrics, OBBMetrics, SegmentMetrics, batch_probiou, box_iou, mask_iou, match_predictions
+from ..utils.metrics import OKS_SIGMA, DetMetrics, OBBMetrics, PoseMetrics, SegmentMetrics, batch_probiou, box_iou, kpt_iou, mask_iou, match_predictions
 
 
 class DetectionValidator:
@@ -330,3 +332,70 @@ class OBBValidator(DetectionValidator):
         if not len(cls) or not len(rows):
             return np.zeros((len(rows), len(self.iouv)), dtype=bool)
         return self._match_host(self._clipped(rows, w, h), tbox, cls, (w, h), (), 0)["tp"]
+
+
+# ---- pose (models/yolo/pose/val.py) ------------------------------------------------------------------------------------------------------
+def pose_label_kpts(kpts: torch.Tensor, w: int, h: int, lim: torch.Tensor) -> torch.Tensor:
+    """``PoseValidator._prepare_batch`` on the (L, nkpt, 2 | 3) normalised label keypoints of a batch: ``x * w``, ``y * h``, then
+    ``scale_coords`` at gain 1 / pad 0, which leaves ``clip_coords`` (x to [0, w], y to [0, h]); the visibility is untouched, and a set without
+    one (ndim 2) gets the all-visible column the reference's dataset appends.  Returns (L, nkpt, 3).  Elementwise fp32 torch operations: the
+    same bits wherever ``kpts`` lives.  ``lim``: fp32 (w, h, w, h) on the same device."""
+    t = kpts.float()
+    xy = torch.minimum((t[..., :2] * lim[:2]).clamp_min(0), lim[:2])
+    vis = t[..., 2:3] if t.shape[-1] == 3 else torch.ones_like(xy[..., :1])
+    return torch.cat((xy, vis), -1)
+
+
+class PoseValidator(DetectionValidator):
+    """``PoseValidator`` of the reference (models/yolo/pose/val.py): ``DetectionValidator`` plus the keypoint statistics ``tp_p``:
+    ``match_predictions`` on ``kpt_iou(gt_kpts, pred_kpts, sigma, area = box area * 0.53)``.  The model pass, the ``multi_label`` NMS (``nc=``
+    given: the keypoint channels ride behind the classes) and the box matching run as in the detection validator; with ``device_match`` the
+    keypoints are scored by ``dy_val_oks_match``, which reads the kept anchors' keypoints out of the head's (N, 4 + nc + nk, A) tensor through the
+    NMS's index (no gather launch, nothing in the batch loop waits for the device), without it by the reference's data flow on the host, image
+    by image.  The dataset carries ``keypoints`` (M, nkpt, 3): normalised x, y and the visibility.  ``sigma``: the COCO constants for
+    ``kpt_shape == [17, 3]``, ``ones(nkpt) / nkpt`` otherwise.  No validation loss (``v8PoseLoss`` is not built): the dict holds the eight
+    metrics and ``fitness``."""
+
+    stat_keys = ("tp", "tp_p")
+    metrics_cls = PoseMetrics
+    val_loss = False
+
+    def __call__(self, model, loader, device, dtype: torch.dtype) -> Dict[str, float]:
+        head = model.model[-1]
+        if getattr(head, "kpt_shape", None) is None:
+            raise RuntimeError("PoseValidator needs a model whose head is Pose")
+        self.kpt_shape = tuple(int(v) for v in head.kpt_shape)
+        self.sigma = OKS_SIGMA if list(self.kpt_shape) == [17, 3] else np.ones(self.kpt_shape[0]) / self.kpt_shape[0]
+        self._lim = {}  # (w, h) -> the fp32 (w, h, w, h) of pose_label_kpts on the device: one upload per image size
+        return super().__call__(model, loader, device, dtype)
+
+    def _nms(self, y, aux, nc, batch):
+        nk = self.kpt_shape[0] * self.kpt_shape[1]
+        if not (isinstance(aux, tuple) and len(aux) == 2) or y.dim() != 3 or y.shape[1] != 4 + nc + nk:  # Pose returns (cat([y, pred_kpt], 1), (feats, kpt))
+            raise RuntimeError("PoseValidator needs a model whose head is Pose")
+        y = y.float().contiguous()
+        bufs, _ = super()._nms(y, aux, nc, batch)
+        self._nc = nc
+        return bufs, (y, batch["keypoints"], batch["batch_idx"], bufs.index)
+
+    def _match_device(self, bufs, tbox, cls, bi, wh, extras) -> Dict[str, torch.Tensor]:
+        y, kpts = extras[0], extras[1].to(bufs.out.device)
+        if tuple(wh) not in self._lim:
+            self._lim[tuple(wh)] = torch.tensor((wh[0], wh[1], wh[0], wh[1]), dtype=torch.float32, device=kpts.device)
+        lim = self._lim[tuple(wh)]
+        tpp = H.val_oks_match(bufs, y, self.kpt_shape, tbox, pose_label_kpts(kpts, wh[0], wh[1], lim), cls, bi, self.sigma, self.iouv, wh,
+                              nc=self._nc, single_cls=self.single_cls)
+        return dict(super()._match_device(bufs, tbox, cls, bi, wh, extras), tp_p=tpp)
+
+    def _match_host(self, pn, tbox, cls, wh, extras, si) -> Dict[str, np.ndarray]:  # pose/val.py:73-91, 146-184
+        y, kpts, bi, index = extras
+        (w, h), k = wh, len(pn)
+        nkpt, ndim = self.kpt_shape
+        pk = y[si][4 + self._nc :, index[si, :k].long()].t().reshape(k, nkpt, ndim).clone()  # the kept anchors' keypoint channels, as the NMS rows carry them
+        pk[..., 0].clamp_(0, w)  # ops.scale_coords at gain 1 / pad 0: clip_coords
+        pk[..., 1].clamp_(0, h)
+        gt = pose_label_kpts(kpts[bi.long() == si], w, h, torch.tensor((w, h, w, h), dtype=torch.float32))
+        tb = torch.from_numpy(np.ascontiguousarray(tbox, dtype=np.float32))
+        area = ((tb[:, 2] - tb[:, 0]) * (tb[:, 3] - tb[:, 1])) * 0.53  # ops.xyxy2xywh(gt_bboxes)[:, 2:].prod(1) * 0.53
+        oks = kpt_iou(gt, pk, area, self.sigma).numpy()
+        return dict(super()._match_host(pn, tbox, cls, wh, extras, si), tp_p=match_predictions(pn[:, 5], cls, oks, self.iouv))

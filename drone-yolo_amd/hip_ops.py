@@ -1387,6 +1387,71 @@ def val_match_rotated(bufs: RNmsBuffers, tbox: torch.Tensor, tcls: torch.Tensor,
     return _val_match(lib().dy_val_match_rotated, bufs, tbox, tcls, timg, iouv, clip_wh, single_cls, want_best)
 
 
+def val_oks_match(bufs: NmsBuffers, kpts: torch.Tensor, kpt_shape, tbox: torch.Tensor, tkpt: torch.Tensor, tcls: torch.Tensor, timg: torch.Tensor,
+                  sigma: Sequence[float], iouv: Sequence[float], clip_wh: Tuple[float, float], nc: Optional[int] = None, single_cls: bool = False,
+                  want_best: bool = False):
+    """The pose validator's keypoint matching (``match_predictions`` on ``kpt_iou(gt, pred, area = box area * 0.53, sigma)``, predictions
+    clipped to ``clip_wh`` as ``scale_coords`` at gain 1 clips them) of a whole batch on the padded NMS output through ``dy_val_oks_match``; no
+    host synchronisation, no gather launch.
+
+    ``bufs``: what ``nms`` returned.  ``kpts``, one of two addressings:
+      dense plus index  the contiguous fp32 (N, 4 + nc + nk, A) tensor the unfused ``Pose.forward`` returns, with ``nc=`` given: the keypoint
+                        channels are read at offset 4 + nc through ``bufs.index``;
+      gathered rows     the contiguous fp32 (N, max_det, nk) rows ``kpt_gather`` returns (``nc`` None).
+    ``kpt_shape`` = (nkpt, ndim), nkpt <= 32; ``tbox`` (L, 4) the label boxes (xyxy in pixels, clipped), ``tkpt`` (L, nkpt, 3) their keypoints
+    (pixels, clipped) and visibilities, ``tcls`` (L,), ``timg`` (L,) (any order); ``sigma``: nkpt host values; ``iouv``: 1..16 thresholds.
+    Returns ``tp`` uint8 (N, max_det, len(iouv)), new tensors on every call; with ``want_best`` ``(tp, best_iou, best_label)``.  Rows at or beyond
+    ``bufs.count`` are 0 / 0 / -1."""
+    nkpt, ndim = int(kpt_shape[0]), int(kpt_shape[1])
+    nk = nkpt * ndim
+    n, max_det, dev = bufs.batch, bufs.max_det, bufs.out.device
+    if nkpt > _lib.OKS_MAX_KPT:
+        raise NotImplementedError(f"val_oks_match: {nkpt} keypoints; dy_val_oks_match takes at most {_lib.OKS_MAX_KPT} (the LDS stage)")
+    if ndim not in (2, 3) or nkpt < 1 or len(sigma) != nkpt:
+        raise ValueError("val_oks_match: kpt_shape must be (nkpt >= 1, 2 | 3) with one sigma per keypoint")
+    if bufs.out.shape[-1] != NmsBuffers.ROW:
+        raise ValueError("val_oks_match: the NMS buffers must hold 6-column rows (NmsBuffers)")
+    require_device(kpts, "keypoints")
+    if kpts.dtype != torch.float32 or not kpts.is_contiguous() or kpts.dim() != 3 or kpts.shape[0] != n:
+        raise ValueError("val_oks_match: kpts must be a contiguous fp32 (N, 4 + nc + nk, A) or (N, max_det, nk) tensor")
+    d = _lib.ValOksMatchDesc()
+    if nc is not None:
+        if kpts.shape[1] != 4 + nc + nk or kpts.shape[2] != bufs.anchors:
+            raise ValueError(f"val_oks_match: the dense form takes (N, {4 + nc + nk}, {bufs.anchors}), got {tuple(kpts.shape)}")
+        a = int(kpts.shape[2])
+        d.kpts, d.index = kpts.data_ptr() + 4 * (4 + nc) * a, bufs.index.data_ptr()
+        d.stride_b, d.stride_ch, d.stride_d, d.anchors = int(kpts.shape[1]) * a, a, 1, a
+    else:
+        if tuple(kpts.shape[1:]) != (max_det, nk):
+            raise ValueError(f"val_oks_match: the gathered form takes (N, {max_det}, {nk}), got {tuple(kpts.shape)}")
+        d.kpts, d.index = kpts.data_ptr(), None
+        d.stride_b, d.stride_ch, d.stride_d, d.anchors = max_det * nk, 1, nk, 0
+    L = _check_labels("val_oks_match", "", 4, tbox, tcls, timg)
+    if L:
+        require_device(tkpt, "label")
+        if tuple(tkpt.shape) != (L, nkpt, 3):
+            raise ValueError(f"val_oks_match: tkpt must be (L, {nkpt}, 3): x, y in pixels and the visibility")
+        tbox = tbox.to(torch.float32).contiguous()
+        tkpt = tkpt.to(torch.float32).contiguous()
+        tcls = tcls.reshape(-1).to(torch.float32).contiguous()
+        timg = timg.reshape(-1).to(torch.int32).contiguous()
+    thr = (C.c_float * len(iouv))(*[float(v) for v in iouv])
+    sg = (C.c_float * nkpt)(*[float(v) for v in sigma])
+    tp = torch.empty((n, max_det, len(iouv)), dtype=torch.uint8, device=dev)
+    best_iou = torch.empty((n, max_det), dtype=torch.float32, device=dev) if want_best else None
+    best_label = torch.empty((n, max_det), dtype=torch.int32, device=dev) if want_best else None
+    d.rows, d.counts = bufs.out.data_ptr(), bufs.count.data_ptr()
+    d.tbox, d.tkpt, d.tcls, d.timg = (tbox.data_ptr(), tkpt.data_ptr(), tcls.data_ptr(), timg.data_ptr()) if L else (None, None, None, None)
+    d.sigma, d.iouv = sg, thr
+    d.batch, d.max_det, d.n_labels, d.n_iouv, d.nkpt, d.ndim = n, max_det, L, len(iouv), nkpt, ndim
+    d.clip_w, d.clip_h, d.single_cls = float(clip_wh[0]), float(clip_wh[1]), int(bool(single_cls))
+    d.tp = tp.data_ptr()
+    d.best_iou = best_iou.data_ptr() if want_best else None
+    d.best_label = best_label.data_ptr() if want_best else None
+    _launch(lib().dy_val_oks_match, (C.byref(d),), keep=(d, thr, sg, bufs, kpts, tbox, tkpt, tcls, timg, tp, best_iou, best_label))
+    return (tp, best_iou, best_label) if want_best else tp
+
+
 def label_offsets(timg: torch.Tensor, batch: int) -> torch.Tensor:
     """int32 (batch + 1) exclusive prefix of the labels per image, from the image index of every label, built where ``timg`` lives without a
     host synchronisation (``torch.bincount`` would read the largest index back)."""

@@ -59,6 +59,27 @@ def batch_probiou(obb1, obb2, eps: float = 1e-7):
     return 1 - hd
 
 
+# the COCO keypoint constants (metrics.py:16-19): per-keypoint standard deviations, / 10
+OKS_SIGMA = np.array([0.26, 0.25, 0.25, 0.35, 0.35, 0.79, 0.79, 0.72, 0.72, 0.62, 0.62, 1.07, 1.07, 0.87, 0.87, 0.89, 0.89]) / 10.0
+
+
+def kpt_iou(kpt1, kpt2, area, sigma, eps: float = 1e-7):
+    """(N, nkpt, 3) label keypoints x (M, nkpt, 2 | 3) predicted keypoints, (N,) label areas, nkpt sigmas -> (N, M) object keypoint
+    similarity tensor in the inputs' precision — metrics.py:156-175, in torch, operation by operation as there (``sigma`` takes the keypoints'
+    dtype; the mask count + eps is a default-dtype tensor).  It is what ``dy_val_oks_match`` (csrc/val_oks.hip) evaluates pair by pair on the
+    device and what that kernel is tested against."""
+    import torch
+
+    kpt1 = torch.from_numpy(kpt1) if isinstance(kpt1, np.ndarray) else kpt1
+    kpt2 = torch.from_numpy(kpt2) if isinstance(kpt2, np.ndarray) else kpt2
+    area = torch.from_numpy(area) if isinstance(area, np.ndarray) else area
+    d = (kpt1[:, None, :, 0] - kpt2[..., 0]).pow(2) + (kpt1[:, None, :, 1] - kpt2[..., 1]).pow(2)  # (N, M, nkpt)
+    sigma = torch.tensor(np.asarray(sigma).tolist(), device=kpt1.device, dtype=kpt1.dtype)
+    kpt_mask = kpt1[..., 2] != 0
+    e = d / ((2 * sigma).pow(2) * (area[:, None, None] + eps) * 2)
+    return ((-e).exp() * kpt_mask[:, None]).sum(-1) / (kpt_mask.sum(-1)[:, None] + eps)
+
+
 def match_predictions(pred_classes: np.ndarray, true_classes: np.ndarray, iou: np.ndarray, iouv: np.ndarray) -> np.ndarray:
     """(D,) predicted classes, (L,) target classes, (L, D) IoU -> (D, len(iouv)) bool "correct" — validator.py:224-264 (the
     non-scipy branch: per threshold, matches sorted by IoU, each detection and then each label kept once)."""
@@ -187,3 +208,25 @@ class SegmentMetrics:
 class OBBMetrics(DetMetrics):
     """Metrics of an oriented-box model — ``OBBMetrics`` (metrics.py): ``DetMetrics`` under its own name.  The statistics it is fed are
     matched on ProbIoU (``OBBValidator``); the AP code, the keys (the four (B) entries) and ``fitness`` are the detection ones."""
+
+
+class PoseMetrics(SegmentMetrics):
+    """Box and keypoint metrics of a pose model — ``PoseMetrics`` (metrics.py): ``SegmentMetrics``' shape with (P) keys: two ``Metric`` sets,
+    fed by ``tp`` (boxes) and ``tp_p`` (keypoints: matched on OKS) with the same ``conf`` / ``pred_cls`` / ``target_cls``.  ``fitness`` is the sum
+    of the two sets' fitness."""
+
+    keys = DetMetrics.keys + ("metrics/precision(P)", "metrics/recall(P)", "metrics/mAP50(P)", "metrics/mAP50-95(P)")
+
+    def __init__(self):
+        self.box, self.pose = DetMetrics(), DetMetrics()
+
+    def process(self, tp, tp_p, conf, pred_cls, target_cls) -> None:
+        self.pose.process(tp_p, conf, pred_cls, target_cls)
+        self.box.process(tp, conf, pred_cls, target_cls)
+
+    def mean_results(self):
+        return self.box.mean_results() + self.pose.mean_results()
+
+    @property
+    def fitness(self) -> float:
+        return self.pose.fitness + self.box.fitness

@@ -1316,6 +1316,53 @@ int32_t dy_scale_coords(float* kpts, float* boxes, const int32_t* counts, const 
 int32_t dy_crops_letterbox_u8_to_nchw_f32(const uint8_t* frames, const int32_t* table, const int32_t* table_host, float* dst, int32_t f, int32_t hf,
                                           int32_t wf, int32_t k, int32_t hn, int32_t wn, int32_t swap_rb, float pad_value, dy_stream_t stream);
 
+/* ---- pose validation: object keypoint similarity and matching on the padded NMS output (csrc/val_oks.hip) --------------------
+ * dy_val_oks_match.  Replaces: PoseValidator._process_batch's keypoint branch (models/yolo/pose/val.py: match_predictions on
+ * kpt_iou(gt_kpts, pred_kpts, sigma, area = box area * 0.53), utils/metrics.py:156-175) with the clip of its _prepare_pred
+ * (ops.scale_coords at gain 1 / pad 0 = clip_coords), for a whole batch in one launch behind dy_nms; no host synchronisation, no
+ * allocation, capturable in a hipGraph.
+ * rows: fp32 (batch, max_det, 6) and counts: int32 (batch): the dy_nms outputs; only the class column is read, rows >= counts[b] never.
+ * kpts: the predictions' keypoints.  Coordinate c of keypoint k of kept row d of image b is
+ *     kpts[b * stride_b + (k * ndim + c) * stride_ch + (index ? index[b * max_det + d] : d) * stride_d]       (strides in floats)
+ *   dense plus index  index = dy_nms out_index, stride_b = C * A, stride_ch = A, stride_d = 1 and kpts = pred + (4 + nc) * A read the
+ *                     (batch, C, A) tensor the unfused Pose.forward returns; an index outside [0, anchors) is clamped into it;
+ *   gathered rows     index = NULL, stride_b = max_det * nk, stride_d = nk, stride_ch = 1: the dy_kpt_decode gather output.
+ *   Only c = 0 and 1 are read (a prediction's visibility is not used); rows >= counts[b] are never read in either form.
+ * tbox: fp32 (n_labels, 4) label boxes, xyxy in pixels, clipped, 16-byte aligned; tkpt: fp32 (n_labels, nkpt, 3) x, y in pixels, clipped,
+ * and visibility; tcls: fp32 (n_labels); timg: int32 (n_labels), any order.  n_labels = 0 with null label pointers is valid.
+ * sigma: HOST array of nkpt floats, iouv: HOST array of n_iouv (1..16) thresholds, both read during the call.
+ * nkpt in [1, DY_OKS_MAX_KPT] (above: DY_ERR_UNSUPPORTED), ndim 2 or 3, max_det <= 4096.
+ * fp32 in kpt_iou's order of operations without contraction:  px = min(max(x, 0), clip_w), py likewise;  per label
+ *   area = ((x2 - x1) * (y2 - y1)) * 0.53f,  den[k] = (((2 sigma[k]) * (2 sigma[k])) * (area + 1e-7f)) * 2;  per pair
+ *   d[k] = dx * dx + dy * dy,  e[k] = d[k] / den[k] (correctly rounded),  oks = (sum_k expf(-e[k]) * (vis[k] != 0)) / (n_visible + 1e-7f);
+ *   m(l, d) = oks if tcls[l] == cls[d] (0 with single_cls) else 0; a label without a visible keypoint scores 0.  expf is the device's
+ *   and the sum runs k = 0, 1, ...: not bit-equal to the host's.  best / biou / tp by dy_val_match's rule (ties to the lower position in
+ *   tbox, a NaN never becomes the best).
+ * tp: uint8 (batch, max_det, n_iouv); best_iou / best_label: optional, as in dy_val_match.  Every element is written; rows >= counts[b]
+ * get 0 / 0 / -1.  One workgroup per image; labels per image are unbounded. */
+#define DY_OKS_MAX_KPT 32
+typedef struct dy_val_oks_match_desc {
+  const float* rows;
+  const int32_t* counts;
+  const float* kpts;
+  const int32_t* index; /* (batch, max_det) dy_nms out_index, or NULL */
+  int64_t stride_b, stride_ch, stride_d;
+  int32_t anchors; /* dense form: the range of index */
+  const float* tbox;
+  const float* tkpt;
+  const float* tcls;
+  const int32_t* timg;
+  const float* sigma;
+  const float* iouv;
+  int32_t batch, max_det, n_labels, n_iouv, nkpt, ndim;
+  float clip_w, clip_h;
+  int32_t single_cls;
+  uint8_t* tp;
+  float* best_iou;
+  int32_t* best_label;
+} dy_val_oks_match_desc;
+int32_t dy_val_oks_match(const dy_val_oks_match_desc* d, dy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
